@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the raymarching hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the render path over one batch of synthetic input: the next
 `--frames-per-launch` (default 48) frames of the workload's ORBIT -- one camera pose and one
 destination per frame, packed by the host camera model exactly as the reference does per frame
 (render.rs:320-345) -- rendered by one kifs_render_batch_async launch.  The default workload is
 BASELINE.json's metric configuration: 1920x1080 quaternion-Julia, 256 march steps, 12 SDF
-iterations.  Rank 0 prints ONE JSON line; besides the headline it carries, measured in the same
-process after the timed region, `secondary.lone_frame` (one frame per launch: the latency path),
+iterations.  Rank 0 prints ONE JSON line.  A plain run does what the headline needs and no more: it
+sets up, settles, warms up, times the K steps and prints the line.  `--dump-outputs DIR` also writes
+the frames of the last timed step into DIR (dump_outputs()).  With `--full` the line also carries
+`cpu_baseline`, `roofline.secondary` and, measured in the same process after the timed region,
+`secondary.lone_frame` (one frame per launch: the latency path),
 `secondary.orbit_x8` (8 frames per launch), `secondary.fixed_camera` (the same view in all 8 slots
 of a batch: round 1's headline, the most favourable case for the tile-order feedback) and, for the headline
 workload, the north star's other sizes: `secondary.cfg4_julia_4096` (4096 x 4096, 512 / 16; batched and lone) and
@@ -28,7 +31,7 @@ scaling by default: a step has N x frames-per-launch frames, so every GPU keeps 
 frames-per-launch frames' worth of pixels per step (`--scaling strong` fixes the step at
 frames-per-launch frames instead).  `--shard bands` uses contiguous runs of stripes,
 `--shard frames` whole frames per rank (no exchange unless `--deliver root`); the latter is also
-measured after the timed region and reported as `secondary.frame_parallel`.
+measured after the timed region and reported as `secondary.frame_parallel` (--full).
 
 `--host one-process` (N > 1): the form the reference's own host would use -- ONE process and one thread drive all N
 devices through the C ABI's kifs_multi_render_batch_async (sparse records gathered by RCCL grouped send/recv inside
@@ -37,7 +40,7 @@ orbit (120 frames for cfg5) in launches of --frames-per-launch frames, every fra
 
 There are no HBM-resident inputs beyond the 156 uniform bytes; the output frames live in HBM
 (torch tensors) and are written by the kernel.  `roofline` prices the dominant kernel against
-the HBM-write roofline the north star mandates (4 algorithmic bytes per pixel); `cpu_baseline`
+the HBM-write roofline the north star mandates (4 algorithmic bytes per pixel); `cpu_baseline` (--full)
 times the CPU oracle (the stand-in for the reference's wgpu path, which cannot run here) on the
 host cores -- a reported baseline, not the target.
 """
@@ -66,7 +69,7 @@ def parse():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default=None, help="name in kifs_raymarching_amd.configs.WORKLOADS")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="wall-clock budget of the cpu_baseline sample (0 disables it)")
+                    help="--full: wall-clock budget of the cpu_baseline sample (0 disables it)")
     ap.add_argument("--encode", type=int, default=1, help="1 = sRGB target (reference default), 0 = UNORM")
     ap.add_argument("--camera", default="orbit", choices=["orbit", "fixed"],
                     help="orbit (default): a distinct pose per frame, phi = 2*pi*frame/120 (host camera model + "
@@ -108,20 +111,27 @@ def parse():
     ap.add_argument("--transport", default="auto", choices=["auto", "rccl", "copy"],
                     help="--host one-process: the library's transport (auto = RCCL on distinct devices, peer copies otherwise)")
     ap.add_argument("--one-process-secondary", default="auto", choices=["auto", "off"],
-                    help="N > 1, per-GPU host, row shards: once every collective of this job is done, rank 0 also runs the "
+                    help="--full, N > 1, per-GPU host, row shards: once every collective of this job is done, rank 0 also runs the "
                          "ONE-process form (kifs_multi_render_batch_async: RCCL inside the library) in a child process with "
                          "a time limit and reports it as secondary.one_process_c_abi; 'off' skips it")
     ap.add_argument("--whole-orbit", action="store_true",
                     help="N = 1: a step is the workload's WHOLE orbit (max(frames, 120) poses, every frame resident in HBM) "
                          "in launches of --frames-per-launch frames")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the secondary measurements, the CPU baseline and "
+                         "its work count, and (N > 1) the one-process form in a child process.  Off (default): set up, "
+                         "warm up, time the steps, print the line")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames of the last timed step to DIR as float32 .npy files "
+                         "(all of them, or a fixed sample of their pixels when they exceed 64 MB: dump_outputs())")
     ap.add_argument("--calibration-note", default=None, help=argparse.SUPPRESS)  # set by self_launch()'s second attempt
     ap.add_argument("--dist-at-one", action="store_true",
                     help="--gpus 1 only: run the N > 1 code path with a world of one rank -- process group (backend as given), "
                          "its barrier / all_reduce / all_gather, the CPU side group, the sharded pipeline with no peers -- the "
                          "half of a multi-GPU run that a one-GPU box can prove (tests/test_gpu_bench.py)")
     ap.add_argument("--cfg5-secondary", default="auto", choices=["auto", "off"],
-                    help="headline workload at N = 1: 'auto' also times BASELINE config 5 as it is named -- the whole 120-frame "
+                    help="--full, headline workload at N = 1: 'auto' also times BASELINE config 5 as it is named -- the whole 120-frame "
                          "7680x4320 Sierpinski orbit, every frame resident (15.9 GB) -- in a child process under a time limit "
                          "(secondary.cfg5_whole_orbit); 'off' skips it")
     return ap.parse_args()
@@ -511,6 +521,34 @@ def child_line(flags, limit_s, pick):
         return {"error": repr(e)[:300]}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: every file together
+DUMP_SAMPLE_PIXELS = 1 << 20
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the frames the timed path delivered in its last step -- `frames`, (n, H, W, 4) uint8 RGBA, on the
+    device or the host -- as float32 .npy files in `out_dir`, at most DUMP_BUDGET_BYTES in all.  `frames.npy`
+    (n, H, W, 4) when every pixel fits; otherwise a fixed sample of pixels (seed DUMP_SEED: the same pixels for every
+    run and build with the same arguments): `frames_sample.npy` (m, 4), their RGBA, and `frames_sample_at.npy` (m, 3),
+    their (frame of the step, row, column).  Returns the names of the files written."""
+    import numpy as np
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    n, H, W, C = frames.shape
+    if frames.numel() * 4 <= DUMP_BUDGET_BYTES:
+        np.save(out / "frames.npy", frames.float().cpu().numpy())
+        return ["frames.npy"]
+    rng = np.random.default_rng(DUMP_SEED)
+    pix = np.unique(rng.integers(0, n * H * W, size=DUMP_SAMPLE_PIXELS, dtype=np.int64))
+    flat = frames.reshape(n * H * W, C)
+    np.save(out / "frames_sample.npy", flat[torch.from_numpy(pix).to(flat.device)].float().cpu().numpy())
+    np.save(out / "frames_sample_at.npy", np.stack([pix // (H * W), pix // W % H, pix % W], axis=1).astype(np.float32))
+    return ["frames_sample.npy", "frames_sample_at.npy"]
+
+
 def one_process(args):
     """--host one-process: this process alone drives all N devices through kifs_multi_render_batch_async -- what the
     reference's single-process host (application.rs:37-48) would call.  Same protocol and JSON shape as the
@@ -589,6 +627,9 @@ def one_process(args):
     elapsed = time.perf_counter() - t0
     stats = mg.stats()
     shards = mg.shards()
+    if args.dump_outputs:
+        stage("dump outputs")
+        dump_outputs(args.dump_outputs, frames[(base + args.steps - 1) % 2])
     check = None
     if not args.no_check:
         stage("one-process: check")
@@ -1083,7 +1124,19 @@ def main():
                             for r, f in enumerate(delivered) for i in range(B))
             gs.set_camera(w.camera)
 
-    # ---- secondary measurements, same process, after the timed region
+    if args.dump_outputs and rank == 0:
+        stage("dump outputs")
+        last = settle_steps + args.warmup + args.steps - 1
+        if sharded:
+            got = pipe.frames(last)
+        elif args.whole_orbit and world == 1:
+            got = pipe.frames
+        else:  # the frames of the step that reached rank 0, in sequence order
+            got = pipe.frames(last)
+            got = got[0] if len(got) == 1 else torch.cat(got)
+        dump_outputs(args.dump_outputs, got.view(-1, H, W, 4))
+
+    # ---- secondary measurements, same process, after the timed region (--full)
     secondary = {}
     alg_frame = 4.0 * W * H  # 4 B written per pixel, 0 read
 
@@ -1094,7 +1147,7 @@ def main():
                 "mpix_s": round(frames * W * H / (ms * 1e-3) / 1e6, 2), "kernel_ms": round(k_ms, 5),
                 "hbm_frac": round(frames * alg_frame / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6), "note": note}
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec_steps = max(20, min(args.steps, 200))
         sec_warm = max(6, min(args.warmup, 20))
         if not dist_on:
@@ -1223,7 +1276,7 @@ def main():
     rows_per_rank = list(pipe.rows) if sharded else None
     tiles_sent_fraction = (round(pipe.records_sent / pipe.tiles_seen, 4)
                            if sharded and args.gather == "sparse" and getattr(pipe, "tiles_seen", 0) else None)
-    if world > 1 and sharded and args.one_process_secondary == "auto" and not args.no_secondary:
+    if world > 1 and sharded and args.one_process_secondary == "auto" and args.full and not args.no_secondary:
         if rank != 0:
             for g in gss:
                 g.close()
@@ -1344,7 +1397,7 @@ def main():
             out["secondary"] = secondary
         if check is not None:
             out["gathered_frame_equals_single_gpu_frame"] = check
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             stage("cpu baseline", deadline_s=args.cpu_seconds + 170.0)
             out["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
             out["roofline"]["secondary"] = work_count(w, launch_s / frames_per_launch)

@@ -1,7 +1,7 @@
-"""bench.py's contract with the driver, on the GPU box: the one JSON line of a default-shaped run
-carries metric / value / roofline / cpu_baseline / the secondary measurements, and `--gpus 2` without a
-launcher starts its own ranks and gathers frames equal to single-GPU frames (ranks share the one GPU
-and talk over gloo: RCCL needs a GPU per rank)."""
+"""bench.py's contract, on a machine with a GPU: the one JSON line of a plain run carries the headline alone,
+and --dump-outputs writes the same frames run after run; with --full the line also carries cpu_baseline and the
+secondary measurements; `--gpus 2` without a launcher starts its own ranks and gathers frames equal to single-GPU
+frames (ranks share the one GPU and talk over gloo: RCCL needs a GPU per rank)."""
 import json
 import os
 import subprocess
@@ -25,7 +25,7 @@ def _run(*args, timeout=600):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run("--steps", "12", "--warmup", "4", "--cpu-seconds", "1")
+    d = _run("--steps", "12", "--warmup", "4", "--cpu-seconds", "1", "--full")
     assert d["metric"].startswith("Mpixels/s at 1920x1080") and d["unit"] == "Mpixels/s"
     assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 4 and d["higher_is_better"] is True
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
@@ -86,9 +86,53 @@ def test_single_gpu_line_has_the_contract_fields():
     assert d["per_rank_kernel_ms"] == [pytest.approx(r["kernel_ms"], rel=1e-3)]
 
 
+def test_a_plain_run_times_the_headline_alone_and_dumps_the_same_frames_every_time(tmp_path):
+    """Without --full: settle, warm-up, exactly --steps timed steps and the line -- no secondary measurement, no CPU
+    baseline.  --dump-outputs: a fixed sample of the last timed step's 48 frames, float32, within 64 MB; a second run
+    with the same arguments writes the same values, and they are the pixels of single-frame renders of the same poses."""
+    import numpy as np
+
+    runs = []
+    for i in range(2):
+        p = _run_raw("--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / f"run{i}"))
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "Mpixels/s"
+        assert d["metric"].startswith("Mpixels/s at 1920x1080") and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 48 * 1920 * 1080 / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+        assert "secondary" not in d and "cpu_baseline" not in d and "secondary" not in d["roofline"]
+        assert "bench.py[rank 0] stage: timed (7 steps)" in p.stderr
+        assert "stage: secondary" not in p.stderr and "stage: cpu baseline" not in p.stderr
+        files = sorted(f.name for f in (tmp_path / f"run{i}").iterdir())
+        assert files == ["frames_sample.npy", "frames_sample_at.npy"]
+        assert sum(f.stat().st_size for f in (tmp_path / f"run{i}").iterdir()) <= 64 << 20
+        runs.append((d, np.load(tmp_path / f"run{i}" / "frames_sample.npy"),
+                     np.load(tmp_path / f"run{i}" / "frames_sample_at.npy")))
+    (d, rgba, at), (d1, rgba1, at1) = runs
+    assert rgba.dtype == np.float32 and rgba.shape[1] == 4 and at.shape == (rgba.shape[0], 3) and rgba.shape[0] > 900_000
+    assert d1["settle_steps"] == d["settle_steps"] and np.array_equal(at, at1) and np.array_equal(rgba, rgba1)
+    assert at[:, 0].max() == 47 and at[:, 1].max() < 1080 and at[:, 2].max() < 1920
+    assert (rgba != rgba[0]).any(-1).sum() > 1000  # fractal pixels, not background alone
+
+    import kifs_raymarching_amd as K
+    from kifs_raymarching_amd.configs import WORKLOADS, orbit_camera
+    w = WORKLOADS["cfg2_julia_1080p"]
+    last = d["settle_steps"] + 2 + 7 - 1
+    for j in (0, 47):
+        with K.GraphicState(0, screen_data=w.screen, camera_data=orbit_camera(w, (last * 48 + j) % 120),
+                           gui_data=w.gui) as g:
+            g.set_iters(*w.iters)
+            frame = g.render()
+        mine = at[:, 0] == j
+        ys, xs = at[mine, 1].astype(np.int64), at[mine, 2].astype(np.int64)
+        assert np.array_equal(rgba[mine], frame[ys, xs].astype(np.float32)), j
+
+
 def test_two_ranks_are_started_by_bench_itself_and_gather_exact_frames():
     d = _run("--gpus", "2", "--backend", "gloo", "--share-device", "--check", "--steps", "4", "--warmup", "2",
-             "--cpu-seconds", "0", "--frames-per-launch", "4")
+             "--cpu-seconds", "0", "--frames-per-launch", "4", "--full")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["gathered_frame_equals_single_gpu_frame"] is True
     cfg = d["config"]
@@ -165,7 +209,7 @@ def test_the_rccl_backend_with_a_world_of_one_rank():
     barrier(device_ids=...), all_reduce / all_gather on the device, the gloo side group for the message sizes, the
     sharded pipeline (no peers), the default frame check, frame_parallel and the 4096 x 4096 figure through the
     sharded pipeline, destroy_process_group -- so that hardware day only adds the second rank."""
-    p = _run_raw("--dist-at-one", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0", "--frames-per-launch", "4")
+    p = _run_raw("--dist-at-one", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0", "--frames-per-launch", "4", "--full")
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     comm = d["comm"]

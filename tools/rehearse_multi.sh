@@ -6,7 +6,7 @@
 set -e
 run() { python3 bench.py --gpus $1 --backend gloo --share-device --check --steps 6 --warmup 3 --cpu-seconds 0 "${@:2}" \
         | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['config']['parallelism'], '| scaling', d['scaling'], '| frames/step', d['config']['frames_per_step'], '| check', d.get('gathered_frame_equals_single_gpu_frame'), '| Mpix/s', d['value'], '| per-rank kernel ms', d['per_rank_kernel_ms'], '| gather', d['config'].get('gather'), d['config'].get('tiles_sent_fraction'), '| root : peer weight', d['config'].get('root_weight'), ':', d['config'].get('peer_weight'), d['config'].get('root_weight_calibration'), '| secondary', sorted(d.get('secondary', {})))"; }
-run 2 --frames-per-launch 8             # the default shape: stripes, weak scaling, rank 0's share calibrated
+run 2 --frames-per-launch 8 --full      # the default shape: stripes, weak scaling, rank 0's share calibrated
 run 3 --frames-per-launch 2 --no-secondary --root-weight 1
 run 4 --scaling strong --frames-per-launch 8 --no-secondary   # 8 frames per step, a quarter of each per rank
 run 2 --root-weight 3 --frames-per-launch 8 --no-secondary
