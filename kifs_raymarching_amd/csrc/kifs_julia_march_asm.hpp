@@ -1,6 +1,7 @@
 // The asm statement of julia_fast_march (kifs_scene.hpp), included once per variant with
 // KIFS_JULIA_DIVSQRT / KIFS_JULIA_DIVSQRT_OUT_OF_LINE, KIFS_FAST_TRIP / KIFS_TRIP_EXIT / KIFS_TRIP_EXIT_BACK / KIFS_JULIA_PROLOGUE /
-// KIFS_JULIA_C_OPERANDS / KIFS_ORBIT_LOOP / KIFS_ORBIT_LOOP_OUT_OF_LINE defined by the includer.  See the
+// KIFS_JULIA_C_OPERANDS / KIFS_ORBIT_LOOP / KIFS_ORBIT_LOOP_OUT_OF_LINE / KIFS_ORBIT_REMAINDER / KIFS_JULIA_LOG_BIAS /
+// KIFS_JULIA_ORBIT_OUT (operands) defined by the includer.  See the
 // register map and the description there.
     asm volatile(
         "s_mov_b64 s[84:85], exec\n"
@@ -40,8 +41,8 @@
         "v_and_or_b32 v56, v44, s92, 0.5\n"                   // mantissa in [0.5, 1)
         "v_lshrrev_b32_e32 v58, 23, v44\n"                    // biased exponent
         "v_cmp_gt_f32_e32 vcc, 0x3f3504f3, v56\n"             // m < sqrt(1/2)
-        "v_add_u32_e32 v58, 0xffffff82, v58\n"                // e = biased - 126
-        "v_mul_f32_e32 v53, v43, v47\n"                       // dqs = dq * (4|q_last|^2)
+        "v_add_u32_e32 v58, " KIFS_JULIA_LOG_BIAS ", v58\n"  // e = biased exponent of |q|^2 - 126
+        "v_mul_f32_e32 " KIFS_JULIA_ORBIT_OUT "\n"           // v53 = dqs, v44 = |q|^2
         "v_cndmask_b32_e32 v55, 0, v56, vcc\n"                // m or +0.0
         "v_subbrev_co_u32_e32 v58, vcc, 0, v58, vcc\n"        // e -= 1 where m < sqrt(1/2)
         "v_add_f32_e32 v56, v55, v56\n"                       // m + m  or  m
@@ -90,14 +91,7 @@
         "s_branch 20f\n"
         KIFS_ORBIT_LOOP_OUT_OF_LINE
         // ---- remainder trips (sdf_iters % 6), out of the hot line
-        "30:\n"
-        "s_mov_b32 s97, %[rem]\n"
-        "31:\n"
-        KIFS_FAST_TRIP KIFS_TRIP_EXIT_BACK
-        "s_sub_u32 s97, s97, 1\n"
-        "s_cmp_lg_u32 s97, 0\n"
-        "s_cbranch_scc1 31b\n"
-        "s_branch 12b\n"
+        KIFS_ORBIT_REMAINDER
         // ---- sqrt(n2) - 2 for the outside lanes (n2 = v52 is still intact: the orbit lanes
         //      only overwrite it inside their own sqrt, under their own exec)
         "45:\n"

@@ -776,6 +776,8 @@ static unsigned residency_pad_bytes(int workgroups_per_cu) {
 // primitive_id per SDF call (kifs.wgsl:139-155).  Here both are template parameters.
 template <int GROUP, int PRIM>
 static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
+    // (Julia: bit 1 of the PRIM slot, the doubled orbit trip, only changes the throughput kernel)
+    constexpr int LPRIM = GROUP == GROUP_JULIA ? (PRIM & 1) : PRIM;
     const FrameParams& P = B.frame;
     const unsigned pad = residency_pad_bytes(P.workgroups_per_cu);
     if (pad > 48 * 1024) {
@@ -787,7 +789,7 @@ static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
         if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-            hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>),
+            hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<GROUP, LPRIM>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
             if (attr != hipSuccess) return attr;
             if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
@@ -800,15 +802,15 @@ static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
     }
     if (P.round_steps > 0) {  // the throughput path: rays re-queued, one or two tiles per workgroup
         if (P.group_tiles >= 2) {
-            hipLaunchKernelGGL((render_group_kernel<GROUP, PRIM, 2>), dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)),
+            hipLaunchKernelGGL((render_group_kernel<GROUP, LPRIM, 2>), dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)),
                                dim3(BLOCK), 0, stream, B);
         } else {
-            hipLaunchKernelGGL((render_group_kernel<GROUP, PRIM, 1>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), 0,
+            hipLaunchKernelGGL((render_group_kernel<GROUP, LPRIM, 1>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), 0,
                                stream, B);
         }
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), pad, stream, B);
+    hipLaunchKernelGGL((render_kernel<GROUP, LPRIM>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), pad, stream, B);
     return hipGetLastError();
 }
 
@@ -839,7 +841,10 @@ hipError_t launch_render(const BatchParams& B, uint32_t group, uint32_t primitiv
     if (P.y1 <= P.y0 || P.width <= 0 || P.tile_count == 0) return hipSuccess;
     if (B.count < 1 || B.count > MAX_BATCH) return hipErrorInvalidValue;
     switch (group) {
-    case GROUP_JULIA:  // two builds of the long-ray loop, see KIFS_DIVSQRT_ORDINARY in kifs_scene.hpp
+    case GROUP_JULIA:  // builds of the long-ray loop, see KIFS_DIVSQRT_ORDINARY and KIFS_FAST_TRIP_X2_ in kifs_scene.hpp
+        if (P.orbit_x2)
+            return P.sdf_iters <= 24 ? launch_variant<GROUP_JULIA, 3>(B, stream)
+                                     : launch_variant<GROUP_JULIA, 2>(B, stream);
         return P.sdf_iters <= 24 ? launch_variant<GROUP_JULIA, 1>(B, stream)
                                  : launch_variant<GROUP_JULIA, 0>(B, stream);
     case GROUP_GENJULIA: return launch_variant<GROUP_GENJULIA, 0>(B, stream);

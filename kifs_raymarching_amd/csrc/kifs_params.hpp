@@ -81,6 +81,13 @@ struct FrameParams {
     // Host-side launch hint, not read by the kernels: how many workgroups may share a CU
     // (0 = no cap).  See residency_for() in kifs_api.cpp.
     int workgroups_per_cu;
+    // (at the end: the fields above keep their offsets in the kernel argument)
+    // The throughput kernels' orbit trip in doubled coordinates (KIFS_FAST_TRIP_X2_ in kifs_scene.hpp): its constants
+    // 2c and 4 max_distance (exact), and whether the scene meets the conditions under which it equals the contract's
+    // trip bit for bit (orbit_x2_eligible() in kifs_schedule.cpp).  0: the plain trip.
+    V4 c2;
+    float max_distance4;
+    int orbit_x2;
 };
 
 // A launch renders a batch of up to MAX_BATCH frames that share screen, options and tile

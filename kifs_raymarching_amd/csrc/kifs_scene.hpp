@@ -591,6 +591,44 @@ KIFS_DEV float soft_shadow(const FrameParams& P, V3 p, V3 n, bool lanes_hit, Sdf
     "v_fma_f32 v44, v32, v32, v48\n"                                                         \
     "v_fma_f32 v45, v32, v32, -v48\n"                                                        \
     "v_add_f32_e32 v45, %[cx], v45\n"
+// SCALAR, DOUBLED: the scalar trip with the orbit carried as Q = 2q (X = 2x, Y = 2y, Z = 2z, W = 2w): 11 plain f32
+// operations + v_cmpx instead of 13 -- the `2x` of ijk' and the `4|q|^2` of dq come for free.  Every result is the
+// contract's value times an exact power of two ("exactness-preserving rewrites", for the proof and
+// its condition, FrameParams::orbit_x2, checked on the host):
+//   Y' = fma(X, Y, 2c.y) = 2 y'   S = Y*Y + Z*Z = 4 s   D = fma(W, W, S) = 4 d   N4 = fma(X, X, D) = 4 |q|^2
+//   R = fma(X, X, -D) = 4 fma(x, x, -d)   X' = fma(R, 0.5, 2c.x) = 2 x' (R * 0.5 is exact inside the fma)
+// dq is NOT scaled: DQ = fma(N4, DQ, 0) is the contract's dq *= 4|q|^2 on the same operands, applied at the start of
+// the next trip, so after the last trip DQ is already dqs.  Registers: v40 Y  v41 z  v52 W  v53 DQ  v44 N4
+// v45 / v46 X (X_k and X_{k+1} alternate: trip A reads X_k from v46 and writes X_{k+2} there, trip B the other way
+// round, so a block of six trips ends where it began)  v48-v50 scratch.
+#define KIFS_FAST_TRIP_X2_(xk, xk1)                                                         \
+    "v_fma_f32 v40, " xk ", v40, %[cy]\n"     /* Y' = fma(X, Y, 2c.y) */                      \
+    "v_fma_f32 v41, " xk ", v41, %[cz]\n"                                                     \
+    "v_fma_f32 v52, " xk ", v52, %[cw]\n"                                                     \
+    "v_fma_f32 v53, v44, v53, 0\n"            /* dq = fma(4|q_prev|^2, dq, 0) */              \
+    "v_mul_f32_e32 v48, v40, v40\n"                                                           \
+    "v_mul_f32_e32 v49, v41, v41\n"                                                           \
+    "v_add_f32_e32 v50, v48, v49\n"           /* S = Y*Y + Z*Z */                             \
+    "v_fma_f32 v48, v52, v52, v50\n"          /* D = fma(W, W, S) */                          \
+    "v_fma_f32 v44, " xk1 ", " xk1 ", v48\n"  /* N4 = fma(X, X, D) */                         \
+    "v_fma_f32 v49, " xk1 ", " xk1 ", -v48\n" /* R = fma(X, X, -D) */                         \
+    "v_fma_f32 " xk ", v49, 0.5, %[cx]\n"     /* X after next = fma(R, 0.5, 2c.x) */          \
+    "v_cmpx_nlt_f32 vcc, %[maxd4], v44\n"     /* !(4|q|^2 > 4 max_distance) */
+#define KIFS_FAST_TRIP_X2_A KIFS_FAST_TRIP_X2_("v46", "v45")
+#define KIFS_FAST_TRIP_X2_B KIFS_FAST_TRIP_X2_("v45", "v46")
+// The squares of Q_0 = 2 q_0 (w_0 = 0.1: v38 holds 0.2).  No test on the start point is needed: a y_0^2 or z_0^2 that
+// rounds differently at 4x scale is below 2^-124, and d_0 = fma(w_0, w_0, s_0) >= 0.01 absorbs it.
+#define KIFS_JULIA_PROLOGUE_X2                                                              \
+    "v_add_f32_e32 v46, v32, v32\n"                       /* X_0 = 2 x_0 */                  \
+    "v_pk_add_f32 v[40:41], v[30:31], v[30:31]\n"         /* [Y_0, Z_0] */                   \
+    "v_mov_b64 v[52:53], v[38:39]\n"                      /* [W_0, DQ] = [0.2, 1] */         \
+    "v_mul_f32_e32 v48, v40, v40\n"                                                          \
+    "v_mul_f32_e32 v49, v41, v41\n"                                                          \
+    "v_add_f32_e32 v50, v48, v49\n"                                                          \
+    "v_fma_f32 v48, v52, v52, v50\n"                                                         \
+    "v_fma_f32 v44, v46, v46, v48\n"                                                         \
+    "v_fma_f32 v49, v46, v46, -v48\n"                                                        \
+    "v_fma_f32 v45, v49, 0.5, %[cx]\n"                    /* X_1 */
 
 // The loop over blocks of six trips (s96 = blocks left; label 12 in, label 14 out), two forms:
 //  * SINGLE: one block per pass -- the throughput kernel's (its SIMDs hold several busy waves: a taken branch is
@@ -611,7 +649,48 @@ KIFS_DEV float soft_shadow(const FrameParams& P, V3 p, V3 n, bool lanes_hit, Sdf
     "s_sub_u32 s96, s96, 1\n"                                                               \
     "s_cmp_lg_u32 s96, 0\n"                                                                 \
     "s_cbranch_scc1 13b\n"
-#define KIFS_ORBIT_LOOP_PAIRED                                                              \
+// SINGLE for the doubled trip: the six trips of a pass alternate A, B (see KIFS_FAST_TRIP_X2_)
+#define KIFS_ORBIT_LOOP_SINGLE_X2                                                           \
+    "12:\n"                                                                                 \
+    "s_cmp_eq_u32 s96, 0\n"                                                                 \
+    "s_cbranch_scc1 14f\n"                                                                  \
+    "13:\n"                                                                                 \
+    KIFS_FAST_TRIP_X2_A KIFS_TRIP_EXIT KIFS_FAST_TRIP_X2_B KIFS_TRIP_EXIT                   \
+    KIFS_FAST_TRIP_X2_A "s_cbranch_execz 14f\n"                                             \
+    KIFS_FAST_TRIP_X2_B KIFS_TRIP_EXIT KIFS_FAST_TRIP_X2_A KIFS_TRIP_EXIT                   \
+    KIFS_FAST_TRIP_X2_B "s_cbranch_execz 14f\n"                                             \
+    "s_sub_u32 s96, s96, 1\n"                                                               \
+    "s_cmp_lg_u32 s96, 0\n"                                                                 \
+    "s_cbranch_scc1 13b\n"
+// The remainder trips (sdf_iters % 6) of the doubled trip, out of line: in pairs A, B; an odd last one is an A trip
+// followed by a swap of v45 / v46, so that the blocks start from the A state again.
+#define KIFS_ORBIT_REMAINDER_X2                                                             \
+    "30:\n"                                                                                 \
+    "s_mov_b32 s97, %[rem]\n"                                                               \
+    "s_cmp_lt_u32 s97, 2\n"                                                                 \
+    "s_cbranch_scc1 32f\n"                                                                  \
+    "31:\n"                                                                                 \
+    KIFS_FAST_TRIP_X2_A KIFS_TRIP_EXIT_BACK KIFS_FAST_TRIP_X2_B KIFS_TRIP_EXIT_BACK         \
+    "s_sub_u32 s97, s97, 2\n"                                                               \
+    "s_cmp_gt_u32 s97, 1\n"                                                                 \
+    "s_cbranch_scc1 31b\n"                                                                  \
+    "32:\n"                                                                                 \
+    "s_cmp_eq_u32 s97, 0\n"                                                                 \
+    "s_cbranch_scc1 12b\n"                                                                  \
+    KIFS_FAST_TRIP_X2_A KIFS_TRIP_EXIT_BACK                                                 \
+    "v_swap_b32 v45, v46\n"                                                                 \
+    "s_branch 12b\n"
+// the remainder trips of the other forms: one trip at a time
+#define KIFS_ORBIT_REMAINDER_ONE                                                             \
+    "30:\n"                                                                                 \
+    "s_mov_b32 s97, %[rem]\n"                                                               \
+    "31:\n"                                                                                 \
+    KIFS_FAST_TRIP KIFS_TRIP_EXIT_BACK                                                      \
+    "s_sub_u32 s97, s97, 1\n"                                                               \
+    "s_cmp_lg_u32 s97, 0\n"                                                                 \
+    "s_cbranch_scc1 31b\n"                                                                  \
+    "s_branch 12b\n"
+#define KIFS_ORBIT_LOOP_PAIRED                                                            \
     "12:\n"                                                                                 \
     "s_cmp_lt_u32 s96, 2\n"                                                                 \
     "s_cbranch_scc1 16f\n"                                                                  \
@@ -709,23 +788,61 @@ KIFS_DEV float soft_shadow(const FrameParams& P, V3 p, V3 n, bool lanes_hit, Sdf
     "47:\n"
 
 // SHORT_DIVSQRT: the launcher's choice for frames with few SDF iterations (KIFS_DIVSQRT_ORDINARY);
-// THROUGHPUT: the scalar form of the orbit trip (launches whose SIMDs hold several busy waves).
-template <bool SHORT_DIVSQRT, bool THROUGHPUT>
+// THROUGHPUT: the scalar form of the orbit trip (launches whose SIMDs hold several busy waves);
+// X2 (with THROUGHPUT): that trip in doubled coordinates, for scenes with FrameParams::orbit_x2 (a separate kernel: two
+// of these asm statements in one kernel are more than the register allocator can take).
+template <bool SHORT_DIVSQRT, bool THROUGHPUT, bool X2>
 KIFS_DEV void julia_fast_march(const FrameParams& P, V3 dir, float& t, V3& p, bool& hit,
                                bool& marching, int& trips, int& outside_steps, int limit) {
+    static_assert(THROUGHPUT || !X2, "the doubled trip is a form of the scalar one");
     F2 pyz{p.y, p.z}, px1{p.x, 1.0f}, tdx{t, dir.x};
-    const F2 dyz{dir.y, dir.z}, w0{0.1f, 1.0f};
+    const F2 dyz{dir.y, dir.z};
     const F2 oyz{P.origin.y, P.origin.z};
     const float c1 = -1.1514610310E-1f;  // second log coefficient, needed in a VGPR
     const unsigned long long lanes = __builtin_amdgcn_ballot_w64(marching);
     unsigned long long hit_mask = 0, live_out;
     if constexpr (THROUGHPUT) {
-#define KIFS_FAST_TRIP KIFS_FAST_TRIP_SCALAR
 #define KIFS_TRIP_EXIT "s_cbranch_execz 14f\n"  /* scalar slots are free where the vector pipe is the limit: test every trip */
 #define KIFS_TRIP_EXIT_BACK "s_cbranch_execz 14b\n"  /* the same from the remainder trips, which sit BEHIND label 14 */
+#define KIFS_ORBIT_LOOP_OUT_OF_LINE
+        if constexpr (X2) {  // the doubled trip
+            const F2 w0{2.0f * 0.1f, 1.0f};
+#define KIFS_FAST_TRIP KIFS_FAST_TRIP_X2_A
+#define KIFS_JULIA_PROLOGUE KIFS_JULIA_PROLOGUE_X2
+#define KIFS_ORBIT_LOOP KIFS_ORBIT_LOOP_SINGLE_X2
+#define KIFS_ORBIT_REMAINDER KIFS_ORBIT_REMAINDER_X2
+#define KIFS_JULIA_LOG_BIAS "0xffffff80"  /* v44 = 4|q|^2: biased - 128 */
+#define KIFS_JULIA_ORBIT_OUT "v44, 0x3e800000, v44"  /* |q|^2 = 0.25 (4|q|^2), exact; DQ (v53) is dqs */
+#define KIFS_JULIA_C_OPERANDS [cy] "s"(P.c2.y), [cz] "s"(P.c2.z), [cw] "s"(P.c2.w), [cx] "s"(P.c2.x), \
+                              [maxd4] "s"(P.max_distance4)
+        if constexpr (SHORT_DIVSQRT) {
+#define KIFS_JULIA_DIVSQRT KIFS_DIVSQRT_ORDINARY
+#define KIFS_JULIA_DIVSQRT_OUT_OF_LINE "46:\n" KIFS_DIVSQRT_FULL "s_branch 47b\n"
+#include "kifs_julia_march_asm.hpp"
+#undef KIFS_JULIA_DIVSQRT
+#undef KIFS_JULIA_DIVSQRT_OUT_OF_LINE
+        } else {
+#define KIFS_JULIA_DIVSQRT KIFS_DIVSQRT_FULL
+#define KIFS_JULIA_DIVSQRT_OUT_OF_LINE
+#include "kifs_julia_march_asm.hpp"
+#undef KIFS_JULIA_DIVSQRT
+#undef KIFS_JULIA_DIVSQRT_OUT_OF_LINE
+        }
+#undef KIFS_FAST_TRIP
+#undef KIFS_JULIA_PROLOGUE
+#undef KIFS_ORBIT_LOOP
+#undef KIFS_ORBIT_REMAINDER
+#undef KIFS_JULIA_LOG_BIAS
+#undef KIFS_JULIA_ORBIT_OUT
+#undef KIFS_JULIA_C_OPERANDS
+        } else {
+            const F2 w0{0.1f, 1.0f};
+#define KIFS_FAST_TRIP KIFS_FAST_TRIP_SCALAR
 #define KIFS_JULIA_PROLOGUE KIFS_JULIA_PROLOGUE_SCALAR
 #define KIFS_ORBIT_LOOP KIFS_ORBIT_LOOP_SINGLE
-#define KIFS_ORBIT_LOOP_OUT_OF_LINE
+#define KIFS_ORBIT_REMAINDER KIFS_ORBIT_REMAINDER_ONE
+#define KIFS_JULIA_LOG_BIAS "0xffffff82"
+#define KIFS_JULIA_ORBIT_OUT "v53, v43, v47"  /* dqs = dq * (4|q_last|^2) */
 #define KIFS_JULIA_C_OPERANDS [cy] "s"(P.c.y), [cz] "s"(P.c.z), [cw] "s"(P.c.w), [cx] "s"(P.c.x)
         if constexpr (SHORT_DIVSQRT) {
 #define KIFS_JULIA_DIVSQRT KIFS_DIVSQRT_ORDINARY
@@ -741,13 +858,18 @@ KIFS_DEV void julia_fast_march(const FrameParams& P, V3 dir, float& t, V3& p, bo
 #undef KIFS_JULIA_DIVSQRT_OUT_OF_LINE
         }
 #undef KIFS_FAST_TRIP
-#undef KIFS_TRIP_EXIT
-#undef KIFS_TRIP_EXIT_BACK
 #undef KIFS_JULIA_PROLOGUE
 #undef KIFS_ORBIT_LOOP
-#undef KIFS_ORBIT_LOOP_OUT_OF_LINE
+#undef KIFS_ORBIT_REMAINDER
+#undef KIFS_JULIA_LOG_BIAS
+#undef KIFS_JULIA_ORBIT_OUT
 #undef KIFS_JULIA_C_OPERANDS
+        }
+#undef KIFS_TRIP_EXIT
+#undef KIFS_TRIP_EXIT_BACK
+#undef KIFS_ORBIT_LOOP_OUT_OF_LINE
     } else {
+        const F2 w0{0.1f, 1.0f};
         const F2 cyz{P.c.y, P.c.z}, cw0{P.c.w, 0.0f}, c0x{0.0f, P.c.x};
 #define KIFS_FAST_TRIP KIFS_FAST_TRIP_PACKED
 #define KIFS_TRIP_EXIT  /* a lone wave pays for every instruction: test every third trip only */
@@ -755,6 +877,9 @@ KIFS_DEV void julia_fast_march(const FrameParams& P, V3 dir, float& t, V3& p, bo
 #define KIFS_JULIA_PROLOGUE KIFS_JULIA_PROLOGUE_PACKED
 #define KIFS_ORBIT_LOOP KIFS_ORBIT_LOOP_PAIRED
 #define KIFS_ORBIT_LOOP_OUT_OF_LINE KIFS_ORBIT_LOOP_PAIRED_OUT_OF_LINE
+#define KIFS_ORBIT_REMAINDER KIFS_ORBIT_REMAINDER_ONE
+#define KIFS_JULIA_LOG_BIAS "0xffffff82"
+#define KIFS_JULIA_ORBIT_OUT "v53, v43, v47"  /* dqs = dq * (4|q_last|^2) */
 #define KIFS_JULIA_C_OPERANDS [cyz] "s"(cyz), [cw0] "s"(cw0), [c0x] "s"(c0x)
         if constexpr (SHORT_DIVSQRT) {
 #define KIFS_JULIA_DIVSQRT KIFS_DIVSQRT_ORDINARY
@@ -775,6 +900,9 @@ KIFS_DEV void julia_fast_march(const FrameParams& P, V3 dir, float& t, V3& p, bo
 #undef KIFS_JULIA_PROLOGUE
 #undef KIFS_ORBIT_LOOP
 #undef KIFS_ORBIT_LOOP_OUT_OF_LINE
+#undef KIFS_ORBIT_REMAINDER
+#undef KIFS_JULIA_LOG_BIAS
+#undef KIFS_JULIA_ORBIT_OUT
 #undef KIFS_JULIA_C_OPERANDS
     }
     const unsigned lane = __lane_id();
@@ -814,7 +942,7 @@ struct JuliaDiag {  // diagnostics of one wave's march (SGPRs)
 // The march loop proper: steps the wave's marching lanes until none is left or `trips` reaches
 // `limit` (max_iterations for a whole ray, the end of the current round when the workgroup
 // re-queues its rays).  State in, state out; i_final is the heatmap's loop counter.
-template <bool SHORT_DIVSQRT, bool THROUGHPUT>
+template <bool SHORT_DIVSQRT, bool THROUGHPUT, bool X2 = false>
 KIFS_DEV void julia_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& hit, bool& marching,
                          int& trips, int& i_final, int limit, JuliaDiag& diag) {
     const bool fast_ok = (P.is_heatmap == 0u) && (P.sdf_iters >= 1);  // wave-uniform
@@ -835,8 +963,8 @@ KIFS_DEV void julia_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& hi
             // launch 105.5 -> 106.4 Gpixel/s, 4096^2 x16 64.6 -> 65.3, nothing either way at 8 / 1 per launch; of the other
             // marks tried 64 / 16 and 48 / 16 were 0.7 % behind, and level 0 for the first round cost 5 % at 8 per launch)
             march_priority(trips);
-            julia_fast_march<SHORT_DIVSQRT, THROUGHPUT>(P, dir, t, p, hit, marching, trips, outside_steps,
-                                            limit < P.max_iterations ? limit : P.max_iterations);
+            julia_fast_march<SHORT_DIVSQRT, THROUGHPUT, X2>(P, dir, t, p, hit, marching, trips, outside_steps,
+                                                limit < P.max_iterations ? limit : P.max_iterations);
             diag.general_steps += outside_steps;
             diag.fast_ticks += __builtin_amdgcn_s_memtime() - t0;
             ++diag.fast_entries;
@@ -1010,8 +1138,9 @@ KIFS_DEV V3 raymarch_with(const FrameParams& P, V3 dir, bool valid, int& steps, 
 
 template <int GROUP, int PRIM>
 KIFS_DEV V3 raymarch(const FrameParams& P, V3 dir, bool valid, int& steps) {
-    // for the Julia pipeline the PRIM slot carries the long-ray loop's variant (launch_render)
-    if constexpr (GROUP == GROUP_JULIA) return raymarch_julia<PRIM == 1>(P, dir, valid, steps);
+    // for the Julia pipeline the PRIM slot carries the long-ray loop's variant (launch_render): bit 0 the short divide /
+    // square root, bit 1 the doubled orbit trip (throughput kernel only)
+    if constexpr (GROUP == GROUP_JULIA) return raymarch_julia<(PRIM & 1) != 0>(P, dir, valid, steps);
     return raymarch_with(
         P, dir, valid, steps,
         [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); },
@@ -1027,7 +1156,7 @@ KIFS_DEV void march_round(const FrameParams& P, V3 dir, float& t, V3& p, bool& h
     int i_final = 0;  // heatmap frames do not take this path
     if constexpr (GROUP == GROUP_JULIA) {
         JuliaDiag diag;
-        julia_loop<PRIM == 1, THROUGHPUT>(P, dir, t, p, hit, marching, trips, i_final, limit, diag);
+        julia_loop<(PRIM & 1) != 0, THROUGHPUT, (PRIM & 2) != 0>(P, dir, t, p, hit, marching, trips, i_final, limit, diag);
     } else {
         generic_loop<THROUGHPUT>(P, dir, t, p, hit, marching, trips, i_final, limit,
                                  [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });

@@ -123,6 +123,18 @@ float squared_lower_threshold(float T) {
     return v;
 }
 
+// The doubled orbit trip (FrameParams::orbit_x2) equals the contract's trip bit for bit when no unscaled intermediate
+// lands in the denormal range and no scaled one overflows.  Sufficient (DESIGN section 4 has the argument): every
+// |c_i| in [2^-14, 2^10] -- a nonzero fma(2x, y, c.y) or x^2 - d + c.x is then at least 2^-62 -- and max_distance and
+// bound_n2 in (0, 2^60], which keep 4|q|^2 below 2^124 on every trip a lane is still inside.  Nothing depends on the
+// ray: the start point's squares are absorbed by w_0^2 = 0.01.
+static bool orbit_x2_eligible(const kifs::FrameParams& P) {
+    const float lo = 0x1p-14f, hi = 0x1p10f, far = 0x1p60f;
+    for (float ci : {P.c.x, P.c.y, P.c.z, P.c.w})
+        if (!(std::fabs(ci) >= lo && std::fabs(ci) <= hi)) return false;
+    return P.max_distance > 0.0f && P.max_distance <= far && P.bound_n2 > 0.0f && P.bound_n2 <= far;
+}
+
 int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
     int w, h;
     int st = frame_dims(c, &w, &h);
@@ -204,6 +216,9 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
     }
     P->orbit_blocks = c->sdf_iters / 6;
     P->orbit_rem = c->sdf_iters % 6;
+    P->orbit_x2 = orbit_x2_eligible(*P) ? 1 : 0;
+    P->c2 = {2.0f * P->c.x, 2.0f * P->c.y, 2.0f * P->c.z, 2.0f * P->c.w};
+    P->max_distance4 = 4.0f * P->max_distance;
     P->fold_n2_stop = squared_lower_threshold(o.max_distance);
     P->width = w;
     P->y0 = 0;
