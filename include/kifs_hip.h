@@ -144,6 +144,23 @@ typedef struct KifsExtensions {
 } KifsExtensions;
 int kifs_set_extensions(kifs_ctx* ctx, const KifsExtensions* ext);
 
+/* ---- extension: k x k supersampled anti-aliasing ------------------------------------------
+ * NOT part of the reference (one sample per pixel at its centre: MultisampleState { count: 1 },
+ * graphics.rs:107-108).  A per-context factor k, 1 <= k <= KIFS_MAX_SUPERSAMPLING (default 1);
+ * another value gives KIFS_ERR_BAD_ARG.  With k > 1 output pixel (x, y) of the W x H frame takes k^2 samples:
+ *   sample (i, j), 0 <= i, j < k, is fs_main at fragment centre (k x + i + 0.5, k y + j + 0.5) of a VIRTUAL screen
+ *   of width k W, height k H and the same aspect_ratio float (camera, options, iteration counts and extensions the
+ *   context's own; soft shadows apply per sample) -- i.e. pixel (k x + i, k y + j) of that screen;
+ *   resolve, per channel in f32: acc = c(0,0); acc = acc + c(i,j) for the others, j outer, i inner, no fma;
+ *   mean = acc / float(k*k), correctly rounded; then the frame's encoder (sRGB or UNORM; alpha 255).  Heatmap
+ *   frames resolve their heatmap colours the same way.
+ * k W and k H must be at most 65536: otherwise a render returns KIFS_ERR_BAD_SIZE and writes nothing.  The factor
+ * applies to kifs_render, kifs_render_async, kifs_render_batch_async and kifs_render_shard_async; pixel coordinates
+ * stay global, so bands, shards and batch frames are bit-identical to the same rows of the lone frame, and
+ * kifs_multi_set_supersampling gives the kifs_multi_* renders the same frames.  k = 1 is the plain path exactly. */
+#define KIFS_MAX_SUPERSAMPLING 4
+int kifs_set_supersampling(kifs_ctx* ctx, int factor);
+
 /* ---- render ---------------------------------------------------------------
  * Replaces GraphicState::render (graphics.rs:310-325): pipeline chosen by
  * options.fractal_group_id, one kernel launch instead of draw(0..3, 0..2).
@@ -288,6 +305,7 @@ int kifs_multi_set_camera(kifs_multi* m, const KifsCameraUniform* camera);
 int kifs_multi_set_options(kifs_multi* m, const KifsOptionsUniform* options);
 int kifs_multi_set_iters(kifs_multi* m, int sdf_iters, int normal_iters, int fold_iters);
 int kifs_multi_set_extensions(kifs_multi* m, const KifsExtensions* ext);
+int kifs_multi_set_supersampling(kifs_multi* m, int factor); /* kifs_set_supersampling on every device */
 /* Shares of the devices, one integer per device in the order they were listed (NULL: equal). */
 int kifs_multi_set_weights(kifs_multi* m, const int* weights);
 /* `out_rgba8`: host memory or device memory of the root device; full frame, `pitch_bytes`
@@ -427,7 +445,8 @@ enum KifsKernel {
     KIFS_KERNEL_GROUP = 1,       /* render_group_kernel: rays re-queued by a 256-thread workgroup */
     KIFS_KERNEL_WAVE = 2,        /* render_wave_kernel: rays re-queued, one wave per tile */
     KIFS_KERNEL_BUNNY_QUAD = 3,  /* render_bunny_quad_kernel: whole rays, four lanes per pixel */
-    KIFS_KERNEL_BUNNY_COOP = 4   /* render_bunny_coop_kernel: rays re-queued, four waves per 64 rays */
+    KIFS_KERNEL_BUNNY_COOP = 4,  /* render_bunny_coop_kernel: rays re-queued, four waves per 64 rays */
+    KIFS_KERNEL_SSAA = 5         /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
 };
 int kifs_debug_last_kernel(kifs_ctx* ctx);
 /* The bunny's throughput form in the context's latest launch: 0 = four lanes per ray with every weight in VGPRs, 1 = four

@@ -82,6 +82,8 @@ SIGNATURES = {
     "kifs_set_iters": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "kifs_set_extensions": (C.c_int, [_ctx, _P(ExtensionsC)]),
     "kifs_multi_set_extensions": (C.c_int, [_ctx, _P(ExtensionsC)]),
+    "kifs_set_supersampling": (C.c_int, [_ctx, C.c_int]),
+    "kifs_multi_set_supersampling": (C.c_int, [_ctx, C.c_int]),
     "kifs_render": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_render_async": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                     C.c_int]),

@@ -157,6 +157,12 @@ int kifs_set_extensions(kifs_ctx* c, const KifsExtensions* ext) {
     return KIFS_OK;
 }
 
+int kifs_set_supersampling(kifs_ctx* c, int factor) {
+    if (!c || factor < 1 || factor > KIFS_MAX_SUPERSAMPLING) return KIFS_ERR_BAD_ARG;
+    c->supersampling = factor;
+    return KIFS_OK;
+}
+
 int kifs_order_after(kifs_ctx* c, void* hip_stream, void* producer_stream) {
     if (!c) return KIFS_ERR_BAD_ARG;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
@@ -199,7 +205,7 @@ int kifs_render(kifs_ctx* c, uint8_t* out, size_t pitch, int y0, int y1, int enc
     if (!on_device) {
         if (!c->have_screen) return KIFS_ERR_UNCONFIGURED;
         int w, h;
-        int st = frame_dims(c, &w, &h);
+        int st = render_dims(c, &w, &h);
         if (st != KIFS_OK) return st;
         if (y0 < 0 || y1 > h || y0 > y1) return KIFS_ERR_BAD_ARG;
         if (pitch < size_t(w) * 4) return KIFS_ERR_BAD_SIZE;

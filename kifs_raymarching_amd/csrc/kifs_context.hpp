@@ -63,6 +63,7 @@ struct kifs_ctx {
     bool have_screen = false, have_camera = false, have_options = false;
     int sdf_iters = 100, normal_iters = 10, fold_iters = 10;  // julia.wgsl:2-3, kifs.wgsl:72
     KifsExtensions ext{};  // all zero: the reference's behaviour
+    int supersampling = 1;  // kifs_set_supersampling: k x k samples per pixel (1: the reference's one)
     int frames_in_flight = 1;  // kifs_set_frames_in_flight
     int last_round_steps = 0;  // kifs_debug_last_round_steps
     int last_group_tiles = -1; // kifs_debug_last_group_tiles
@@ -116,6 +117,8 @@ struct DeviceGuard {  // make ctx's device current for the duration of a call
 };
 
 int frame_dims(const kifs_ctx* c, int* w, int* h);
+// frame_dims for a render: with k x k supersampling the virtual k W x k H screen must meet the same limit (BAD_SIZE)
+int render_dims(const kifs_ctx* c, int* w, int* h);
 int fill_params(const kifs_ctx* c, kifs::FrameParams* P);
 bool is_device_pointer(const void* p);
 void free_table(TileTable& t);

@@ -15,6 +15,7 @@
 //                                       no barrier, the orbit in its scalar form (VALU bound)
 //   render_bunny_quad_kernel            the bunny primitive, four lanes per pixel       } kifs_bunny_kernels.hip
 //   render_bunny_coop_kernel            the bunny's batches, four waves per 64 rays     }
+//   ssaa::render_kernel<GROUP, PRIM>    k x k supersampling, every pipeline             kifs_ssaa_kernels.hip
 // (which one a launch gets: enqueue_batch in kifs_schedule.cpp, from the projected-disc tile count)
 // Tile order: a frame's run time is set by its longest rays (a lone wave pays ~5 cycles per
 // instruction whatever else the chip does), so workgroups start with the expensive tiles --
@@ -840,6 +841,7 @@ hipError_t launch_render(const BatchParams& B, uint32_t group, uint32_t primitiv
     const FrameParams& P = B.frame;
     if (P.y1 <= P.y0 || P.width <= 0 || P.tile_count == 0) return hipSuccess;
     if (B.count < 1 || B.count > MAX_BATCH) return hipErrorInvalidValue;
+    if (P.ssaa > 1) return launch_ssaa(B, group, primitive, stream);  // supersampled: one kernel form for everything
     switch (group) {
     case GROUP_JULIA:  // builds of the long-ray loop, see KIFS_DIVSQRT_ORDINARY and KIFS_FAST_TRIP_X2_ in kifs_scene.hpp
         if (P.orbit_x2)

@@ -519,6 +519,7 @@ int kifs_multi_set_camera(kifs_multi* m, const KifsCameraUniform* cam) { KIFS_MU
 int kifs_multi_set_options(kifs_multi* m, const KifsOptionsUniform* o) { KIFS_MULTI_FORWARD(kifs_set_options(c, o)) }
 int kifs_multi_set_iters(kifs_multi* m, int a, int b, int f) { KIFS_MULTI_FORWARD(kifs_set_iters(c, a, b, f)) }
 int kifs_multi_set_extensions(kifs_multi* m, const KifsExtensions* e) { KIFS_MULTI_FORWARD(kifs_set_extensions(c, e)) }
+int kifs_multi_set_supersampling(kifs_multi* m, int k) { KIFS_MULTI_FORWARD(kifs_set_supersampling(c, k)) }
 
 int kifs_multi_set_weights(kifs_multi* m, const int* weights) {
     if (!m) return KIFS_ERR_BAD_ARG;
@@ -568,7 +569,7 @@ int kifs_multi_render(kifs_multi* m, uint8_t* out, size_t pitch, int encode) {
     kifs_ctx* root = m->ctx[0];
     if (!root->have_screen || !root->have_camera || !root->have_options) return KIFS_ERR_UNCONFIGURED;
     int w, h;
-    int st = frame_dims(root, &w, &h);
+    int st = render_dims(root, &w, &h);
     if (st != KIFS_OK) return st;
     const size_t row_bytes = size_t(w) * 4;
     if (pitch < row_bytes || (pitch & 3u)) return KIFS_ERR_BAD_SIZE;
@@ -682,7 +683,7 @@ int kifs_multi_render_batch_async(kifs_multi* m, int count, const KifsCameraUnif
     kifs_ctx* root = m->ctx[0];
     if (!root->have_screen || !root->have_options) return KIFS_ERR_UNCONFIGURED;
     int w, h;
-    int st = frame_dims(root, &w, &h);
+    int st = render_dims(root, &w, &h);
     if (st != KIFS_OK) return st;
     const size_t row_bytes = size_t(w) * 4;
     if (frame_pitch < row_bytes || ((frame_pitch | frame_stride) & 3u) || (reinterpret_cast<uintptr_t>(dev_frames) & 3u) ||

@@ -88,6 +88,10 @@ struct FrameParams {
     V4 c2;
     float max_distance4;
     int orbit_x2;
+    // k x k supersampling (kifs_set_supersampling; kifs_ssaa_kernels.hip): 1 = one ray per pixel, the plain kernels;
+    // k > 1 = the samples are the pixels of a virtual k W x k H screen, whose 1 / height the quick cull takes from here
+    int ssaa;
+    float ssaa_inv_height;
 };
 
 // A launch renders a batch of up to MAX_BATCH frames that share screen, options and tile
@@ -108,5 +112,6 @@ struct BatchParams {
     const BatchView* table; // non-null: the views live there (count > MAX_BATCH_INLINE)
     BatchView view[MAX_BATCH_INLINE];
 };
+static_assert(sizeof(BatchParams) <= 4096, "the kernel argument is limited to 4 KB");
 
 }  // namespace kifs

@@ -133,5 +133,7 @@ __device__ __forceinline__ uint32_t encode_rgba(V3 colour, bool srgb, const floa
 // the bunny's kernels (kifs_bunny_kernels.hip), launched from launch_render's dispatch in kifs_kernels.hip
 hipError_t launch_bunny_coop(const BatchParams& B, hipStream_t stream);        // four waves per 64 rays, re-queued
 hipError_t launch_bunny_whole_rays(const BatchParams& B, hipStream_t stream);  // four lanes per pixel, start to finish
+// k x k supersampling (FrameParams::ssaa > 1), every pipeline (kifs_ssaa_kernels.hip)
+hipError_t launch_ssaa(const BatchParams& B, uint32_t group, uint32_t primitive, hipStream_t stream);
 
 }  // namespace kifs

@@ -89,6 +89,13 @@ int frame_dims(const kifs_ctx* c, int* w, int* h) {
     return KIFS_OK;
 }
 
+int render_dims(const kifs_ctx* c, int* w, int* h) {
+    const int st = frame_dims(c, w, h);
+    if (st != KIFS_OK) return st;
+    const int64_t k = c->supersampling;  // the virtual k W x k H screen stays within frame_dims' limit
+    return (int64_t(*w) * k > 65536 || int64_t(*h) * k > 65536) ? KIFS_ERR_BAD_SIZE : KIFS_OK;
+}
+
 // Exact squared form of `norm > T` for norm = sqrtf(n2) (correctly rounded, monotone):
 // returns the largest binary32 v with sqrtf(v) <= T, so that norm > T  <=>  n2 > v.
 float squared_threshold(float T) {
@@ -214,6 +221,8 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
         if (o.is_heatmap || !(o.epsilon > 0.0f) || o.max_iterations < 2 * rounds) rounds = 0;
         P->round_steps = rounds;
     }
+    P->ssaa = c->supersampling;
+    P->ssaa_inv_height = 1.0f / (float(c->supersampling) * c->screen.height);
     P->orbit_blocks = c->sdf_iters / 6;
     P->orbit_rem = c->sdf_iters % 6;
     P->orbit_x2 = orbit_x2_eligible(*P) ? 1 : 0;
@@ -412,6 +421,32 @@ uint32_t background_pixel(const kifs_ctx* c, kifs::V3 colour, int encode) {
     return ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
 }
 
+// The launch itself and what goes with every one: the profiling event pair around it, and the view table of a batch
+// beyond the kernel argument (ring slot `vs`) uploaded before it and marked in use after it.
+static int launch(kifs_ctx* c, hipStream_t stream, kifs::BatchParams& B, bool big, int vs) {
+    const bool timed = c->profiling && !c->prof_a.empty() && (c->prof_seen++ % uint64_t(c->prof_every)) == 0;
+    const size_t pslot = c->prof_count % (c->prof_a.empty() ? 1 : c->prof_a.size());
+    if (timed && !hip_ok(hipEventRecord(c->prof_a[pslot], stream), "record(profile start)")) return KIFS_ERR_RUNTIME;
+    if (big) {
+        if (!hip_ok(hipMemcpyAsync(c->d_views[vs], c->h_views[vs], sizeof(kifs::BatchView) * size_t(B.count),
+                                   hipMemcpyHostToDevice, stream), "copy(view table)"))
+            return KIFS_ERR_RUNTIME;
+        B.table = c->d_views[vs];
+    }
+    hipError_t e = kifs::launch_render(B, c->options.fractal_group_id, c->options.primitive_id,
+                                       stream);
+    if (!hip_ok(e, "render_kernel launch")) return KIFS_ERR_RUNTIME;
+    if (big) {
+        if (!hip_ok(hipEventRecord(c->views_used[vs], stream), "record(view table)")) return KIFS_ERR_RUNTIME;
+        c->views_busy[vs] = true;
+    }
+    if (timed) {
+        if (!hip_ok(hipEventRecord(c->prof_b[pslot], stream), "record(profile stop)")) return KIFS_ERR_RUNTIME;
+        ++c->prof_count;
+    }
+    return KIFS_OK;
+}
+
 int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras,
                   uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
                   const int* stripes, int n_stripes, int in_place) {
@@ -425,6 +460,9 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     kifs::BatchParams B;
     kifs::FrameParams& P = B.frame;
     int st = fill_params(c, &P);
+    if (st != KIFS_OK) return st;
+    int rw, rh;
+    st = render_dims(c, &rw, &rh);  // (the virtual screen of a supersampled launch)
     if (st != KIFS_OK) return st;
     B.count = count;
     B.table = nullptr;
@@ -527,6 +565,22 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
             return KIFS_ERR_RUNTIME;
     }
     if (use_feedback) tt->last_stream = stream;
+    if (P.ssaa > 1) {
+        // k x k supersampling: the output's tile table, stripes, band, views and current order, one kernel form for
+        // every scene.  Its tiles cost k^2 times theirs, so it neither records costs nor moves the sort: a later plain
+        // launch of the same geometry finds the order where the plain launches left it.
+        P.tile_order = tt->d_order;
+        P.tile_count = tt->count;
+        P.tile_cost = nullptr;
+        P.counters = nullptr;
+        P.round_steps = 0;
+        P.workgroups_per_cu = 0;
+        c->last_kernel = KIFS_KERNEL_SSAA;
+        c->last_round_steps = 0;
+        c->last_group_tiles = -1;
+        c->last_bunny_form = -1;
+        return launch(c, stream, B, big, vs);
+    }
     // a batch is launched with the sort in its own stream and refreshes every third launch (its
     // launches are long and its views move: an orbit; measured best for fixed and moving cameras;
     // KIFS_BATCH_PERIOD overrides)
@@ -633,9 +687,6 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
         if (shape == 0 && kifs_scene && !bunny_scene && P.round_steps == rules::ROUND_STEPS_OTHER && tuning_knob("KIFS_ROUND_STEPS") < 0)
             P.round_steps = rules::ROUND_STEPS_KIFS_WAVE;
     }
-    const bool timed = c->profiling && !c->prof_a.empty() && (c->prof_seen++ % uint64_t(c->prof_every)) == 0;
-    const size_t pslot = c->prof_count % (c->prof_a.empty() ? 1 : c->prof_a.size());
-    if (timed && !hip_ok(hipEventRecord(c->prof_a[pslot], stream), "record(profile start)")) return KIFS_ERR_RUNTIME;
     if (record_costs) {
         // render_kernel / render_group_kernel record run times in units of 1024 cycles; the stream kernel
         // sums the march steps of a tile's long rays over the batch's views: scale to the sort's 1024 bins
@@ -647,23 +698,8 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     c->last_kernel = P.round_steps > 0 ? (bunny_scene ? (P.bunny_coop == 1 ? KIFS_KERNEL_BUNNY_COOP : KIFS_KERNEL_GROUP)
                                                       : (P.group_tiles == 0 ? KIFS_KERNEL_WAVE : KIFS_KERNEL_GROUP))
                                        : (bunny_scene ? KIFS_KERNEL_BUNNY_QUAD : KIFS_KERNEL_BLOCK);
-    if (big) {
-        if (!hip_ok(hipMemcpyAsync(c->d_views[vs], c->h_views[vs], sizeof(kifs::BatchView) * size_t(count),
-                                   hipMemcpyHostToDevice, stream), "copy(view table)"))
-            return KIFS_ERR_RUNTIME;
-        B.table = c->d_views[vs];
-    }
-    hipError_t e = kifs::launch_render(B, c->options.fractal_group_id, c->options.primitive_id,
-                                       stream);
-    if (!hip_ok(e, "render_kernel launch")) return KIFS_ERR_RUNTIME;
-    if (big) {
-        if (!hip_ok(hipEventRecord(c->views_used[vs], stream), "record(view table)")) return KIFS_ERR_RUNTIME;
-        c->views_busy[vs] = true;
-    }
-    if (timed) {
-        if (!hip_ok(hipEventRecord(c->prof_b[pslot], stream), "record(profile stop)")) return KIFS_ERR_RUNTIME;
-        ++c->prof_count;
-    }
+    st = launch(c, stream, B, big, vs);
+    if (st != KIFS_OK) return st;
     if (!use_feedback) {  // no bookkeeping, no events: nothing depends on this launch
         tt->launches = 0;  // (a pending side-stream sort stays pending: the next feedback launch waits for it)
         return KIFS_OK;

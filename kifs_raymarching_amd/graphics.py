@@ -288,6 +288,11 @@ class GraphicState:
         e = ExtensionsC(1 if soft_shadow else 0, shadow_steps, shadow_k, shadow_t0, shadow_max_t)
         check(lib.kifs_set_extensions(self._ctx, C.byref(e)), "set_extensions")
 
+    def set_supersampling(self, k: int = 1):
+        """k x k supersampled anti-aliasing (an extension; the reference takes one sample per pixel): every render of
+        this context averages k^2 samples per pixel in linear colour before the encode.  1 <= k <= 4; 1 = off."""
+        check(lib.kifs_set_supersampling(self._ctx, int(k)), "set_supersampling")
+
     # -- render (graphics.rs:310-325) -----------------------------------------------------
     def _order_after_producer(self, dest, launch_stream):
         """The wrapper's stream rule for torch destinations: the library launches on non-blocking streams, which
@@ -514,7 +519,7 @@ class GraphicState:
         return int(lib.kifs_debug_last_group_tiles(self._ctx))
 
     KERNEL_NAMES = ("render_kernel", "render_group_kernel", "render_wave_kernel", "render_bunny_quad_kernel",
-                    "render_bunny_coop_kernel")
+                    "render_bunny_coop_kernel", "render_ssaa_kernel")
 
     def debug_last_kernel(self) -> str:
         """Name of the render kernel the latest launch used ("" before the first)."""
@@ -653,6 +658,10 @@ class MultiGraphicState:
     def set_extensions(self, soft_shadow=False, shadow_steps=0, shadow_k=0.0, shadow_t0=0.0, shadow_max_t=0.0):
         e = ExtensionsC(1 if soft_shadow else 0, int(shadow_steps), float(shadow_k), float(shadow_t0), float(shadow_max_t))
         check(lib.kifs_multi_set_extensions(self._m, C.byref(e)), "multi set_extensions")
+
+    def set_supersampling(self, k: int = 1):
+        """GraphicState.set_supersampling on every device: the gathered frames equal one device's."""
+        check(lib.kifs_multi_set_supersampling(self._m, int(k)), "multi set_supersampling")
 
     def set_gather(self, gather: str = "sparse", transport: str = "auto"):
         """gather: 'sparse' (the other devices send only the tiles that hold something) or 'dense';

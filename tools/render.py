@@ -2,6 +2,7 @@
 """Render a workload (or an orbit of it) with the HIP library and write PNG files.
 
     python tools/render.py cfg2_julia_1080p out.png
+    python tools/render.py cfg2_julia_1080p out.png --aa 3          # 3 x 3 supersampled
     python tools/render.py cfg5_sierpinski_8k_orbit frames/orbit_%03d.png --frames 0 30 60 --scale 0.25
 """
 import argparse
@@ -19,6 +20,7 @@ ap.add_argument("out")
 ap.add_argument("--frames", type=int, nargs="*", default=None, help="orbit frame indices (out needs %%d)")
 ap.add_argument("--scale", type=float, default=1.0, help="resolution scale")
 ap.add_argument("--heatmap", action="store_true")
+ap.add_argument("--aa", type=int, default=1, metavar="K", help="K x K supersampled anti-aliasing (1..4; 1 = off)")
 args = ap.parse_args()
 w = WORKLOADS[args.workload]
 screen = K.ScreenData(max(1, int(w.screen.width * args.scale)), max(1, int(w.screen.height * args.scale)))
@@ -29,6 +31,7 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
     gs.set_iters(*w.iters)
     if w.extensions:
         gs.set_extensions(**w.extensions)
+    gs.set_supersampling(args.aa)
     if args.frames is None:
         write_png(args.out, gs.render())
         print(f"{args.out}: {screen.width}x{screen.height}, kernel {gs.last_kernel_ms():.3f} ms")
