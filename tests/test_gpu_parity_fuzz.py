@@ -98,6 +98,15 @@ def test_random_batch_bit_exact_on_the_throughput_kernels(index, gs, kifs, oracl
     assert gs.debug_last_round_steps() > 0, "the launch was meant to re-queue its rays"
     if shape == 0 or gs.debug_last_group_tiles() == 0:
         assert gs.debug_last_group_tiles() == shape, (gs.debug_last_group_tiles(), shape)
+    # the rest of the debug tuple: the kernel that goes with the shape, no bunny form, and the round length of the
+    # pipeline (kifs_schedule.cpp: 16 Julia; 8 KIFS, 4 on one wave per tile; gen-Julia 8 under 32 steps, else 16)
+    tiles = gs.debug_last_group_tiles()
+    FG = kifs.FractalGroup
+    rounds = {FG.JuliaSet: 16, FG.GeneralizedJuliaSet: 8 if gui.max_iterations < 32 else 16}.get(gui.fractal_group,
+                                                                                                  4 if tiles == 0 else 8)
+    assert tiles in (0, 1, 2)
+    assert (gs.debug_last_kernel(), gs.debug_last_bunny_form(), gs.debug_last_round_steps()) == \
+        ("render_wave_kernel" if tiles == 0 else "render_group_kernel", -1, rounds), (index, tiles)
     got = outs.cpu().numpy()
     for k in sorted({0, len(cams) // 2, len(cams) - 1, int(index) % len(cams)}):
         want = oracle_frame(oracle, kifs, screen, cams[k], gui, iters, encode=encode)

@@ -1,0 +1,89 @@
+"""The form table (tests/kernel_forms.py) against what hipcc compiles: every render kernel instantiation `make report`
+lists has a recipe, and every recipe names an instantiation that still exists.  A new template instantiation without a
+recipe, or a recipe left behind by a removed one, fails here on the CPU, before any GPU run.  The recipes themselves are
+checked for consistency with the launch plan the GPU test renders.  CPU only (hipcc cross-compiles)."""
+import re
+from pathlib import Path
+
+import pytest
+
+import kernel_forms as F
+from kernel_report import kernel_report
+
+RENDER = re.compile(r"\bkifs::(ssaa::)?render\w*_kernel\b")
+
+
+def test_table_equals_the_compiled_render_instantiations():
+    compiled = {n for n in kernel_report() if RENDER.search(n)}
+    table = set(F.RENDER_FORMS) | set(F.SSAA_FORMS)
+    assert not set(F.RENDER_FORMS) & set(F.SSAA_FORMS)
+    assert sorted(compiled - table) == [], "compiled, but no recipe in tests/kernel_forms.py"
+    assert sorted(table - compiled) == [], "a recipe for an instantiation that is no longer compiled"
+
+
+def test_ssaa_claims_name_cases_of_the_ssaa_test():
+    text = (Path(__file__).resolve().parent / "test_gpu_ssaa.py").read_text()
+    m = re.search(r'@pytest\.mark\.parametrize\("name", \[([^\]]*)\]\)\s*\n(?:@pytest\.mark\.parametrize\([^\n]*\n)*'
+                  r'def test_aa_frame_bit_exact\(', text)
+    assert m, "the parameter list of test_aa_frame_bit_exact"
+    cases = set(re.findall(r'"([^"]+)"', m.group(1)))
+    assert cases and set(F.SSAA_FORMS.values()) <= cases, sorted(set(F.SSAA_FORMS.values()) - cases)
+
+
+@pytest.mark.parametrize("name", list(F.RENDER_FORMS))
+def test_recipe_is_consistent_with_the_plan(name):
+    """The recipe's configuration renders its scene in a batched launch, expects the recipe's tuple there, and that
+    tuple maps back to this instantiation."""
+    r = F.RENDER_FORMS[name]
+    launches = [L for L in F.plan(r.config) if L.scene == r.scene and len(L.cams) == F.VIEWS and L.y1 is None]
+    assert launches, (r.config, r.scene)
+    for L in launches:
+        assert F.expected_tuple(r.config, L) == r.tuple, (L.label, F.expected_tuple(r.config, L), r.tuple)
+    assert F.instantiation(r.tuple, r.scene) == name
+
+
+def test_the_plan_reaches_only_instantiations_of_the_table():
+    reached = {F.instantiation(F.expected_tuple(c, L), L.scene) for c in F.CONFIGS for L in F.plan(c)}
+    assert reached == set(F.RENDER_FORMS), (sorted(reached - set(F.RENDER_FORMS)), sorted(set(F.RENDER_FORMS) - reached))
+
+
+def test_every_re_queuing_launch_re_queues():
+    """The knobs force a form only where rounds run at all: every launch outside the block configuration re-queues, and
+    the block configuration re-queues nothing."""
+    for c in F.CONFIGS:
+        for L in F.plan(c):
+            t = F.expected_tuple(c, L)
+            assert (t[3] == 0) == (c == "block"), (c, L.label, t)
+
+
+def test_launch_geometry():
+    w, h = F.FRAME
+    n = F.tiles(w, h)
+    assert (n, n % 2, w % F.TILE_W, h % F.TILE_H) == (209, 1, 10, 5)
+    assert n * F.VIEWS >= F.REQUEUE_MIN_WORKGROUPS and F.tiles(w, h, *F.BAND) * F.VIEWS >= F.REQUEUE_MIN_WORKGROUPS
+    assert F.BAND[0] % F.TILE_H and F.BAND[1] % F.TILE_H and (F.BAND[1] - F.BAND[0]) % F.TILE_H
+    assert F.tiles(*F.LONE) >= F.REQUEUE_MIN_WORKGROUPS and F.BIG_VIEWS > F.MAX_BATCH_INLINE
+    assert F.VIEWS >= 20 and F.VIEWS % len(F.CAMERAS) == 0
+    for c in ("group1", "group2", "wave"):
+        labels = [L.label for L in F.plan(c)]
+        assert any(x.endswith("/band") for x in labels) and any(x.endswith("/shuffled") for x in labels)
+        assert sum(x.endswith("/lone") for x in labels) == 2 and any(x.endswith(f"/views{F.BIG_VIEWS}") for x in labels)
+
+
+def test_julia_variants_and_encodes():
+    """The four Julia builds with constants far from the doubled trip's window edges, sdf_iters 24 and 25 on both
+    sides of the divide / square root switch, and both encodes on every form for at least two pipelines."""
+    slots = {F.prim_slot(s): s for s, v in F.SCENES.items() if v.group == F.JULIA}
+    assert sorted(slots) == [0, 1, 2, 3]
+    for s in slots.values():
+        c = F.SCENES[s].constant
+        assert (0.0 in c) != all(0.1 <= abs(x) <= 1.0 for x in c), c
+        assert F.SCENES[s].iters[0] in (24, 25)
+    for c in F.CONFIGS:
+        both = {L.scene for L in F.plan(c) if L.encode == 0} & {L.scene for L in F.plan(c) if L.encode == 1}
+        assert len({F.SCENES[s].group * 10 + min(F.SCENES[s].prim, 6) for s in both}) >= (1 if c.startswith("bunny") else 2), c
+
+
+def test_child_environment_drops_every_kifs_variable():
+    env = F.child_env({"PATH": "/bin", "KIFS_GROUP_TILES": "2", "KIFS_DEBUG": "1", "KIFS_TUNING": "0"}, "group1")
+    assert env == {"PATH": "/bin", "KIFS_TUNING": "1", "KIFS_GROUP_TILES": "1"}

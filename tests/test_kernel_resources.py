@@ -3,29 +3,15 @@ no scratch, no spills, VGPR budgets per pipeline.  The hand-written loops pin ph
 (v30-v63, s74-s97: kifs_scene.hpp, kifs_julia_march_asm.hpp); after a toolchain bump or an edit
 this is the test that notices a spill or a lost occupancy step.  CPU only (hipcc cross-compiles)."""
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "kifs_raymarching_amd" / "csrc"
+from kernel_report import kernel_report
 
 
 @pytest.fixture(scope="module")
 def report():
-    p = subprocess.run(["make", "-C", str(CSRC), "report"], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in (p.stdout + p.stderr).splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\S+) \[-Rpass", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
-    names = subprocess.run(["c++filt"] + list(kernels), capture_output=True, text=True).stdout.split("\n")
-    return {n.strip(): v for n, v in zip(names, kernels.values())}
+    return kernel_report()
 
 
 def _budget(name):
