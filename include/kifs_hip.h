@@ -233,8 +233,11 @@ int kifs_band_range(int height, int rank, int world, int* y0, int* y1);
  * kifs_unpack_shard_async: the root's side of the gather.  Copies `count` packed shards
  * (dev_shards + i * shard_stride, rows shard_pitch apart) into the frames dev_frames + i *
  * frame_stride (rows frame_pitch apart), stripe k to frame rows [8 stripes[k], ..).  Frame size from
- * the context's screen; all strides in bytes, multiples of 4. */
+ * the context's screen; all strides in bytes, multiples of 4.  count <= KIFS_MAX_SHARD_COUNT (the shard index is
+ * one dimension of the launch grid): a larger one gives KIFS_ERR_BAD_SIZE and nothing is launched; the same holds
+ * for kifs_fill_shard_async. */
 #define KIFS_STRIPE_ROWS 8
+#define KIFS_MAX_SHARD_COUNT 65535
 int kifs_shard_stripes(int height, int world, const int* weights, int rank, int* stripes,
                        int max_stripes, int* n_stripes, int* rows);
 int kifs_render_shard_async(kifs_ctx* ctx, void* hip_stream, int count,
@@ -268,7 +271,8 @@ int kifs_unpack_shard_async(kifs_ctx* ctx, void* hip_stream, int count, uint8_t*
  * kifs_unpack_sparse_async: the root's side.  Writes records [0, n_records) to their rows of the
  *   frames dev_frames + i * frame_stride; records whose id is out of range are skipped.
  * kifs_fill_shard_async: the background over the rows of the listed stripes of `count` frames
- *   (what the records leave out; any order with kifs_unpack_sparse_async's stream, before it).
+ *   (what the records leave out; any order with kifs_unpack_sparse_async's stream, before it);
+ *   count <= KIFS_MAX_SHARD_COUNT, otherwise KIFS_ERR_BAD_SIZE and nothing is written.
  * kifs_erase_sparse_async: the background over the tiles of records [0, n_records) only -- frame
  *   buffers that are reused need it back just where the previous frames' records went (2 % of the
  *   headline's tiles) instead of a fill of every row. */
@@ -456,6 +460,14 @@ int kifs_debug_last_bunny_form(kifs_ctx* ctx);
  * frame (a permutation of (tile_x | tile_y << 16)); the order only affects speed. */
 int kifs_debug_get_tile_order(kifs_ctx* ctx, uint32_t* order, size_t max_count, size_t* count);
 int kifs_debug_set_tile_order(kifs_ctx* ctx, const uint32_t* order, size_t count);
+/* The tile-order sort on chosen costs, for tests: sorts the n host values `cost` (tile i = column i % tiles_x, row
+ * i / tiles_x) exactly as a render's cost feedback would -- bin = 1023 - min(cost >> shift, 1023), lowest bin
+ * (heaviest tiles) first, any order inside a bin -- on scratch device buffers and the context's stream, and returns
+ * the order (n words, tile_x | tile_y << 16) and the cost table as the kernel left it (n words, all zero).  None of
+ * the context's own tile tables is read or written; no screen is needed.  n == 0, tiles_x == 0, tiles_x > 65536 or
+ * more than 65536 tile rows give KIFS_ERR_BAD_SIZE; shift > 31 or a null pointer KIFS_ERR_BAD_ARG. */
+int kifs_debug_sort_tiles(kifs_ctx* ctx, const uint32_t* cost, size_t n, uint32_t tiles_x, uint32_t shift,
+                          uint32_t* order_out, uint32_t* cost_after_out);
 /* Per-wave records of the last counted render: 4 words per wave (wave = 4 * workgroup + wave
  * in workgroup, workgroups in dispatch order): total s_memtime ticks, ticks in the long-ray
  * loop, long-ray steps | (entries << 32), general steps.  Copies up to max_waves records. */

@@ -140,6 +140,8 @@ SIGNATURES = {
     "kifs_debug_counters": (C.c_int, [_ctx, C.c_int, _P(C.c_uint64)]),
     "kifs_debug_get_tile_order": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t, _P(C.c_size_t)]),
     "kifs_debug_set_tile_order": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t]),
+    "kifs_debug_sort_tiles": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, _P(C.c_uint32),
+                                        _P(C.c_uint32)]),
     "kifs_debug_wave_records": (C.c_int, [_ctx, _P(C.c_uint64), C.c_size_t, _P(C.c_size_t)]),
     "kifs_eval_math": (C.c_int, [_ctx, C.c_int, _f32p, C.c_float, _f32p, C.c_int]),
     "kifs_host_gui_default": (None, [_P(GuiDataC)]),

@@ -368,6 +368,31 @@ int kifs_debug_get_tile_order(kifs_ctx* c, uint32_t* order, size_t max_count, si
                ? KIFS_OK : KIFS_ERR_RUNTIME;
 }
 
+int kifs_debug_sort_tiles(kifs_ctx* c, const uint32_t* cost, size_t n, uint32_t tiles_x, uint32_t shift, uint32_t* order_out,
+                          uint32_t* cost_after_out) {
+    if (!c || !cost || !order_out || !cost_after_out || shift > 31) return KIFS_ERR_BAD_ARG;
+    if (n == 0 || tiles_x == 0 || tiles_x > 65536 || (n + tiles_x - 1) / tiles_x > 65536) return KIFS_ERR_BAD_SIZE;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KIFS_ERR_RUNTIME;
+    uint32_t *d_cost = nullptr, *d_order = nullptr;  // scratch: the context's own tile tables are not touched
+    int rc = KIFS_ERR_RUNTIME;
+    const size_t nb = n * sizeof(uint32_t);
+    do {
+        if (hipMalloc(reinterpret_cast<void**>(&d_cost), nb) != hipSuccess) break;
+        if (hipMalloc(reinterpret_cast<void**>(&d_order), nb) != hipSuccess) break;
+        if (hipMemcpyAsync(d_cost, cost, nb, hipMemcpyHostToDevice, c->stream) != hipSuccess) break;
+        if (hipMemsetAsync(d_order, 0xff, nb, c->stream) != hipSuccess) break;  // a slot the sort skips shows as 0xffffffff
+        if (kifs::launch_tile_order(d_cost, d_order, uint32_t(n), tiles_x, shift, c->stream) != hipSuccess) break;
+        if (hipMemcpyAsync(order_out, d_order, nb, hipMemcpyDeviceToHost, c->stream) != hipSuccess) break;
+        if (hipMemcpyAsync(cost_after_out, d_cost, nb, hipMemcpyDeviceToHost, c->stream) != hipSuccess) break;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) break;
+        rc = KIFS_OK;
+    } while (0);
+    if (d_cost) (void)hipFree(d_cost);
+    if (d_order) (void)hipFree(d_order);
+    return rc;
+}
+
 int kifs_debug_wave_records(kifs_ctx* c, unsigned long long* out, size_t max_waves, size_t* n_waves) {
     if (!c || !out || !n_waves) return KIFS_ERR_BAD_ARG;
     if (!c->d_counters) return KIFS_ERR_UNCONFIGURED;

@@ -90,7 +90,7 @@ int kifs_unpack_shard_async(kifs_ctx* c, void* hip_stream, int count, uint8_t* d
     if (st != KIFS_OK) return st;
     const size_t row_bytes = size_t(w) * 4;
     if (frame_pitch < row_bytes || shard_pitch < row_bytes || ((frame_pitch | shard_pitch | frame_stride | shard_stride) & 3u) ||
-        ((reinterpret_cast<uintptr_t>(dev_frames) | reinterpret_cast<uintptr_t>(dev_shards)) & 3u))
+        ((reinterpret_cast<uintptr_t>(dev_frames) | reinterpret_cast<uintptr_t>(dev_shards)) & 3u) || count > KIFS_MAX_SHARD_COUNT)
         return KIFS_ERR_BAD_SIZE;
     if (n_stripes == 0 || count == 0) return KIFS_OK;
     const RowTable* rows = row_table(c, stripes, n_stripes, h);
@@ -210,7 +210,8 @@ int kifs_fill_shard_async(kifs_ctx* c, void* hip_stream, int count, uint8_t* dev
     uint32_t background = 0;
     int st = sparse_setup(c, stripes, n_stripes, encode, &w, &h, &rows, &background);
     if (st != KIFS_OK) return st;
-    if (frame_pitch < size_t(w) * 4 || ((frame_pitch | frame_stride) & 3u) || (reinterpret_cast<uintptr_t>(dev_frames) & 3u))
+    if (frame_pitch < size_t(w) * 4 || ((frame_pitch | frame_stride) & 3u) || (reinterpret_cast<uintptr_t>(dev_frames) & 3u) ||
+        count > KIFS_MAX_SHARD_COUNT)
         return KIFS_ERR_BAD_SIZE;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     return hip_ok(kifs::launch_fill_stripes(dev_frames, frame_pitch, frame_stride, rows->d_rows, n_stripes, count, w, h,

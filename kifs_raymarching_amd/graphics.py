@@ -590,6 +590,15 @@ class GraphicState:
         check(lib.kifs_debug_set_tile_order(self._ctx, o.ctypes.data_as(C.POINTER(C.c_uint32)),
                                             o.size), "set_tile_order")
 
+    def debug_sort_tiles(self, cost, tiles_x: int, shift: int = 0):
+        """The tile-order sort on chosen costs (kifs_debug_sort_tiles): (order, cost table afterwards), both uint32
+        arrays of cost.size words.  The context's own tile tables are not touched."""
+        cs = np.ascontiguousarray(cost, dtype=np.uint32).ravel()
+        order, after = np.empty_like(cs), np.empty_like(cs)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        check(lib.kifs_debug_sort_tiles(self._ctx, up(cs), cs.size, tiles_x, shift, up(order), up(after)), "debug_sort_tiles")
+        return order, after
+
     def debug_wave_records(self, max_waves: int = 1 << 20):
         """(n_waves, 4) uint64: total ticks, long-ray-loop ticks, long-ray steps, general steps."""
         buf = np.zeros((max_waves, 4), dtype=np.uint64)

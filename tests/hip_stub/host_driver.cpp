@@ -141,6 +141,19 @@ void null_and_argument_checks() {
     int wts[3] = {3, 1, 1};
     CHECK(kifs_shard_stripes(1080, 3, wts, 0, stripes, 200, &n, &rows) == KIFS_OK && n == 81 && rows == 648);
     CHECK(kifs_shard_stripes(1080, 3, wts, 0, stripes, 10, &n, &rows) == KIFS_ERR_BAD_ARG);
+    // the tile-order sort on chosen costs: scratch buffers only, freed on every path
+    uint32_t cost[5] = {0, 900, 0, 7, 900}, order[5], after[5];
+    CHECK(kifs_debug_sort_tiles(c, cost, 5, 2, 0, order, after) == KIFS_OK);
+    CHECK(order[0] == (1u | 0u << 16) && order[1] == (0u | 2u << 16) && order[2] == (1u | 1u << 16) && after[1] == 0 && after[4] == 0);
+    CHECK(kifs_debug_sort_tiles(c, cost, 0, 2, 0, order, after) == KIFS_ERR_BAD_SIZE);
+    CHECK(kifs_debug_sort_tiles(c, cost, 5, 0, 0, order, after) == KIFS_ERR_BAD_SIZE);
+    CHECK(kifs_debug_sort_tiles(c, cost, 5, 65537, 0, order, after) == KIFS_ERR_BAD_SIZE);
+    CHECK(kifs_debug_sort_tiles(c, cost, 5, 2, 32, order, after) == KIFS_ERR_BAD_ARG);
+    CHECK(kifs_debug_sort_tiles(c, nullptr, 5, 2, 0, order, after) == KIFS_ERR_BAD_ARG);
+    // more shards than a launch grid has rows: refused before anything is looked at
+    int one = 0;
+    CHECK(kifs_unpack_shard_async(c, nullptr, KIFS_MAX_SHARD_COUNT + 1, px, 16, 64, px, 16, 64, &one, 1) == KIFS_ERR_BAD_SIZE);
+    CHECK(kifs_fill_shard_async(c, nullptr, KIFS_MAX_SHARD_COUNT + 1, px, 16, 64, &one, 1, 1) == KIFS_ERR_BAD_SIZE);
     kifs_destroy(c);
 }
 

@@ -24,7 +24,8 @@ def test_header_declares_the_expected_surface():
                  "kifs_band_range", "kifs_shard_stripes", "kifs_render_shard_async", "kifs_unpack_shard_async",
                  "kifs_pack_sparse_async", "kifs_unpack_sparse_async", "kifs_fill_shard_async",
                  "kifs_render_batch_async", "kifs_last_kernel_ms", "kifs_strerror", "kifs_host_camera",
-                 "kifs_host_options", "kifs_host_screen", "kifs_eval_points", "kifs_eval_math"):
+                 "kifs_host_options", "kifs_host_screen", "kifs_eval_points", "kifs_eval_math",
+                 "kifs_debug_sort_tiles"):
         assert must in names
     assert len(names) >= 25
 
@@ -89,6 +90,7 @@ def test_null_and_bad_arguments_do_not_crash(kifs):
     assert lib.kifs_unpack_sparse_async(None, None, 1, None, 0, 0, None, 0, None, 0) == 7
     assert lib.kifs_fill_shard_async(None, None, 1, None, 0, 0, None, 0, 1) == 7
     assert lib.kifs_erase_sparse_async(None, None, 1, None, 0, 0, None, 0, None, 0, 1) == 7
+    assert lib.kifs_debug_sort_tiles(None, None, 1, 1, 0, None, None) == 7
     n = C.c_int()
     assert lib.kifs_shard_stripes(8, 2, None, 0, None, 0, None, None) == 7          # nowhere to report the count
     assert lib.kifs_shard_stripes(64, 2, None, 0, None, 0, C.byref(n), None) == 0 and n.value == 4  # counting only
