@@ -203,6 +203,42 @@ int kifs_render_batch_async(kifs_ctx* ctx, void* hip_stream, int count,
                             const KifsCameraUniform* cameras, uint8_t* const* dev_outs_rgba8,
                             size_t pitch_bytes, int y0, int y1, int encode);
 
+/* ---- extension: geometry output -- per-pixel hit distance and surface normal ----------------
+ * NOT part of the reference (its fragment shader returns a colour and nothing else, entry.wgsl:49-59).
+ * kifs_render_batch_async that ALSO writes, for every pixel of the band, what the march and the shading held:
+ * whether the primary ray hit, its parameter t at the hit and the normal the shading used.
+ *   colour    frame i goes to dev_outs_rgba8[i] exactly as kifs_render_batch_async writes it: the same bytes,
+ *             heatmap and soft shadows included.  cameras == NULL with count == 1: the context's camera.
+ *   layout    one 16-byte texel per pixel, four f32 (n.x, n.y, n.z, t).  Row y of frame i sits at
+ *             dev_geometry + i * geometry_stride_bytes + (y - y0) * geometry_pitch_bytes (byte offsets).  The base is
+ *             16-byte aligned; the pitch is at least 16 W and a multiple of 16; the stride is a multiple of 16 and, when
+ *             count > 1, at least (y1 - y0) * pitch.  Otherwise the call returns KIFS_ERR_BAD_ARG and launches nothing.
+ *             (One base plus a stride, not a pointer per frame: the views of a batch travel in the 4 KB kernel
+ *             argument, where a second pointer per view does not fit.)
+ *   hit       the march of entry.wgsl:11-25 broke at d < epsilon.  t is the ray parameter at the break: the position
+ *             that was tested is fma(t, dir, origin), or the origin itself with t = 0 for a hit on the first step.
+ *             n is the vector get_normal returned there -- the same vector the shading dots with (1,1,1), not a
+ *             second evaluation.
+ *   miss      the loop ended any other way (every ray the bounding-sphere, wave and tile culls drop included):
+ *             the texel is (0, 0, 0, +inf), bit pattern 0, 0, 0, 0x7f800000.
+ *   coverage  every pixel of the band gets a texel; bytes of a row beyond 16 W are not touched.
+ *   options   heatmap frames and soft shadows change the colour only: the hit test is the same and the geometry is
+ *             the primary ray's.  No per-pixel step count is given out: the culls make the loop counter
+ *             unobservable outside heatmap mode, and heatmap frames already show it.
+ *   refusals  with the context's supersampling factor above 1 the call returns KIFS_ERR_BAD_ARG and writes nothing
+ *             (a resolved pixel has no single hit).  Row shards and kifs_multi_* have no geometry form.
+ *   bands     rows [y0, y1) are bit-identical to the same rows of the full frame; every frame of a batch is
+ *             bit-identical to the lone call's.
+ *   ordering  as the other async renders: kifs_order_after applies.
+ *   launch    a geometry launch neither records tile costs nor advances the tile-order sort (as a supersampled launch
+ *             does not); kifs_debug_last_kernel reports KIFS_KERNEL_GEOMETRY.
+ * Every value equals the CPU restatement of the contract bit for bit (tests/geometry_reference.c). */
+int kifs_render_geometry_async(kifs_ctx* ctx, void* hip_stream, int count,
+                               const KifsCameraUniform* cameras,
+                               uint8_t* const* dev_outs_rgba8, size_t pitch_bytes,
+                               float* dev_geometry, size_t geometry_pitch_bytes, size_t geometry_stride_bytes,
+                               int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);
@@ -450,7 +486,8 @@ enum KifsKernel {
     KIFS_KERNEL_WAVE = 2,        /* render_wave_kernel: rays re-queued, one wave per tile */
     KIFS_KERNEL_BUNNY_QUAD = 3,  /* render_bunny_quad_kernel: whole rays, four lanes per pixel */
     KIFS_KERNEL_BUNNY_COOP = 4,  /* render_bunny_coop_kernel: rays re-queued, four waves per 64 rays */
-    KIFS_KERNEL_SSAA = 5         /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
+    KIFS_KERNEL_SSAA = 5,        /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
+    KIFS_KERNEL_GEOMETRY = 6     /* geom::render_kernel: colour plus the geometry plane (kifs_render_geometry_async) */
 };
 int kifs_debug_last_kernel(kifs_ctx* ctx);
 /* The bunny's throughput form in the context's latest launch: 0 = four lanes per ray with every weight in VGPRs, 1 = four

@@ -91,6 +91,8 @@ SIGNATURES = {
     "kifs_multi_order_after": (C.c_int, [_ctx, C.c_void_p]),
     "kifs_render_batch_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform),
                                           _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_render_geometry_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

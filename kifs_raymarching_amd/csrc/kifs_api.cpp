@@ -195,6 +195,19 @@ int kifs_render_batch_async(kifs_ctx* c, void* hip_stream, int count, const Kifs
     return enqueue_batch(c, s, count, cameras, dev_outs, pitch, y0, y1, encode);
 }
 
+int kifs_render_geometry_async(kifs_ctx* c, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                               uint8_t* const* dev_outs, size_t pitch, float* dev_geometry, size_t geometry_pitch,
+                               size_t geometry_stride, int y0, int y1, int encode) {
+    if (!c || !dev_outs || !dev_geometry) return KIFS_ERR_BAD_ARG;
+    if (!cameras && count != 1) return KIFS_ERR_BAD_ARG;  // NULL: the context's camera, one frame
+    if (c->supersampling > 1) return KIFS_ERR_BAD_ARG;    // a resolved pixel has no single hit
+    DeviceGuard g(c->device);
+    if (!g.ok) return KIFS_ERR_RUNTIME;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    return enqueue_batch(c, s, count, cameras, dev_outs, pitch, y0, y1, encode, nullptr, 0, 0, dev_geometry,
+                         geometry_pitch, geometry_stride);
+}
+
 int kifs_render(kifs_ctx* c, uint8_t* out, size_t pitch, int y0, int y1, int encode) {
     if (!c || !out) return KIFS_ERR_BAD_ARG;
     DeviceGuard g(c->device);

@@ -131,9 +131,12 @@ uint32_t background_pixel(const kifs_ctx* c, kifs::V3 colour, int encode);
 // One launch: `count` frames (count == 1 and cameras NULL: the context's camera; else cameras[i] -> outs[i])
 // sharing everything else.  `stripes` non-null: the launch renders that row shard (y0 = 0, y1 = height)
 // instead of a band, into packed rows (in_place == 0) or at the rows' frame positions (in_place != 0).
+// `geom` non-null: the launch also writes the geometry plane (kifs_render_geometry_async: 16-byte texels, rows
+// `geom_pitch` bytes apart, view i's plane at geom + i * geom_stride bytes); bands only, no supersampling.
 int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras,
                   uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
-                  const int* stripes = nullptr, int n_stripes = 0, int in_place = 0);
+                  const int* stripes = nullptr, int n_stripes = 0, int in_place = 0,
+                  float* geom = nullptr, size_t geom_pitch = 0, size_t geom_stride = 0);
 int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int y0, int y1, int encode);
 // hipMalloc-backed buffer that only ever grows
 bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what);

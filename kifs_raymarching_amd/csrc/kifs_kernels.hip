@@ -16,6 +16,7 @@
 //   render_bunny_quad_kernel            the bunny primitive, four lanes per pixel       } kifs_bunny_kernels.hip
 //   render_bunny_coop_kernel            the bunny's batches, four waves per 64 rays     }
 //   ssaa::render_kernel<GROUP, PRIM>    k x k supersampling, every pipeline             kifs_ssaa_kernels.hip
+//   geom::render_kernel<GROUP, PRIM>    colour plus hit distance and normal per pixel   kifs_geometry_kernels.hip
 // (which one a launch gets: enqueue_batch in kifs_schedule.cpp, from the projected-disc tile count)
 // Tile order: a frame's run time is set by its longest rays (a lone wave pays ~5 cycles per
 // instruction whatever else the chip does), so workgroups start with the expensive tiles --
@@ -757,7 +758,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
 // Dynamic LDS requested only to cap how many workgroups share a CU (the kernel never touches
 // it); the cap itself is decided on the host (residency_for() in kifs_api.cpp).
 // KIFS_LDS_PAD=<bytes> overrides it (tuning; honoured only with KIFS_TUNING=1).
-static unsigned residency_pad_bytes(int workgroups_per_cu) {
+unsigned residency_pad_bytes(int workgroups_per_cu) {
     static const long forced = [] {
         const char* on = std::getenv("KIFS_TUNING");
         const char* e = (on && on[0] == '1') ? std::getenv("KIFS_LDS_PAD") : nullptr;
@@ -841,6 +842,7 @@ hipError_t launch_render(const BatchParams& B, uint32_t group, uint32_t primitiv
     const FrameParams& P = B.frame;
     if (P.y1 <= P.y0 || P.width <= 0 || P.tile_count == 0) return hipSuccess;
     if (B.count < 1 || B.count > MAX_BATCH) return hipErrorInvalidValue;
+    if (P.geom) return launch_geometry(B, group, primitive, stream);  // colour and geometry: one kernel form for everything
     if (P.ssaa > 1) return launch_ssaa(B, group, primitive, stream);  // supersampled: one kernel form for everything
     switch (group) {
     case GROUP_JULIA:  // builds of the long-ray loop, see KIFS_DIVSQRT_ORDINARY and KIFS_FAST_TRIP_X2_ in kifs_scene.hpp

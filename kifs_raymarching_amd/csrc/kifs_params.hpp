@@ -92,6 +92,12 @@ struct FrameParams {
     // k > 1 = the samples are the pixels of a virtual k W x k H screen, whose 1 / height the quick cull takes from here
     int ssaa;
     float ssaa_inv_height;
+    // Geometry output (kifs_render_geometry_async; kifs_geometry_kernels.hip): the first row of view 0's plane of 16-byte
+    // texels (n.x, n.y, n.z, t); null = a plain launch.  Row pitch and per-view stride in texels: view i's plane starts at
+    // geom + 4 * i * geom_stride_texels floats, for the inline views and the device table alike (a pointer per BatchView
+    // would not fit the kernel argument and would move every kernel's view loads).
+    float* geom;
+    uint32_t geom_pitch_texels, geom_stride_texels;
 };
 
 // A launch renders a batch of up to MAX_BATCH frames that share screen, options and tile

@@ -135,5 +135,9 @@ hipError_t launch_bunny_coop(const BatchParams& B, hipStream_t stream);        /
 hipError_t launch_bunny_whole_rays(const BatchParams& B, hipStream_t stream);  // four lanes per pixel, start to finish
 // k x k supersampling (FrameParams::ssaa > 1), every pipeline (kifs_ssaa_kernels.hip)
 hipError_t launch_ssaa(const BatchParams& B, uint32_t group, uint32_t primitive, hipStream_t stream);
+// the geometry output (FrameParams::geom non-null), every pipeline (kifs_geometry_kernels.hip)
+hipError_t launch_geometry(const BatchParams& B, uint32_t group, uint32_t primitive, hipStream_t stream);
+// dynamic LDS that caps how many workgroups share a CU (kifs_kernels.hip)
+unsigned residency_pad_bytes(int workgroups_per_cu);
 
 }  // namespace kifs

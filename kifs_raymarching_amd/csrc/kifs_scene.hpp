@@ -1002,8 +1002,10 @@ KIFS_DEV void julia_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& hi
 }
 
 // Colour of a Julia hit at p (entry.wgsl:14-19 with julia.wgsl:29-56), soft shadows if enabled.
-KIFS_DEV V3 julia_shade(const FrameParams& P, V3 p) {
+// n_out, when given, receives the normal the shading used (the geometry output's).
+KIFS_DEV V3 julia_shade(const FrameParams& P, V3 p, V3* n_out = nullptr) {
     V3 n = julia_normal(P, p);
+    if (n_out) *n_out = n;
     float ndl = (n.x + n.y) + n.z;
     float lit = clamp_(ndl, 0.0f, 1.0f);
     if (__builtin_expect(P.soft_shadow != 0u, 0))
@@ -1100,10 +1102,11 @@ KIFS_DEV void generic_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& 
     }
 }
 
-// Colour of a hit at p (entry.wgsl:14-19), soft shadows if enabled.
+// Colour of a hit at p (entry.wgsl:14-19), soft shadows if enabled.  n_out: as julia_shade's.
 template <class Sdf, class Normal>
-KIFS_DEV V3 generic_shade(const FrameParams& P, V3 p, Sdf sdf, Normal normal) {
+KIFS_DEV V3 generic_shade(const FrameParams& P, V3 p, Sdf sdf, Normal normal, V3* n_out = nullptr) {
     V3 n = normal(p);
+    if (n_out) *n_out = n;
     float ndl = (n.x + n.y) + n.z;  // dot(n, (1,1,1)): the light is not normalised (:17)
     float lit = clamp_(ndl, 0.0f, 1.0f);
     // (a lane whose direct term is not positive marches no secondary ray: its factor is 1 and 0 * 1 = 0)
@@ -1164,12 +1167,45 @@ KIFS_DEV void march_round(const FrameParams& P, V3 dir, float& t, V3& p, bool& h
 }
 
 template <int GROUP, int PRIM>
-KIFS_DEV V3 shade_hit(const FrameParams& P, V3 p) {
-    if constexpr (GROUP == GROUP_JULIA) return julia_shade(P, p);
+KIFS_DEV V3 shade_hit(const FrameParams& P, V3 p, V3* n_out = nullptr) {
+    if constexpr (GROUP == GROUP_JULIA) return julia_shade(P, p, n_out);
     else
         return generic_shade(
             P, p, [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); },
-            [&](V3 q) { return scene_normal<GROUP, PRIM>(P, q); });
+            [&](V3 q) { return scene_normal<GROUP, PRIM>(P, q); }, n_out);
+}
+
+// raymarch<GROUP, PRIM> for the geometry output (kifs_geometry_kernels.hip): the same whole ray per lane, handing out
+// what the march and the shading held -- whether the loop broke at d < epsilon, the ray parameter t at the break (the
+// tested position is fma(t, dir, origin), or the origin itself with t = 0 on the first step) and the normal the
+// shading dotted with (1,1,1).  A lane that did not hit leaves n and t as they were passed in.
+template <int GROUP, int PRIM>
+KIFS_DEV V3 raymarch_geometry(const FrameParams& P, V3 dir, bool valid, bool& hit, float& t_hit, V3& n) {
+    float t = 0.0f;
+    V3 p = P.origin;
+    hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = valid && (0 < P.max_iterations) && (t < P.max_distance);
+    if (P.is_heatmap == 0u && P.cull_n2 > 0.0f) marching = marching && !ray_never_inside(P, dir);
+    if constexpr (GROUP == GROUP_JULIA) {
+        JuliaDiag diag;
+        julia_loop<(PRIM & 1) != 0, false>(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, diag);
+    } else {
+        generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations,
+                     [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });
+    }
+    __builtin_amdgcn_s_setprio(0);
+    V3 colour = P.background_color;
+    if (hit) {
+        colour = shade_hit<GROUP, PRIM>(P, p, &n);
+        t_hit = t;
+    }
+    if (P.is_heatmap) {
+        float f = float(i_final) / float(P.max_iterations);
+        colour = V3{f * P.fractal_color.x, f * P.fractal_color.y, f * P.fractal_color.z};
+    }
+    return colour;
 }
 
 }  // namespace kifs

@@ -245,6 +245,9 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
     P->workgroups_per_cu = 0;
     P->group_tiles = 1;
     P->bunny_coop = 0;
+    P->geom = nullptr;
+    P->geom_pitch_texels = 0;
+    P->geom_stride_texels = 0;
     return KIFS_OK;
 }
 
@@ -449,7 +452,7 @@ static int launch(kifs_ctx* c, hipStream_t stream, kifs::BatchParams& B, bool bi
 
 int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras,
                   uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
-                  const int* stripes, int n_stripes, int in_place) {
+                  const int* stripes, int n_stripes, int in_place, float* geom, size_t geom_pitch, size_t geom_stride) {
     hip_ok(hipGetLastError(), "stale error before enqueue");
     if (!c->have_screen || !c->have_options || (!c->have_camera && !cameras)) return KIFS_ERR_UNCONFIGURED;
     if (count < 1 || count > kifs::MAX_BATCH || !outs) return KIFS_ERR_BAD_ARG;
@@ -517,6 +520,16 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     if (y0 < 0 || y1 > h || y0 > y1) return KIFS_ERR_BAD_ARG;
     if (pitch < size_t(P.width) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull)
         return KIFS_ERR_BAD_SIZE;
+    if (geom) {  // the geometry plane: 16-byte texels, rows of a band packed, one plane per view `geom_stride` apart
+        if (stripes || P.ssaa > 1) return KIFS_ERR_BAD_ARG;
+        if ((reinterpret_cast<uintptr_t>(geom) & 15u) != 0 || geom_pitch < size_t(P.width) * 16 || (geom_pitch & 15u) != 0 ||
+            (geom_stride & 15u) != 0 || (count > 1 && geom_stride < size_t(y1 - y0) * geom_pitch) ||
+            (geom_pitch >> 4) > 0xffffffffull || (geom_stride >> 4) > 0xffffffffull)
+            return KIFS_ERR_BAD_ARG;
+        P.geom = geom;
+        P.geom_pitch_texels = uint32_t(geom_pitch >> 4);
+        P.geom_stride_texels = uint32_t(geom_stride >> 4);
+    }
     P.y0 = y0;
     P.y1 = y1;
     P.encode = encode;
@@ -565,6 +578,24 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
             return KIFS_ERR_RUNTIME;
     }
     if (use_feedback) tt->last_stream = stream;
+    if (P.geom) {
+        // The geometry output: the plain launch's tile table, band, views and current order, one kernel form for every
+        // scene, whole rays.  Like a supersampled launch it neither records costs nor moves the sort, so a later plain
+        // launch of the same geometry finds the order where the plain launches left it.  A lone frame keeps the block
+        // kernel's residency cap.
+        P.tile_order = tt->d_order;
+        P.tile_count = tt->count;
+        P.tile_cost = nullptr;
+        P.counters = nullptr;
+        P.round_steps = 0;
+        const bool lone = count == 1 && c->frames_in_flight <= 1;
+        P.workgroups_per_cu = lone ? residency_for(P, c->options.fractal_group_id, disc_tiles(P, h, tt->count)) : 0;
+        c->last_kernel = KIFS_KERNEL_GEOMETRY;
+        c->last_round_steps = 0;
+        c->last_group_tiles = -1;
+        c->last_bunny_form = -1;
+        return launch(c, stream, B, big, vs);
+    }
     if (P.ssaa > 1) {
         // k x k supersampling: the output's tile table, stripes, band, views and current order, one kernel form for
         // every scene.  Its tiles cost k^2 times theirs, so it neither records costs nor moves the sort: a later plain

@@ -364,6 +364,51 @@ class GraphicState:
         check(lib.kifs_render_batch_async(self._ctx, stream, n, cams, ptrs, pitch, y0, y1, encode),
               "render_batch_async")
 
+    # ---- geometry output (kifs_render_geometry_async): colour plus (n.x, n.y, n.z, t) per pixel
+    def render_geometry_batch(self, cameras=None, stream=None, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB,
+                              colour=None, geometry=None):
+        """One launch for len(cameras) <= MAX_BATCH frames (cameras None: one frame with the context's camera) that
+        writes the frames AND their geometry planes.  Returns (colour, geometry): a uint8 (count, rows, W, 4) and a
+        float32 (count, rows, W, 4) torch tensor on this context's device -- texel (n.x, n.y, n.z, t) on a hit,
+        (0, 0, 0, +inf) on a miss.  `colour` / `geometry`: contiguous destination tensors of those shapes to reuse.
+        Enqueued on `stream` like render_async; the caller synchronises before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if not 1 <= n <= MAX_BATCH:
+            raise ValueError(f"render_geometry_batch: 1..{MAX_BATCH} frames")
+        dev = torch.device("cuda", self.device)
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=dev)
+        if geometry is None:
+            geometry = torch.empty((n, rows, w, 4), dtype=torch.float32, device=dev)
+        if (tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous()
+                or tuple(geometry.shape) != (n, rows, w, 4) or geometry.dtype != torch.float32
+                or not geometry.is_contiguous()):
+            raise ValueError(f"render_geometry_batch: colour uint8 and geometry float32, both ({n}, {rows}, {w}, 4), contiguous")
+        stream = self._stream_handle(stream, "render_geometry_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        ptrs = (C.c_void_p * n)(*[_device_pointer(colour[i]) for i in range(n)])
+        self._order_after_producer(colour, stream)
+        self._order_after_producer(geometry, stream)
+        check(lib.kifs_render_geometry_async(self._ctx, stream, n, cams, ptrs, w * 4, _device_pointer(geometry), w * 16,
+                                             rows * w * 16, y0, y1, encode), "render_geometry")
+        return colour, geometry
+
+    def render_geometry(self, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, stream=None):
+        """The context's frame and its geometry plane, synchronously: (colour uint8 rows x W x 4, geometry float32
+        rows x W x 4) torch tensors on this context's device; geometry[..., :3] is the normal, geometry[..., 3] is t
+        (+inf on a miss)."""
+        import torch
+        colour, geometry = self.render_geometry_batch(None, stream=stream, y0=y0, y1=y1, encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0], geometry[0]
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -519,7 +564,7 @@ class GraphicState:
         return int(lib.kifs_debug_last_group_tiles(self._ctx))
 
     KERNEL_NAMES = ("render_kernel", "render_group_kernel", "render_wave_kernel", "render_bunny_quad_kernel",
-                    "render_bunny_coop_kernel", "render_ssaa_kernel")
+                    "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel")
 
     def debug_last_kernel(self) -> str:
         """Name of the render kernel the latest launch used ("" before the first)."""

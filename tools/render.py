@@ -3,6 +3,7 @@
 
     python tools/render.py cfg2_julia_1080p out.png
     python tools/render.py cfg2_julia_1080p out.png --aa 3          # 3 x 3 supersampled
+    python tools/render.py cfg2_julia_1080p out.png --geometry out.npz --depth-png depth.png   # + normal and hit distance
     python tools/render.py cfg5_sierpinski_8k_orbit frames/orbit_%03d.png --frames 0 30 60 --scale 0.25
 """
 import argparse
@@ -21,7 +22,16 @@ ap.add_argument("--frames", type=int, nargs="*", default=None, help="orbit frame
 ap.add_argument("--scale", type=float, default=1.0, help="resolution scale")
 ap.add_argument("--heatmap", action="store_true")
 ap.add_argument("--aa", type=int, default=1, metavar="K", help="K x K supersampled anti-aliasing (1..4; 1 = off)")
+ap.add_argument("--geometry", metavar="OUT.npz", default=None,
+                help="also write the frame's geometry plane (kifs_render_geometry_async): arrays rgba (H, W, 4) uint8, "
+                     "normal (H, W, 3) float32 and t (H, W) float32, +inf where the ray missed; not with --aa or --frames")
+ap.add_argument("--depth-png", metavar="OUT.png", default=None,
+                help="with --geometry: t as a grey image for a quick look (nearest hit white, misses black)")
 args = ap.parse_args()
+if args.geometry and (args.aa != 1 or args.frames is not None):
+    ap.error("--geometry renders one frame without supersampling")
+if args.depth_png and not args.geometry:
+    ap.error("--depth-png goes with --geometry")
 w = WORKLOADS[args.workload]
 screen = K.ScreenData(max(1, int(w.screen.width * args.scale)), max(1, int(w.screen.height * args.scale)))
 gui = w.gui
@@ -32,7 +42,22 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
     if w.extensions:
         gs.set_extensions(**w.extensions)
     gs.set_supersampling(args.aa)
-    if args.frames is None:
+    if args.geometry:
+        import numpy as np
+        colour, geometry = gs.render_geometry()
+        rgba, geometry = colour.cpu().numpy(), geometry.cpu().numpy()
+        write_png(args.out, rgba)
+        np.savez_compressed(args.geometry, rgba=rgba, normal=geometry[..., :3], t=geometry[..., 3])
+        hit = np.isfinite(geometry[..., 3])
+        print(f"{args.out}, {args.geometry}: {screen.width}x{screen.height}, {int(hit.sum())} pixels hit")
+        if args.depth_png:
+            t = geometry[..., 3]
+            grey = np.zeros(t.shape, dtype=np.uint8)
+            if hit.any():
+                lo, hi = float(t[hit].min()), float(t[hit].max())
+                grey[hit] = (255.0 - 215.0 * (t[hit] - lo) / max(hi - lo, 1e-30)).astype(np.uint8)
+            write_png(args.depth_png, np.dstack([grey, grey, grey, np.full_like(grey, 255)]))
+    elif args.frames is None:
         write_png(args.out, gs.render())
         print(f"{args.out}: {screen.width}x{screen.height}, kernel {gs.last_kernel_ms():.3f} ms")
     else:
