@@ -470,7 +470,11 @@ int kifs_eval_math(kifs_ctx* ctx, int fn, const float* in, float param, float* o
 
 /* Diagnostics: with enable != 0, subsequent Julia renders write one record per wave into a
  * device buffer sized for the current screen; each call zeroes the buffer (out[8] receives
- * the 8 reserved header words).  enable == 0 frees it.  Not for timed runs. */
+ * the 8 reserved header words).  enable == 0 frees it.  Not for timed runs.
+ * The buffer holds 4 records per tile of the screen that is current at the call and is never resized by a
+ * launch.  A launch whose 4 * tiles * count wave records do not fit -- after kifs_set_screen to a larger frame,
+ * or a batch of count > 1 -- runs as a normal launch with diagnostics off: its pixels and its kernel are those
+ * of a context without diagnostics, and the records stay as they were.  Call again to size for a new screen. */
 int kifs_debug_counters(kifs_ctx* ctx, int enable, unsigned long long out[8]);
 /* Round length (march steps) of the ray re-queuing used by the context's latest launch; 0 = that
  * launch marched one wave per 8x8 block.  For tests. */

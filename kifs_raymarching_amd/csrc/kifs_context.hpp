@@ -38,6 +38,7 @@ struct TileTable {
     uint64_t launches = 0;            // consecutive feedback launches made with this table
     hipStream_t last_stream = nullptr;  // stream of the latest of them
     bool sort_pending = false;        // d_order_alt holds (or will hold) a fresh order
+    bool costs_marked = false;        // rendered[0] was recorded after the launch that last wrote d_cost[0]
     bool feedback = true;             // reorder from costs (off once the caller pins an order)
     uint32_t count = 0;
     uint32_t cost_shift = 0;          // scale of the costs the latest recording launch wrote (see record_costs)

@@ -652,6 +652,10 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     P.tile_order = tt->d_order;
     P.tile_count = tt->count;
     P.tile_cost = record_costs ? tt->d_cost[0] : nullptr;
+    // The diagnostics buffer holds one record per wave of the screen kifs_debug_counters saw (counter_words).  A launch
+    // with more waves -- a larger screen set since, a batch -- runs as if diagnostics were off: nothing is reallocated
+    // here, an earlier enqueued launch may still be writing the buffer.
+    if (P.counters && 8ull + 16ull * uint64_t(tt->count) * uint64_t(count) > uint64_t(c->counter_words)) P.counters = nullptr;
     if (P.counters) P.round_steps = 0;  // the per-wave diagnostics belong to the one-wave-per-block march
     // ---- launch shape.  Everything below is decided from `load`: the launch's tiles that can hold rays
     // with real work (the projected bounding sphere's tiles, all views), tools/cliff_sweep.py's x axis.
@@ -736,12 +740,21 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
         return KIFS_OK;
     }
     tt->launches += 1;
+    if (record_costs) tt->costs_marked = false;
     if (inline_sort) return KIFS_OK;
     if (record_costs) {
         // Launch k = 0 of the period wrote d_cost[0].  The previous sort (period before) read it
         // and finished before that period's launch 2 started, i.e. long ago on this timeline.
         if (!hip_ok(hipEventRecord(tt->rendered[0], stream), "record(render)")) return KIFS_ERR_RUNTIME;
+        tt->costs_marked = true;
     } else if (k == 1) {
+        // The costs may come from a launch that sorts inline and records no event -- a batch, or frames_in_flight > 1,
+        // before this lone launch.  rendered[0] is then unrecorded or a period old, and a wait for it would let the sort
+        // read costs that launch is still writing: mark this point of the stream instead (it follows that launch).
+        if (!tt->costs_marked) {
+            if (!hip_ok(hipEventRecord(tt->rendered[0], stream), "record(render, late)")) return KIFS_ERR_RUNTIME;
+            tt->costs_marked = true;
+        }
         // sort those costs into d_order_alt: the buffer last read by launches of the period
         // before the previous adoption, all of which precede launch 0 of this period
         if (!c->side_stream &&

@@ -1,0 +1,112 @@
+"""Seeded walks over the state of one long-lived context (tests/test_gpu_context_lifecycle.py::test_seeded_walk).
+
+plan(seed) is a pure function of the seed: a list of 60 operations, each a tuple (kind, argument).  The GPU test replays
+it on one GraphicState and checks every render; tests/test_context_walk_plan.py (CPU) replays it on the model below --
+the context's eight tile-table slots, least recently used replaced (kifs_schedule.cpp, tile_table) -- and asserts what a
+walk must cover.  Nothing here touches the library.
+"""
+import random
+
+SIZES = ((1024, 512), (330, 149), (64, 40), (1056, 516), (200, 135))  # 2048 tiles (feedback), ragged, tiny, 33 x 65, small
+N_CAMERAS, N_OPTIONS, N_ITERS, N_BANDS, N_STREAMS = 4, 3, 2, 12, 3
+TABLE_SLOTS = 8  # MAX_TILE_TABLES of kifs_context.hpp
+STEPS = 60
+SEEDS = (4, 16, 39)
+
+# kind -> (weight, arguments to draw from); the renders outweigh the state changes so that the set of distinct
+# (scene, camera, size) references stays small
+OPS = {
+    "screen": (3, range(len(SIZES))),
+    "camera": (3, range(N_CAMERAS)),
+    "options": (2, range(N_OPTIONS)),
+    "iters": (2, range(N_ITERS)),
+    "extensions": (2, (0, 1)),
+    "supersampling": (2, (1, 2)),
+    "frames_in_flight": (2, (1, 3)),
+    "band": (14, range(N_BANDS)),
+    "batch3": (3, (0,)),
+    "batch66": (2, (0,)),
+    "shard": (3, (0, 1, 2)),      # the rank of three whose stripes are rendered
+    "geometry": (3, (0,)),
+    "stream": (2, range(N_STREAMS)),  # 0: the context's stream, 1 / 2: caller streams
+}
+RENDERS = ("band", "batch3", "batch66", "shard", "geometry")
+
+
+def band_rows(height, i):
+    """Band i of 12: a quarter of the frame starting at sixteenths, neither end on a tile row for most heights."""
+    return (i * height) // 16, ((i + 4) * height) // 16 + (1 if i % 2 else 0)
+
+
+def shard_stripes(height, rank):
+    """Stripes rank, rank + 3, ... of the frame's 8-row stripes (equal shares of kifs_shard_stripes for a world of 3)."""
+    return tuple(range(rank, (height + 7) // 8, 3))
+
+
+def plan(seed):
+    rng = random.Random(seed)
+    kinds = list(OPS)
+    weights = [OPS[k][0] for k in kinds]
+    ops, supersampling = [], 1
+    while len(ops) < STEPS:
+        kind = rng.choices(kinds, weights)[0]
+        arg = rng.choice(list(OPS[kind][1]))
+        if kind == "geometry" and supersampling > 1:
+            continue  # refused by the API: a resolved pixel has no single hit
+        if kind == "supersampling":
+            supersampling = arg
+        ops.append((kind, arg))
+    return ops
+
+
+def trace(ops):
+    """(op index, kind, argument, state) for every render of a plan; state is the context's configuration at that
+    point: size, camera, options, iters, extensions, supersampling, frames_in_flight and stream, as indices."""
+    state = dict(size=0, camera=0, options=0, iters=0, extensions=0, supersampling=1, frames_in_flight=1, stream=0)
+    for i, (kind, arg) in enumerate(ops):
+        if kind in RENDERS:
+            yield i, kind, arg, dict(state)
+        else:
+            state["size" if kind == "screen" else kind] = arg
+
+
+def batch_cameras(camera, n):
+    """The views of a batch: the four cameras in turn, starting at the context's."""
+    return [(camera + j) % N_CAMERAS for j in range(n)]
+
+
+def replay(ops):
+    """The tile-table geometries a plan visits: yields (op index, key, event) for every render, event one of "hit",
+    "fill" (an empty slot), "evict" and "return" (a miss on a geometry this walk has evicted before: also an eviction)."""
+    size = SIZES[0]
+    slots, clock, evicted = {}, 0, set()
+    for i, (kind, arg) in enumerate(ops):
+        if kind == "screen":
+            size = SIZES[arg]
+        if kind not in RENDERS:
+            continue
+        w, h = size
+        if kind == "band":
+            key = (w, h) + band_rows(h, arg) + (None,)
+        elif kind == "shard":
+            key = (w, h, 0, h, shard_stripes(h, arg))
+        else:
+            key = (w, h, 0, h, None)
+        clock += 1
+        if key in slots:
+            event = "hit"
+        elif len(slots) < TABLE_SLOTS:
+            event = "fill"
+        else:
+            victim = min(slots, key=slots.get)
+            del slots[victim]
+            evicted.add(victim)
+            event = "return" if key in evicted else "evict"
+        slots[key] = clock
+        yield i, key, event
+
+
+def coverage(ops):
+    events = [e for _, _, e in replay(ops)]
+    kinds = {k: sum(1 for kind, _ in ops if kind == k) for k in OPS}
+    return {"kinds": kinds, "evictions": events.count("evict") + events.count("return"), "returns": events.count("return")}

@@ -11,9 +11,12 @@
 // has already been recorded.  The render "kernel" writes a pattern that depends on the view's camera and the pixel's
 // FRAME coordinates only, through the launch's own tile table, stripe table, pitch and in-place flag -- so a gathered
 // multi-device frame must equal the frame one context renders, exactly as on the GPU -- and checks that the tile table
-// is a permutation.  The sparse pack / unpack / fill / stripe kernels are restated on the CPU from their documented
-// formats (kifs_support_kernels.hip:115-125,184-187,211).  stub_fail_in(n): the n-th HIP call or launch from now on
-// fails once (hipErrorOutOfMemory / hipErrorLaunchFailure), for the error paths.
+// is a permutation.  With diagnostics on it writes the kernel's per-wave records, and a geometry launch its plane of
+// texels, each at the kernel's own address and through need_device.  A hipStreamWaitEvent on an event that was never
+// recorded aborts: HIP takes it for a wait that is over, so an ordering somebody relied on is missing.  The sparse
+// pack / unpack / fill / stripe kernels are restated on the CPU from their documented formats
+// (kifs_support_kernels.hip:115-125,184-187,211).  stub_fail_in(n): the n-th HIP call or launch from now on fails once
+// (hipErrorOutOfMemory / hipErrorLaunchFailure), for the error paths.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
@@ -39,7 +42,7 @@ long g_fail_in = -1;  // countdown to an injected failure
 std::map<uintptr_t, size_t> g_device_mem, g_host_mem;
 std::set<ihipStream_t*> g_streams;
 std::set<ihipEvent_t*> g_events;
-long g_calls = 0, g_launches = 0;
+long g_calls = 0, g_launches = 0, g_device_syncs = 0;
 
 hipError_t fail(hipError_t e) { g_last = e; return e; }
 
@@ -72,6 +75,7 @@ extern "C" {
 void stub_fail_in(long n) { g_fail_in = n; }
 long stub_calls() { return g_calls; }
 long stub_launches() { return g_launches; }
+long stub_device_synchronizes() { return g_device_syncs; }
 size_t stub_live_device_allocations() { return g_device_mem.size(); }
 size_t stub_live_streams_and_events() { return g_streams.size() + g_events.size() + g_host_mem.size(); }
 
@@ -83,7 +87,7 @@ hipError_t hipSetDevice(int d) {
     g_current = d;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { ++g_device_syncs; return hipSuccess; }
 hipError_t hipDeviceCanAccessPeer(int* can, int a, int b) { *can = a != b; return hipSuccess; }
 hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
 hipError_t hipGetLastError(void) { hipError_t e = g_last; g_last = hipSuccess; return e; }
@@ -161,6 +165,10 @@ hipError_t hipStreamDestroy(hipStream_t s) {
 hipError_t hipStreamSynchronize(hipStream_t s) { if (s && !g_streams.count(s)) std::abort(); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     if ((s && !g_streams.count(s)) || !g_events.count(e)) std::abort();  // a destroyed stream or event
+    if (!e->recorded) {  // HIP takes this for a wait that is already over: whoever meant to order two streams has not
+        std::fprintf(stderr, "hip_stub: hipStreamWaitEvent on an event that was never recorded\n");
+        std::abort();
+    }
     return hipSuccess;
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
@@ -239,13 +247,31 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t) 
                 const int y = base + r;
                 if (y >= P.y1) break;
                 const size_t row = P.out_frame_rows ? size_t(y) : (P.stripe_rows ? size_t(TH) * tj + size_t(r) : size_t(y - P.y0));
-                for (int x = int(tx) * TW; x < int(tx) * TW + TW && x < P.width; ++x) {
+                const int x0 = int(tx) * TW, x1 = std::min(x0 + TW, P.width);
+                need_device(out + row * P.pitch_words + x0, size_t(x1 - x0) * 4, "render: a tile row's pixels");
+                for (int x = x0; x < x1; ++x) {
                     uint32_t* dst = out + row * P.pitch_words + x;
-                    need_device(dst, 4, "render: a pixel");
                     *dst = stub_pixel(v, x, y, P.background_rgba);
+                    if (P.geom) {  // the geometry plane: rows of a band packed, one plane per view (kifs_geometry_kernels.hip:62-66)
+                        float* texel = P.geom + 4 * (size_t(f) * P.geom_stride_texels + (size_t(TH) * tj + size_t(r)) * P.geom_pitch_texels + size_t(x));
+                        need_device(texel, 16, "render: a geometry texel");
+                        const float value[4] = {float(x), float(y), v.origin.x, v.origin.z};
+                        std::memcpy(texel, value, sizeof value);
+                    }
                 }
             }
         }
+    }
+    if (P.counters) {  // the diagnostics: one 4-word record per wave, four waves per workgroup, tile_count * count workgroups
+        const size_t workgroups = size_t(P.tile_count) * size_t(B.count);  // (kifs_scene.hpp: counters + 8 + 4 * (blockIdx.x * 4 + wave))
+        for (size_t g = 0; g < workgroups; ++g)
+            for (size_t wave = 0; wave < 4; ++wave) {
+                unsigned long long* rec = P.counters + 8 + 4 * (g * 4 + wave);
+                need_device(rec, 4 * sizeof(unsigned long long), "render: a wave record");
+                rec[0] = 1000 + g;
+                rec[1] = wave;
+                rec[2] = rec[3] = 1;
+            }
     }
     if (P.tile_cost) {  // the feedback's per-tile costs: something the sort can chew on
         need_device(P.tile_cost, size_t(P.tile_count) * 4, "render: tile costs");

@@ -2,13 +2,16 @@
 // under AddressSanitizer + UndefinedBehaviorSanitizer (make -C kifs_raymarching_amd/csrc asan; tests/
 // test_host_sanitizers.py).  The scenarios are the ones tests/test_gpu_multi_batch.py, test_gpu_shards.py and
 // test_gpu_api.py run on the GPU -- here what is checked is the HOST side: every frame gathered from four "devices"
-// must equal the frame one context renders (the stub's pixels depend on camera and frame coordinates only), nothing may
+// must equal the frame one context renders (the stub's pixels depend on camera and frame coordinates only), one
+// long-lived context must keep rendering exact frames across evictions, feedback transitions, resizes and diagnostics
+// (context_lifecycle), nothing may
 // touch memory it does not own, every failure that is injected must leave the object usable, and after the last
 // destroy the stub must hold no allocation, stream or event.  Prints "host_driver: N checks ok".
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
@@ -18,6 +21,7 @@
 extern "C" {
 void stub_fail_in(long n);
 long stub_calls();
+long stub_device_synchronizes();
 size_t stub_live_device_allocations();
 size_t stub_live_streams_and_events();
 }
@@ -455,6 +459,246 @@ void injected_failures(int w, int h) {
     CHECK(hipFree(frames) == hipSuccess);
 }
 
+
+// ---- one long-lived context: tile-table eviction, the feedback state machine at every phase, resizes, diagnostics ----
+struct Lifecycle {
+    kifs_ctx* c = nullptr;
+    Scene s{};
+    std::vector<KifsCameraUniform> cams;
+    std::vector<uint8_t> want;  // single_frames(s, cams)
+    uint8_t* dev = nullptr;     // room for 70 frames of the largest size
+    size_t dev_bytes = 0;
+    int next_band = 0, next_cam = 0;
+
+    size_t fb() const { return size_t(s.w) * s.h * 4; }
+    const uint8_t* expect(int cam, int y0 = 0) const { return want.data() + size_t(cam) * fb() + size_t(y0) * s.w * 4; }
+    void use(const Scene& sc) {
+        s = sc;
+        want = single_frames(s, cams);
+        CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK && kifs_set_options(c, &s.options) == KIFS_OK);
+    }
+    // one lone launch of rows [y0, y1) into a sentinel-filled device band, on `stream` (null: the context's)
+    void lone(int y0 = 0, int y1 = -1, hipStream_t stream = nullptr) {
+        if (y1 < 0) y1 = s.h;
+        const int cam = next_cam++ % int(cams.size());
+        const size_t bytes = size_t(y1 - y0) * s.w * 4;
+        std::memset(dev, 0xEE, bytes + 64);
+        CHECK(kifs_set_camera(c, &cams[size_t(cam)]) == KIFS_OK);
+        CHECK(kifs_render_async(c, stream, dev, size_t(s.w) * 4, y0, y1, 1) == KIFS_OK);
+        CHECK(std::memcmp(dev, expect(cam, y0), bytes) == 0 && dev[bytes] == 0xEE && dev[bytes + 63] == 0xEE);
+    }
+    void batch(int n) {
+        std::vector<KifsCameraUniform> v(static_cast<size_t>(n));
+        std::vector<uint8_t*> outs(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) {
+            v[size_t(i)] = cams[size_t(i) % cams.size()];
+            outs[size_t(i)] = dev + fb() * size_t(i);
+        }
+        std::memset(dev, 0xEE, fb() * size_t(n));
+        CHECK(kifs_render_batch_async(c, nullptr, n, v.data(), outs.data(), size_t(s.w) * 4, 0, s.h, 1) == KIFS_OK);
+        for (int i = 0; i < n; ++i) CHECK(std::memcmp(outs[size_t(i)], expect(i % int(cams.size())), fb()) == 0);
+    }
+    // a band geometry this context has never rendered: always a miss in the tile-table cache
+    void new_band() {
+        const int n = next_band++;
+        const int y0 = 8 * (n % 61), y1 = y0 + 8 + n / 61;
+        CHECK(y1 <= s.h);
+        lone(y0, y1);
+    }
+    std::vector<uint32_t> order() {
+        std::vector<uint32_t> o(size_t((s.w + 31) / 32) * size_t((s.h + 7) / 8));
+        size_t n = 0;
+        CHECK(kifs_debug_get_tile_order(c, o.data(), o.size(), &n) == KIFS_OK && n == o.size());
+        return o;
+    }
+};
+
+// The centre-first order of a context that has rendered nothing.
+std::vector<uint32_t> fresh_order(const Scene& s) {
+    int st = 0;
+    kifs_ctx* c = kifs_create(0, &st);
+    CHECK(c && st == KIFS_OK && kifs_set_screen(c, &s.screen) == KIFS_OK);
+    std::vector<uint32_t> o(size_t((s.w + 31) / 32) * size_t((s.h + 7) / 8));
+    size_t n = 0;
+    CHECK(kifs_debug_get_tile_order(c, o.data(), o.size(), &n) == KIFS_OK && n == o.size());
+    kifs_destroy(c);
+    return o;
+}
+
+void context_lifecycle() {
+    Lifecycle L;
+    int st = 0;
+    L.c = kifs_create(0, &st);
+    CHECK(L.c && st == KIFS_OK);
+    L.cams = cameras(4, 50);
+    const Scene full = scene(1024, 512, 40);     // 32 x 64 = 2048 tiles: the >= edge of FEEDBACK_MIN_TILES
+    const Scene ragged = scene(1056, 516, 40);   // 33 x 65 tiles, the last column and row partial
+    L.dev_bytes = size_t(1056) * 516 * 4 * 70 + 64;
+    L.dev = dev_alloc(L.dev_bytes);
+    kifs_ctx* const c = L.c;
+
+    for (const Scene& sc : {full, ragged}) {
+        L.use(sc);
+        L.next_band = 0;
+        const std::vector<uint32_t> centre_first = fresh_order(sc);
+        for (int i = 0; i < 8; ++i) L.new_band();  // every slot of the cache is in use from here on
+        // ---- eviction: the full-frame table at phase k of the lone period, eight other geometries, and back
+        for (int k = 0; k < 4; ++k) {
+            for (int i = 0; i < 8; ++i) L.new_band();  // (the full-frame table is rebuilt below: phase 0)
+            for (int i = 0; i < k; ++i) L.lone();
+            long syncs = stub_device_synchronizes();
+            for (int i = 0; i < 8; ++i) L.new_band();
+            CHECK(stub_device_synchronizes() - syncs == 8);  // one drain per eviction, nothing else drains
+            L.lone();
+            CHECK(stub_device_synchronizes() - syncs == 9);
+            for (int i = 0; i < 6; ++i) L.lone();
+            CHECK(stub_device_synchronizes() - syncs == 9);  // a cached geometry drains nothing
+            // a pinned order survives seven other geometries and is gone after eight
+            std::vector<uint32_t> pin = L.order();
+            std::reverse(pin.begin(), pin.end());
+            CHECK(pin != centre_first);
+            CHECK(kifs_debug_set_tile_order(c, pin.data(), pin.size()) == KIFS_OK);
+            L.lone();
+            for (int i = 0; i < 7; ++i) L.new_band();
+            CHECK(L.order() == pin);
+            L.lone();
+            for (int i = 0; i < 8; ++i) L.new_band();
+            CHECK(L.order() == centre_first);
+            for (int i = 0; i < 6; ++i) L.lone();  // (feedback is on again: the sixth launch has adopted a sorted order)
+            CHECK(L.order() != centre_first);  // (the stub's costs are a hash of the tile index: their sort is not centre-first)
+        }
+        // ---- transitions: from phase k, one transition, then six lone launches
+        hipStream_t caller = nullptr;
+        CHECK(hipStreamCreateWithFlags(&caller, hipStreamNonBlocking) == hipSuccess);
+        const size_t texels = size_t(sc.w) * sc.h;
+        float* geom = reinterpret_cast<float*>(dev_alloc(texels * 16));
+        Scene sphere = sc;
+        {
+            KifsGuiData gui;
+            kifs_host_gui_default(&gui);
+            gui.fractal_group = 0;  // KIFS, sphere: no feedback below 16384 tiles
+            gui.background_color[0] = 40;
+            gui.background_color[1] = 20;
+            CHECK(kifs_host_options(&gui, &sphere.options) == KIFS_OK);
+        }
+        for (int transition = 0; transition < 8; ++transition)
+            for (int k = 0; k < 4; ++k) {
+                for (int i = 0; i < 8; ++i) L.new_band();  // evicts the full-frame table: the next launch is phase 0
+                for (int i = 0; i < k; ++i) L.lone();
+                switch (transition) {
+                case 0: L.batch(3); break;
+                case 1: L.batch(70); break;
+                case 2:
+                    CHECK(kifs_set_frames_in_flight(c, 3) == KIFS_OK);
+                    L.lone();
+                    L.lone();
+                    CHECK(kifs_set_frames_in_flight(c, 1) == KIFS_OK);
+                    break;
+                case 3: L.lone(0, -1, caller); L.lone(0, -1, caller); break;
+                case 4:
+                    CHECK(kifs_set_supersampling(c, 2) == KIFS_OK);
+                    L.lone();
+                    CHECK(kifs_set_supersampling(c, 1) == KIFS_OK);
+                    break;
+                case 5: {
+                    const std::vector<uint32_t> before = L.order();
+                    uint8_t* outs[1] = {L.dev};
+                    std::memset(L.dev, 0xEE, L.fb());
+                    std::memset(geom, 0xEE, texels * 16);
+                    CHECK(kifs_render_geometry_async(c, nullptr, 1, &L.cams[1], outs, size_t(sc.w) * 4, geom, size_t(sc.w) * 16,
+                                                     texels * 16, 0, sc.h, 1) == KIFS_OK);
+                    CHECK(std::memcmp(L.dev, L.expect(1), L.fb()) == 0);
+                    for (size_t i = 0; i < texels; i += 997) CHECK(geom[4 * i] == float(i % size_t(sc.w)) && geom[4 * i + 1] == float(i / size_t(sc.w)));
+                    CHECK(geom[4 * (texels - 1)] == float(sc.w - 1) && geom[4 * (texels - 1) + 1] == float(sc.h - 1));
+                    CHECK(L.order() == before);
+                    break;
+                }
+                case 6:
+                    CHECK(kifs_set_options(c, &sphere.options) == KIFS_OK);
+                    L.lone();
+                    CHECK(kifs_set_options(c, &sc.options) == KIFS_OK);
+                    break;
+                case 7: L.lone(0, 504); break;  // 63 tile rows: 2016 tiles at 1024 (no feedback), 2079 at 1056
+                }
+                for (int i = 0; i < 6; ++i) L.lone();
+                (void)L.order();  // (the stub has checked the permutation at every launch; this drains like a caller would)
+            }
+        CHECK(hipFree(geom) == hipSuccess && hipStreamDestroy(caller) == hipSuccess);
+    }
+
+    // ---- resizes: host and device destinations interleaved, stripe lists cached at a tall size refused at a short one
+    {
+        const int sizes[5][2] = {{1024, 512}, {330, 149}, {64, 40}, {1056, 516}, {1024, 512}};
+        const int tall[2] = {3, 64}, mid[2] = {0, 18};  // stripe 64: rows 512..515 of 516; stripe 18: rows 144..148 of 149
+        for (int i = 0; i < 5; ++i) {
+            const Scene sc = scene(sizes[i][0], sizes[i][1], 40);
+            L.use(sc);
+            std::vector<uint8_t> host(L.fb(), 0xEE);
+            for (int rep = 0; rep < 3; ++rep) {
+                const int cam = L.next_cam++ % 4;
+                CHECK(kifs_set_camera(c, &L.cams[size_t(cam)]) == KIFS_OK);
+                if (rep % 2 == i % 2) {
+                    CHECK(kifs_render(c, host.data(), size_t(sc.w) * 4, 0, sc.h, 1) == KIFS_OK);
+                    CHECK(std::memcmp(host.data(), L.expect(cam), L.fb()) == 0);
+                } else {
+                    L.lone();
+                    L.lone(sc.h / 3, sc.h - 3);
+                }
+            }
+            uint8_t* outs[1] = {L.dev};
+            auto shard = [&](const int* stripes) {
+                return kifs_render_shard_async(c, nullptr, 1, &L.cams[0], outs, size_t(sc.w) * 4, stripes, 2, 1, 1);
+            };
+            std::memset(L.dev, 0xEE, L.fb());
+            if (sc.h == 516) {
+                CHECK(shard(tall) == KIFS_OK);
+                for (int y : {24, 31, 512, 515}) CHECK(std::memcmp(L.dev + size_t(y) * sc.w * 4, L.expect(0, y), size_t(sc.w) * 4) == 0);
+                CHECK(L.dev[size_t(32) * sc.w * 4] == 0xEE);
+            } else {
+                CHECK(shard(tall) == KIFS_ERR_BAD_ARG);  // (on the last visit it sits in the cache)
+            }
+            if (sc.h == 149) CHECK(shard(mid) == KIFS_OK);
+            if (sc.h == 40) CHECK(shard(mid) == KIFS_ERR_BAD_ARG);
+        }
+    }
+
+    // ---- diagnostics: the buffer is sized by the call, a launch with more waves than it holds runs without it
+    {
+        const Scene small = scene(330, 149, 40);  // 11 x 19 tiles
+        L.use(small);
+        unsigned long long head[8];
+        size_t n = 0;
+        std::vector<unsigned long long> rec(size_t(4) * 4 * 2048), zero(rec.size(), 0ull);
+        CHECK(kifs_debug_wave_records(c, rec.data(), 1, &n) == KIFS_ERR_UNCONFIGURED);
+        CHECK(kifs_debug_counters(c, 1, head) == KIFS_OK);
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && n == size_t(4) * 11 * 19);
+        CHECK(std::memcmp(rec.data(), zero.data(), n * 32) == 0);
+        L.lone();
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && n == size_t(4) * 11 * 19);
+        CHECK(rec[0] == 1000 && rec[4 * (n - 1)] == 1000 + 11 * 19 - 1);
+        CHECK(kifs_debug_counters(c, 1, head) == KIFS_OK);
+        L.lone(16, 56);  // five tile rows: 55 workgroups
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK);
+        CHECK(rec[4 * (4 * 55 - 1)] == 1000 + 54 && std::memcmp(rec.data() + 16 * 55, zero.data(), (n - 4 * 55) * 32) == 0);
+        CHECK(kifs_debug_counters(c, 1, head) == KIFS_OK);
+        L.batch(3);  // 3 x 209 workgroups: three times the buffer
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && std::memcmp(rec.data(), zero.data(), n * 32) == 0);
+        L.use(full);
+        L.lone();    // 2048 workgroups after the resize
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && n == size_t(4) * 11 * 19);
+        CHECK(std::memcmp(rec.data(), zero.data(), n * 32) == 0);
+        CHECK(kifs_debug_counters(c, 1, head) == KIFS_OK);  // re-enabling sizes for the new screen
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && n == size_t(4) * 2048);
+        L.lone();
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_OK && rec[4 * (n - 1)] == 1000 + 2047);
+        CHECK(kifs_debug_counters(c, 0, head) == KIFS_OK);
+        CHECK(kifs_debug_wave_records(c, rec.data(), rec.size() / 4, &n) == KIFS_ERR_UNCONFIGURED);
+        L.lone();
+    }
+    CHECK(hipFree(L.dev) == hipSuccess);
+    kifs_destroy(c);
+}
+
 }  // namespace
 
 int main() {
@@ -468,6 +712,7 @@ int main() {
     multi_pipeline(320, 200);
     multi_pipeline(70, 37);
     injected_failures(100, 50);
+    context_lifecycle();
     CHECK(stub_live_device_allocations() == 0);
     CHECK(stub_live_streams_and_events() == 0);
     std::printf("host_driver: %ld checks ok\n", g_checks);

@@ -1,0 +1,464 @@
+"""One long-lived context against the oracle across state changes: what kifs_schedule.cpp keeps BETWEEN launches.
+
+A kifs_ctx caches eight tile tables (least recently used replaced, the device drained first), runs a per-table state
+machine for the tile-order feedback (launches % period, a side-stream sort, a double-buffered order), and owns the
+diagnostics buffer and the profiling ring.  Every test here opens its own GraphicState, so that it knows the context's
+whole history, enqueues a sequence of launches without synchronising in between (each launch has a sentinel-filled
+destination of its own), and only then compares every band byte for byte with the oracle.  Supersampled and geometry
+launches are compared with the same call on a fresh context: test_gpu_ssaa.py and test_gpu_geometry.py hold those
+kernels to the oracle.
+
+Oracle frames are whole frames, cached per (options, iters, extensions, camera, size) for the module and never written
+to; a band's reference is a slice of its frame (a pixel depends on its frame coordinates only).
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import context_walk as W
+from helpers import oracle_uniforms
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 0xEE
+FULL = (1024, 512)   # 32 x 64 = 2048 tiles: the >= edge of FEEDBACK_MIN_TILES
+ITERS = ((12, 10, 10), (10, 6, 8))
+SHADOWS = dict(soft_shadow=True, shadow_steps=16, shadow_k=8.0, shadow_t0=0.02, shadow_max_t=10.0)
+
+
+def _cameras(K):
+    return [K.CameraData(origin_distance=3.0 + 0.3 * i, phi=0.4 + 0.9 * i, theta=0.25 * i - 0.3) for i in range(W.N_CAMERAS)]
+
+
+def _options(K):
+    FG, PS = K.FractalGroup, K.PrimitiveShape
+    return [K.GuiData(fractal_group=FG.JuliaSet, constant=(-0.2, 0.6, 0.2, 0.2), max_iterations=64),
+            K.GuiData(primitive_shape=PS.SierpinskiTetrahedron, max_iterations=64),
+            K.GuiData(primitive_shape=PS.Sphere, is_heatmap=True, max_iterations=64)]
+
+
+class Refs:
+    """The module's oracle frames, on the device, read-only."""
+
+    def __init__(self, K, O):
+        self.K, self.O, self.cams, self.opts, self.frames = K, O, _cameras(K), _options(K), {}
+
+    def frame(self, size, cam, options=0, iters=0, ext=0):
+        import torch
+        key = (size, cam, options, iters, ext)
+        if key not in self.frames:
+            K, O = self.K, self.O
+            s, c, o = oracle_uniforms(O, K, (K.ScreenData(*size), self.cams[cam], self.opts[options]))
+            e = O.Ext(1, SHADOWS["shadow_steps"], SHADOWS["shadow_k"], SHADOWS["shadow_t0"], SHADOWS["shadow_max_t"]) if ext else None
+            kw = dict(ext=e) if ext else {}
+            self.frames[key] = torch.from_numpy(O.render(s, c, o, O.iters(*ITERS[iters]), **kw)).to("cuda:0")
+        return self.frames[key]
+
+
+@pytest.fixture(scope="module")
+def refs(kifs, oracle):
+    return Refs(kifs, oracle)
+
+
+class Ctx:
+    """A GraphicState of its own, the launches it has enqueued, and what each must equal."""
+
+    def __init__(self, K, refs, size=FULL, options=0, iters=0):
+        import torch
+        self.K, self.refs, self.torch = K, refs, torch
+        self.gs = K.GraphicState(0)
+        self.state = dict(size=size, camera=0, options=options, iters=iters, ext=0)
+        self.gs.update_screen_data(K.ScreenData(*size))
+        self.gs.update_options(refs.opts[options])
+        self.gs.set_iters(*ITERS[iters])
+        self.gs.set_camera(refs.cams[0])
+        self.pending, self.log, self.kernels = [], [], []
+
+    def close(self):
+        self.gs.close()
+
+    # -- state
+    def screen(self, size):
+        self.gs.update_screen_data(self.K.ScreenData(*size))
+        self.state["size"] = size
+        self.log.append(("screen", size))
+
+    def camera(self, i):
+        self.gs.set_camera(self.refs.cams[i])
+        self.state["camera"] = i
+
+    def options(self, i):
+        self.gs.update_options(self.refs.opts[i])
+        self.state["options"] = i
+        self.log.append(("options", i))
+
+    def want(self, cam, y0, y1):
+        st = self.state
+        return self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"])[y0:y1]
+
+    def dest(self, rows, n=None):
+        w = self.state["size"][0]
+        shape = (rows, w, 4) if n is None else (n, rows, w, 4)
+        return self.torch.full(shape, SENTINEL, dtype=self.torch.uint8, device="cuda:0")
+
+    # -- launches: enqueued, not waited for
+    def lone(self, cam=None, y0=0, y1=None, stream=None, record_kernel=False):
+        cam = self.state["camera"] if cam is None else cam
+        y1 = self.state["size"][1] if y1 is None else y1
+        self.camera(cam)
+        out = self.dest(y1 - y0)
+        self.gs.render_async(out, stream=stream, y0=y0, y1=y1)
+        self.log.append(("lone", cam, y0, y1, "caller stream" if stream is not None else "context stream"))
+        self.pending.append((out, self.want(cam, y0, y1), len(self.log)))
+        if record_kernel:
+            self.kernels.append(self.gs.debug_last_kernel())
+        return out
+
+    def batch(self, n, y0=0, y1=None, stream=None):
+        y1 = self.state["size"][1] if y1 is None else y1
+        cams = W.batch_cameras(self.state["camera"], n)
+        outs = self.dest(y1 - y0, n)
+        self.gs.render_batch_async([outs[i] for i in range(n)], [self.refs.cams[c] for c in cams], stream=stream, y0=y0, y1=y1)
+        self.log.append(("batch", n, y0, y1))
+        for i, c in enumerate(cams):
+            self.pending.append((outs[i], self.want(c, y0, y1), len(self.log)))
+
+    def expect(self, out, want, what):
+        self.log.append(what)
+        self.pending.append((out, want, len(self.log)))
+
+    def verify(self):
+        """Wait once, then every destination against its reference; a failure prints the history up to its launch."""
+        self.torch.cuda.synchronize()
+        for out, want, upto in self.pending:
+            out = out() if callable(out) else out  # (a gather of a destination's rows: only once the launch is over)
+            if not self.torch.equal(out, want):
+                bad = int((out != want).any(-1).sum())
+                raise AssertionError(f"{bad} pixels differ after {self.log[:upto]}")
+        self.pending = []
+
+    def other_band(self, n):
+        """The n-th of a supply of distinct bands, none the full frame: 8 rows from row 8 (n % 60), then longer ones."""
+        h = self.state["size"][1]
+        y0 = 8 * (n % 60)
+        return y0, min(h, y0 + 8 + 3 * (n // 60))
+
+    def permutation(self):
+        order = self.gs.debug_get_tile_order()
+        w, h = self.state["size"]
+        tx, ty = (w + 31) // 32, (h + 7) // 8
+        assert order.size == tx * ty
+        assert np.array_equal(np.sort((order >> 16) * tx + (order & 0xffff)), np.arange(tx * ty)) and (order & 0xffff).max() < tx
+        return order
+
+
+@pytest.fixture
+def ctx(kifs, refs):
+    made = []
+
+    def make(**kw):
+        made.append(Ctx(kifs, refs, **kw))
+        return made[-1]
+    yield make
+    for c in made:
+        c.close()
+
+
+def _fresh_order(K, size):
+    with K.GraphicState(0, screen_data=K.ScreenData(*size)) as g:
+        return g.debug_get_tile_order()
+
+
+@pytest.mark.parametrize("k", range(4))
+def test_eviction_round_trip(k, ctx, kifs):
+    """The full-frame table at phase k of the lone period (k = 2, 3: its side-stream sort still pending), eight other
+    geometries on the eight slots, and back: every frame before, during and after equals the oracle.  Then a pinned
+    order survives seven other geometries and is gone after eight."""
+    c = ctx()
+    bands = iter(range(1000))
+    for i in range(k):
+        c.lone(cam=i % 4)
+    for _ in range(8):
+        c.lone(0, *c.other_band(next(bands)))
+    for i in range(7):
+        c.lone(cam=i % 4)
+    c.verify()
+    centre_first = _fresh_order(kifs, FULL)
+    pin = c.permutation()[::-1].copy()
+    assert not np.array_equal(pin, centre_first)
+    c.gs.debug_set_tile_order(pin)
+    c.lone(cam=1)
+    for _ in range(7):
+        c.lone(2, *c.other_band(next(bands)))
+    assert np.array_equal(c.gs.debug_get_tile_order(), pin)
+    c.lone(cam=3)
+    for _ in range(8):
+        c.lone(0, *c.other_band(next(bands)))
+    assert np.array_equal(c.gs.debug_get_tile_order(), centre_first)
+    for i in range(6):
+        c.lone(cam=i % 4)
+    c.verify()
+    c.permutation()
+
+
+TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504")
+
+
+@pytest.mark.parametrize("k", range(4))
+@pytest.mark.parametrize("transition", TRANSITIONS)
+def test_transition_at_every_phase(transition, k, ctx, kifs):
+    """k lone launches bring the full-frame table to phase k of its period; then one transition the comments of
+    enqueue_batch call out, then six more lone launches.  Everything equals the oracle, the order table stays a
+    permutation, and the lone launches before and after run the same kernel."""
+    import torch
+    c = ctx()
+    for i in range(k):
+        c.lone(cam=i % 4, record_kernel=True)
+    if transition == "batch3":
+        c.batch(3)
+    elif transition == "batch70":
+        c.batch(70)
+    elif transition == "frames_in_flight":
+        c.gs.set_frames_in_flight(3)
+        c.lone(cam=1)
+        c.lone(cam=2)
+        c.gs.set_frames_in_flight(1)
+    elif transition == "caller_stream":
+        s = torch.cuda.Stream()
+        c.lone(cam=1, stream=s)
+        c.lone(cam=2, stream=s)
+    elif transition in ("supersampled", "geometry"):
+        before = c.gs.debug_get_tile_order()
+        with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[1], gui_data=c.refs.opts[0]) as fresh:
+            fresh.set_iters(*ITERS[0])
+            c.camera(1)
+            if transition == "supersampled":
+                fresh.set_supersampling(2)
+                want = torch.full((FULL[1], FULL[0], 4), SENTINEL, dtype=torch.uint8, device="cuda:0")
+                fresh.render_async(want)
+                fresh.synchronize()
+                c.gs.set_supersampling(2)
+                out = c.dest(FULL[1])
+                c.gs.render_async(out)
+                c.gs.set_supersampling(1)
+                c.expect(out, want, ("supersampled x2",))
+                assert not torch.equal(want, c.want(1, 0, FULL[1]))  # (the resolve is not the one-sample frame)
+            else:
+                want_c, want_g = fresh.render_geometry()
+                out_c, out_g = c.gs.render_geometry_batch(None)
+                c.expect(out_c[0], want_c, ("geometry: colour",))
+                c.expect(out_g[0].view(torch.uint8), want_g.view(torch.uint8), ("geometry: texels",))
+                c.expect(out_c[0], c.want(1, 0, FULL[1]), ("geometry: colour against the oracle",))
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)  # neither moves the sort nor the order
+    elif transition == "sphere":
+        c.options(2)
+        c.lone(cam=1)
+        c.options(0)
+    elif transition == "band504":
+        c.lone(1, 0, 504)  # 63 tile rows, 2016 tiles: a geometry without feedback
+    for i in range(6):
+        c.lone(cam=(i + 1) % 4, record_kernel=True)
+    c.verify()
+    c.permutation()
+    assert len(set(c.kernels)) == 1 and c.kernels[0], c.kernels
+
+
+def test_resize_sequence(ctx, kifs):
+    """1024x512 -> 330x149 -> 64x40 -> 1056x516 -> 1024x512 on one context: every set_screen is issued while the previous
+    size's launch is still enqueued, host and device destinations alternate, and one stripe list is rendered in place and
+    packed at two sizes."""
+    import torch
+    sizes = [(1024, 512), (330, 149), (64, 40), (1056, 516), (1024, 512)]
+    stripes = [0, 2, 4]  # rows 0..7, 16..23, 32..39: inside every size
+    c = ctx()
+    for size in sizes:  # every reference before the first launch: nothing but launches between two set_screen calls
+        for cam in range(W.N_CAMERAS):
+            c.refs.frame(size, cam)
+    host = []
+    for n, (w, h) in enumerate(sizes):
+        c.screen((w, h))            # (the previous size's launches are still in flight)
+        c.lone(cam=n % 4)
+        if n % 2:
+            c.camera((n + 1) % 4)
+            host.append((c.gs.render(), c.want((n + 1) % 4, 0, h).cpu().numpy(), (w, h)))   # synchronous, host destination
+        c.lone((n + 2) % 4, h // 3, h - 3)
+        if (w, h) in ((330, 149), (1056, 516)):
+            cams = [c.refs.cams[1], c.refs.cams[2]]
+            packed = c.dest(24, 2)
+            c.gs.render_shard_async([packed[0], packed[1]], cams, stripes)
+            placed = c.dest(h, 2)
+            c.gs.render_shard_async([placed[0], placed[1]], cams, stripes, in_place=True)
+            rows = torch.tensor([r for s in stripes for r in range(8 * s, 8 * s + 8)], device="cuda:0")
+            for i, cam in enumerate((1, 2)):
+                want = c.want(cam, 0, h)
+                c.expect(packed[i], want[rows], ("shard packed", (w, h), cam))
+                c.expect(lambda t=placed[i], r=rows: t[r], want[rows], ("shard in place", (w, h), cam))
+                mask = torch.ones(h, dtype=torch.bool, device="cuda:0")
+                mask[rows] = False
+                untouched = torch.full((h - len(rows), w, 4), SENTINEL, dtype=torch.uint8, device="cuda:0")
+                c.expect(lambda t=placed[i], m=mask: t[m], untouched, ("shard in place: other rows", (w, h), cam))
+        c.lone(cam=(n + 3) % 4)
+    c.verify()
+    for got, want, size in host:
+        assert (got == want).all(), size
+    # a stripe list cached at the tall size is refused at the short one
+    c.screen((1056, 516))
+    tall = c.dest(516, 1)
+    c.gs.render_shard_async([tall[0]], [c.refs.cams[0]], [3, 64], in_place=True)
+    c.gs.synchronize()
+    c.screen((1024, 512))
+    from kifs_raymarching_amd._lib import lib
+    arr = (C.c_int * 2)(3, 64)
+    ptrs = (C.c_void_p * 1)(tall.data_ptr())
+    cam = c.refs.cams[0].into_buffer_data()
+    assert lib.kifs_render_shard_async(c.gs._ctx, None, 1, C.byref(cam), ptrs, 1024 * 4, arr, 2, 1, 1) == 7  # BAD_ARG
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_seeded_walk(seed, ctx, kifs):
+    """60 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
+    checked, and a failure prints the plan up to it."""
+    import torch
+    ops = W.plan(seed)
+    c = ctx()
+    streams = [None, torch.cuda.Stream(), torch.cuda.Stream()]
+    fresh = kifs.GraphicState(0)   # the reference for supersampled and geometry launches: configured alike, no history
+    try:
+        for _, kind, _, st in W.trace(ops):  # every oracle frame before the first launch
+            if st["supersampling"] == 1:
+                n = {"batch3": 3, "batch66": 66}.get(kind, 1)
+                for cam in set(W.batch_cameras(st["camera"], n)):
+                    c.refs.frame(W.SIZES[st["size"]], cam, st["options"], st["iters"], st["extensions"])
+        state = dict(size=0, camera=0, options=0, iters=0, extensions=0, supersampling=1, frames_in_flight=1, stream=0)
+
+        def mirror(g):
+            g.update_screen_data(kifs.ScreenData(*W.SIZES[state["size"]]))
+            g.update_options(c.refs.opts[state["options"]])
+            g.set_iters(*ITERS[state["iters"]])
+            g.set_extensions(**SHADOWS) if state["extensions"] else g.set_extensions(soft_shadow=False)
+            g.set_supersampling(state["supersampling"])
+
+        for i, (kind, arg) in enumerate(ops):
+            if kind not in W.RENDERS:
+                state["size" if kind == "screen" else kind] = arg
+                if kind == "screen":
+                    c.screen(W.SIZES[arg])
+                elif kind == "camera":
+                    c.camera(arg)
+                elif kind == "options":
+                    c.options(arg)
+                elif kind == "iters":
+                    c.gs.set_iters(*ITERS[arg])
+                    c.state["iters"] = arg
+                elif kind == "extensions":
+                    c.gs.set_extensions(**SHADOWS) if arg else c.gs.set_extensions(soft_shadow=False)
+                    c.state["ext"] = arg
+                elif kind == "supersampling":
+                    c.gs.set_supersampling(arg)
+                elif kind == "frames_in_flight":
+                    c.gs.set_frames_in_flight(arg)
+                continue
+            w, h = W.SIZES[state["size"]]
+            stream = streams[state["stream"]]
+            cam0 = state["camera"]
+            what = (i, kind, arg, dict(state))
+            exact = state["supersampling"] == 1  # else: against the same call on the fresh context
+            if not exact or kind == "geometry":
+                mirror(fresh)
+            if kind == "band" or kind in ("batch3", "batch66"):
+                n = {"band": 1, "batch3": 3, "batch66": 66}[kind]
+                y0, y1 = W.band_rows(h, arg) if kind == "band" else (0, h)
+                cams = W.batch_cameras(cam0, n)
+                outs = c.dest(y1 - y0, n)
+                uniforms = [c.refs.cams[j] for j in cams]
+                if kind == "band":
+                    c.gs.render_async(outs[0], stream=stream, y0=y0, y1=y1)
+                else:
+                    c.gs.render_batch_async([outs[j] for j in range(n)], uniforms, stream=stream, y0=y0, y1=y1)
+                if exact:
+                    wants = [c.want(j, y0, y1) for j in cams]
+                else:
+                    ref = c.dest(y1 - y0, min(n, W.N_CAMERAS))
+                    fresh.render_batch_async([ref[j] for j in range(ref.shape[0])], uniforms[:ref.shape[0]], y0=y0, y1=y1)
+                    wants = [ref[j % W.N_CAMERAS] for j in range(n)]
+                for j in range(n):
+                    c.expect(outs[j], wants[j], what + (j,))
+            elif kind == "shard":
+                stripes = list(W.shard_stripes(h, arg))
+                rows = torch.tensor([r for s in stripes for r in range(8 * s, min(h, 8 * s + 8))], device="cuda:0")
+                out = c.dest(len(rows), 1)
+                c.gs.render_shard_async([out[0]], [c.refs.cams[cam0]], stripes, stream=stream)
+                if exact:
+                    want = c.want(cam0, 0, h)[rows]
+                else:
+                    want = c.dest(len(rows), 1)
+                    fresh.render_shard_async([want[0]], [c.refs.cams[cam0]], stripes)
+                    want = want[0]
+                c.expect(out[0], want, what)
+            else:  # geometry: colour and texels against the fresh context, colour against the oracle too
+                fresh.set_camera(c.refs.cams[cam0])
+                want_c, want_g = fresh.render_geometry()
+                out_c, out_g = c.gs.render_geometry_batch(None, stream=stream)
+                c.expect(out_c[0], want_c, what + ("colour",))
+                c.expect(out_g[0].view(torch.uint8), want_g.view(torch.uint8), what + ("texels",))
+                c.expect(out_c[0], c.want(cam0, 0, h), what + ("oracle",))
+            fresh.synchronize()
+        c.verify()
+    finally:
+        fresh.close()
+
+
+def test_diagnostics_buffer(ctx, kifs):
+    """kifs_debug_counters sizes the per-wave record buffer for the screen of the call; a launch with more waves than it
+    holds (a batch, a larger screen set since) runs as a normal launch without diagnostics.  Then the profiling ring."""
+    from kifs_raymarching_amd._lib import lib
+    small, tiles = (330, 149), 11 * 19
+    c = ctx(size=small)
+    gs = c.gs
+    plain = c.lone(cam=1)
+    c.verify()
+    out8 = (C.c_uint64 * 8)()
+    zero = lambda: lib.kifs_debug_counters(gs._ctx, 1, out8)
+    assert zero() == 0
+    assert gs.debug_wave_records().shape == (4 * tiles, 4)
+    assert not gs.debug_wave_records().any()
+    counted = c.lone(cam=1)
+    assert gs.debug_last_round_steps() == 0
+    c.verify()
+    assert c.torch.equal(counted, plain)   # pixels with counters on == pixels with counters off
+    assert gs.debug_wave_records().any()
+    assert zero() == 0
+    c.lone(2, 16, 56)                      # a band of five tile rows: 55 workgroups
+    c.verify()
+    rec = gs.debug_wave_records()
+    assert rec[:4 * 55].any() and not rec[4 * 55:].any()
+    # more waves than the buffer holds: normal launches, the records as the re-zeroing call left them
+    assert zero() == 0
+    c.batch(3)
+    c.verify()
+    assert gs.debug_wave_records().shape == (4 * tiles, 4) and not gs.debug_wave_records().any()
+    c.screen(FULL)
+    c.lone(cam=3)
+    c.verify()
+    assert gs.debug_wave_records().shape == (4 * tiles, 4) and not gs.debug_wave_records().any()
+    assert zero() == 0                     # re-enabling sizes for the new screen
+    assert gs.debug_wave_records().shape == (4 * 2048, 4)
+    c.lone(cam=3)
+    assert gs.debug_last_round_steps() == 0
+    c.verify()
+    assert gs.debug_wave_records().any()
+    assert lib.kifs_debug_counters(gs._ctx, 0, out8) == 0
+    buf, n = (C.c_uint64 * 4)(), C.c_size_t(0)
+    assert lib.kifs_debug_wave_records(gs._ctx, buf, 1, C.byref(n)) == 4  # KIFS_ERR_UNCONFIGURED
+    c.lone(cam=0)
+    c.verify()
+    # profiling: every third launch of ten is timed
+    gs.set_profiling(3)
+    for i in range(10):
+        c.lone(cam=i % 4)
+    launches, mean, lo, hi = gs.profile_read()
+    assert launches == 4 and 0 < lo <= mean <= hi, (launches, mean, lo, hi)
+    assert gs.profile_read()[0] == 0
+    gs.set_profiling(0)
+    c.verify()
