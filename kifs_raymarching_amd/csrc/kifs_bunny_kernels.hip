@@ -13,48 +13,26 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_quad_kernel(const BatchPar
     __shared__ float s_srgb[256];
     __shared__ uint32_t s_tile[2][TILE_W];
 
-    const uint32_t batch = uint32_t(B.count);
-    const uint32_t view = batch > 1 ? blockIdx.x % batch : 0u;
-    const uint32_t block = batch > 1 ? blockIdx.x / batch : blockIdx.x;
-    const FrameParams P = batch_frame(B, view);
+    const TileFrame F = tile_frame<4>(B, s_srgb);  // four lanes per pixel: two rows of the tile per workgroup
+    const FrameParams& P = F.P;
     const int tid = threadIdx.x;
-    const bool srgb = (P.encode == 1);
-    if (srgb) s_srgb[tid] = P.srgb_table[tid];
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const int pixel = lane >> 2, group = lane & 3;
-    const int lx = (wave << 3) | (pixel & 7);
-    const int ly = pixel >> 3;
-    const uint32_t tile = P.tile_order[block >> 2];
-    const int sub = int(block & 3u);
-    const int tile_x = int(tile & 0xffffu) * TILE_W;
-    const int tile_y = int(tile >> 16) * TILE_H + 2 * sub;  // row offset within the launch's rows
-    const int frame_y = tile_frame_row(P, tile >> 16) + 2 * sub;
-    const int x = tile_x + lx;
-    const int y = frame_y + ly;
-    const bool valid = (x < P.width) && (y < P.y1);
+    const int group = tid & 3;
 
     V3 colour{0.0f, 0.0f, 0.0f};
-    int steps = 0;
-    const bool culled = wave_is_culled(P, x, y, valid);  // wave-uniform
-    if (!culled && __ballot(valid) != 0ull) {
-        V3 dir = ray_direction(P, x, y);
-        colour = raymarch_bunny_quad(P, dir, valid, group, steps);
+    const bool culled = wave_is_culled(P, F.x, F.y, F.valid);  // wave-uniform
+    if (!culled && __ballot(F.valid) != 0ull) {
+        int steps = 0;
+        V3 dir = ray_direction(P, F.x, F.y);
+        colour = raymarch_bunny_quad(P, dir, F.valid, group, steps);
     }
-    (void)steps;
     __syncthreads();  // s_srgb visible
     uint32_t rgba = P.background_rgba;
     if (!culled) {
-        rgba = encode_rgba(colour, srgb, s_srgb);
+        rgba = encode_rgba(colour, F.srgb, s_srgb);
     }
-    if (group == 0) s_tile[ly][lx] = rgba;
+    if (group == 0) s_tile[F.ly][F.lx] = rgba;
     __syncthreads();
-    if (tid < 2 * TILE_W) {
-        const int sx = tid & (TILE_W - 1), sy = tid >> 5;
-        const int ox = tile_x + sx;
-        if (ox < P.width && (frame_y + sy) < P.y1)
-            P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + ox] = s_tile[sy][sx];
-    }
+    store_tile<2>(P, F.tile_x, F.tile_y, F.frame_y, s_tile, tid);
 }
 
 // render_bunny_coop_kernel<T>: the bunny's throughput path.  render_group_kernel's ray queue, but the four waves
@@ -80,10 +58,9 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_coop_kernel(const BatchPar
     __shared__ uint32_t q_count[3], h_count;
     __shared__ float x_a[4][4][64], x_b[4][4][64], x_c[4][64];  // the network's exchanges
 
-    const uint32_t batch = uint32_t(B.count);
-    const uint32_t view = batch > 1 ? blockIdx.x % batch : 0u;
-    const uint32_t group = batch > 1 ? blockIdx.x / batch : blockIdx.x;
-    const FrameParams P = batch_frame(B, view);
+    const LaunchSlot S = launch_slot(B);
+    const uint32_t group = S.index;
+    const FrameParams P = batch_frame(B, S.view);
     const int tid = threadIdx.x;
     const bool srgb = (P.encode == 1);
     const float* const s_srgb = P.srgb_table;
@@ -160,9 +137,7 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_coop_kernel(const BatchPar
                 t = q_t[cur][idx];
                 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
             }
-            V3 p = (trips == 0) ? P.origin
-                                : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                     fmaf_(t, dir.z, P.origin.z)};
+            V3 p = (trips == 0) ? P.origin : ray_at(P, t, dir);
             bool hit = false, marching = have;
             int wave_trips = trips, i_final = 0;
             generic_loop(P, dir, t, p, hit, marching, wave_trips, i_final, limit, sdf);
@@ -203,9 +178,7 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_coop_kernel(const BatchPar
         const float t = h_t[i];
         const int hx = int(pix & 31u), hy = int((pix >> 5) & 7u);
         const V3 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
-        const V3 p = (t == 0.0f) ? P.origin
-                                 : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                      fmaf_(t, dir.z, P.origin.z)};
+        const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
         const V3 colour = generic_shade(P, p, sdf, [&](V3 q) {
             return normal_fd(P.epsilon, q, [&](V3 u) { return bunny_sdf_coop(X, u); });
         });
@@ -215,26 +188,7 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_coop_kernel(const BatchPar
     __syncthreads();
 
     // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's run time
-    const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
-    uint32_t cost = 0;
-    if (feedback) {
-        const unsigned long long cycles = __builtin_amdgcn_s_memtime() - t_start;
-        cost = uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
-    }
-    const int sx = tid & (TILE_W - 1), sy = tid >> 5;
-    for (int j = 0; j < T; ++j) {
-        const uint32_t tile = s_tiles[j];
-        if (tile == 0xffffffffu) break;
-        const int ox = int(tile & 0xffffu) * TILE_W + sx;
-        const int oy = int(tile >> 16) * TILE_H + sy;
-        const int fy = s_rows[j] + sy;
-        if (ox < P.width && fy < P.y1) P.out[out_row(P, fy, oy) * P.pitch_words + ox] = s_tile[j][sy][sx];
-        if (tid == 0 && feedback) {
-            uint32_t* slot = &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)];
-            if (batch > 1) atomicMax(slot, cost);
-            else *slot = cost;
-        }
-    }
+    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, t_start);
 }
 
 hipError_t launch_bunny_coop(const BatchParams& B, hipStream_t stream) {

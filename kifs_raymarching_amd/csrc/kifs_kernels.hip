@@ -1,6 +1,7 @@
 // kifs_kernels.hip -- the render kernels and their dispatch.  (The bunny's two own kernels: kifs_bunny_kernels.hip;
-// tile order, shard packing and the parity tooling's kernels: kifs_support_kernels.hip; shared helpers:
-// kifs_render_common.hpp.)
+// supersampling: kifs_ssaa_kernels.hip; the geometry output: kifs_geometry_kernels.hip; tile order, shard packing and
+// the parity tooling's kernels: kifs_support_kernels.hip.  What they share -- tile prologue, tile store, cost
+// write-back, pipeline dispatch: kifs_render_common.hpp.)
 //
 // Render kernels over 32 x 8 pixel tiles taken from a tile ORDER table, all fed by the kernel
 // argument (BatchParams: frame constants + up to 64 views; scalar loads -> SGPRs), all storing encoded
@@ -29,7 +30,6 @@
 // Replaces: vs_main + rasteriser + fs_main + ROP of the reference
 // (src/shaders/dependencies/entry.wgsl:35-59, src/render/graphics.rs:310-325,
 // src/render.rs:72-80).
-#include <atomic>
 #include <cstdlib>
 
 #include "kifs_render_common.hpp"
@@ -42,66 +42,40 @@ __global__ __launch_bounds__(BLOCK) void render_kernel(const BatchParams B) {
     __shared__ uint32_t s_tile[TILE_H][TILE_W];
     __shared__ int s_steps[BLOCK / 64];
 
-    const uint32_t batch = uint32_t(B.count);
-    const uint32_t view = batch > 1 ? blockIdx.x % batch : 0u;
-    const uint32_t slot = batch > 1 ? blockIdx.x / batch : blockIdx.x;
-    const FrameParams P = batch_frame(B, view);
+    const TileFrame F = tile_frame(B, s_srgb);  // wave w -> 8x8 block w of the tile, lane -> (lane & 7, lane >> 3)
+    const FrameParams& P = F.P;
     const int tid = threadIdx.x;
-    const bool srgb = (P.encode == 1);
-    if (srgb) s_srgb[tid] = P.srgb_table[tid];
-
-    // compute mapping: wave w -> 8x8 sub-tile w, lane -> (lane & 7, lane >> 3)
     const int wave = tid >> 6, lane = tid & 63;
-    const int lx = (wave << 3) | (lane & 7);
-    const int ly = lane >> 3;
-    const uint32_t tile = P.tile_order[slot];  // scalar load: uniform per workgroup
-    const int tile_x = int(tile & 0xffffu) * TILE_W;
-    const int tile_y = int(tile >> 16) * TILE_H;     // row offset within the launch's rows
-    const int frame_y = tile_frame_row(P, tile >> 16);  // the tile's first frame row
-    const int x = tile_x + lx;
-    const int y = frame_y + ly;
-    const bool valid = (x < P.width) && (y < P.y1);
 
     const bool feedback = P.tile_cost != nullptr;  // wave-uniform
     const unsigned long long wave_start = feedback ? __builtin_amdgcn_s_memtime() : 0ull;
-    const bool culled = wave_is_culled(P, x, y, valid);  // wave-uniform
-    const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
-    uint32_t* const cost_slot = feedback ? &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)] : nullptr;
+    const bool culled = wave_is_culled(P, F.x, F.y, F.valid);  // wave-uniform
+    uint32_t* const cost_slot = feedback ? tile_cost_slot(P, F.tile) : nullptr;
 
     // one wave per 8x8 block, every ray from start to finish
     V3 colour{0.0f, 0.0f, 0.0f};
-    int steps = 0;  // wave-uniform: march steps this wave needed
-    if (!culled && __ballot(valid) != 0ull) {
-        V3 dir = ray_direction(P, x, y);
-        colour = raymarch<GROUP, PRIM>(P, dir, valid, steps);
+    if (!culled && __ballot(F.valid) != 0ull) {
+        int steps = 0;  // wave-uniform: march steps this wave needed
+        V3 dir = ray_direction(P, F.x, F.y);
+        colour = raymarch<GROUP, PRIM>(P, dir, F.valid, steps);
     }
-    // cost of this wave for the next frame's tile order: its run time in units of 1024 cycles,
-    // minus a floor that maps culled / instant waves to 0 (march steps alone are too coarse:
-    // hundreds of tiles tie at max_iterations)
+    // cost of this wave for the next frame's tile order: its run time
     if (feedback) {
         const unsigned long long wave_cycles = __builtin_amdgcn_s_memtime() - wave_start;
-        if (lane == 0)
-            s_steps[wave] = int(min(wave_cycles > 4096ull ? (wave_cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
+        if (lane == 0) s_steps[wave] = int(cost_from_cycles(wave_cycles));
     }
-    (void)steps;
     __syncthreads();  // s_srgb and s_steps visible
     if (tid == 0 && feedback) {  // the tile's slowest wave
         const int m = max(max(s_steps[0], s_steps[1]), max(s_steps[2], s_steps[3]));
-        if (batch > 1) atomicMax(cost_slot, uint32_t(m));  // the batch's views share the table (the sort clears it)
-        else *cost_slot = uint32_t(m);
+        record_tile_cost(cost_slot, uint32_t(m), F.batch);
     }
     uint32_t rgba = P.background_rgba;
     if (!culled) {
-        rgba = encode_rgba(colour, srgb, s_srgb);
+        rgba = encode_rgba(colour, F.srgb, s_srgb);
     }
-    s_tile[ly][lx] = rgba;
+    s_tile[F.ly][F.lx] = rgba;
     __syncthreads();
-
-    // store mapping: thread -> (tid & 31, tid >> 5): linear rows of 128 bytes
-    const int sx = tid & (TILE_W - 1), sy = tid >> 5;
-    const int ox = tile_x + sx;
-    if (ox < P.width && (frame_y + sy) < P.y1)
-        P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + ox] = s_tile[sy][sx];
+    store_tile(P, F.tile_x, F.tile_y, F.frame_y, s_tile, tid);
 }
 
 // render_group_kernel<GROUP, PRIM, T>: the throughput path.  A workgroup renders T consecutive
@@ -149,10 +123,9 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     static_assert(!W2LDS || (GROUP == GROUP_KIFS && PRIM == PRIM_BUNNY), "W2LDS is a form of the bunny's network");
     __shared__ float s_w2[W2LDS ? 256 : 1];  // (bunny, W2LDS: layer 2 of the network for the four column groups, see kifs_bunny.hpp)
 
-    const uint32_t batch = uint32_t(B.count);
-    const uint32_t view = batch > 1 ? blockIdx.x % batch : 0u;
-    const uint32_t group = batch > 1 ? blockIdx.x / batch : blockIdx.x;
-    const FrameParams P = batch_frame(B, view);
+    const LaunchSlot S = launch_slot(B);
+    const uint32_t group = S.index;
+    const FrameParams P = batch_frame(B, S.view);
     const int tid = threadIdx.x;
     const bool srgb = (P.encode == 1);
     if (srgb) s_srgb[tid] = P.srgb_table[tid];
@@ -242,9 +215,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
             }
             // a ray that has advanced has t > 0 (epsilon > 0 on this path), and then its position
             // is what the march last computed: fma(t, dir, origin)
-            V3 p = (trips == 0) ? P.origin
-                                : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                     fmaf_(t, dir.z, P.origin.z)};
+            V3 p = (trips == 0) ? P.origin : ray_at(P, t, dir);
             bool hit = false, marching = have;
             int wave_trips = trips;
             if constexpr (BUNNY) {
@@ -315,9 +286,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
                 V3 start{0.0f, 0.0f, 0.0f};
                 if (have) {
                     const V3 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
-                    const V3 p = (t == 0.0f) ? P.origin
-                                             : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                                  fmaf_(t, dir.z, P.origin.z)};
+                    const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
                     const V3 nrm = scene_normal<GROUP, NPRIM>(P, p);
                     const float ndl = (nrm.x + nrm.y) + nrm.z;
                     lit = clamp_(ndl, 0.0f, 1.0f);
@@ -417,9 +386,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
             const float t = h_t[i];
             const int hx = int(pix & 31u), hy = int((pix >> 5) & 7u);
             const V3 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
-            const V3 p = (t == 0.0f) ? P.origin
-                                     : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                          fmaf_(t, dir.z, P.origin.z)};
+            const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
             V3 colour;
             if constexpr (BUNNY) {
                 colour = generic_shade(
@@ -435,26 +402,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     __syncthreads();
 
     // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's run time
-    const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
-    uint32_t cost = 0;
-    if (feedback) {
-        const unsigned long long cycles = __builtin_amdgcn_s_memtime() - t_start;
-        cost = uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
-    }
-    const int sx = tid & (TILE_W - 1), sy = tid >> 5;
-    for (int j = 0; j < T; ++j) {
-        const uint32_t tile = s_tiles[j];
-        if (tile == 0xffffffffu) break;
-        const int ox = int(tile & 0xffffu) * TILE_W + sx;
-        const int oy = int(tile >> 16) * TILE_H + sy;  // row within the launch's rows
-        const int fy = s_rows[j] + sy;                 // row of the frame
-        if (ox < P.width && fy < P.y1) P.out[out_row(P, fy, oy) * P.pitch_words + ox] = s_tile[j][sy][sx];
-        if (tid == 0 && feedback) {
-            uint32_t* slot = &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)];
-            if (batch > 1) atomicMax(slot, cost);  // the batch's views share the table (the sort clears it)
-            else *slot = cost;
-        }
-    }
+    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, t_start);
 }
 
 // Shading of a tile's hits with the soft-shadow extension (include/kifs_hip.h), for render_wave_kernel (every pipeline).
@@ -644,13 +592,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     if (n == 0u) {
         // No ray survives the culls (a ragged tile, or one in the ring the tile-level test leaves): the
         // background straight from registers -- no LDS, no table.
-#pragma unroll
-        for (int r = 0; r < TILE_H; r += 2) {
-            const int sx = int(lane & 31u), sy = r + int(lane >> 5);
-            const int ox = tile_x + sx;
-            if (ox < P.width && (frame_y + sy) < P.y1)
-                P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + uint32_t(ox)] = P.background_rgba;
-        }
+        store_tile_wave<true>(P, tile_x, tile_y, frame_y, lane, nullptr);
         if (feedback && lane == 0 && batch == 1) {  // (in a batch the sort has cleared the table: atomicMax with 0 is a no-op)
             const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
             P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)] = 0u;
@@ -736,13 +678,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     __syncthreads();
 
     // ---- store: two full 128-byte rows per instruction; cost of the tile: the wave's run time
-#pragma unroll
-    for (int r = 0; r < TILE_H; r += 2) {
-        const int sx = int(lane & 31u), sy = r + int(lane >> 5);
-        const int ox = tile_x + sx;
-        if (ox < P.width && (frame_y + sy) < P.y1)
-            P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + uint32_t(ox)] = s_tile[sy][sx];
-    }
+    store_tile_wave(P, tile_x, tile_y, frame_y, lane, s_tile);
     if (feedback) {
         const unsigned long long cycles = __builtin_amdgcn_s_memtime() - t_start;
         const uint32_t cost = uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
@@ -773,30 +709,14 @@ unsigned residency_pad_bytes(int workgroups_per_cu) {
     }
 }
 
-// Pipeline selection: the reference keeps three render pipelines and picks one per
-// frame by fractal_group (graphics.rs:310-321); the KIFS shader then switches on
-// primitive_id per SDF call (kifs.wgsl:139-155).  Here both are template parameters.
+// One pipeline's launch (dispatch_pipeline in kifs_render_common.hpp): which of its kernels, and the grid.
 template <int GROUP, int PRIM>
 static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
     // (Julia: bit 1 of the PRIM slot, the doubled orbit trip, only changes the throughput kernel)
     constexpr int LPRIM = GROUP == GROUP_JULIA ? (PRIM & 1) : PRIM;
     const FrameParams& P = B.frame;
     const unsigned pad = residency_pad_bytes(P.workgroups_per_cu);
-    if (pad > 48 * 1024) {
-        // beyond the default dynamic-LDS limit: opt in once per kernel AND per device (the
-        // attribute belongs to the device's copy of the code object)
-        // (two contexts on two threads may come through here at once -- the header allows one caller thread per
-        // context -- hence atomics; setting the attribute twice is harmless, a torn flag would not be)
-        static std::atomic<bool> opted_in[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-        if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-            hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<GROUP, LPRIM>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            if (attr != hipSuccess) return attr;
-            if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
-        }
-    }
+    if (hipError_t e = ensure_dynamic_lds<&render_kernel<GROUP, LPRIM>>(pad); e != hipSuccess) return e;
     if (P.round_steps > 0 && P.group_tiles == 0) {  // the throughput path, one wave per tile
         hipLaunchKernelGGL((render_wave_kernel<GROUP, PRIM>), dim3(P.tile_count * uint32_t(B.count)), dim3(64),
                            residency_pad_bytes(0), stream, B);  // (the pad: KIFS_LDS_PAD under KIFS_TUNING, else 0)
@@ -844,28 +764,14 @@ hipError_t launch_render(const BatchParams& B, uint32_t group, uint32_t primitiv
     if (B.count < 1 || B.count > MAX_BATCH) return hipErrorInvalidValue;
     if (P.geom) return launch_geometry(B, group, primitive, stream);  // colour and geometry: one kernel form for everything
     if (P.ssaa > 1) return launch_ssaa(B, group, primitive, stream);  // supersampled: one kernel form for everything
-    switch (group) {
-    case GROUP_JULIA:  // builds of the long-ray loop, see KIFS_DIVSQRT_ORDINARY and KIFS_FAST_TRIP_X2_ in kifs_scene.hpp
-        if (P.orbit_x2)
-            return P.sdf_iters <= 24 ? launch_variant<GROUP_JULIA, 3>(B, stream)
-                                     : launch_variant<GROUP_JULIA, 2>(B, stream);
-        return P.sdf_iters <= 24 ? launch_variant<GROUP_JULIA, 1>(B, stream)
-                                 : launch_variant<GROUP_JULIA, 0>(B, stream);
-    case GROUP_GENJULIA: return launch_variant<GROUP_GENJULIA, 0>(B, stream);
-    case GROUP_KIFS:
-        switch (primitive) {
-        case PRIM_SPHERE: return launch_variant<GROUP_KIFS, PRIM_SPHERE>(B, stream);
-        case PRIM_CYLINDER: return launch_variant<GROUP_KIFS, PRIM_CYLINDER>(B, stream);
-        case PRIM_BOX: return launch_variant<GROUP_KIFS, PRIM_BOX>(B, stream);
-        case PRIM_TORUS: return launch_variant<GROUP_KIFS, PRIM_TORUS>(B, stream);
-        case PRIM_SIERPINSKI: return launch_variant<GROUP_KIFS, PRIM_SIERPINSKI>(B, stream);
-        case PRIM_BUNNY: return launch_bunny_quad(B, stream);
-        default: return launch_variant<GROUP_KIFS, PRIM_OTHER>(B, stream);  // kifs.wgsl:154
-        }
-    default: return hipErrorInvalidValue;
-    }
+    // the Julia pipeline's build of the long-ray loop: bit 0 the short divide / square root, bit 1 the doubled orbit trip
+    const uint32_t julia_slot = uint32_t(P.sdf_iters <= 24) | (P.orbit_x2 ? 2u : 0u);
+    return dispatch_pipeline<4>(group, primitive, julia_slot, [&](auto g, auto prim) {
+        constexpr int GROUP = decltype(g)::value, PRIM = decltype(prim)::value;
+        if constexpr (GROUP == GROUP_KIFS && PRIM == PRIM_BUNNY) return launch_bunny_quad(B, stream);  // its own kernels
+        else return launch_variant<GROUP, PRIM>(B, stream);
+    });
 }
-
 
 }  // namespace kifs
 

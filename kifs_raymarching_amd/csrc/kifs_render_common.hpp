@@ -1,7 +1,17 @@
-// kifs_render_common.hpp -- what the render kernels of kifs_kernels.hip and kifs_bunny_kernels.hip share: a view's
-// parameters out of the batch, the tile <-> frame row mapping of bands and row shards, and the wave- and tile-level
-// forms of the bounding-sphere cull.
+// kifs_render_common.hpp -- what the render kernels of kifs_kernels.hip, kifs_bunny_kernels.hip, kifs_ssaa_kernels.hip
+// and kifs_geometry_kernels.hip share.  Device side: a workgroup's place in the launch and its view's parameters
+// (launch_slot, batch_frame), the tile <-> frame row mapping of bands and row shards, the tile and lane prologue of the
+// whole-ray kernels (tile_origin, tile_frame), the wave- and tile-level forms of the bounding-sphere cull, a ray's
+// position (ray_at), the guarded store of a staged tile (store_tile, store_tile_wave, store_group) and the cost
+// write-back (tile_cost_slot, cost_from_cycles, record_tile_cost).  Host side: the pipeline dispatch
+// (dispatch_pipeline) and the opt-in to large dynamic LDS (ensure_dynamic_lds).
+// render_wave_kernel and the Julia builds are at the edge of their register budgets (the hand-written loop pins v30-v63
+// and s74-s97): where a helper cost one of them a register or a spill, that kernel keeps the text in place -- the
+// wave kernel its scalar prologue, ray positions and cost write-back, the two queue kernels their round 0.
 #pragma once
+
+#include <atomic>
+#include <type_traits>
 
 #include "kifs_internal.hpp"
 #include "kifs_scene.hpp"
@@ -39,6 +49,16 @@ __device__ __forceinline__ FrameParams batch_frame(const BatchParams& B, uint32_
     return P;
 }
 
+// Where workgroup blockIdx.x stands in its launch: the launch's number of views, this one's view and its index among
+// the view's workgroups (an entry of the tile order, or a group or a part of entries).  All uniform.
+struct LaunchSlot {
+    uint32_t batch, view, index;
+};
+__device__ __forceinline__ LaunchSlot launch_slot(const BatchParams& B) {
+    const uint32_t batch = uint32_t(B.count);
+    return LaunchSlot{batch, batch > 1 ? blockIdx.x % batch : 0u, batch > 1 ? blockIdx.x / batch : blockIdx.x};
+}
+
 // Frame row at which local tile row `tile_row` of the launch starts: a contiguous band counts on
 // from y0, a row shard looks its stripe up (scalar load: tile_row is uniform per workgroup).
 __device__ __forceinline__ int tile_frame_row(const FrameParams& P, uint32_t tile_row) {
@@ -47,6 +67,52 @@ __device__ __forceinline__ int tile_frame_row(const FrameParams& P, uint32_t til
 // Row of the destination for frame row `y` = row `local` of the launch's rows.
 __device__ __forceinline__ size_t out_row(const FrameParams& P, int y, int local) {
     return size_t(P.out_frame_rows ? y : local);
+}
+
+// The tile a workgroup renders, or its part of one: the view's parameters, the tile-order entry (x | y << 16) and the
+// first pixel's column, row within the launch's rows and row of the frame.  ROWS < TILE_H: TILE_H / ROWS workgroups
+// share an entry, each with ROWS of its rows.  Scalar loads and scalar arithmetic throughout.
+struct TileOrigin {
+    FrameParams P;
+    uint32_t batch, view, tile;  // views of the launch, this one, the entry
+    int tile_x, tile_y, frame_y;
+};
+template <int ROWS = TILE_H>
+__device__ __forceinline__ TileOrigin tile_origin(const FrameParams& P, const LaunchSlot& S) {
+    constexpr uint32_t PARTS = TILE_H / ROWS;
+    const uint32_t tile = P.tile_order[S.index / PARTS];
+    const int first = ROWS * int(S.index % PARTS);
+    return TileOrigin{P, S.batch, S.view, tile, int(tile & 0xffffu) * TILE_W, int(tile >> 16) * TILE_H + first,
+                      tile_frame_row(P, tile >> 16) + first};
+}
+__device__ __forceinline__ TileOrigin tile_origin(const BatchParams& B) {
+    const LaunchSlot S = launch_slot(B);
+    return tile_origin(batch_frame(B, S.view), S);
+}
+
+// The whole-ray kernels' prologue, 256 threads: the sRGB table staged into `s_srgb` (256 floats of LDS, visible after
+// the next barrier), the tile and this lane's pixel.  Wave w owns columns [8 w, 8 w + 8) of the tile; its lanes take
+// the pixels of that block row by row, LPP lanes to a pixel, so a workgroup covers TILE_H / LPP rows.
+struct TileFrame : TileOrigin {
+    bool srgb;
+    int lx, ly;  // pixel within the workgroup's rows
+    int x, y;    // pixel of the frame
+    bool valid;  // inside the frame and the launch's rows
+};
+template <int LPP = 1>
+__device__ __forceinline__ TileFrame tile_frame(const BatchParams& B, float* s_srgb) {
+    const LaunchSlot S = launch_slot(B);
+    const FrameParams P = batch_frame(B, S.view);
+    const int tid = threadIdx.x;
+    const bool srgb = (P.encode == 1);
+    if (srgb) s_srgb[tid] = P.srgb_table[tid];
+    const int wave = tid >> 6, pixel = (tid & 63) / LPP;
+    const int lx = (wave << 3) | (pixel & 7);
+    const int ly = pixel >> 3;
+    const TileOrigin O = tile_origin<TILE_H / LPP>(P, S);
+    const int x = O.tile_x + lx;
+    const int y = O.frame_y + ly;
+    return TileFrame{O, srgb, lx, ly, x, y, (x < P.width) && (y < P.y1)};
 }
 
 // True when no pixel of this wave can ever be hit: every valid lane's ray passes the origin at more
@@ -128,6 +194,123 @@ __device__ __forceinline__ uint32_t encode_rgba(V3 colour, bool srgb, const floa
         b = unorm8(colour.z);
     }
     return r | (g << 8) | (b << 16) | 0xff000000u;  // alpha = 1.0 -> 255
+}
+
+// Where a ray stands after it has advanced by t: what the march last computed.  The callers choose when the origin's
+// own bits stand in for it, and the two conditions in use are not interchangeable: a hit list's entry asks its own
+// `t == 0` (per lane), a queue's round the uniform `trips == 0` (every ray of round 0 stands at the origin, every ray
+// of a later round has advanced).
+__device__ __forceinline__ V3 ray_at(const FrameParams& P, float t, V3 dir) {
+    return V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y), fmaf_(t, dir.z, P.origin.z)};
+}
+
+// The staged tile to the destination, 256 threads: thread -> (tid & 31, tid >> 5), linear rows of 128 bytes, the first
+// ROWS rows of `s_tile`, under the guards of a ragged frame edge and a band's last row.
+template <int ROWS = TILE_H>
+__device__ __forceinline__ void store_tile(const FrameParams& P, int tile_x, int tile_y, int frame_y,
+                                           const uint32_t (*s_tile)[TILE_W], int tid) {
+    if (ROWS < TILE_H && tid >= ROWS * TILE_W) return;
+    const int sx = tid & (TILE_W - 1), sy = tid >> 5;
+    const int ox = tile_x + sx;
+    if (ox < P.width && (frame_y + sy) < P.y1)
+        P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + ox] = s_tile[sy][sx];
+}
+// The same with one wave: two full 128-byte rows per instruction, from the staged tile or, BACKGROUND, the background
+// colour straight from a register (`s_tile` is not read then).
+template <bool BACKGROUND = false>
+__device__ __forceinline__ void store_tile_wave(const FrameParams& P, int tile_x, int tile_y, int frame_y, uint32_t lane,
+                                                const uint32_t (*s_tile)[TILE_W]) {
+#pragma unroll
+    for (int r = 0; r < TILE_H; r += 2) {
+        const int sx = int(lane & 31u), sy = r + int(lane >> 5);
+        const int ox = tile_x + sx;
+        if (ox < P.width && (frame_y + sy) < P.y1)
+            P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + uint32_t(ox)] =
+                BACKGROUND ? P.background_rgba : s_tile[sy][sx];
+    }
+}
+
+// Cost of a tile for the next frame's tile order (tile_order_kernel): the run time of the wave or workgroup that
+// rendered it in units of 1024 cycles, minus a floor that maps culled / instant ones to 0 (march steps alone are too
+// coarse: hundreds of tiles tie at max_iterations).
+__device__ __forceinline__ uint32_t* tile_cost_slot(const FrameParams& P, uint32_t tile) {
+    const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
+    return &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)];
+}
+__device__ __forceinline__ uint32_t cost_from_cycles(unsigned long long cycles) {
+    return uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
+}
+__device__ __forceinline__ void record_tile_cost(uint32_t* slot, uint32_t cost, uint32_t batch) {
+    if (batch > 1) atomicMax(slot, cost);  // the batch's views share the table (the sort clears it)
+    else *slot = cost;
+}
+
+// The end of the two queue kernels, 256 threads: the T staged tiles of the group to the destination; cost of each of
+// them: the workgroup's run time since `t_start`.
+template <int T>
+__device__ __forceinline__ void store_group(const FrameParams& P, const uint32_t* s_tiles, const int* s_rows,
+                                            const uint32_t (*s_tile)[TILE_H][TILE_W], int tid, uint32_t batch, bool feedback,
+                                            unsigned long long t_start) {
+    const uint32_t cost = feedback ? cost_from_cycles(__builtin_amdgcn_s_memtime() - t_start) : 0u;
+    for (int j = 0; j < T; ++j) {
+        const uint32_t tile = s_tiles[j];
+        if (tile == 0xffffffffu) break;
+        store_tile(P, int(tile & 0xffffu) * TILE_W, int(tile >> 16) * TILE_H, s_rows[j], s_tile[j], tid);
+        if (tid == 0 && feedback) record_tile_cost(tile_cost_slot(P, tile), cost, batch);
+    }
+}
+
+// Pipeline selection: the reference keeps three render pipelines and picks one per frame by fractal_group
+// (graphics.rs:310-321); the KIFS shader then switches on primitive_id per SDF call (kifs.wgsl:139-155).  Here both are
+// template parameters: launch(integral_constant<int, GROUP>, integral_constant<int, PRIM>) is called with the pair
+// that (group, primitive) stand for.  The Julia pipeline's PRIM slot is the build of its long-ray loop (see
+// KIFS_DIVSQRT_ORDINARY and KIFS_FAST_TRIP_X2_ in kifs_scene.hpp), `julia_slot` < JULIA_SLOTS, chosen by the caller;
+// slots at and above JULIA_SLOTS are not instantiated.
+template <int JULIA_SLOTS, class Launch>
+hipError_t dispatch_pipeline(uint32_t group, uint32_t primitive, uint32_t julia_slot, Launch&& launch) {
+    using std::integral_constant;
+    static_assert(JULIA_SLOTS == 2 || JULIA_SLOTS == 4, "sdf_iters <= 24, and the doubled orbit trip above it");
+    switch (group) {
+    case GROUP_JULIA:
+        if constexpr (JULIA_SLOTS == 4) {
+            if (julia_slot == 2) return launch(integral_constant<int, GROUP_JULIA>{}, integral_constant<int, 2>{});
+            if (julia_slot == 3) return launch(integral_constant<int, GROUP_JULIA>{}, integral_constant<int, 3>{});
+        }
+        if (julia_slot == 0) return launch(integral_constant<int, GROUP_JULIA>{}, integral_constant<int, 0>{});
+        if (julia_slot == 1) return launch(integral_constant<int, GROUP_JULIA>{}, integral_constant<int, 1>{});
+        return hipErrorInvalidValue;
+    case GROUP_GENJULIA: return launch(integral_constant<int, GROUP_GENJULIA>{}, integral_constant<int, 0>{});
+    case GROUP_KIFS:
+        switch (primitive) {
+        case PRIM_SPHERE: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_SPHERE>{});
+        case PRIM_CYLINDER: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_CYLINDER>{});
+        case PRIM_BOX: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_BOX>{});
+        case PRIM_TORUS: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_TORUS>{});
+        case PRIM_SIERPINSKI: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_SIERPINSKI>{});
+        case PRIM_BUNNY: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_BUNNY>{});
+        default: return launch(integral_constant<int, GROUP_KIFS>{}, integral_constant<int, PRIM_OTHER>{});  // kifs.wgsl:154
+        }
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// Before a launch of KERNEL with `bytes` of dynamic LDS: beyond the default limit of 48 KB the kernel has to opt in,
+// once per kernel AND per device (the attribute belongs to the device's copy of the code object).
+// (two contexts on two threads may come through here at once -- the header allows one caller thread per context --
+// hence atomics; setting the attribute twice is harmless, a torn flag would not be)
+template <void (*KERNEL)(const BatchParams)>
+hipError_t ensure_dynamic_lds(unsigned bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    static std::atomic<bool> opted_in[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
+        hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        if (attr != hipSuccess) return attr;
+        if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
 }
 
 // the bunny's kernels (kifs_bunny_kernels.hip), launched from launch_render's dispatch in kifs_kernels.hip

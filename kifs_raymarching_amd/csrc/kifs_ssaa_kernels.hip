@@ -23,10 +23,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     __shared__ uint32_t s_tile[TILE_H][TILE_W];
     __shared__ float s_acc[3][BLOCK];  // per lane: the running sums of its samples' linear colours
 
-    const uint32_t batch = uint32_t(B.count);
-    const uint32_t view = batch > 1 ? blockIdx.x % batch : 0u;
-    const uint32_t slot = batch > 1 ? blockIdx.x / batch : blockIdx.x;
-    const FrameParams P = batch_frame(B, view);
+    const TileFrame F = tile_frame(B, s_srgb);  // the OUTPUT tile and this lane's output pixel
+    const FrameParams& P = F.P;
+    const int tid = threadIdx.x;
+    const int x = F.x, y = F.y;
+    const bool valid = F.valid;
     // The virtual screen: height k H, same aspect float.  Only the wave-level quick cull is valid on it (with ITS
     // 1 / height); the tile-level cull's margin belongs to the pixel centres of a plain 32 x 8 tile.
     const int k = P.ssaa;  // uniform, 2..KIFS_MAX_SUPERSAMPLING
@@ -34,20 +35,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     V.height = float(k) * P.height;  // exact: integers below 2^24
     V.inv_height = P.ssaa_inv_height;
     V.counters = nullptr;  // (the per-wave diagnostics describe one march per wave)
-    const int tid = threadIdx.x;
-    const bool srgb = (P.encode == 1);
-    if (srgb) s_srgb[tid] = P.srgb_table[tid];
-
-    const int wave = tid >> 6, lane = tid & 63;
-    const int lx = (wave << 3) | (lane & 7);
-    const int ly = lane >> 3;
-    const uint32_t tile = P.tile_order[slot];  // scalar load: uniform per workgroup
-    const int tile_x = int(tile & 0xffffu) * TILE_W;
-    const int tile_y = int(tile >> 16) * TILE_H;        // row offset within the launch's rows
-    const int frame_y = tile_frame_row(P, tile >> 16);  // the tile's first frame row
-    const int x = tile_x + lx;
-    const int y = frame_y + ly;
-    const bool valid = (x < P.width) && (y < P.y1);
 
     // The resolve of the contract, per channel in f32: acc = c(0,0), then acc + c(i,j) with j outer and i inner
     // (-ffp-contract=off: no fma), mean = acc / k^2 correctly rounded.  A culled sample is the background colour.
@@ -73,14 +60,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     const float n = float(k * k);
     const V3 mean{s_acc[0][tid] / n, s_acc[1][tid] / n, s_acc[2][tid] / n};  // (a lane outside the frame: not stored)
     __syncthreads();  // s_srgb visible
-    s_tile[ly][lx] = encode_rgba(mean, srgb, s_srgb);
+    s_tile[F.ly][F.lx] = encode_rgba(mean, F.srgb, s_srgb);
     __syncthreads();
-
-    // store mapping: thread -> (tid & 31, tid >> 5): linear rows of 128 bytes
-    const int sx = tid & (TILE_W - 1), sy = tid >> 5;
-    const int ox = tile_x + sx;
-    if (ox < P.width && (frame_y + sy) < P.y1)
-        P.out[out_row(P, frame_y + sy, tile_y + sy) * P.pitch_words + ox] = s_tile[sy][sx];
+    store_tile(P, F.tile_x, F.tile_y, F.frame_y, s_tile, tid);
 }
 
 template <int GROUP, int PRIM>
@@ -95,23 +77,11 @@ static hipError_t launch(const BatchParams& B, hipStream_t stream) {
 hipError_t launch_ssaa(const BatchParams& B, uint32_t group, uint32_t primitive, hipStream_t stream) {
     const FrameParams& P = B.frame;
     if (P.ssaa < 2 || P.ssaa > 4) return hipErrorInvalidValue;
-    switch (group) {
-    case GROUP_JULIA:  // the short divide / square root by sdf_iters as launch_render; the doubled orbit trip is
-                       // the throughput kernels' only (launch_variant's LPRIM)
-        return P.sdf_iters <= 24 ? ssaa::launch<GROUP_JULIA, 1>(B, stream) : ssaa::launch<GROUP_JULIA, 0>(B, stream);
-    case GROUP_GENJULIA: return ssaa::launch<GROUP_GENJULIA, 0>(B, stream);
-    case GROUP_KIFS:
-        switch (primitive) {
-        case PRIM_SPHERE: return ssaa::launch<GROUP_KIFS, PRIM_SPHERE>(B, stream);
-        case PRIM_CYLINDER: return ssaa::launch<GROUP_KIFS, PRIM_CYLINDER>(B, stream);
-        case PRIM_BOX: return ssaa::launch<GROUP_KIFS, PRIM_BOX>(B, stream);
-        case PRIM_TORUS: return ssaa::launch<GROUP_KIFS, PRIM_TORUS>(B, stream);
-        case PRIM_SIERPINSKI: return ssaa::launch<GROUP_KIFS, PRIM_SIERPINSKI>(B, stream);
-        case PRIM_BUNNY: return ssaa::launch<GROUP_KIFS, PRIM_BUNNY>(B, stream);  // per-lane bunny_sdf: slow, correct
-        default: return ssaa::launch<GROUP_KIFS, PRIM_OTHER>(B, stream);  // kifs.wgsl:154
-        }
-    default: return hipErrorInvalidValue;
-    }
+    // Julia: the short divide / square root by sdf_iters; the doubled orbit trip is the throughput kernels' only
+    // (launch_variant's LPRIM).  The bunny: per-lane bunny_sdf -- slow, correct.
+    return dispatch_pipeline<2>(group, primitive, uint32_t(P.sdf_iters <= 24), [&](auto g, auto prim) {
+        return ssaa::launch<decltype(g)::value, decltype(prim)::value>(B, stream);
+    });
 }
 
 }  // namespace kifs
