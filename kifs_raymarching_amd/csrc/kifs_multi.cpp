@@ -22,6 +22,8 @@
 //   wait(j)     flush(j) if still pending; host waits for rendered and gathered of step j
 //
 // Nothing on a GPU waits for the host, and the host blocks only in flush (on work enqueued a step earlier).
+// In the code, submit is check_step, complete_slot(k - 2), erase_suffices, paint_background, submit_device per device
+// (abandon_step if one fails), advance_pipeline; flush is flush_slot; wait is flush_older, then complete_slot.
 // Host code only; kernels live in kifs_kernels.hip / kifs_support_kernels.hip.
 #include <hip/hip_runtime.h>
 
@@ -30,6 +32,7 @@
 #include <cstring>
 #include <algorithm>
 #include <new>
+#include <set>
 #include <vector>
 
 #include <dlfcn.h>
@@ -98,31 +101,54 @@ namespace {
 
 constexpr int SLOTS = 2;  // steps in flight
 
-// What one device contributes to one step (device 0, the root, uses only `stripes`, `rows`, ev0 / ev1).
+// A payload where it is packed and where it lands: both kifs_multi_render (one shard) and a step (`count` shards, or
+// the sparse records' receive side) own one per non-root device.
+struct Payload {
+    uint8_t* shard = nullptr;  // on the device: packed shards, rows x W x 4 each
+    uint8_t* recv = nullptr;   // on the root: the payload as received
+    size_t shard_bytes = 0, recv_bytes = 0;
+};
+
+// Everything one listed device has for as long as the object lives ([0] is the root).
+struct Device {
+    int id = -1;
+    kifs_ctx* ctx = nullptr;
+    int weight = 1;                        // its share (kifs_shard_stripes weights)
+    std::vector<int> stripes;              // its shard for the current frame height
+    int rows = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // kernel start/stop on its render stream (latest launch)
+    double shard_ms = -1.0;
+    hipStream_t comm_stream = nullptr;     // batched steps; the root's is the gather stream
+    ncclComm_t comm = nullptr;             // RCCL transport only
+    Payload lone;                          // kifs_multi_render (non-root)
+};
+
+// What one device contributes to one step (device 0, the root, uses only `stripes` and `rows`).
 struct PeerPart {
     std::vector<int> stripes;      // the device's shard when the step was submitted
     int rows = 0;
-    uint8_t* shard = nullptr;      // on the device: `count` packed shards, rows x W x 4 each
-    size_t shard_bytes = 0;
+    Payload buf;                   // `count` packed shards; received: the shards (dense) or the records (sparse)
     uint8_t* records = nullptr;    // on the device: the sparse payload
-    size_t records_bytes = 0;
     uint32_t* d_count = nullptr;   // on the device: number of records
     uint32_t* h_count = nullptr;   // pinned host copy
-    uint8_t* recv = nullptr;       // on the root: the payload as received
-    size_t recv_bytes = 0;
     hipEvent_t packed = nullptr;   // device's render stream: payload (and count) ready
     uint32_t n_records = 0;        // as flushed (sparse)
     size_t payload_bytes = 0;      // as flushed
+    size_t records_bytes = 0;      // allocated
 };
 
-struct StepSlot {
-    bool used = false;             // holds a step that has not been completed by a wait
-    bool flushed = false;
-    uint64_t step = 0;
+// What a step renders, and where to.
+struct StepShape {
     int count = 0, encode = 0, gather = 0, width = 0, height = 0;
     uint8_t* frames = nullptr;
     size_t pitch = 0, stride = 0;
     uint32_t background = 0;
+};
+
+struct StepSlot : StepShape {
+    bool used = false;             // holds a step that has not been completed by a wait
+    bool flushed = false;
+    uint64_t step = 0;
     bool background_known = false; // `frames` hold the background outside the records of `part` (sparse, flushed)
     bool overwritten = false;      // something else wrote into `frames` since this step was submitted
     std::vector<PeerPart> part;
@@ -131,31 +157,24 @@ struct StepSlot {
     hipEvent_t gathered = nullptr; // root gather stream: everybody else's are
 };
 
+// One entry of a group of transfers to the root: `bytes` (0: nothing) from `src`, readable after `ready` (null: at once).
+struct Transfer { const uint8_t* src; uint8_t* dst; size_t bytes; hipEvent_t ready; };
+
 }  // namespace
 
 struct kifs_multi {
-    std::vector<kifs_ctx*> ctx;
-    std::vector<int> dev;
-    std::vector<int> weight;               // share of each device (kifs_shard_stripes weights)
-    std::vector<std::vector<int>> stripes; // the shard of each device for the current frame height
-    std::vector<int> rows;
+    // never empty once created; the arrays ncclCommInitAll and kifs_shard_stripes want are built where they are called
+    std::vector<Device> dev;
     int stripes_height = -1;
-    std::vector<uint8_t*> shard;           // kifs_multi_render: per-device packed shard buffer (non-root)
-    std::vector<size_t> shard_bytes;
-    std::vector<uint8_t*> recv;            // kifs_multi_render: the same shards after the peer copy (on the root)
-    std::vector<size_t> recv_bytes;
-    std::vector<hipEvent_t> ev0, ev1;      // kernel start/stop on each device's stream (latest launch)
-    std::vector<double> shard_ms;
     uint8_t* root_frame = nullptr;         // staging frame on the root when the destination is host memory
     size_t root_frame_bytes = 0;
     // ---- batched steps
     int gather = KIFS_GATHER_SPARSE;
     int transport_wanted = KIFS_TRANSPORT_AUTO;
     int transport = KIFS_TRANSPORT_AUTO;   // decided at the first step (or by kifs_multi_set_gather)
-    std::vector<hipStream_t> comm_stream;  // per device; [0] is the root's gather stream
-    std::vector<ncclComm_t> comm;          // per device, RCCL transport only
     StepSlot slot[SLOTS];
     uint64_t next_step = 0;
+    bool streams_tried = false;            // ensure_streams has run (its outcome stands, as it always has)
     bool have_pending = false;             // a submitted step whose transfers are not posted yet
     uint64_t pending = 0;
     std::vector<uint8_t*> outs_scratch;    // destination pointers of one device's launch
@@ -164,37 +183,62 @@ struct kifs_multi {
 
 namespace {
 
-bool all_distinct(const std::vector<int>& v) {
-    for (size_t i = 0; i < v.size(); ++i)
-        for (size_t j = i + 1; j < v.size(); ++j)
-            if (v[i] == v[j]) return false;
-    return true;
+// The two sides of a payload, before they are needed, and both gone.  `shard` is grown and the payload freed under the
+// packing device; `recv` lives on the root.
+bool grow_shard(Payload& b, size_t need, const char* what) { return grow(b.shard, b.shard_bytes, need, what); }
+bool grow_recv(Payload& b, int root_id, size_t need, const char* what) {
+    if (need <= b.recv_bytes) return true;
+    DeviceGuard g(root_id);
+    return grow(b.recv, b.recv_bytes, need, what);
+}
+
+void free_payload(Payload& b, int root_id) {
+    if (b.shard) (void)hipFree(b.shard);
+    if (b.recv) {
+        DeviceGuard g(root_id);
+        (void)hipFree(b.recv);
+    }
+    b = Payload();
 }
 
 // (Re)deal the frame's stripes to the devices.
 int multi_partition(kifs_multi* m, int h) {
     if (m->stripes_height == h) return KIFS_OK;
-    const int n = int(m->ctx.size());
+    const int n = int(m->dev.size());
     const int all = (h + KIFS_STRIPE_ROWS - 1) / KIFS_STRIPE_ROWS;
+    std::vector<int> weights;
+    for (const Device& d : m->dev) weights.push_back(d.weight);
     for (int i = 0; i < n; ++i) {
-        m->stripes[size_t(i)].assign(size_t(all), 0);
-        int count = 0, rows = 0;
-        int st = kifs_shard_stripes(h, n, m->weight.data(), i, m->stripes[size_t(i)].data(), all, &count, &rows);
+        Device& d = m->dev[size_t(i)];
+        d.stripes.assign(size_t(all), 0);
+        int count = 0;
+        int st = kifs_shard_stripes(h, n, weights.data(), i, d.stripes.data(), all, &count, &d.rows);
         if (st != KIFS_OK) return st;
-        m->stripes[size_t(i)].resize(size_t(count));
-        m->rows[size_t(i)] = rows;
+        d.stripes.resize(size_t(count));
     }
     m->stripes_height = h;
     return KIFS_OK;
+}
+
+void destroy_comms(kifs_multi* m) {
+    for (Device& d : m->dev) {
+        if (!d.comm) continue;
+        if (const RcclApi* a = rccl()) (void)a->CommDestroy(d.comm);
+        d.comm = nullptr;
+    }
+    m->stats.comm_ranks = 0;
 }
 
 // Transport of the batched steps: decided once, communicators created on demand.
 int ensure_transport(kifs_multi* m) {
     if (m->transport != KIFS_TRANSPORT_AUTO) return KIFS_OK;
     const int n = int(m->dev.size());
+    std::vector<int> ids;
+    for (const Device& d : m->dev) ids.push_back(d.id);
+    const bool distinct = std::set<int>(ids.begin(), ids.end()).size() == ids.size();
     int want = m->transport_wanted;
     const bool automatic = want == KIFS_TRANSPORT_AUTO;
-    if (automatic) want = (n >= 2 && all_distinct(m->dev)) ? KIFS_TRANSPORT_RCCL : KIFS_TRANSPORT_COPY;
+    if (automatic) want = (n >= 2 && distinct) ? KIFS_TRANSPORT_RCCL : KIFS_TRANSPORT_COPY;
     if (want == KIFS_TRANSPORT_RCCL) {
         // An explicit KIFS_TRANSPORT_RCCL that cannot be had is an error; AUTO falls back to peer copies (a node
         // without a loadable librccl, or whose ncclCommInitAll fails, still gathers) and says so under KIFS_DEBUG
@@ -207,151 +251,164 @@ int ensure_transport(kifs_multi* m) {
         };
         int st = KIFS_OK;
         const RcclApi* a = nullptr;
-        if (!all_distinct(m->dev)) st = give_up("a device is listed twice (ncclCommInitAll refuses that)");
+        if (!distinct) st = give_up("a device is listed twice (ncclCommInitAll refuses that)");
         else if (!(a = rccl())) st = give_up("librccl could not be opened");
         else {
-            m->comm.assign(size_t(n), nullptr);
-            if (!nccl_ok(a->CommInitAll(m->comm.data(), n, m->dev.data()), "ncclCommInitAll")) {
-                m->comm.clear();
+            std::vector<ncclComm_t> comms(size_t(n), nullptr);
+            if (!nccl_ok(a->CommInitAll(comms.data(), n, ids.data()), "ncclCommInitAll")) {
                 (void)hipGetLastError();
                 st = give_up("ncclCommInitAll failed");
             } else {
+                for (int i = 0; i < n; ++i) m->dev[size_t(i)].comm = comms[size_t(i)];
                 m->stats.rccl_version = a->version;
                 m->stats.comm_ranks = n;
             }
         }
         if (st != KIFS_OK) return st;
     }
-    m->transport = want;
-    m->stats.transport = want;
+    m->transport = m->stats.transport = want;
     return KIFS_OK;
 }
 
 int ensure_streams(kifs_multi* m) {
-    if (!m->comm_stream.empty()) return KIFS_OK;
-    const size_t n = m->dev.size();
-    m->comm_stream.assign(n, nullptr);
-    for (size_t i = 0; i < n; ++i) {
-        DeviceGuard g(m->dev[i]);
-        if (!g.ok || !hip_ok(hipStreamCreateWithFlags(&m->comm_stream[i], hipStreamNonBlocking), "comm stream"))
+    if (m->streams_tried) return KIFS_OK;
+    m->streams_tried = true;
+    for (Device& d : m->dev) {
+        DeviceGuard g(d.id);
+        if (!g.ok || !hip_ok(hipStreamCreateWithFlags(&d.comm_stream, hipStreamNonBlocking), "comm stream"))
             return KIFS_ERR_RUNTIME;
     }
     return KIFS_OK;
 }
+
+inline int runtime_status(bool ok) { return ok ? KIFS_OK : KIFS_ERR_RUNTIME; }
 
 bool make_event(hipEvent_t& ev) {
     return ev || hip_ok(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate(multi)");
 }
 
-// One group of point-to-point transfers: device i's `src[i]` (bytes[i] > 0) -> the root's `dst[i]`.  `ready[i]` is
-// an event after which src[i] may be read.  The receives (or the copies) are enqueued on the root's gather stream,
-// so whatever follows there sees the data -- and once that has completed, every src[i] has been read.
-int transfer_to_root(kifs_multi* m, const std::vector<const uint8_t*>& src, const std::vector<uint8_t*>& dst,
-                     const std::vector<size_t>& bytes, const std::vector<hipEvent_t>& ready, bool include_root) {
-    const int n = int(m->dev.size());
-    hipStream_t gstream = m->comm_stream[0];
-    const int first = include_root ? 0 : 1;
+// One group of point-to-point transfers: device i's x[i].src (x[i].bytes > 0) -> the root's x[i].dst, once x[i].ready
+// has happened.  The receives (or the copies) are enqueued on the root's gather stream, so whatever follows there
+// sees the data -- and once that has completed, every src has been read.
+int transfer_to_root(kifs_multi* m, const std::vector<Transfer>& x, bool include_root) {
+    const size_t n = m->dev.size();
+    const Device& root = m->dev[0];
+    hipStream_t gstream = root.comm_stream;
+    const size_t first = include_root ? 0 : 1;
     if (m->transport == KIFS_TRANSPORT_RCCL) {
         const RcclApi* a = rccl();
-        if (!a || m->comm.size() != size_t(n)) return KIFS_ERR_COMM;
-        for (int i = first; i < n; ++i) {
-            if (!bytes[size_t(i)] || !ready[size_t(i)]) continue;
-            DeviceGuard g(m->dev[size_t(i)]);
-            hipStream_t s = i == 0 ? gstream : m->comm_stream[size_t(i)];
-            if (!hip_ok(hipStreamWaitEvent(s, ready[size_t(i)], 0), "wait(payload ready)")) return KIFS_ERR_RUNTIME;
+        if (!a || !root.comm) return KIFS_ERR_COMM;
+        for (size_t i = first; i < n; ++i) {
+            if (!x[i].bytes || !x[i].ready) continue;
+            DeviceGuard g(m->dev[i].id);
+            if (!hip_ok(hipStreamWaitEvent(m->dev[i].comm_stream, x[i].ready, 0), "wait(payload ready)")) return KIFS_ERR_RUNTIME;
         }
         if (!nccl_ok(a->GroupStart(), "ncclGroupStart")) return KIFS_ERR_COMM;
         bool ok = true;
-        for (int i = first; i < n && ok; ++i) {
-            if (!bytes[size_t(i)]) continue;
-            hipStream_t s = i == 0 ? gstream : m->comm_stream[size_t(i)];
-            ok = nccl_ok(a->Send(src[size_t(i)], bytes[size_t(i)], ncclUint8, 0, m->comm[size_t(i)], s), "ncclSend");
+        for (size_t i = first; i < n && ok; ++i) {
+            if (!x[i].bytes) continue;
+            ok = nccl_ok(a->Send(x[i].src, x[i].bytes, ncclUint8, 0, m->dev[i].comm, m->dev[i].comm_stream), "ncclSend");
         }
-        for (int i = first; i < n && ok; ++i) {
-            if (!bytes[size_t(i)]) continue;
-            ok = nccl_ok(a->Recv(dst[size_t(i)], bytes[size_t(i)], ncclUint8, i, m->comm[0], gstream), "ncclRecv");
+        for (size_t i = first; i < n && ok; ++i) {
+            if (!x[i].bytes) continue;
+            ok = nccl_ok(a->Recv(x[i].dst, x[i].bytes, ncclUint8, int(i), root.comm, gstream), "ncclRecv");
         }
         const bool ended = nccl_ok(a->GroupEnd(), "ncclGroupEnd");
         return ok && ended ? KIFS_OK : KIFS_ERR_COMM;
     }
     // COPY: the root pulls every payload with the copy engines, one peer copy each, on its gather stream
-    DeviceGuard g(m->dev[0]);
-    for (int i = first; i < n; ++i) {
-        if (!bytes[size_t(i)]) continue;
-        if (ready[size_t(i)] && !hip_ok(hipStreamWaitEvent(gstream, ready[size_t(i)], 0), "wait(payload ready)"))
-            return KIFS_ERR_RUNTIME;
-        const hipError_t e = m->dev[size_t(i)] == m->dev[0]
-                                 ? hipMemcpyAsync(dst[size_t(i)], src[size_t(i)], bytes[size_t(i)], hipMemcpyDeviceToDevice, gstream)
-                                 : hipMemcpyPeerAsync(dst[size_t(i)], m->dev[0], src[size_t(i)], m->dev[size_t(i)],
-                                                      bytes[size_t(i)], gstream);
+    DeviceGuard g(root.id);
+    for (size_t i = first; i < n; ++i) {
+        if (!x[i].bytes) continue;
+        if (x[i].ready && !hip_ok(hipStreamWaitEvent(gstream, x[i].ready, 0), "wait(payload ready)")) return KIFS_ERR_RUNTIME;
+        const hipError_t e = m->dev[i].id == root.id
+                                 ? hipMemcpyAsync(x[i].dst, x[i].src, x[i].bytes, hipMemcpyDeviceToDevice, gstream)
+                                 : hipMemcpyPeerAsync(x[i].dst, root.id, x[i].src, m->dev[i].id, x[i].bytes, gstream);
         if (!hip_ok(e, "peer copy of a payload")) return KIFS_ERR_COMM;
     }
     return KIFS_OK;
 }
 
+// The dense scatter, on the root: the packed shards at `src` (one per frame of `s`, `shard_stride` apart) go to their
+// stripes' rows of the frames.
+int unpack_dense(const Device& root, hipStream_t stream, const StepShape& s, const uint8_t* src, size_t shard_stride,
+                 const std::vector<int>& stripes) {
+    const RowTable* rows = row_table(root.ctx, stripes.data(), int(stripes.size()), s.height);
+    if (!rows) return KIFS_ERR_RUNTIME;
+    return runtime_status(hip_ok(kifs::launch_unpack_stripes(s.frames, s.pitch, s.stride, src, size_t(s.width) * 4, shard_stride, rows->d_rows,
+                                                             int(stripes.size()), s.count, s.width, s.height, stream),
+                                 "unpack_stripes_kernel launch"));
+}
+
+// The sparse scatter, on the root's gather stream: the records received from `p` go to their tiles of the frames of
+// `s` -- or, to erase them, the background does.
+int unpack_records(const Device& root, const StepShape& s, const PeerPart& p, int erase, const char* what) {
+    const RowTable* rows = row_table(root.ctx, p.stripes.data(), int(p.stripes.size()), s.height);
+    if (!rows) return KIFS_ERR_RUNTIME;
+    return runtime_status(hip_ok(kifs::launch_unpack_sparse(s.frames, s.pitch, s.stride, reinterpret_cast<const uint32_t*>(p.buf.recv),
+                                                            p.n_records, rows->d_rows, int(p.stripes.size()), s.count, s.width, s.height,
+                                                            erase, erase ? s.background : 0u, root.comm_stream), what));
+}
+
+// The most records a device can pack for a step: one per tile of its shard of every frame.
+inline size_t record_capacity(const StepShape& s, const PeerPart& p) {
+    return size_t(s.count) * p.stripes.size() * size_t((s.width + kifs::TILE_W - 1) / kifs::TILE_W);
+}
+
 // Posts the transfers of the step in `sl` and the root's scatter of what arrives.
 int flush_slot(kifs_multi* m, StepSlot& sl) {
     if (!sl.used || sl.flushed) return KIFS_OK;
-    const int n = int(m->dev.size());
+    const size_t n = m->dev.size();
     const size_t row_bytes = size_t(sl.width) * 4;
     const bool sparse = sl.gather == KIFS_GATHER_SPARSE;
-    std::vector<const uint8_t*> src(size_t(n), nullptr);
-    std::vector<uint8_t*> dst(size_t(n), nullptr);
-    std::vector<size_t> bytes(size_t(n), 0);
-    std::vector<hipEvent_t> ready(size_t(n), nullptr);
+    std::vector<Transfer> x(n);
     uint64_t records = 0, tiles = 0, payload = 0;
-    for (int i = 1; i < n; ++i) {
-        PeerPart& p = sl.part[size_t(i)];
-        p.n_records = 0;
-        p.payload_bytes = 0;
+    for (size_t i = 1; i < n; ++i) {
+        PeerPart& p = sl.part[i];
+        p.n_records = 0, p.payload_bytes = 0;
         if (p.stripes.empty()) continue;
         if (sparse) {
             // the count was copied to pinned memory before `packed` was recorded
             if (!hip_ok(hipEventSynchronize(p.packed), "wait(packed)")) return KIFS_ERR_RUNTIME;
-            const size_t capacity = size_t(sl.count) * p.stripes.size() * size_t((sl.width + kifs::TILE_W - 1) / kifs::TILE_W);
+            const size_t capacity = record_capacity(sl, p);
             if (*p.h_count > capacity) return KIFS_ERR_RUNTIME;
             p.n_records = *p.h_count;
             p.payload_bytes = size_t(p.n_records) * KIFS_SPARSE_RECORD_BYTES;
-            src[size_t(i)] = p.records;
             records += p.n_records;
             tiles += capacity;
         } else {
             p.payload_bytes = size_t(sl.count) * size_t(p.rows) * row_bytes;
-            src[size_t(i)] = p.shard;
         }
-        dst[size_t(i)] = p.recv;
-        bytes[size_t(i)] = p.payload_bytes;
-        ready[size_t(i)] = p.packed;
+        x[i] = Transfer{sparse ? p.records : p.buf.shard, p.buf.recv, p.payload_bytes, p.packed};
         payload += p.payload_bytes;
     }
-    int st = transfer_to_root(m, src, dst, bytes, ready, false);
+    int st = transfer_to_root(m, x, false);
     if (st != KIFS_OK) return st;
     m->stats.records_received += records;  // (counted once the transfers are posted: a failed flush that is
     m->stats.tiles_covered += tiles;       // tried again must not count twice)
     m->stats.bytes_received += payload;
     {   // the root moves what arrived to its rows of the frames
-        DeviceGuard g(m->dev[0]);
-        kifs_ctx* root = m->ctx[0];
-        hipStream_t gstream = m->comm_stream[0];
-        for (int i = 1; i < n; ++i) {
-            PeerPart& p = sl.part[size_t(i)];
+        const Device& root = m->dev[0];
+        DeviceGuard g(root.id);
+        for (size_t i = 1; i < n; ++i) {
+            PeerPart& p = sl.part[i];
             if (!p.payload_bytes) continue;
-            const RowTable* rows = row_table(root, p.stripes.data(), int(p.stripes.size()), sl.height);
-            if (!rows) return KIFS_ERR_RUNTIME;
-            const hipError_t e =
-                sparse ? kifs::launch_unpack_sparse(sl.frames, sl.pitch, sl.stride, reinterpret_cast<const uint32_t*>(p.recv),
-                                                    p.n_records, rows->d_rows, int(p.stripes.size()), sl.count, sl.width,
-                                                    sl.height, 0, 0u, gstream)
-                       : kifs::launch_unpack_stripes(sl.frames, sl.pitch, sl.stride, p.recv, row_bytes, size_t(p.rows) * row_bytes,
-                                                     rows->d_rows, int(p.stripes.size()), sl.count, sl.width, sl.height, gstream);
-            if (!hip_ok(e, "scatter of a received payload")) return KIFS_ERR_RUNTIME;
+            st = sparse ? unpack_records(root, sl, p, 0, "scatter of a received payload")
+                        : unpack_dense(root, root.comm_stream, sl, p.buf.recv, size_t(p.rows) * row_bytes, p.stripes);
+            if (st != KIFS_OK) return st;
         }
-        if (!hip_ok(hipEventRecord(sl.gathered, gstream), "record(gathered)")) return KIFS_ERR_RUNTIME;
+        if (!hip_ok(hipEventRecord(sl.gathered, root.comm_stream), "record(gathered)")) return KIFS_ERR_RUNTIME;
     }
     sl.flushed = true;
     sl.background_known = sparse && !sl.overwritten;
     if (m->have_pending && m->pending == sl.step) m->have_pending = false;
     return KIFS_OK;
+}
+
+// An older step that is still unflushed goes before `step`: the gather stream runs them in order.
+int flush_older(kifs_multi* m, uint64_t step) {
+    StepSlot& other = m->slot[(step + 1) % SLOTS];
+    return other.used && other.step < step ? flush_slot(m, other) : int(KIFS_OK);
 }
 
 // Host-side completion of a slot's step (flushes it first if need be).
@@ -368,19 +425,25 @@ int complete_slot(kifs_multi* m, StepSlot& sl) {
 
 int drain(kifs_multi* m) {
     // oldest first: a step's erase may depend on the step before it in the gather stream
-    StepSlot* order[SLOTS];
-    for (int s = 0; s < SLOTS; ++s) order[s] = &m->slot[s];
-    std::sort(order, order + SLOTS, [](const StepSlot* a, const StepSlot* b) { return a->step < b->step; });
-    for (StepSlot* sl : order) {
-        int st = complete_slot(m, *sl);
-        if (st != KIFS_OK) return st;
-    }
-    return KIFS_OK;
+    static_assert(SLOTS == 2, "drain orders two slots");
+    const int first = m->slot[1].step < m->slot[0].step ? 1 : 0;
+    int st = complete_slot(m, m->slot[first]);
+    return st != KIFS_OK ? st : complete_slot(m, m->slot[1 - first]);
+}
+
+// Uniform changes apply to the steps submitted afterwards; steps in flight are completed first (their buffers and
+// row partition belong to the old settings).
+template <class Call>
+int forward(kifs_multi* m, Call call) {
+    if (!m) return KIFS_ERR_BAD_ARG;
+    int st = drain(m);
+    for (size_t i = 0; st == KIFS_OK && i < m->dev.size(); ++i) st = call(m->dev[i].ctx);
+    return st;
 }
 
 // [frames, end) of what a step writes
-inline const uint8_t* frames_end(const uint8_t* frames, int count, size_t pitch, size_t stride, int width, int height) {
-    return frames + size_t(count - 1) * stride + size_t(height - 1) * pitch + size_t(width) * 4;
+inline const uint8_t* frames_end(const StepShape& s) {
+    return s.frames + size_t(s.count - 1) * s.stride + size_t(s.height - 1) * s.pitch + size_t(s.width) * 4;
 }
 
 // Something is about to write [lo, hi) on the root: a slot whose frames overlap that range no longer knows that they
@@ -389,9 +452,7 @@ inline const uint8_t* frames_end(const uint8_t* frames, int count, size_t pitch,
 void forget_background(kifs_multi* m, const StepSlot* except, const uint8_t* lo, const uint8_t* hi) {
     for (StepSlot& o : m->slot) {
         if (&o == except || !o.frames || o.count < 1) continue;
-        const uint8_t* olo = o.frames;
-        const uint8_t* ohi = frames_end(o.frames, o.count, o.pitch, o.stride, o.width, o.height);
-        if (lo < ohi && olo < hi) {
+        if (lo < frames_end(o) && o.frames < hi) {
             o.background_known = false;
             o.overwritten = true;  // (also for a flush of that slot's step that is still to come)
         }
@@ -401,26 +462,191 @@ void forget_background(kifs_multi* m, const StepSlot* except, const uint8_t* lo,
 void free_slot(kifs_multi* m, StepSlot& sl) {
     for (size_t i = 0; i < sl.part.size(); ++i) {
         PeerPart& p = sl.part[i];
-        {
-            DeviceGuard g(m->dev[i]);
-            if (p.shard) (void)hipFree(p.shard);
-            if (p.records) (void)hipFree(p.records);
-            if (p.d_count) (void)hipFree(p.d_count);
-            if (p.h_count) (void)hipHostFree(p.h_count);
-            if (p.packed) (void)hipEventDestroy(p.packed);
-        }
-        if (p.recv) {
-            DeviceGuard g(m->dev[0]);
-            (void)hipFree(p.recv);
-        }
+        DeviceGuard g(m->dev[i].id);
+        free_payload(p.buf, m->dev[0].id);
+        if (p.records) (void)hipFree(p.records);
+        if (p.d_count) (void)hipFree(p.d_count);
+        if (p.h_count) (void)hipHostFree(p.h_count);
+        if (p.packed) (void)hipEventDestroy(p.packed);
     }
-    if (!m->dev.empty()) {
-        DeviceGuard g(m->dev[0]);
+    if (sl.rendered || sl.gathered) {
+        DeviceGuard g(m->dev[0].id);
         if (sl.rendered) (void)hipEventDestroy(sl.rendered);
         if (sl.gathered) (void)hipEventDestroy(sl.gathered);
     }
     sl = StepSlot();
 }
+
+// A Device is filled and emptied as a unit -- but for its context, which comes first and goes last.
+int open_device(Device& d, int id, int root_id) {
+    int st = KIFS_OK;
+    d.id = id;
+    d.ctx = kifs_create(id, &st);
+    if (!d.ctx) return st;
+    DeviceGuard g(id);
+    if (hipEventCreate(&d.ev0) != hipSuccess || hipEventCreate(&d.ev1) != hipSuccess) return KIFS_ERR_DEVICE_INIT;
+    if (id != root_id) {  // direct xGMI access both ways; failure only means staged copies
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, id, root_id) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(root_id, 0);
+        (void)hipGetLastError();
+    }
+    return KIFS_OK;
+}
+
+void close_device(Device& d, int root_id) {
+    if (!d.ctx) return;  // (nothing else is made without it)
+    DeviceGuard g(d.id);
+    if (d.comm_stream) (void)hipStreamDestroy(d.comm_stream);
+    free_payload(d.lone, root_id);
+    if (d.ev0) (void)hipEventDestroy(d.ev0);
+    if (d.ev1) (void)hipEventDestroy(d.ev1);
+}
+
+// ---- a submission, piece by piece.  The argument and size checks; `now` is the step they describe.
+int check_step(kifs_multi* m, int count, const KifsCameraUniform* cameras, uint8_t* dev_frames, size_t frame_pitch,
+               size_t frame_stride, int encode, StepShape* now) {
+    if (!m || !cameras || !dev_frames || count < 1 || count > KIFS_MAX_BATCH) return KIFS_ERR_BAD_ARG;
+    if (encode != KIFS_ENCODE_UNORM && encode != KIFS_ENCODE_SRGB) return KIFS_ERR_BAD_ARG;
+    const Device& root = m->dev[0];
+    if (!root.ctx->have_screen || !root.ctx->have_options) return KIFS_ERR_UNCONFIGURED;
+    int w, h;
+    int st = render_dims(root.ctx, &w, &h);
+    if (st != KIFS_OK) return st;
+    const size_t row_bytes = size_t(w) * 4;
+    if (frame_pitch < row_bytes || ((frame_pitch | frame_stride) & 3u) || (reinterpret_cast<uintptr_t>(dev_frames) & 3u) ||
+        (count > 1 && frame_stride < frame_pitch * size_t(h - 1) + row_bytes))
+        return KIFS_ERR_BAD_SIZE;
+    DeviceGuard g(root.id);
+    if (!g.ok) return KIFS_ERR_RUNTIME;
+    if (!is_device_pointer(dev_frames)) return KIFS_ERR_BAD_ARG;
+    const float* bc = root.ctx->options.background_color;
+    *now = StepShape{count, encode, m->gather, w, h, dev_frames, frame_pitch, frame_stride,
+                     background_pixel(root.ctx, kifs::V3{bc[0], bc[1], bc[2]}, encode)};
+    return KIFS_OK;
+}
+
+// May the frames be assumed to hold the background everywhere but under the slot's last records?  Decided from the
+// slot's record of its previous step and the step that is about to take its place, nothing else.
+bool erase_suffices(const kifs_multi* m, const StepSlot& sl, const StepShape& now, int flags) {
+    if (now.gather != KIFS_GATHER_SPARSE || !(flags & KIFS_MULTI_FRAMES_UNTOUCHED) || !sl.background_known) return false;
+    if (sl.part.size() != m->dev.size()) return false;
+    for (size_t i = 0; i < sl.part.size(); ++i)
+        if (sl.part[i].stripes != m->dev[i].stripes) return false;
+    return sl.frames == now.frames && sl.pitch == now.pitch && sl.stride == now.stride && sl.count == now.count &&
+           sl.encode == now.encode && sl.background == now.background && sl.width == now.width && sl.height == now.height &&
+           sl.gather == now.gather;
+}
+
+// The root's gather stream: background under everybody else's rows of the frames of `now` -- an erase under the
+// records the slot still holds of its previous step, or a fill of every such row.
+int paint_background(kifs_multi* m, StepSlot& sl, const StepShape& now, bool erase_only) {
+    const Device& root = m->dev[0];
+    DeviceGuard g(root.id);
+    if (erase_only) {
+        int st = KIFS_OK;
+        for (size_t i = 1; st == KIFS_OK && i < sl.part.size(); ++i)
+            if (sl.part[i].n_records) st = unpack_records(root, now, sl.part[i], 1, "erase of the previous records");
+        return st;
+    }
+    sl.peer_stripes.clear();
+    for (size_t i = 1; i < m->dev.size(); ++i)
+        sl.peer_stripes.insert(sl.peer_stripes.end(), m->dev[i].stripes.begin(), m->dev[i].stripes.end());
+    std::sort(sl.peer_stripes.begin(), sl.peer_stripes.end());
+    if (sl.peer_stripes.empty()) return KIFS_OK;
+    const RowTable* rows = row_table(root.ctx, sl.peer_stripes.data(), int(sl.peer_stripes.size()), now.height);
+    if (!rows) return KIFS_ERR_RUNTIME;
+    return runtime_status(hip_ok(kifs::launch_fill_stripes(now.frames, now.pitch, now.stride, rows->d_rows, int(sl.peer_stripes.size()),
+                                                           now.count, now.width, now.height, now.background, root.comm_stream),
+                                 "fill under the other devices' rows"));
+}
+
+// One device's part of the step in `sl`: one launch for its shard of all the step's frames (the root: in place, then
+// `rendered`), then its payload and `packed`.
+int submit_device(kifs_multi* m, StepSlot& sl, size_t i, const KifsCameraUniform* cameras) {
+    Device& d = m->dev[i];
+    PeerPart& p = sl.part[i];
+    const bool is_root = i == 0, sparse = sl.gather == KIFS_GATHER_SPARSE;
+    hipStream_t stream = d.ctx->stream;
+    p.stripes = d.stripes;
+    p.rows = d.rows;
+    p.n_records = 0, p.payload_bytes = 0;
+    DeviceGuard g(d.id);
+    if (!g.ok) return KIFS_ERR_RUNTIME;
+    d.shard_ms = -1.0;
+    if (p.stripes.empty()) return runtime_status(!is_root || hip_ok(hipEventRecord(sl.rendered, stream), "record(rendered)"));
+    const size_t row_bytes = size_t(sl.width) * 4, shard_stride = size_t(p.rows) * row_bytes;
+    if (is_root) {
+        for (int f = 0; f < sl.count; ++f) m->outs_scratch[size_t(f)] = sl.frames + size_t(f) * sl.stride;
+    } else {
+        const size_t need = shard_stride * size_t(sl.count);
+        const size_t record_bytes = record_capacity(sl, p) * KIFS_SPARSE_RECORD_BYTES;
+        if (!make_event(p.packed)) return KIFS_ERR_RUNTIME;
+        // buffers that grow are replaced while nothing reads them: the slot's previous step is complete, and its
+        // completion includes the root's scatter, which follows the transfer in the gather stream
+        if (!grow_shard(p.buf, need, "hipMalloc(step shards)")) return KIFS_ERR_RUNTIME;
+        if (sparse) {
+            if (!grow(p.records, p.records_bytes, record_bytes, "hipMalloc(step records)")) return KIFS_ERR_RUNTIME;
+            if (!p.d_count && !hip_ok(hipMalloc(reinterpret_cast<void**>(&p.d_count), sizeof(uint32_t)), "hipMalloc(record count)"))
+                return KIFS_ERR_RUNTIME;
+            if (!p.h_count && !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&p.h_count), sizeof(uint32_t), hipHostMallocDefault),
+                                      "hipHostMalloc(record count)"))
+                return KIFS_ERR_RUNTIME;
+        }
+        if (!grow_recv(p.buf, m->dev[0].id, sparse ? record_bytes : need, "hipMalloc(step receive)")) return KIFS_ERR_RUNTIME;
+        for (int f = 0; f < sl.count; ++f) m->outs_scratch[size_t(f)] = p.buf.shard + size_t(f) * shard_stride;
+    }
+    if (!hip_ok(hipEventRecord(d.ev0, stream), "record(launch start)")) return KIFS_ERR_RUNTIME;
+    int st = enqueue_batch(d.ctx, stream, sl.count, cameras, m->outs_scratch.data(), is_root ? sl.pitch : row_bytes, 0, sl.height,
+                           sl.encode, p.stripes.data(), int(p.stripes.size()), is_root ? 1 : 0);
+    if (st != KIFS_OK) return st;
+    if (!hip_ok(hipEventRecord(d.ev1, stream), "record(launch stop)")) return KIFS_ERR_RUNTIME;
+    if (is_root) return runtime_status(hip_ok(hipEventRecord(sl.rendered, stream), "record(rendered)"));
+    if (sparse) {
+        const RowTable* rows = row_table(d.ctx, p.stripes.data(), int(p.stripes.size()), sl.height);
+        if (!rows) return KIFS_ERR_RUNTIME;
+        if (!hip_ok(hipMemsetAsync(p.d_count, 0, sizeof(uint32_t), stream), "memset(record count)") ||
+            !hip_ok(kifs::launch_pack_sparse(p.buf.shard, row_bytes, shard_stride, rows->d_rows, int(p.stripes.size()), sl.count,
+                                             sl.width, sl.height, sl.background, reinterpret_cast<uint32_t*>(p.records), p.d_count,
+                                             stream), "pack_sparse_kernel launch") ||
+            !hip_ok(hipMemcpyAsync(p.h_count, p.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "copy(record count)"))
+            return KIFS_ERR_RUNTIME;
+    }
+    return runtime_status(hip_ok(hipEventRecord(p.packed, stream), "record(packed)"));
+}
+
+// A step that was only partly enqueued is no step: whatever was launched is waited for (it writes into the caller's
+// frames and the slot's buffers), the slot is free again, the step number is not used up -- a later submit, wait or
+// destroy must not flush record counts and events of a launch that never happened.
+int abandon_step(kifs_multi* m, StepSlot& sl, int st) {
+    for (Device& d : m->dev) {
+        DeviceGuard g(d.id);
+        (void)hipStreamSynchronize(d.ctx->stream);
+    }
+    DeviceGuard g(m->dev[0].id);
+    (void)hipStreamSynchronize(m->dev[0].comm_stream);
+    (void)hipGetLastError();
+    sl.used = sl.flushed = sl.background_known = false;
+    return st;
+}
+
+// The pipeline after the step in `sl` has been enqueued: the step before it is flushed -- its senders have had a
+// whole submission to pack -- and this one becomes the pending one.
+int advance_pipeline(kifs_multi* m, StepSlot& sl) {
+    if (m->have_pending) {
+        StepSlot& prev = m->slot[m->pending % SLOTS];
+        int st = KIFS_OK;
+        if (prev.used && prev.step == m->pending && (st = flush_slot(m, prev)) != KIFS_OK) return st;
+        m->have_pending = false;
+    }
+    if (!sl.flushed) {
+        m->have_pending = true;
+        m->pending = sl.step;
+    }
+    return KIFS_OK;
+}
+
+// what device i sends in kifs_multi_comm_selftest
+inline uint8_t selftest_byte(size_t k, size_t i) { return uint8_t((k * 131u + i * 29u + 7u) & 255u); }
 
 }  // namespace
 
@@ -429,33 +655,20 @@ extern "C" {
 void kifs_multi_destroy(kifs_multi* m) {
     if (!m) return;
     (void)drain(m);
-    for (size_t i = 0; i < m->ctx.size(); ++i) {
-        if (!m->ctx[i]) continue;
-        DeviceGuard g(m->dev[i]);
-        (void)hipStreamSynchronize(m->ctx[i]->stream);
-        if (i < m->comm_stream.size() && m->comm_stream[i]) (void)hipStreamSynchronize(m->comm_stream[i]);
+    for (Device& d : m->dev) {
+        if (!d.ctx) continue;
+        DeviceGuard g(d.id);
+        (void)hipStreamSynchronize(d.ctx->stream);
+        if (d.comm_stream) (void)hipStreamSynchronize(d.comm_stream);
     }
-    if (!m->comm.empty()) {
-        const RcclApi* a = rccl();
-        for (ncclComm_t c : m->comm)
-            if (a && c) (void)a->CommDestroy(c);
-    }
+    destroy_comms(m);
     for (StepSlot& sl : m->slot) free_slot(m, sl);
-    for (size_t i = 0; i < m->ctx.size(); ++i) {
-        if (!m->ctx[i]) continue;
-        DeviceGuard g(m->dev[i]);
-        if (i < m->comm_stream.size() && m->comm_stream[i]) (void)hipStreamDestroy(m->comm_stream[i]);
-        if (i < m->shard.size() && m->shard[i]) (void)hipFree(m->shard[i]);
-        if (i < m->ev0.size() && m->ev0[i]) (void)hipEventDestroy(m->ev0[i]);
-        if (i < m->ev1.size() && m->ev1[i]) (void)hipEventDestroy(m->ev1[i]);
+    for (Device& d : m->dev) close_device(d, m->dev[0].id);
+    if (m->root_frame) {
+        DeviceGuard g(m->dev[0].id);
+        (void)hipFree(m->root_frame);
     }
-    if (!m->dev.empty()) {
-        DeviceGuard g(m->dev[0]);
-        for (uint8_t* r : m->recv)
-            if (r) (void)hipFree(r);
-        if (m->root_frame) (void)hipFree(m->root_frame);
-    }
-    for (kifs_ctx* c : m->ctx) kifs_destroy(c);
+    for (Device& d : m->dev) kifs_destroy(d.ctx);
     delete m;
 }
 
@@ -468,63 +681,28 @@ kifs_multi* kifs_multi_create(const int* devices, int n, int* status) {
     if (!devices || n <= 0 || n > 64) return fail(KIFS_ERR_BAD_ARG, nullptr);
     kifs_multi* m = new (std::nothrow) kifs_multi();
     if (!m) return fail(KIFS_ERR_DEVICE_INIT, nullptr);
-    const size_t N = size_t(n);
-    m->weight.assign(N, 1);
-    m->stripes.assign(N, {});
-    m->rows.assign(N, 0);
-    m->shard.assign(N, nullptr);
-    m->shard_bytes.assign(N, 0);
-    m->recv.assign(N, nullptr);
-    m->recv_bytes.assign(N, 0);
-    m->ev0.assign(N, nullptr);
-    m->ev1.assign(N, nullptr);
-    m->shard_ms.assign(N, -1.0);
     m->stats.gather = m->gather;
+    m->dev.reserve(size_t(n));
     for (int i = 0; i < n; ++i) {
-        int st = KIFS_OK;
-        kifs_ctx* c = kifs_create(devices[i], &st);
-        if (!c) return fail(st, m);
-        m->ctx.push_back(c);
-        m->dev.push_back(devices[i]);
-        DeviceGuard g(devices[i]);
-        if (hipEventCreate(&m->ev0[size_t(i)]) != hipSuccess || hipEventCreate(&m->ev1[size_t(i)]) != hipSuccess)
-            return fail(KIFS_ERR_DEVICE_INIT, m);
-        if (devices[i] != devices[0]) {  // direct xGMI access both ways; failure only means staged copies
-            int can = 0;
-            if (hipDeviceCanAccessPeer(&can, devices[i], devices[0]) == hipSuccess && can)
-                (void)hipDeviceEnablePeerAccess(devices[0], 0);
-            (void)hipGetLastError();
-        }
+        m->dev.emplace_back();
+        int st = open_device(m->dev.back(), devices[i], devices[0]);
+        if (st != KIFS_OK) return fail(st, m);
     }
     if (status) *status = KIFS_OK;
     return m;
 }
 
-// Uniform changes apply to the steps submitted afterwards; steps in flight are completed first (their buffers and
-// row partition belong to the old settings).
-#define KIFS_MULTI_FORWARD(call)                 \
-    if (!m) return KIFS_ERR_BAD_ARG;             \
-    {                                            \
-        int dst_ = drain(m);                     \
-        if (dst_ != KIFS_OK) return dst_;        \
-    }                                            \
-    for (kifs_ctx* c : m->ctx) {                 \
-        int st = (call);                         \
-        if (st != KIFS_OK) return st;            \
-    }                                            \
-    return KIFS_OK;
-
-int kifs_multi_set_screen(kifs_multi* m, const KifsScreenUniform* s) { KIFS_MULTI_FORWARD(kifs_set_screen(c, s)) }
-int kifs_multi_set_camera(kifs_multi* m, const KifsCameraUniform* cam) { KIFS_MULTI_FORWARD(kifs_set_camera(c, cam)) }
-int kifs_multi_set_options(kifs_multi* m, const KifsOptionsUniform* o) { KIFS_MULTI_FORWARD(kifs_set_options(c, o)) }
-int kifs_multi_set_iters(kifs_multi* m, int a, int b, int f) { KIFS_MULTI_FORWARD(kifs_set_iters(c, a, b, f)) }
-int kifs_multi_set_extensions(kifs_multi* m, const KifsExtensions* e) { KIFS_MULTI_FORWARD(kifs_set_extensions(c, e)) }
-int kifs_multi_set_supersampling(kifs_multi* m, int k) { KIFS_MULTI_FORWARD(kifs_set_supersampling(c, k)) }
+int kifs_multi_set_screen(kifs_multi* m, const KifsScreenUniform* s) { return forward(m, [=](kifs_ctx* c) { return kifs_set_screen(c, s); }); }
+int kifs_multi_set_camera(kifs_multi* m, const KifsCameraUniform* s) { return forward(m, [=](kifs_ctx* c) { return kifs_set_camera(c, s); }); }
+int kifs_multi_set_options(kifs_multi* m, const KifsOptionsUniform* s) { return forward(m, [=](kifs_ctx* c) { return kifs_set_options(c, s); }); }
+int kifs_multi_set_iters(kifs_multi* m, int a, int b, int f) { return forward(m, [=](kifs_ctx* c) { return kifs_set_iters(c, a, b, f); }); }
+int kifs_multi_set_extensions(kifs_multi* m, const KifsExtensions* e) { return forward(m, [=](kifs_ctx* c) { return kifs_set_extensions(c, e); }); }
+int kifs_multi_set_supersampling(kifs_multi* m, int k) { return forward(m, [=](kifs_ctx* c) { return kifs_set_supersampling(c, k); }); }
 
 int kifs_multi_set_weights(kifs_multi* m, const int* weights) {
     if (!m) return KIFS_ERR_BAD_ARG;
     long long total = 0;
-    for (size_t i = 0; i < m->ctx.size(); ++i) {
+    for (size_t i = 0; i < m->dev.size(); ++i) {
         const int w = weights ? weights[i] : 1;
         if (w < 0 || w > (1 << 20)) return KIFS_ERR_BAD_ARG;
         total += w;
@@ -532,59 +710,55 @@ int kifs_multi_set_weights(kifs_multi* m, const int* weights) {
     if (total <= 0) return KIFS_ERR_BAD_ARG;
     int st = drain(m);
     if (st != KIFS_OK) return st;
-    for (size_t i = 0; i < m->ctx.size(); ++i) m->weight[i] = weights ? weights[i] : 1;
+    for (size_t i = 0; i < m->dev.size(); ++i) m->dev[i].weight = weights ? weights[i] : 1;
     m->stripes_height = -1;
     return KIFS_OK;
 }
 
 int kifs_multi_shard(kifs_multi* m, int i, int* device, int* n_stripes, int* rows) {
-    if (!m || i < 0 || size_t(i) >= m->ctx.size()) return KIFS_ERR_BAD_ARG;
+    if (!m || i < 0 || size_t(i) >= m->dev.size()) return KIFS_ERR_BAD_ARG;
     int w, h;
-    if (!m->ctx[0]->have_screen) return KIFS_ERR_UNCONFIGURED;
-    int st = frame_dims(m->ctx[0], &w, &h);
-    if (st != KIFS_OK) return st;
-    st = multi_partition(m, h);
-    if (st != KIFS_OK) return st;
-    if (device) *device = m->dev[size_t(i)];
-    if (n_stripes) *n_stripes = int(m->stripes[size_t(i)].size());
-    if (rows) *rows = m->rows[size_t(i)];
+    if (!m->dev[0].ctx->have_screen) return KIFS_ERR_UNCONFIGURED;
+    int st = frame_dims(m->dev[0].ctx, &w, &h);
+    if (st != KIFS_OK || (st = multi_partition(m, h)) != KIFS_OK) return st;
+    const Device& d = m->dev[size_t(i)];
+    if (device) *device = d.id;
+    if (n_stripes) *n_stripes = int(d.stripes.size());
+    if (rows) *rows = d.rows;
     return KIFS_OK;
 }
 
 double kifs_multi_shard_ms(kifs_multi* m, int i) {
-    if (!m || i < 0 || size_t(i) >= m->shard_ms.size()) return -1.0;
+    if (!m || i < 0 || size_t(i) >= m->dev.size()) return -1.0;
+    Device& d = m->dev[size_t(i)];
     // batched steps leave their launches' event pairs behind: resolved here, once they have completed
-    if (m->shard_ms[size_t(i)] < 0.0 && m->ev0[size_t(i)] && m->ev1[size_t(i)]) {
-        DeviceGuard g(m->dev[size_t(i)]);
+    if (d.shard_ms < 0.0 && d.ev0 && d.ev1) {
+        DeviceGuard g(d.id);
         float ms = 0.0f;
-        if (hipEventQuery(m->ev1[size_t(i)]) == hipSuccess && hipEventElapsedTime(&ms, m->ev0[size_t(i)], m->ev1[size_t(i)]) == hipSuccess)
-            m->shard_ms[size_t(i)] = double(ms);
+        if (hipEventQuery(d.ev1) == hipSuccess && hipEventElapsedTime(&ms, d.ev0, d.ev1) == hipSuccess) d.shard_ms = double(ms);
         (void)hipGetLastError();
     }
-    return m->shard_ms[size_t(i)];
+    return d.shard_ms;
 }
 
 int kifs_multi_render(kifs_multi* m, uint8_t* out, size_t pitch, int encode) {
     if (!m || !out) return KIFS_ERR_BAD_ARG;
-    kifs_ctx* root = m->ctx[0];
-    if (!root->have_screen || !root->have_camera || !root->have_options) return KIFS_ERR_UNCONFIGURED;
+    Device& root = m->dev[0];
+    if (!root.ctx->have_screen || !root.ctx->have_camera || !root.ctx->have_options) return KIFS_ERR_UNCONFIGURED;
     int w, h;
-    int st = render_dims(root, &w, &h);
+    int st = render_dims(root.ctx, &w, &h);
     if (st != KIFS_OK) return st;
     const size_t row_bytes = size_t(w) * 4;
     if (pitch < row_bytes || (pitch & 3u)) return KIFS_ERR_BAD_SIZE;
-    st = drain(m);  // batched steps in flight use the same contexts and streams
-    if (st != KIFS_OK) return st;
-    st = multi_partition(m, h);
-    if (st != KIFS_OK) return st;
-    const int n = int(m->ctx.size());
+    // (batched steps in flight use the same contexts and streams)
+    if ((st = drain(m)) != KIFS_OK || (st = multi_partition(m, h)) != KIFS_OK) return st;
     forget_background(m, nullptr, out, out + size_t(h - 1) * pitch + row_bytes);  // (a host pointer overlaps nothing)
     // the frame the shards are collected into: the caller's buffer if it is root-device memory
     uint8_t* frame = out;
     size_t fpitch = pitch;
     bool host_dst;
     {
-        DeviceGuard g(m->dev[0]);
+        DeviceGuard g(root.id);
         host_dst = !is_device_pointer(out);
         if (host_dst) {
             if (!grow(m->root_frame, m->root_frame_bytes, row_bytes * size_t(h), "hipMalloc(multi frame)")) return KIFS_ERR_RUNTIME;
@@ -593,56 +767,50 @@ int kifs_multi_render(kifs_multi* m, uint8_t* out, size_t pitch, int encode) {
         }
     }
     // 1. every device renders its shard: the root straight into the frame, the others into a packed buffer
-    for (int i = 0; i < n; ++i) {
-        kifs_ctx* c = m->ctx[size_t(i)];
-        DeviceGuard g(m->dev[size_t(i)]);
-        const std::vector<int>& stripes = m->stripes[size_t(i)];
+    for (Device& d : m->dev) {
+        const bool is_root = &d == &root;
+        DeviceGuard g(d.id);
         uint8_t* dst = frame;
         size_t dpitch = fpitch;
-        if (i != 0) {
-            if (!grow(m->shard[size_t(i)], m->shard_bytes[size_t(i)], row_bytes * size_t(m->rows[size_t(i)]), "hipMalloc(shard)"))
-                return KIFS_ERR_RUNTIME;
-            dst = m->shard[size_t(i)];
+        if (!is_root) {
+            if (!grow_shard(d.lone, row_bytes * size_t(d.rows), "hipMalloc(shard)")) return KIFS_ERR_RUNTIME;
+            dst = d.lone.shard;
             dpitch = row_bytes;
         }
-        if (hipEventRecord(m->ev0[size_t(i)], c->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
-        if (!stripes.empty()) {
-            st = enqueue_batch(c, c->stream, 1, nullptr, &dst, dpitch, 0, h, encode, stripes.data(), int(stripes.size()),
-                               i == 0 ? 1 : 0);
+        if (hipEventRecord(d.ev0, d.ctx->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
+        if (!d.stripes.empty()) {
+            st = enqueue_batch(d.ctx, d.ctx->stream, 1, nullptr, &dst, dpitch, 0, h, encode, d.stripes.data(), int(d.stripes.size()),
+                               is_root ? 1 : 0);
             if (st != KIFS_OK) return st;
         }
-        if (hipEventRecord(m->ev1[size_t(i)], c->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
+        if (hipEventRecord(d.ev1, d.ctx->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
     }
-    // 2. the root pulls each finished shard over xGMI and moves its stripes to their frame rows
+    // 2. the root pulls each finished shard over xGMI and moves its stripes to their frame rows: a peer copy on its
+    //    render stream, whatever the transport of the batched steps is
     {
-        DeviceGuard g(m->dev[0]);
-        for (int i = 1; i < n; ++i) {
-            const std::vector<int>& stripes = m->stripes[size_t(i)];
-            if (stripes.empty()) continue;
-            const size_t bytes = row_bytes * size_t(m->rows[size_t(i)]);
-            if (!grow(m->recv[size_t(i)], m->recv_bytes[size_t(i)], bytes, "hipMalloc(received shard)")) return KIFS_ERR_RUNTIME;
-            if (hipStreamWaitEvent(root->stream, m->ev1[size_t(i)], 0) != hipSuccess) return KIFS_ERR_RUNTIME;
-            if (!hip_ok(hipMemcpyPeerAsync(m->recv[size_t(i)], m->dev[0], m->shard[size_t(i)], m->dev[size_t(i)], bytes,
-                                           root->stream), "peer copy of a shard"))
+        DeviceGuard g(root.id);
+        hipStream_t rstream = root.ctx->stream;
+        const StepShape one{1, encode, KIFS_GATHER_DENSE, w, h, frame, fpitch, 0, 0u};
+        for (size_t i = 1; i < m->dev.size(); ++i) {
+            Device& d = m->dev[i];
+            if (d.stripes.empty()) continue;
+            if (!grow_recv(d.lone, root.id, row_bytes * size_t(d.rows), "hipMalloc(received shard)")) return KIFS_ERR_RUNTIME;
+            if (hipStreamWaitEvent(rstream, d.ev1, 0) != hipSuccess) return KIFS_ERR_RUNTIME;
+            if (!hip_ok(hipMemcpyPeerAsync(d.lone.recv, root.id, d.lone.shard, d.id, row_bytes * size_t(d.rows), rstream),
+                        "peer copy of a shard"))
                 return KIFS_ERR_COMM;
-            const RowTable* rows = row_table(root, stripes.data(), int(stripes.size()), h);
-            if (!rows) return KIFS_ERR_RUNTIME;
-            if (!hip_ok(kifs::launch_unpack_stripes(frame, fpitch, 0, m->recv[size_t(i)], row_bytes, 0, rows->d_rows,
-                                                    int(stripes.size()), 1, w, h, root->stream), "unpack_stripes_kernel launch"))
-                return KIFS_ERR_RUNTIME;
+            if ((st = unpack_dense(root, rstream, one, d.lone.recv, 0, d.stripes)) != KIFS_OK) return st;
         }
         if (host_dst &&
-            !hip_ok(hipMemcpy2DAsync(out, pitch, frame, fpitch, row_bytes, size_t(h), hipMemcpyDeviceToHost,
-                                     root->stream), "frame to host"))
+            !hip_ok(hipMemcpy2DAsync(out, pitch, frame, fpitch, row_bytes, size_t(h), hipMemcpyDeviceToHost, rstream), "frame to host"))
             return KIFS_ERR_RUNTIME;
-        if (!hip_ok(hipStreamSynchronize(root->stream), "multi sync")) return KIFS_ERR_RUNTIME;
+        if (!hip_ok(hipStreamSynchronize(rstream), "multi sync")) return KIFS_ERR_RUNTIME;
     }
-    for (int i = 0; i < n; ++i) {
-        DeviceGuard g(m->dev[size_t(i)]);
-        if (hipStreamSynchronize(m->ctx[size_t(i)]->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
+    for (Device& d : m->dev) {
+        DeviceGuard g(d.id);
+        if (hipStreamSynchronize(d.ctx->stream) != hipSuccess) return KIFS_ERR_RUNTIME;
         float ms = 0.0f;
-        m->shard_ms[size_t(i)] =
-            hipEventElapsedTime(&ms, m->ev0[size_t(i)], m->ev1[size_t(i)]) == hipSuccess ? double(ms) : -1.0;
+        d.shard_ms = hipEventElapsedTime(&ms, d.ev0, d.ev1) == hipSuccess ? double(ms) : -1.0;
     }
     return KIFS_OK;
 }
@@ -655,20 +823,12 @@ int kifs_multi_set_gather(kifs_multi* m, int gather, int transport) {
         return KIFS_ERR_BAD_ARG;
     int st = drain(m);
     if (st != KIFS_OK) return st;
-    m->gather = gather;
-    m->stats.gather = gather;
+    m->gather = m->stats.gather = gather;
     if (transport != m->transport_wanted || (transport != KIFS_TRANSPORT_AUTO && transport != m->transport)) {
         // a different transport: communicators go, the next step (or the lines below) decides anew
-        if (!m->comm.empty()) {
-            const RcclApi* a = rccl();
-            for (ncclComm_t c : m->comm)
-                if (a && c) (void)a->CommDestroy(c);
-            m->comm.clear();
-            m->stats.comm_ranks = 0;
-        }
+        destroy_comms(m);
         m->transport_wanted = transport;
-        m->transport = KIFS_TRANSPORT_AUTO;
-        m->stats.transport = KIFS_TRANSPORT_AUTO;
+        m->transport = m->stats.transport = KIFS_TRANSPORT_AUTO;
     }
     for (StepSlot& sl : m->slot) sl.background_known = false;
     if (transport == KIFS_TRANSPORT_AUTO) return KIFS_OK;
@@ -678,200 +838,49 @@ int kifs_multi_set_gather(kifs_multi* m, int gather, int transport) {
 
 int kifs_multi_render_batch_async(kifs_multi* m, int count, const KifsCameraUniform* cameras, uint8_t* dev_frames,
                                   size_t frame_pitch, size_t frame_stride, int encode, int flags, uint64_t* step_out) {
-    if (!m || !cameras || !dev_frames || count < 1 || count > KIFS_MAX_BATCH) return KIFS_ERR_BAD_ARG;
-    if (encode != KIFS_ENCODE_UNORM && encode != KIFS_ENCODE_SRGB) return KIFS_ERR_BAD_ARG;
-    kifs_ctx* root = m->ctx[0];
-    if (!root->have_screen || !root->have_options) return KIFS_ERR_UNCONFIGURED;
-    int w, h;
-    int st = render_dims(root, &w, &h);
-    if (st != KIFS_OK) return st;
-    const size_t row_bytes = size_t(w) * 4;
-    if (frame_pitch < row_bytes || ((frame_pitch | frame_stride) & 3u) || (reinterpret_cast<uintptr_t>(dev_frames) & 3u) ||
-        (count > 1 && frame_stride < frame_pitch * size_t(h - 1) + row_bytes))
-        return KIFS_ERR_BAD_SIZE;
-    {
-        DeviceGuard g(m->dev[0]);
-        if (!g.ok) return KIFS_ERR_RUNTIME;
-        if (!is_device_pointer(dev_frames)) return KIFS_ERR_BAD_ARG;
-    }
-    if ((st = ensure_streams(m)) != KIFS_OK || (st = ensure_transport(m)) != KIFS_OK || (st = multi_partition(m, h)) != KIFS_OK)
+    StepShape now;
+    int st = check_step(m, count, cameras, dev_frames, frame_pitch, frame_stride, encode, &now);
+    if (st != KIFS_OK || (st = ensure_streams(m)) != KIFS_OK || (st = ensure_transport(m)) != KIFS_OK ||
+        (st = multi_partition(m, now.height)) != KIFS_OK)
         return st;
-    const int n = int(m->ctx.size());
+    const size_t n = m->dev.size();
     const uint64_t step = m->next_step;
     StepSlot& sl = m->slot[step % SLOTS];
     // the slot's previous step (k - 2) ends here: its consumer has had it since the wait, or never asked
     if ((st = complete_slot(m, sl)) != KIFS_OK) return st;
-    const bool sparse = m->gather == KIFS_GATHER_SPARSE;
-    const float* bc = root->options.background_color;
-    const uint32_t background = background_pixel(root, kifs::V3{bc[0], bc[1], bc[2]}, encode);
-    // may the frames be assumed to hold the background everywhere but under the slot's last records?
-    bool same_parts = sl.part.size() == size_t(n);
-    for (int i = 0; same_parts && i < n; ++i) same_parts = sl.part[size_t(i)].stripes == m->stripes[size_t(i)];
-    const bool erase_only = sparse && (flags & KIFS_MULTI_FRAMES_UNTOUCHED) && sl.background_known && same_parts &&
-                            sl.frames == dev_frames && sl.pitch == frame_pitch && sl.stride == frame_stride &&
-                            sl.count == count && sl.encode == encode && sl.background == background &&
-                            sl.width == w && sl.height == h && sl.gather == KIFS_GATHER_SPARSE;
-    // (erase_only looked at this slot's own record of the buffer; the OTHER slot's record of any buffer this step
-    // writes into is void from here on)
-    forget_background(m, &sl, dev_frames, frames_end(dev_frames, count, frame_pitch, frame_stride, w, h));
-    if (sl.part.size() != size_t(n)) sl.part.resize(size_t(n));
+    const bool erase_only = erase_suffices(m, sl, now, flags);
+    // (that looked at this slot's own record of the buffer; the OTHER slot's record of any buffer this step writes
+    // into is void from here on)
+    forget_background(m, &sl, now.frames, frames_end(now));
+    if (sl.part.size() != n) sl.part.resize(n);
     {
-        DeviceGuard g(m->dev[0]);
+        DeviceGuard g(m->dev[0].id);
         if (!make_event(sl.rendered) || !make_event(sl.gathered)) return KIFS_ERR_RUNTIME;
     }
-    // ---- the root's gather stream: background under everybody else's rows
-    hipStream_t gstream = m->comm_stream[0];
-    if (sparse && n > 1) {
-        DeviceGuard g(m->dev[0]);
-        if (erase_only) {
-            for (int i = 1; i < n; ++i) {
-                PeerPart& p = sl.part[size_t(i)];
-                if (!p.n_records) continue;
-                const RowTable* rows = row_table(root, p.stripes.data(), int(p.stripes.size()), h);
-                if (!rows) return KIFS_ERR_RUNTIME;
-                if (!hip_ok(kifs::launch_unpack_sparse(dev_frames, frame_pitch, frame_stride, reinterpret_cast<const uint32_t*>(p.recv),
-                                                       p.n_records, rows->d_rows, int(p.stripes.size()), count, w, h, 1, background,
-                                                       gstream), "erase of the previous records"))
-                    return KIFS_ERR_RUNTIME;
-            }
-        } else {
-            sl.peer_stripes.clear();
-            for (int i = 1; i < n; ++i) sl.peer_stripes.insert(sl.peer_stripes.end(), m->stripes[size_t(i)].begin(), m->stripes[size_t(i)].end());
-            std::sort(sl.peer_stripes.begin(), sl.peer_stripes.end());
-            if (!sl.peer_stripes.empty()) {
-                const RowTable* rows = row_table(root, sl.peer_stripes.data(), int(sl.peer_stripes.size()), h);
-                if (!rows) return KIFS_ERR_RUNTIME;
-                if (!hip_ok(kifs::launch_fill_stripes(dev_frames, frame_pitch, frame_stride, rows->d_rows, int(sl.peer_stripes.size()),
-                                                      count, w, h, background, gstream), "fill under the other devices' rows"))
-                    return KIFS_ERR_RUNTIME;
-            }
-        }
-    }
-    sl.used = true;
-    sl.flushed = false;
-    sl.background_known = false;
-    sl.overwritten = false;
+    if (now.gather == KIFS_GATHER_SPARSE && n > 1 && (st = paint_background(m, sl, now, erase_only)) != KIFS_OK) return st;
+    static_cast<StepShape&>(sl) = now;
     sl.step = step;
-    sl.count = count; sl.encode = encode; sl.gather = m->gather; sl.width = w; sl.height = h;
-    sl.frames = dev_frames; sl.pitch = frame_pitch; sl.stride = frame_stride; sl.background = background;
-    // ---- every device: one launch for its shard of all the step's frames, then its payload
-    const size_t tiles_x = size_t((w + kifs::TILE_W - 1) / kifs::TILE_W);
+    sl.used = true;
+    sl.flushed = sl.background_known = sl.overwritten = false;
     m->outs_scratch.resize(size_t(count));
-    auto launch_all = [&]() -> int {
-        for (int i = 0; i < n; ++i) {
-            kifs_ctx* c = m->ctx[size_t(i)];
-            PeerPart& p = sl.part[size_t(i)];
-            p.stripes = m->stripes[size_t(i)];
-            p.rows = m->rows[size_t(i)];
-            p.n_records = 0;
-            p.payload_bytes = 0;
-            DeviceGuard g(m->dev[size_t(i)]);
-            if (!g.ok) return KIFS_ERR_RUNTIME;
-            m->shard_ms[size_t(i)] = -1.0;
-            if (p.stripes.empty()) {
-                if (i == 0 && !hip_ok(hipEventRecord(sl.rendered, c->stream), "record(rendered)")) return KIFS_ERR_RUNTIME;
-                continue;
-            }
-            const size_t shard_stride = size_t(p.rows) * row_bytes;
-            if (i == 0) {
-                for (int f = 0; f < count; ++f) m->outs_scratch[size_t(f)] = dev_frames + size_t(f) * frame_stride;
-            } else {
-                const size_t need = shard_stride * size_t(count);
-                const size_t capacity = size_t(count) * p.stripes.size() * tiles_x;
-                if (!make_event(p.packed)) return KIFS_ERR_RUNTIME;
-                // buffers that grow are replaced while nothing reads them: the slot's previous step is complete
-                if (!grow(p.shard, p.shard_bytes, need, "hipMalloc(step shards)")) return KIFS_ERR_RUNTIME;
-                if (sparse) {
-                    if (!grow(p.records, p.records_bytes, capacity * KIFS_SPARSE_RECORD_BYTES, "hipMalloc(step records)")) return KIFS_ERR_RUNTIME;
-                    if (!p.d_count && !hip_ok(hipMalloc(reinterpret_cast<void**>(&p.d_count), sizeof(uint32_t)), "hipMalloc(record count)"))
-                        return KIFS_ERR_RUNTIME;
-                    if (!p.h_count && !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&p.h_count), sizeof(uint32_t), hipHostMallocDefault),
-                                              "hipHostMalloc(record count)"))
-                        return KIFS_ERR_RUNTIME;
-                }
-                {
-                    DeviceGuard gr(m->dev[0]);
-                    if (!grow(p.recv, p.recv_bytes, sparse ? capacity * KIFS_SPARSE_RECORD_BYTES : need, "hipMalloc(step receive)"))
-                        return KIFS_ERR_RUNTIME;
-                }
-                // (the payload of the slot's previous step has left these buffers: that step was completed above, and
-                // its completion includes the root's scatter, which follows the transfer in the gather stream)
-                for (int f = 0; f < count; ++f) m->outs_scratch[size_t(f)] = p.shard + size_t(f) * shard_stride;
-            }
-            if (!hip_ok(hipEventRecord(m->ev0[size_t(i)], c->stream), "record(launch start)")) return KIFS_ERR_RUNTIME;
-            st = enqueue_batch(c, c->stream, count, cameras, m->outs_scratch.data(), i == 0 ? frame_pitch : row_bytes, 0, h, encode,
-                               p.stripes.data(), int(p.stripes.size()), i == 0 ? 1 : 0);
-            if (st != KIFS_OK) return st;
-            if (!hip_ok(hipEventRecord(m->ev1[size_t(i)], c->stream), "record(launch stop)")) return KIFS_ERR_RUNTIME;
-            if (i == 0) {
-                if (!hip_ok(hipEventRecord(sl.rendered, c->stream), "record(rendered)")) return KIFS_ERR_RUNTIME;
-                continue;
-            }
-            if (sparse) {
-                const RowTable* rows = row_table(c, p.stripes.data(), int(p.stripes.size()), h);
-                if (!rows) return KIFS_ERR_RUNTIME;
-                if (!hip_ok(hipMemsetAsync(p.d_count, 0, sizeof(uint32_t), c->stream), "memset(record count)") ||
-                    !hip_ok(kifs::launch_pack_sparse(p.shard, row_bytes, shard_stride, rows->d_rows, int(p.stripes.size()), count, w, h,
-                                                     background, reinterpret_cast<uint32_t*>(p.records), p.d_count, c->stream),
-                            "pack_sparse_kernel launch") ||
-                    !hip_ok(hipMemcpyAsync(p.h_count, p.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream), "copy(record count)"))
-                    return KIFS_ERR_RUNTIME;
-            }
-            if (!hip_ok(hipEventRecord(p.packed, c->stream), "record(packed)")) return KIFS_ERR_RUNTIME;
-        }
-        return KIFS_OK;
-    };
-    st = launch_all();
-    if (st == KIFS_OK && n == 1) {
-        DeviceGuard g(m->dev[0]);
-        if (hip_ok(hipEventRecord(sl.gathered, gstream), "record(gathered)")) sl.flushed = true;
+    for (size_t i = 0; st == KIFS_OK && i < n; ++i) st = submit_device(m, sl, i, cameras);
+    if (st == KIFS_OK && n == 1) {  // nothing to gather
+        DeviceGuard g(m->dev[0].id);
+        if (hip_ok(hipEventRecord(sl.gathered, m->dev[0].comm_stream), "record(gathered)")) sl.flushed = true;
         else st = KIFS_ERR_RUNTIME;
     }
-    if (st != KIFS_OK) {
-        // A step that was only partly enqueued is no step: whatever was launched is waited for (it writes into the
-        // caller's frames and the slot's buffers), the slot is free again, the step number is not used up -- a later
-        // submit, wait or destroy must not flush record counts and events of a launch that never happened.
-        for (int i = 0; i < n; ++i) {
-            DeviceGuard g(m->dev[size_t(i)]);
-            (void)hipStreamSynchronize(m->ctx[size_t(i)]->stream);
-        }
-        {
-            DeviceGuard g(m->dev[0]);
-            (void)hipStreamSynchronize(gstream);
-        }
-        (void)hipGetLastError();
-        sl.used = false;
-        sl.flushed = false;
-        sl.background_known = false;
-        return st;
-    }
+    if (st != KIFS_OK) return abandon_step(m, sl, st);
     m->next_step = step + 1;
     if (step_out) *step_out = step;
-    // ---- the step before this one: its senders have had a whole submission to pack
-    if (m->have_pending) {
-        StepSlot& prev = m->slot[m->pending % SLOTS];
-        if (prev.used && prev.step == m->pending && (st = flush_slot(m, prev)) != KIFS_OK) return st;
-        m->have_pending = false;
-    }
-    if (!sl.flushed) {
-        m->have_pending = true;
-        m->pending = step;
-    }
-    return KIFS_OK;
+    return advance_pipeline(m, sl);
 }
 
 int kifs_multi_wait(kifs_multi* m, uint64_t step) {
-    if (!m) return KIFS_ERR_BAD_ARG;
-    if (step >= m->next_step) return KIFS_ERR_BAD_ARG;
+    if (!m || step >= m->next_step) return KIFS_ERR_BAD_ARG;
     StepSlot& sl = m->slot[step % SLOTS];
     if (!sl.used || sl.step != step) return KIFS_OK;  // completed earlier (by a later submission or a wait)
-    // an older step still unflushed goes first: the gather stream runs them in order
-    StepSlot& other = m->slot[(step + 1) % SLOTS];
-    if (other.used && other.step < step) {
-        int st = flush_slot(m, other);
-        if (st != KIFS_OK) return st;
-    }
-    return complete_slot(m, sl);
+    int st = flush_older(m, step);
+    return st != KIFS_OK ? st : complete_slot(m, sl);
 }
 
 int kifs_multi_wait_all(kifs_multi* m) { return m ? drain(m) : KIFS_ERR_BAD_ARG; }
@@ -880,28 +889,25 @@ int kifs_multi_stream_wait(kifs_multi* m, uint64_t step, void* hip_stream) {
     if (!m || !hip_stream || step >= m->next_step) return KIFS_ERR_BAD_ARG;
     StepSlot& sl = m->slot[step % SLOTS];
     if (!sl.used || sl.step != step) return KIFS_OK;
-    StepSlot& other = m->slot[(step + 1) % SLOTS];
-    int st = KIFS_OK;
-    if (other.used && other.step < step && (st = flush_slot(m, other)) != KIFS_OK) return st;
-    if ((st = flush_slot(m, sl)) != KIFS_OK) return st;
-    DeviceGuard g(m->dev[0]);
+    int st = flush_older(m, step);
+    if (st != KIFS_OK || (st = flush_slot(m, sl)) != KIFS_OK) return st;
+    DeviceGuard g(m->dev[0].id);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    return hip_ok(hipStreamWaitEvent(s, sl.rendered, 0), "stream wait(rendered)") &&
-                   hip_ok(hipStreamWaitEvent(s, sl.gathered, 0), "stream wait(gathered)")
-               ? KIFS_OK : KIFS_ERR_RUNTIME;
+    return runtime_status(hip_ok(hipStreamWaitEvent(s, sl.rendered, 0), "stream wait(rendered)") &&
+                          hip_ok(hipStreamWaitEvent(s, sl.gathered, 0), "stream wait(gathered)"));
 }
 
 int kifs_multi_order_after(kifs_multi* m, void* producer_stream) {
     if (!m) return KIFS_ERR_BAD_ARG;
     int st = ensure_streams(m);
     if (st != KIFS_OK) return st;
+    const Device& root = m->dev[0];
     // the root's render stream first (kifs_order_after records the context's ordering event on the producer's
     // stream), then the same event for the gather stream
-    if ((st = kifs_order_after(m->ctx[0], nullptr, producer_stream)) != KIFS_OK) return st;
-    if (m->ctx[0]->stream == static_cast<hipStream_t>(producer_stream)) return KIFS_OK;
-    DeviceGuard g(m->dev[0]);
-    return hip_ok(hipStreamWaitEvent(m->comm_stream[0], m->ctx[0]->ev_order, 0), "wait(multi order_after)") ? KIFS_OK
-                                                                                                          : KIFS_ERR_RUNTIME;
+    if ((st = kifs_order_after(root.ctx, nullptr, producer_stream)) != KIFS_OK) return st;
+    if (root.ctx->stream == static_cast<hipStream_t>(producer_stream)) return KIFS_OK;
+    DeviceGuard g(root.id);
+    return runtime_status(hip_ok(hipStreamWaitEvent(root.comm_stream, root.ctx->ev_order, 0), "wait(multi order_after)"));
 }
 
 int kifs_multi_render_batch(kifs_multi* m, int count, const KifsCameraUniform* cameras, uint8_t* dev_frames,
@@ -927,57 +933,46 @@ int kifs_multi_comm_selftest(kifs_multi* m, size_t bytes) {
     if (!m || bytes == 0 || bytes > (size_t(1) << 30)) return KIFS_ERR_BAD_ARG;
     int st = drain(m);
     if (st != KIFS_OK || (st = ensure_streams(m)) != KIFS_OK || (st = ensure_transport(m)) != KIFS_OK) return st;
-    const int n = int(m->dev.size());
+    const size_t n = m->dev.size();
+    const int root_id = m->dev[0].id;
     const bool self = n == 1;  // one device: the root sends to itself and receives from itself in one group
-    std::vector<uint8_t*> src(size_t(n), nullptr), dst(size_t(n), nullptr);
-    std::vector<const uint8_t*> csrc(size_t(n), nullptr);
-    std::vector<size_t> sizes(size_t(n), 0);
-    std::vector<hipEvent_t> none(size_t(n), nullptr);
+    std::vector<Payload> buf(n);  // what a step would send, for the length of this call
+    std::vector<Transfer> x(n);
     std::vector<uint8_t> pattern(bytes), back(bytes);
     int rc = KIFS_OK;
-    for (int i = self ? 0 : 1; i < n && rc == KIFS_OK; ++i) {
-        for (size_t k = 0; k < bytes; ++k) pattern[k] = uint8_t((k * 131u + size_t(i) * 29u + 7u) & 255u);
+    for (size_t i = self ? 0 : 1; i < n && rc == KIFS_OK; ++i) {
+        for (size_t k = 0; k < bytes; ++k) pattern[k] = selftest_byte(k, i);
         {
-            DeviceGuard g(m->dev[size_t(i)]);
-            if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&src[size_t(i)]), bytes), "hipMalloc(selftest)") ||
-                !hip_ok(hipMemcpy(src[size_t(i)], pattern.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(selftest)"))
+            DeviceGuard g(m->dev[i].id);
+            if (!grow_shard(buf[i], bytes, "hipMalloc(selftest)") ||
+                !hip_ok(hipMemcpy(buf[i].shard, pattern.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(selftest)"))
                 rc = KIFS_ERR_RUNTIME;
         }
-        DeviceGuard g(m->dev[0]);
-        if (rc == KIFS_OK && (!hip_ok(hipMalloc(reinterpret_cast<void**>(&dst[size_t(i)]), bytes), "hipMalloc(selftest)") ||
-                              !hip_ok(hipMemset(dst[size_t(i)], 0, bytes), "hipMemset(selftest)")))
+        DeviceGuard g(root_id);
+        if (rc == KIFS_OK && (!grow_recv(buf[i], root_id, bytes, "hipMalloc(selftest)") ||
+                              !hip_ok(hipMemset(buf[i].recv, 0, bytes), "hipMemset(selftest)")))
             rc = KIFS_ERR_RUNTIME;
-        csrc[size_t(i)] = src[size_t(i)];
-        sizes[size_t(i)] = bytes;
+        x[i] = Transfer{buf[i].shard, buf[i].recv, bytes, nullptr};
     }
-    if (rc == KIFS_OK) rc = transfer_to_root(m, csrc, dst, sizes, none, self);
+    if (rc == KIFS_OK) rc = transfer_to_root(m, x, self);
     if (rc == KIFS_OK) {
-        for (int i = 0; i < n; ++i) {
-            DeviceGuard g(m->dev[size_t(i)]);
-            if (!hip_ok(hipStreamSynchronize(m->comm_stream[size_t(i)]), "sync(selftest)")) rc = KIFS_ERR_COMM;
+        for (Device& d : m->dev) {
+            DeviceGuard g(d.id);
+            if (!hip_ok(hipStreamSynchronize(d.comm_stream), "sync(selftest)")) rc = KIFS_ERR_COMM;
         }
     }
-    for (int i = self ? 0 : 1; i < n && rc == KIFS_OK; ++i) {
-        DeviceGuard g(m->dev[0]);
-        if (!hip_ok(hipMemcpy(back.data(), dst[size_t(i)], bytes, hipMemcpyDeviceToHost), "hipMemcpy(selftest back)")) {
+    for (size_t i = self ? 0 : 1; i < n && rc == KIFS_OK; ++i) {
+        DeviceGuard g(root_id);
+        if (!hip_ok(hipMemcpy(back.data(), x[i].dst, bytes, hipMemcpyDeviceToHost), "hipMemcpy(selftest back)")) {
             rc = KIFS_ERR_RUNTIME;
             break;
         }
-        for (size_t k = 0; k < bytes; ++k)
-            if (back[k] != uint8_t((k * 131u + size_t(i) * 29u + 7u) & 255u)) {
-                rc = KIFS_ERR_COMM;
-                break;
-            }
+        for (size_t k = 0; k < bytes && rc == KIFS_OK; ++k)
+            if (back[k] != selftest_byte(k, i)) rc = KIFS_ERR_COMM;
     }
-    for (int i = 0; i < n; ++i) {
-        if (src[size_t(i)]) {
-            DeviceGuard g(m->dev[size_t(i)]);
-            (void)hipFree(src[size_t(i)]);
-        }
-        if (dst[size_t(i)]) {
-            DeviceGuard g(m->dev[0]);
-            (void)hipFree(dst[size_t(i)]);
-        }
+    for (size_t i = 0; i < n; ++i) {
+        DeviceGuard g(m->dev[i].id);
+        free_payload(buf[i], root_id);
     }
     return rc;
 }

@@ -16,7 +16,9 @@
 // recorded aborts: HIP takes it for a wait that is over, so an ordering somebody relied on is missing.  The sparse
 // pack / unpack / fill / stripe kernels are restated on the CPU from their documented formats
 // (kifs_support_kernels.hip:115-125,184-187,211).  stub_fail_in(n): the n-th HIP call or launch from now on fails once
-// (hipErrorOutOfMemory / hipErrorLaunchFailure), for the error paths.
+// (hipErrorOutOfMemory / hipErrorLaunchFailure), for the error paths.  A hipFree under another device than the one that
+// was current at the hipMalloc aborts.  KIFS_STUB_TRACE=FILE writes one line per call (see trace() below): two builds of
+// the host code are compared call for call by running the driver on both and diffing the files.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
@@ -30,8 +32,8 @@
 
 #include "../../kifs_raymarching_amd/csrc/kifs_internal.hpp"
 
-struct ihipStream_t { int device; };
-struct ihipEvent_t { int device; bool recorded; };
+struct ihipStream_t { int device; int ordinal; };
+struct ihipEvent_t { int device; bool recorded; int ordinal; };
 
 namespace {
 
@@ -40,11 +42,27 @@ int g_current = 0;
 hipError_t g_last = hipSuccess;
 long g_fail_in = -1;  // countdown to an injected failure
 std::map<uintptr_t, size_t> g_device_mem, g_host_mem;
+std::map<uintptr_t, int> g_device_of;  // the device that was current at the hipMalloc
 std::set<ihipStream_t*> g_streams;
 std::set<ihipEvent_t*> g_events;
 long g_calls = 0, g_launches = 0, g_device_syncs = 0;
 
 hipError_t fail(hipError_t e) { g_last = e; return e; }
+
+// KIFS_STUB_TRACE=FILE: one line per call -- name, current device, stream and event as ordinals in order of creation
+// (0: the null stream / no event), bytes of a copy, memset or allocation -- so that two builds of the host code can be
+// compared call for call (what the synchronous stub itself cannot see: a wrong stream, a missing wait).
+std::FILE* g_trace = [] {
+    const char* e = std::getenv("KIFS_STUB_TRACE");
+    std::FILE* f = e ? std::fopen(e, "w") : nullptr;
+    if (f) std::setvbuf(f, nullptr, _IOLBF, 0);  // line by line: an abort must not lose the tail
+    return f;
+}();
+int g_stream_ordinals = 0, g_event_ordinals = 0;
+
+void trace(const char* call, hipStream_t s = nullptr, hipEvent_t e = nullptr, size_t bytes = 0) {
+    if (g_trace) std::fprintf(g_trace, "%s dev=%d stream=%d event=%d bytes=%zu\n", call, g_current, s ? s->ordinal : 0, e ? e->ordinal : 0, bytes);
+}
 
 bool injected() {
     ++g_calls;
@@ -73,6 +91,7 @@ extern "C" {
 
 // ---- test hooks
 void stub_fail_in(long n) { g_fail_in = n; }
+void stub_trace_mark(const char* what) { if (g_trace) std::fprintf(g_trace, "# %s\n", what); }
 long stub_calls() { return g_calls; }
 long stub_launches() { return g_launches; }
 long stub_device_synchronizes() { return g_device_syncs; }
@@ -87,7 +106,7 @@ hipError_t hipSetDevice(int d) {
     g_current = d;
     return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { ++g_device_syncs; return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { trace("hipDeviceSynchronize"); ++g_device_syncs; return hipSuccess; }
 hipError_t hipDeviceCanAccessPeer(int* can, int a, int b) { *can = a != b; return hipSuccess; }
 hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
 hipError_t hipGetLastError(void) { hipError_t e = g_last; g_last = hipSuccess; return e; }
@@ -95,25 +114,34 @@ const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error
 
 // ---- memory
 hipError_t hipMalloc(void** p, size_t bytes) {
+    trace("hipMalloc", nullptr, nullptr, bytes);
     if (injected()) return fail(hipErrorOutOfMemory);
     *p = std::malloc(bytes ? bytes : 1);
     if (!*p) return fail(hipErrorOutOfMemory);
     std::memset(*p, 0xCD, bytes);  // fresh device memory holds garbage: nobody may rely on zeros
     g_device_mem[reinterpret_cast<uintptr_t>(*p)] = bytes ? bytes : 1;
+    g_device_of[reinterpret_cast<uintptr_t>(*p)] = g_current;
     return hipSuccess;
 }
 hipError_t hipFree(void* p) {
     if (!p) return hipSuccess;
+    trace("hipFree");
     auto it = g_device_mem.find(reinterpret_cast<uintptr_t>(p));
     if (it == g_device_mem.end()) {
         std::fprintf(stderr, "hip_stub: hipFree(%p): not a live device allocation\n", p);
         std::abort();
     }
+    if (g_device_of[it->first] != g_current) {  // HIP would find the owner; the library frees under the device it allocated under
+        std::fprintf(stderr, "hip_stub: hipFree(%p) under device %d: allocated under device %d\n", p, g_current, g_device_of[it->first]);
+        std::abort();
+    }
+    g_device_of.erase(it->first);
     g_device_mem.erase(it);
     std::free(p);
     return hipSuccess;
 }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
+    trace("hipHostMalloc", nullptr, nullptr, bytes);
     if (injected()) return fail(hipErrorOutOfMemory);
     *p = std::malloc(bytes ? bytes : 1);
     g_host_mem[reinterpret_cast<uintptr_t>(*p)] = bytes ? bytes : 1;
@@ -121,6 +149,7 @@ hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
 }
 hipError_t hipHostFree(void* p) {
     if (!p) return hipSuccess;
+    trace("hipHostFree");
     if (!g_host_mem.erase(reinterpret_cast<uintptr_t>(p))) std::abort();
     std::free(p);
     return hipSuccess;
@@ -131,40 +160,52 @@ hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* p) {
     if (inside(g_host_mem, p)) { a->type = hipMemoryTypeHost; return hipSuccess; }
     return fail(hipErrorInvalidValue);  // plain host memory: what the real runtime says too
 }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) std::memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t) {
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { trace("hipMemcpy", nullptr, nullptr, n); if (n) std::memmove(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) {
+    trace("hipMemcpyAsync", st, nullptr, n);
     if (injected()) return fail(hipErrorLaunchFailure);
-    return hipMemcpy(d, s, n, k);
+    if (n) std::memmove(d, s, n);
+    return hipSuccess;
 }
-hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t) {
+hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t st) {
+    trace("hipMemcpyPeerAsync", st, nullptr, n);
     if (injected()) return fail(hipErrorLaunchFailure);
     need_device(d, n, "hipMemcpyPeerAsync(dst)");
     need_device(s, n, "hipMemcpyPeerAsync(src)");
     if (n) std::memmove(d, s, n);
     return hipSuccess;
 }
-hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t) {
+hipError_t hipMemcpy2DAsync(void* d, size_t dp, const void* s, size_t sp, size_t w, size_t h, hipMemcpyKind, hipStream_t st) {
+    trace("hipMemcpy2DAsync", st, nullptr, w * h);
     for (size_t y = 0; y < h; ++y) std::memmove(static_cast<char*>(d) + y * dp, static_cast<const char*>(s) + y * sp, w);
     return hipSuccess;
 }
-hipError_t hipMemset(void* d, int v, size_t n) { need_device(d, n, "hipMemset"); std::memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { return hipMemset(d, v, n); }
+hipError_t hipMemset(void* d, int v, size_t n) { trace("hipMemset", nullptr, nullptr, n); need_device(d, n, "hipMemset"); std::memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    trace("hipMemsetAsync", st, nullptr, n);
+    need_device(d, n, "hipMemsetAsync");
+    std::memset(d, v, n);
+    return hipSuccess;
+}
 
 // ---- streams and events (everything has already happened by the time anybody asks)
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
     if (injected()) return fail(hipErrorOutOfMemory);
-    *s = new ihipStream_t{g_current};
+    *s = new ihipStream_t{g_current, ++g_stream_ordinals};
     g_streams.insert(*s);
+    trace("hipStreamCreateWithFlags", *s);
     return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
     if (!g_streams.erase(s)) std::abort();
+    trace("hipStreamDestroy", s);
     delete s;
     return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t s) { if (s && !g_streams.count(s)) std::abort(); return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { if (s && !g_streams.count(s)) std::abort(); trace("hipStreamSynchronize", s); return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     if ((s && !g_streams.count(s)) || !g_events.count(e)) std::abort();  // a destroyed stream or event
+    trace("hipStreamWaitEvent", s, e);
     if (!e->recorded) {  // HIP takes this for a wait that is already over: whoever meant to order two streams has not
         std::fprintf(stderr, "hip_stub: hipStreamWaitEvent on an event that was never recorded\n");
         std::abort();
@@ -173,26 +214,30 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
 }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
     if (injected()) return fail(hipErrorOutOfMemory);
-    *e = new ihipEvent_t{g_current, false};
+    *e = new ihipEvent_t{g_current, false, ++g_event_ordinals};
     g_events.insert(*e);
+    trace("hipEventCreate", nullptr, *e);
     return hipSuccess;
 }
 hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
 hipError_t hipEventDestroy(hipEvent_t e) {
     if (!g_events.erase(e)) std::abort();
+    trace("hipEventDestroy", nullptr, e);
     delete e;
     return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     if (injected()) return fail(hipErrorLaunchFailure);
     if (!g_events.count(e) || (s && !g_streams.count(s))) std::abort();
+    trace("hipEventRecord", s, e);
     e->recorded = true;
     return hipSuccess;
 }
-hipError_t hipEventSynchronize(hipEvent_t e) { if (!g_events.count(e)) std::abort(); return hipSuccess; }
-hipError_t hipEventQuery(hipEvent_t e) { if (!g_events.count(e)) std::abort(); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { if (!g_events.count(e)) std::abort(); trace("hipEventSynchronize", nullptr, e); return hipSuccess; }
+hipError_t hipEventQuery(hipEvent_t e) { if (!g_events.count(e)) std::abort(); trace("hipEventQuery", nullptr, e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     if (!g_events.count(a) || !g_events.count(b)) std::abort();
+    trace("hipEventElapsedTime", nullptr, b);
     if (!a->recorded || !b->recorded) return fail(hipErrorInvalidHandle);
     *ms = 0.125f;
     return hipSuccess;
@@ -218,8 +263,9 @@ uint32_t stub_pixel(const BatchView& v, int x, int y, uint32_t background) {
 }
 }  // namespace
 
-hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t) {
+hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t st) {
     ++g_launches;
+    trace("launch_render", st);
     if (injected()) return fail(hipErrorLaunchFailure);
     const FrameParams& P = B.frame;
     const int tiles_x = (P.width + TW - 1) / TW;
@@ -280,8 +326,9 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t) 
     return hipSuccess;
 }
 
-hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count, uint32_t tiles_x, uint32_t shift, hipStream_t) {
+hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count, uint32_t tiles_x, uint32_t shift, hipStream_t st) {
     ++g_launches;
+    trace("launch_tile_order", st);
     need_device(cost, size_t(tile_count) * 4, "tile_order: costs");
     need_device(order, size_t(tile_count) * 4, "tile_order: order");
     std::vector<std::pair<uint32_t, uint32_t>> keyed(tile_count);
@@ -297,8 +344,9 @@ hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_coun
 
 hipError_t launch_unpack_stripes(uint8_t* dst, size_t dst_pitch, size_t dst_frame_stride, const uint8_t* src, size_t src_pitch,
                                  size_t src_shard_stride, const uint32_t* stripe_rows, int n_stripes, int count, int width,
-                                 int height, hipStream_t) {
+                                 int height, hipStream_t st) {
     ++g_launches;
+    trace("launch_unpack_stripes", st);
     if (injected()) return fail(hipErrorLaunchFailure);
     for (int f = 0; f < count; ++f)
         for (int s = 0; s < n_stripes; ++s)
@@ -313,8 +361,9 @@ hipError_t launch_unpack_stripes(uint8_t* dst, size_t dst_pitch, size_t dst_fram
 }
 
 hipError_t launch_pack_sparse(const uint8_t* src, size_t src_pitch, size_t src_shard_stride, const uint32_t* stripe_rows, int n_stripes,
-                              int count, int width, int height, uint32_t background, uint32_t* records, uint32_t* n_records, hipStream_t) {
+                              int count, int width, int height, uint32_t background, uint32_t* records, uint32_t* n_records, hipStream_t st) {
     ++g_launches;
+    trace("launch_pack_sparse", st);
     if (injected()) return fail(hipErrorLaunchFailure);
     const int tiles_x = (width + TW - 1) / TW;
     need_device(n_records, 4, "pack_sparse: count");
@@ -350,8 +399,9 @@ hipError_t launch_pack_sparse(const uint8_t* src, size_t src_pitch, size_t src_s
 
 hipError_t launch_unpack_sparse(uint8_t* dst, size_t dst_pitch, size_t dst_frame_stride, const uint32_t* records, uint32_t n_records,
                                 const uint32_t* stripe_rows, int n_stripes, int count, int width, int height, int erase,
-                                uint32_t background, hipStream_t) {
+                                uint32_t background, hipStream_t st) {
     ++g_launches;
+    trace("launch_unpack_sparse", st);
     if (injected()) return fail(hipErrorLaunchFailure);
     const int tiles_x = (width + TW - 1) / TW;
     for (uint32_t i = 0; i < n_records; ++i) {
@@ -373,8 +423,9 @@ hipError_t launch_unpack_sparse(uint8_t* dst, size_t dst_pitch, size_t dst_frame
 }
 
 hipError_t launch_fill_stripes(uint8_t* dst, size_t dst_pitch, size_t dst_frame_stride, const uint32_t* stripe_rows, int n_stripes,
-                               int count, int width, int height, uint32_t background, hipStream_t) {
+                               int count, int width, int height, uint32_t background, hipStream_t st) {
     ++g_launches;
+    trace("launch_fill_stripes", st);
     if (injected()) return fail(hipErrorLaunchFailure);
     for (int f = 0; f < count; ++f)
         for (int s = 0; s < n_stripes; ++s)
@@ -386,15 +437,17 @@ hipError_t launch_fill_stripes(uint8_t* dst, size_t dst_pitch, size_t dst_frame_
     return hipSuccess;
 }
 
-hipError_t launch_eval_points(const FrameParams&, uint32_t, uint32_t, const float*, int n, float* sdf, float* nrm, hipStream_t) {
+hipError_t launch_eval_points(const FrameParams&, uint32_t, uint32_t, const float*, int n, float* sdf, float* nrm, hipStream_t st) {
     ++g_launches;
+    trace("launch_eval_points", st);
     if (sdf) std::memset(sdf, 0, size_t(n) * 4);
     if (nrm) std::memset(nrm, 0, size_t(n) * 12);
     return hipSuccess;
 }
 
-hipError_t launch_eval_math(int, const float* in, float, const float*, float* out, int n, hipStream_t) {
+hipError_t launch_eval_math(int, const float* in, float, const float*, float* out, int n, hipStream_t st) {
     ++g_launches;
+    trace("launch_eval_math", st);
     std::memcpy(out, in, size_t(n) * 4);
     return hipSuccess;
 }

@@ -20,6 +20,8 @@
 
 extern "C" {
 void stub_fail_in(long n);
+void stub_trace_mark(const char* what);
+long stub_launches();
 long stub_calls();
 long stub_device_synchronizes();
 size_t stub_live_device_allocations();
@@ -109,6 +111,7 @@ kifs_multi* multi(const std::vector<int>& devs, const Scene& s, int gather, int 
 // ---- scenarios -----------------------------------------------------------------------------------------------
 
 void null_and_argument_checks() {
+    stub_trace_mark("null_and_argument_checks");
     CHECK(kifs_abi_version() == KIFS_ABI_VERSION);
     CHECK(kifs_set_screen(nullptr, nullptr) == KIFS_ERR_BAD_ARG && kifs_render(nullptr, nullptr, 0, 0, 0, 0) == KIFS_ERR_BAD_ARG);
     CHECK(kifs_order_after(nullptr, nullptr, nullptr) == KIFS_ERR_BAD_ARG && kifs_multi_order_after(nullptr, nullptr) == KIFS_ERR_BAD_ARG);
@@ -163,6 +166,7 @@ void null_and_argument_checks() {
 
 // One context: bands, batches (inline and through the view table), shards packed and in place, the sparse round trip.
 void single_context(int w, int h) {
+    stub_trace_mark("single_context");
     Scene s = scene(w, h, 40);
     const size_t fb = size_t(w) * h * 4;
     auto cams = cameras(70, 3);
@@ -259,6 +263,7 @@ void single_context(int w, int h) {
 
 // kifs_multi: batches on four devices, both gathers, against single frames; the lone-frame form; weights.
 void multi_batches(int w, int h, int gather) {
+    stub_trace_mark("multi_batches");
     Scene s = scene(w, h, 90);
     const size_t fb = size_t(w) * h * 4;
     const int B = 9;
@@ -320,6 +325,7 @@ void multi_batches(int w, int h, int gather) {
 // Pipelined steps: two buffers handed back untouched; ONE buffer for every step; a lone render in between; overlapping
 // buffers; a change of options / partition / gather under the untouched flag; destroy with steps in flight.
 void multi_pipeline(int w, int h) {
+    stub_trace_mark("multi_pipeline");
     Scene s = scene(w, h, 0);
     const size_t fb = size_t(w) * h * 4;
     const int B = 5;
@@ -340,6 +346,15 @@ void multi_pipeline(int w, int h) {
     CHECK(kifs_multi_wait_all(m) == KIFS_OK && equal_dev(buf[1], wants[7]) && equal_dev(buf[0], wants[8]));
     KifsMultiStats st{};
     CHECK(kifs_multi_stats(m, &st, 1) == KIFS_OK && st.steps == 9);
+    // the flag with the other encoding: black is the same pixel both ways and everything else matches the slot's record,
+    // but "anything differs" means a fill -- it repairs rows that (against the flag's promise) do not hold the background
+    {
+        auto cams = cameras(B, 77);
+        uint64_t sn = 0;
+        std::memset(buf[1], 0x11, fb * B);
+        CHECK(kifs_multi_render_batch_async(m, B, cams.data(), buf[1], size_t(w) * 4, fb, 0, KIFS_MULTI_FRAMES_UNTOUCHED, &sn) == KIFS_OK);
+        CHECK(kifs_multi_wait(m, sn) == KIFS_OK && equal_dev(buf[1], single_frames(s, cams, 0)));
+    }
     // ONE buffer for every step, the flag always set: step k - 1's tiles must not survive under step k's background
     for (int k = 0; k < 6; ++k) {
         auto cams = cameras(B, 100 + 13 * k);
@@ -411,15 +426,17 @@ void multi_pipeline(int w, int h) {
     CHECK(hipFree(buf[0]) == hipSuccess && hipFree(buf[1]) == hipSuccess);
 }
 
-// Every HIP call and launch of a submit / wait cycle fails once, in turn: the call reports an error (or absorbs it), the
-// object stays usable, the next steps are exact, and nothing leaks.
+// Every HIP call and launch of a submit / wait cycle -- and of a lone frame, an explicit transport, the self-test --
+// fails once, in turn: the call reports an error (or absorbs it), the object stays usable, the next steps are exact,
+// and nothing leaks.
 void injected_failures(int w, int h) {
+    stub_trace_mark("injected_failures");
     Scene s = scene(w, h, 10);
     const size_t fb = size_t(w) * h * 4;
     const int B = 4;
     auto cams = cameras(B, 21);
     auto want = single_frames(s, cams);
-    uint8_t* frames = dev_alloc(fb * B);
+    uint8_t* frames = dev_alloc(fb * B * 2);  // (the second half: a second step's frames, or a lone frame)
     int failed_calls = 0;
     for (int gather : {KIFS_GATHER_SPARSE, KIFS_GATHER_DENSE}) {
         for (long n = 1; n < 400; ++n) {
@@ -447,6 +464,72 @@ void injected_failures(int w, int h) {
         }
     }
     CHECK(failed_calls > 10);
+    // the same for the other calls that enqueue or allocate: a lone frame (device and host destination), an explicit
+    // transport on a fresh object, the transport self-test -- each with a batched step in flight where one can be
+    std::vector<uint8_t> host(fb);
+    const auto lone_want = single_frames(s, cameras(1, 0));  // (the camera multi() sets)
+    for (int call = 0; call < 4; ++call) {
+        failed_calls = 0;
+        for (long n = 1; n < 400; ++n) {
+            kifs_multi* m = nullptr;
+            uint64_t s0 = 0;
+            if (call == 2) {
+                int st0 = 0;
+                const int devs[3] = {0, 1, 2};
+                m = kifs_multi_create(devs, 3, &st0);
+                CHECK(m && kifs_multi_set_screen(m, &s.screen) == KIFS_OK && kifs_multi_set_options(m, &s.options) == KIFS_OK);
+            } else {
+                m = multi({0, 1, 2}, s, KIFS_GATHER_SPARSE);
+                CHECK(kifs_multi_render_batch_async(m, B, cams.data(), frames, size_t(w) * 4, fb, 1, 0, &s0) == KIFS_OK);
+            }
+            uint8_t* lone_dst = call == 0 ? frames + fb * B : host.data();
+            const long before = stub_calls();
+            stub_fail_in(n);
+            const int st = call <= 1   ? kifs_multi_render(m, lone_dst, size_t(w) * 4, 1)
+                           : call == 2 ? kifs_multi_set_gather(m, KIFS_GATHER_SPARSE, KIFS_TRANSPORT_COPY)
+                                       : kifs_multi_comm_selftest(m, 4096);
+            const bool reached = stub_calls() - before >= n;
+            stub_fail_in(-1);
+            if (st != KIFS_OK) ++failed_calls;
+            CHECK(st == KIFS_OK || st == KIFS_ERR_RUNTIME || st == KIFS_ERR_COMM);
+            if (call <= 1 && st == KIFS_OK) CHECK(std::memcmp(lone_dst, lone_want.data(), fb) == 0);
+            (void)kifs_multi_wait_all(m);
+            std::memset(frames, 0x42, fb * B);
+            uint64_t s2 = 0;
+            CHECK(kifs_multi_render_batch_async(m, B, cams.data(), frames, size_t(w) * 4, fb, 1, 0, &s2) == KIFS_OK);
+            CHECK(kifs_multi_wait(m, s2) == KIFS_OK && equal_dev(frames, want));
+            kifs_multi_destroy(m);
+            if (!reached) break;
+        }
+        CHECK(failed_calls > 2);
+    }
+    // A flush that fails inside a submit leaves the older step unflushed beside the new one: kifs_multi_stream_wait for
+    // the newer step posts the older one first (the gather stream runs them in order), so the wait for the older one
+    // that follows has nothing left to launch.
+    hipStream_t consumer = nullptr;
+    CHECK(hipStreamCreateWithFlags(&consumer, hipStreamNonBlocking) == hipSuccess);
+    int older_first = 0;
+    for (long n = 1; n < 400; ++n) {
+        kifs_multi* m = multi({0, 1, 2}, s, KIFS_GATHER_SPARSE);
+        uint64_t s0 = 0, s1 = ~uint64_t(0);
+        CHECK(kifs_multi_render_batch_async(m, B, cams.data(), frames, size_t(w) * 4, fb, 1, 0, &s0) == KIFS_OK);
+        const long before = stub_calls();
+        stub_fail_in(n);
+        const int st = kifs_multi_render_batch_async(m, B, cams.data(), frames + fb * B, size_t(w) * 4, fb, 1, 0, &s1);
+        const bool reached = stub_calls() - before >= n;
+        stub_fail_in(-1);
+        if (st != KIFS_OK && s1 == s0 + 1) {  // the new step exists; what failed is the flush of the one before it
+            ++older_first;
+            CHECK(kifs_multi_stream_wait(m, s1, consumer) == KIFS_OK);
+            const long launches = stub_launches();
+            CHECK(kifs_multi_wait(m, s0) == KIFS_OK && stub_launches() == launches);
+            CHECK(kifs_multi_wait(m, s1) == KIFS_OK && equal_dev(frames, want) && equal_dev(frames + fb * B, want));
+        }
+        kifs_multi_destroy(m);
+        if (!reached) break;
+    }
+    CHECK(older_first > 0);
+    CHECK(hipStreamDestroy(consumer) == hipSuccess);
     // a context whose creation fails half way
     for (long n = 1; n < 12; ++n) {
         stub_fail_in(n);
@@ -526,6 +609,7 @@ std::vector<uint32_t> fresh_order(const Scene& s) {
 }
 
 void context_lifecycle() {
+    stub_trace_mark("context_lifecycle");
     Lifecycle L;
     int st = 0;
     L.c = kifs_create(0, &st);
