@@ -32,16 +32,16 @@ struct TileTable {
     const RowTable* rows = nullptr;   // non-null: the table of a row shard (then y0 = 0, y1 = height)
     uint32_t* d_order = nullptr;      // order used by the next launch
     uint32_t* d_order_alt = nullptr;  // the other half of the double buffer (the sort's target)
-    uint32_t* d_cost[2] = {nullptr, nullptr};  // per-tile cost, written by launch k into [k & 1]
-    hipEvent_t rendered[2] = {nullptr, nullptr};  // [0]: after the cost-recording launch; [1]: stream changes
+    uint32_t* d_cost = nullptr;       // per-tile cost, written by the first launch of a feedback period, read by the sort
+    hipEvent_t costs_written = nullptr;  // recorded after the launch that wrote d_cost
+    hipEvent_t stream_left = nullptr;    // recorded on the stream the caller moved away from
     hipEvent_t sorted = nullptr;      // recorded after the sort that fills d_order_alt
     uint64_t launches = 0;            // consecutive feedback launches made with this table
     hipStream_t last_stream = nullptr;  // stream of the latest of them
     bool sort_pending = false;        // d_order_alt holds (or will hold) a fresh order
-    bool costs_marked = false;        // rendered[0] was recorded after the launch that last wrote d_cost[0]
+    bool costs_marked = false;        // costs_written was recorded after the launch that last wrote d_cost
     bool feedback = true;             // reorder from costs (off once the caller pins an order)
     uint32_t count = 0;
-    uint32_t cost_shift = 0;          // scale of the costs the latest recording launch wrote (see record_costs)
     uint64_t last_use = 0;
 };
 constexpr int MAX_TILE_TABLES = 8;
@@ -93,11 +93,6 @@ struct kifs_ctx {
 
 namespace kifs {
 namespace host {
-
-// Tuning overrides (KIFS_ROUND_STEPS, KIFS_GROUP_TILES, KIFS_TILE_FEEDBACK, KIFS_FEEDBACK_PERIOD,
-// KIFS_BATCH_PERIOD; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as
-// well: they exist for tools/sweep_kernels.sh and friends, not for production hosts.  -1 = not set.
-int tuning_knob(const char* name);
 
 // KIFS_DEBUG=1 prints the failing HIP call to stderr (status codes stay the contract).
 bool hip_ok(hipError_t e, const char* what);

@@ -62,14 +62,29 @@ constexpr double BUNNY_W2LDS_FROM = 2600.0;   // pairs with layer 2 of the netwo
 constexpr double BUNNY_COOP_FROM = 5000.0;    // four waves per 64 rays (same file: x28 43.9 against 49.0 for the form above, x32 48.4 / 49.1, x40 55.0 / 50.0, x48 58.0 / 50.0)
 }  // namespace rules
 
-int tuning_knob(const char* name) {
-    static const bool enabled = [] {
-        const char* e = std::getenv("KIFS_TUNING");
-        return e && e[0] == '1';
+// Tuning overrides (KIFS_ROUND_STEPS, KIFS_GROUP_TILES, KIFS_BUNNY_COOP, KIFS_TILE_FEEDBACK, KIFS_FEEDBACK_PERIOD,
+// KIFS_BATCH_PERIOD; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as well: they exist
+// for tools/sweep_kernels.sh and friends, not for production hosts.  Read once per process, clamped here.
+struct Knobs {
+    int round_steps, group_tiles;        // -1: not set
+    int bunny_coop;                      // -1, or a form 0 / 1 / 2 (FrameParams::bunny_coop)
+    int tile_feedback;                   // 0 = never, 1 (default) = per pipeline thresholds, 2 = every frame of 2048+ tiles
+    uint64_t period_lone, period_batch;  // launches between two refreshes of the tile order
+};
+static const Knobs& knobs() {
+    static const Knobs k = [] {
+        const char* on = std::getenv("KIFS_TUNING");
+        const auto knob = [on](const char* name) {
+            const char* e = (on && on[0] == '1') ? std::getenv(name) : nullptr;
+            return e ? int(std::strtol(e, nullptr, 10)) : -1;
+        };
+        const int coop = knob("KIFS_BUNNY_COOP"), mode = knob("KIFS_TILE_FEEDBACK");
+        const int lone = knob("KIFS_FEEDBACK_PERIOD"), batch = knob("KIFS_BATCH_PERIOD");
+        return Knobs{knob("KIFS_ROUND_STEPS"), knob("KIFS_GROUP_TILES"), std::min(coop, 2), mode >= 0 ? mode : 1,
+                     uint64_t(lone < 0 ? rules::FEEDBACK_PERIOD_LONE : lone < 3 ? 3 : lone),
+                     uint64_t(batch < 0 ? rules::FEEDBACK_PERIOD_BATCH : batch < 2 ? 2 : batch)};
     }();
-    if (!enabled) return -1;
-    const char* e = std::getenv(name);
-    return e ? int(std::strtol(e, nullptr, 10)) : -1;
+    return k;
 }
 
 bool hip_ok(hipError_t e, const char* what) {
@@ -193,7 +208,7 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
         }
         const float R = B + o.epsilon;
         // (max_distance below 1e15 -- the GUI's range ends at 1e4 -- and, per view, an origin within 1e15 of the
-        // scene: enqueue_batch; the long-ray loop's square root of |p|^2 relies on |p|^2 being finite then)
+        // scene: fill_views; the long-ray loop's square root of |p|^2 relies on |p|^2 being finite then)
         const bool sane = B > 0.0f && R > 0.5f && R < 1.0e6f && o.epsilon >= 0.0f && o.max_distance < 1.0e15f;
         P->cull_n2 = sane ? 1.1f * R * R : 0.0f;
         // the wave-level quick exit uses a sphere 9 % larger again; like the culls, not in heatmap mode
@@ -203,7 +218,7 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
         // centres of a 32 x 8 tile are at most (31, 7) pixels = (31, 7) * 2 / height apart in uv, so a
         // ray of the tile and the ray through the tile's centre differ by at most
         // asin(|(31, 7)| / height) <= 1.05 * 31.8 / height radians (the ratio is below 0.5 from 64 rows);
-        // 34 / height leaves 2 % for the matrix check's tolerance.  enqueue_batch() switches it off when
+        // 34 / height leaves 2 % for the matrix check's tolerance.  fill_views() switches it off when
         // a view's matrix is not orthonormal.
         P->tile_cull_sqrtk = std::sqrt(P->quick_cull_n2);
         P->tile_cull_beta = (P->quick_cull_n2 > 0.0f && c->screen.height >= 64.0f) ? 34.0f / c->screen.height : 0.0f;
@@ -214,7 +229,7 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
         // Not for heatmap frames (their per-ray step count is kept by the one-wave-per-block
         // march), not with a non-positive epsilon (the queue rebuilds p from t and relies on
         // t > 0 after a step), not for marches too short to repay the rounds' barriers.
-        static const int forced = tuning_knob("KIFS_ROUND_STEPS");
+        const int forced = knobs().round_steps;
         int rounds = forced >= 0 ? forced : (o.fractal_group_id != uint32_t(kifs::GROUP_KIFS) ? rules::ROUND_STEPS_JULIA : rules::ROUND_STEPS_OTHER);
         if (forced < 0 && rounds == rules::ROUND_STEPS_JULIA && o.max_iterations < 32 && o.fractal_group_id == uint32_t(kifs::GROUP_GENJULIA))
             rounds = rules::ROUND_STEPS_OTHER;  // (a short march of heavy steps still repays shorter rounds)
@@ -264,21 +279,11 @@ bool is_device_pointer(const void* p) {
 void free_table(TileTable& t) {
     if (t.d_order) (void)hipFree(t.d_order);
     if (t.d_order_alt) (void)hipFree(t.d_order_alt);
-    for (int i = 0; i < 2; ++i) {
-        if (t.d_cost[i]) (void)hipFree(t.d_cost[i]);
-        if (t.rendered[i]) (void)hipEventDestroy(t.rendered[i]);
-    }
+    if (t.d_cost) (void)hipFree(t.d_cost);
+    if (t.costs_written) (void)hipEventDestroy(t.costs_written);
+    if (t.stream_left) (void)hipEventDestroy(t.stream_left);
     if (t.sorted) (void)hipEventDestroy(t.sorted);
     t = TileTable();
-}
-
-// KIFS_TILE_FEEDBACK (tuning): 0 = never, 1 (default) = per pipeline thresholds, 2 = every frame of 2048+ tiles.
-static int tile_feedback_mode() {
-    static const int mode = [] {
-        const int v = tuning_knob("KIFS_TILE_FEEDBACK");
-        return v >= 0 ? v : 1;
-    }();
-    return mode;
 }
 
 // Device image of a stripe list, cached by content.  Stripes must be ascending and inside the frame: the
@@ -348,14 +353,12 @@ TileTable* tile_table(kifs_ctx* c, int width, int height, int y0, int y1, const 
     const size_t bytes = order.size() * sizeof(uint32_t);
     if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_order), bytes), "hipMalloc(tile order)") ||
         !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_order_alt), bytes), "hipMalloc(tile order 2)") ||
-        !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_cost[0]), bytes), "hipMalloc(tile cost)") ||
-        !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_cost[1]), bytes), "hipMalloc(tile cost 2)") ||
-        !hip_ok(hipEventCreateWithFlags(&slot->rendered[0], hipEventDisableTiming), "hipEventCreate") ||
-        !hip_ok(hipEventCreateWithFlags(&slot->rendered[1], hipEventDisableTiming), "hipEventCreate") ||
+        !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_cost), bytes), "hipMalloc(tile cost)") ||
+        !hip_ok(hipEventCreateWithFlags(&slot->costs_written, hipEventDisableTiming), "hipEventCreate") ||
+        !hip_ok(hipEventCreateWithFlags(&slot->stream_left, hipEventDisableTiming), "hipEventCreate") ||
         !hip_ok(hipEventCreateWithFlags(&slot->sorted, hipEventDisableTiming), "hipEventCreate") ||
         !hip_ok(hipMemcpy(slot->d_order, order.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(tile order)") ||
-        !hip_ok(hipMemset(slot->d_cost[0], 0, bytes), "hipMemset(tile cost)") ||
-        !hip_ok(hipMemset(slot->d_cost[1], 0, bytes), "hipMemset(tile cost)")) {
+        !hip_ok(hipMemset(slot->d_cost, 0, bytes), "hipMemset(tile cost)")) {
         free_table(*slot);
         return nullptr;
     }
@@ -424,72 +427,46 @@ uint32_t background_pixel(const kifs_ctx* c, kifs::V3 colour, int encode) {
     return ch[0] | (ch[1] << 8) | (ch[2] << 16) | 0xff000000u;
 }
 
-// The launch itself and what goes with every one: the profiling event pair around it, and the view table of a batch
-// beyond the kernel argument (ring slot `vs`) uploaded before it and marked in use after it.
-static int launch(kifs_ctx* c, hipStream_t stream, kifs::BatchParams& B, bool big, int vs) {
-    const bool timed = c->profiling && !c->prof_a.empty() && (c->prof_seen++ % uint64_t(c->prof_every)) == 0;
-    const size_t pslot = c->prof_count % (c->prof_a.empty() ? 1 : c->prof_a.size());
-    if (timed && !hip_ok(hipEventRecord(c->prof_a[pslot], stream), "record(profile start)")) return KIFS_ERR_RUNTIME;
-    if (big) {
-        if (!hip_ok(hipMemcpyAsync(c->d_views[vs], c->h_views[vs], sizeof(kifs::BatchView) * size_t(B.count),
-                                   hipMemcpyHostToDevice, stream), "copy(view table)"))
-            return KIFS_ERR_RUNTIME;
-        B.table = c->d_views[vs];
-    }
-    hipError_t e = kifs::launch_render(B, c->options.fractal_group_id, c->options.primitive_id,
-                                       stream);
-    if (!hip_ok(e, "render_kernel launch")) return KIFS_ERR_RUNTIME;
-    if (big) {
-        if (!hip_ok(hipEventRecord(c->views_used[vs], stream), "record(view table)")) return KIFS_ERR_RUNTIME;
-        c->views_busy[vs] = true;
-    }
-    if (timed) {
-        if (!hip_ok(hipEventRecord(c->prof_b[pslot], stream), "record(profile stop)")) return KIFS_ERR_RUNTIME;
-        ++c->prof_count;
-    }
-    return KIFS_OK;
+// ---- one launch, step by step: enqueue_batch() below calls these in order ----------------------------------------
+static bool is_bunny(const kifs_ctx* c) {
+    return c->options.fractal_group_id == uint32_t(kifs::GROUP_KIFS) && c->options.primitive_id == uint32_t(kifs::PRIM_BUNNY);
 }
 
-int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras,
-                  uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
-                  const int* stripes, int n_stripes, int in_place, float* geom, size_t geom_pitch, size_t geom_stride) {
-    hip_ok(hipGetLastError(), "stale error before enqueue");
+// What a caller can get wrong before anything is looked up: state, count, destinations, encoding, frame size.
+static int check_arguments(const kifs_ctx* c, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, int encode) {
     if (!c->have_screen || !c->have_options || (!c->have_camera && !cameras)) return KIFS_ERR_UNCONFIGURED;
     if (count < 1 || count > kifs::MAX_BATCH || !outs) return KIFS_ERR_BAD_ARG;
     for (int i = 0; i < count; ++i)
         if (!outs[i] || (reinterpret_cast<uintptr_t>(outs[i]) & 3u) != 0) return KIFS_ERR_BAD_ARG;
-    uint8_t* const dev_out = outs[0];
     if (encode != KIFS_ENCODE_UNORM && encode != KIFS_ENCODE_SRGB) return KIFS_ERR_BAD_ARG;
-    kifs::BatchParams B;
-    kifs::FrameParams& P = B.frame;
-    int st = fill_params(c, &P);
-    if (st != KIFS_OK) return st;
-    int rw, rh;
-    st = render_dims(c, &rw, &rh);  // (the virtual screen of a supersampled launch)
-    if (st != KIFS_OK) return st;
-    B.count = count;
-    B.table = nullptr;
-    // a batch beyond the kernel argument's room: the views go through a device table (ring slot `vs`)
-    const bool big = count > kifs::MAX_BATCH_INLINE;
-    int vs = -1;
-    if (big) {
-        vs = c->view_slot;
-        c->view_slot = (vs + 1) % kifs_ctx::VIEW_RING;
-        if (!c->d_views[vs]) {
-            const size_t bytes = sizeof(kifs::BatchView) * size_t(kifs::MAX_BATCH);
-            if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_views[vs]), bytes), "hipMalloc(view table)") ||
-                !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_views[vs]), bytes, hipHostMallocDefault), "hipHostMalloc(view table)") ||
-                !hip_ok(hipEventCreateWithFlags(&c->views_used[vs], hipEventDisableTiming), "hipEventCreate(view table)"))
-                return KIFS_ERR_RUNTIME;
-        }
-        // the launch that last read this slot (four big launches ago) must be over before its images change
-        if (c->views_busy[vs] && !hip_ok(hipEventSynchronize(c->views_used[vs]), "wait(view table)")) return KIFS_ERR_RUNTIME;
-        c->views_busy[vs] = false;
+    return KIFS_OK;
+}
+
+// A batch beyond the kernel argument's room: the views go through a device table, the next slot of the ring.
+static int take_view_slot(kifs_ctx* c, int* slot) {
+    const int vs = *slot = c->view_slot;
+    c->view_slot = (vs + 1) % kifs_ctx::VIEW_RING;
+    if (!c->d_views[vs]) {
+        const size_t bytes = sizeof(kifs::BatchView) * size_t(kifs::MAX_BATCH);
+        if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_views[vs]), bytes), "hipMalloc(view table)") ||
+            !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_views[vs]), bytes, hipHostMallocDefault), "hipHostMalloc(view table)") ||
+            !hip_ok(hipEventCreateWithFlags(&c->views_used[vs], hipEventDisableTiming), "hipEventCreate(view table)"))
+            return KIFS_ERR_RUNTIME;
     }
+    // the launch that last read this slot (four big launches ago) must be over before its images change
+    if (c->views_busy[vs] && !hip_ok(hipEventSynchronize(c->views_used[vs]), "wait(view table)")) return KIFS_ERR_RUNTIME;
+    c->views_busy[vs] = false;
+    return KIFS_OK;
+}
+
+// The views, and what they decide for the whole launch: P's camera is view 0's, and the culls go when a view does not
+// meet what they assume.
+static void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
+                       uint8_t* const* outs) {
     bool far_origin = false;  // a view whose origin is not within 1e15 of the scene: no culls for this launch
     for (int i = 0; i < count; ++i) {
         const KifsCameraUniform& cam = cameras ? cameras[i] : c->camera;
-        kifs::BatchView& v = big ? c->h_views[vs][i] : B.view[i];
+        kifs::BatchView& v = views[i];
         v.origin = {cam.origin[0], cam.origin[1], cam.origin[2]};
         v.m0 = {cam.matrix[0][0], cam.matrix[0][1], cam.matrix[0][2]};
         v.m1 = {cam.matrix[1][0], cam.matrix[1][1], cam.matrix[1][2]};
@@ -506,22 +483,20 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
                 }
         }
     }
-    if (far_origin) {
-        P.cull_n2 = 0.0f;
-        P.quick_cull_n2 = 0.0f;
-        P.tile_cull_beta = 0.0f;
-    }
-    const kifs::BatchView& view0 = big ? c->h_views[vs][0] : B.view[0];
-    P.origin = view0.origin;
-    P.m0 = view0.m0;
-    P.m1 = view0.m1;
-    P.m2 = view0.m2;
-    const int h = P.y1;
-    if (y0 < 0 || y1 > h || y0 > y1) return KIFS_ERR_BAD_ARG;
-    if (pitch < size_t(P.width) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull)
-        return KIFS_ERR_BAD_SIZE;
+    if (far_origin) P.cull_n2 = P.quick_cull_n2 = P.tile_cull_beta = 0.0f;
+    P.origin = views[0].origin;
+    P.m0 = views[0].m0;
+    P.m1 = views[0].m1;
+    P.m2 = views[0].m2;
+}
+
+// Band, pitch and geometry plane: checked against the frame (P.y1 is still its height), then written into P.
+static int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, uint8_t* out, size_t pitch, int y0, int y1, int encode,
+                           bool striped, float* geom, size_t geom_pitch, size_t geom_stride) {
+    if (y0 < 0 || y1 > P.y1 || y0 > y1) return KIFS_ERR_BAD_ARG;
+    if (pitch < size_t(P.width) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull) return KIFS_ERR_BAD_SIZE;
     if (geom) {  // the geometry plane: 16-byte texels, rows of a band packed, one plane per view `geom_stride` apart
-        if (stripes || P.ssaa > 1) return KIFS_ERR_BAD_ARG;
+        if (striped || P.ssaa > 1) return KIFS_ERR_BAD_ARG;
         if ((reinterpret_cast<uintptr_t>(geom) & 15u) != 0 || geom_pitch < size_t(P.width) * 16 || (geom_pitch & 15u) != 0 ||
             (geom_stride & 15u) != 0 || (count > 1 && geom_stride < size_t(y1 - y0) * geom_pitch) ||
             (geom_pitch >> 4) > 0xffffffffull || (geom_stride >> 4) > 0xffffffffull)
@@ -535,7 +510,238 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     P.encode = encode;
     P.background_rgba = background_pixel(c, P.background_color, encode);
     P.pitch_words = uint32_t(pitch >> 2);
-    P.out = reinterpret_cast<uint32_t*>(dev_out);
+    P.out = reinterpret_cast<uint32_t*>(out);
+    return KIFS_OK;
+}
+
+// Temporal feedback on the tile order.  A launch can leave a cost per tile (the run time of the tile's slowest wave); a
+// one-workgroup counting sort on the context's side stream turns those costs into a new order while the following launch
+// is running, so the sort is off the critical path.  The longest rays sit at the fractal's silhouette, which no static
+// order knows; with them first the frame ends when they do.  Tables:
+//   d_order      read by the launches      d_order_alt   written by the sort, then swapped in
+//   d_cost       written by the first launch of a period, read by the sort
+// Events order everything whichever streams the caller uses.  Off for small frames, where it does not pay for itself;
+// KIFS frames gain from it only when they are large (8K: 2.58 -> 2.23 ms; 1080p: nothing).
+// The order is refreshed every `period` launches (views change slowly; the events the refresh needs cost a few
+// microseconds each): every fourth lone launch, every third batched one (its launches are long and its views move: an
+// orbit; measured best for fixed and moving cameras).  Within a period of launches k = 0..period-1:
+//   k == 0: record costs, event;   k == 1: sort the costs of launch 0;   k == 2: the new order is in use.
+// With several frames in flight (several contexts and streams on one device) or a batch the sort runs in the launch stream
+// itself: streams share a handful of hardware queues, and an event wait parked in a queue also holds up whatever other
+// context's launches sit behind it (measured: two contexts fell back to running one after the other).  The 10 us then
+// hide behind the other frames' kernels.  A lone frame keeps the side stream: there nothing else can.
+struct Feedback {  // what the step before a launch hands to the step after it
+    bool use = false, inline_sort = false, record_costs = false; uint64_t k = 0;  // k: the launch's place in its period
+};
+
+// The side stream's sort is done with d_order_alt: wait for it, swap it in.
+static int adopt_sorted_order(TileTable* tt, hipStream_t stream) {
+    if (!hip_ok(hipStreamWaitEvent(stream, tt->sorted, 0), "wait(sorted)")) return KIFS_ERR_RUNTIME;
+    std::swap(tt->d_order, tt->d_order_alt);
+    tt->sort_pending = false;
+    return KIFS_OK;
+}
+
+// Before the launch.  `plain` false: a geometry or supersampled launch, which follows a stream change like any other but
+// neither records costs nor moves the sort (its tiles cost something else), so that a later plain launch of the same
+// geometry finds the order where the plain launches left it.
+static int feedback_before(kifs_ctx* c, TileTable* tt, hipStream_t stream, int count, uint32_t tiles_x, bool plain, Feedback* f) {
+    const bool is_kifs = c->options.fractal_group_id == uint32_t(kifs::GROUP_KIFS);
+    f->use = tt->feedback && knobs().tile_feedback != 0 && !is_bunny(c) &&  // (the bunny's quad kernel records no costs)
+             tt->count >= ((is_kifs && knobs().tile_feedback < 2) ? rules::FEEDBACK_MIN_TILES_KIFS : rules::FEEDBACK_MIN_TILES);
+    if (!f->use) return KIFS_OK;
+    if (tt->last_stream && tt->last_stream != stream) {
+        // The caller moved to another stream: order this stream after the launches of the old one, so that the buffer
+        // rotation below keeps its "nobody still reads it" guarantee.
+        if (!hip_ok(hipEventRecord(tt->stream_left, tt->last_stream), "record(stream change)") ||
+            !hip_ok(hipStreamWaitEvent(stream, tt->stream_left, 0), "wait(stream change)"))
+            return KIFS_ERR_RUNTIME;
+    }
+    tt->last_stream = stream;
+    if (!plain) return KIFS_OK;
+    f->k = tt->launches % (count > 1 ? knobs().period_batch : knobs().period_lone);
+    f->inline_sort = c->frames_in_flight > 1 || count > 1;
+    f->record_costs = f->k == 0;
+    // A side-stream sort from earlier launches owns d_cost and d_order_alt -- the one behind launch 1 of this lone period,
+    // lone launches before a batch, or a period cut short when feedback was switched off in between (options changed to a
+    // pipeline without it and back).  Take its result before anything here records costs or sorts again: the sort reads
+    // cost[] twice and must not see it change.
+    if (tt->sort_pending && adopt_sorted_order(tt, stream) != KIFS_OK) return KIFS_ERR_RUNTIME;
+    if (f->inline_sort && f->k == 1) {
+        if (!hip_ok(kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, 0, stream), "tile_order_kernel launch"))
+            return KIFS_ERR_RUNTIME;
+        std::swap(tt->d_order, tt->d_order_alt);  // stream order: the sort precedes this launch
+    }
+    return KIFS_OK;
+}
+
+// After a plain launch: the event behind the recorded costs, or the side stream's sort of them.
+static int feedback_after(kifs_ctx* c, TileTable* tt, hipStream_t stream, uint32_t tiles_x, const Feedback& f) {
+    if (!f.use) {  // no bookkeeping, no events: nothing depends on this launch
+        tt->launches = 0;  // (a pending side-stream sort stays pending: the next feedback launch waits for it)
+        return KIFS_OK;
+    }
+    tt->launches += 1;
+    if (f.record_costs) tt->costs_marked = false;
+    if (f.inline_sort) return KIFS_OK;
+    if (f.record_costs) {
+        // Launch k = 0 of the period wrote d_cost.  The previous sort (period before) read it and finished before that
+        // period's launch 2 started, i.e. long ago on this timeline.
+        if (!hip_ok(hipEventRecord(tt->costs_written, stream), "record(render)")) return KIFS_ERR_RUNTIME;
+        tt->costs_marked = true;
+    } else if (f.k == 1) {
+        // The costs may come from a launch that sorts inline and records no event -- a batch, or frames_in_flight > 1,
+        // before this lone launch.  costs_written is then unrecorded or a period old, and a wait for it would let the sort
+        // read costs that launch is still writing: mark this point of the stream instead (it follows that launch).
+        if (!tt->costs_marked) {
+            if (!hip_ok(hipEventRecord(tt->costs_written, stream), "record(render, late)")) return KIFS_ERR_RUNTIME;
+            tt->costs_marked = true;
+        }
+        // sort those costs into d_order_alt: the buffer last read by launches of the period before the previous adoption,
+        // all of which precede launch 0 of this period
+        if (!c->side_stream && !hip_ok(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking), "side stream")) return KIFS_ERR_RUNTIME;
+        if (!hip_ok(hipStreamWaitEvent(c->side_stream, tt->costs_written, 0), "wait(render 0)") ||
+            !hip_ok(kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, 0, c->side_stream), "tile_order_kernel launch") ||
+            !hip_ok(hipEventRecord(tt->sorted, c->side_stream), "record(sorted)"))
+            return KIFS_ERR_RUNTIME;
+        tt->sort_pending = true;
+    }
+    return KIFS_OK;
+}
+
+// The shape of a geometry or supersampled launch: one kernel form for every scene, whole rays, no costs, no diagnostics.
+// A lone geometry frame keeps the block kernel's residency cap.
+static void fixed_shape(const kifs_ctx* c, kifs::FrameParams& P, int count, int frame_height) {
+    P.tile_cost = nullptr;
+    P.counters = nullptr;
+    P.round_steps = 0;
+    const bool lone = count == 1 && c->frames_in_flight <= 1;
+    P.workgroups_per_cu = (P.geom && lone) ? residency_for(P, c->options.fractal_group_id, disc_tiles(P, frame_height, P.tile_count)) : 0;
+}
+
+// The shape of a plain launch.  Everything is decided from `load`: the launch's tiles that can hold rays with real work
+// (the projected bounding sphere's tiles, all views), tools/cliff_sweep.py's x axis.
+static void choose_shape(const kifs_ctx* c, kifs::FrameParams& P, int count, int frame_height) {
+    // The diagnostics buffer holds one record per wave of the screen kifs_debug_counters saw (counter_words).  A launch
+    // with more waves -- a larger screen set since, a batch -- runs as if diagnostics were off: nothing is reallocated
+    // here, an earlier enqueued launch may still be writing the buffer.
+    if (P.counters && 8ull + 16ull * uint64_t(P.tile_count) * uint64_t(count) > uint64_t(c->counter_words)) P.counters = nullptr;
+    if (P.counters) P.round_steps = 0;  // the per-wave diagnostics belong to the one-wave-per-block march
+    const uint32_t group_id = c->options.fractal_group_id;
+    const bool free_rounds = knobs().round_steps < 0;  // (a forced KIFS_ROUND_STEPS replaces every round length below)
+    const bool lone = count == 1 && c->frames_in_flight <= 1;
+    const bool bunny_scene = is_bunny(c);
+    const double heavy_tiles = disc_tiles(P, frame_height, P.tile_count);
+    const double load = heavy_tiles * double(count);
+    // the residency cap serves a lone frame's latency; concurrent frames want every slot
+    P.workgroups_per_cu = lone ? residency_for(P, group_id, heavy_tiles) : 0;
+    // a residency-capped launch is a lone frame bound by its longest rays: re-queuing helps throughput, not that (1080p
+    // Julia: 0.143 ms without, 0.146 ms with)
+    if (P.workgroups_per_cu >= 1) P.round_steps = 0;
+    // (an uncapped lone Julia frame -- 4096^2 -- prefers longer rounds: 0.430 ms at 32 steps, 0.445 at 16)
+    if (P.round_steps == rules::ROUND_STEPS_JULIA && count == 1 && group_id == uint32_t(kifs::GROUP_JULIA) && P.max_iterations >= 64 && free_rounds)
+        P.round_steps = rules::ROUND_STEPS_LONE_JULIA;
+    // (nor does the lone bunny frame: 0.461 ms with the quad kernel, 0.670 ms in rounds; nor two of them)
+    if (bunny_scene && (count == 1 || (load < rules::BUNNY_ROUNDS_FROM && free_rounds))) P.round_steps = 0;
+    // nor does a launch too small to fill the device twice over (256x256 x 8 views = 2048 workgroups: 0.038 ms without, 0.062 with)
+    if (uint64_t(P.tile_count) * uint64_t(count) < rules::REQUEUE_MIN_WORKGROUPS) P.round_steps = 0;
+    // Shape of the re-queuing path (profiles/r02/sweep_shapes.jsonl: 5 frame sizes x 4 camera distances x 2 scenes x
+    // batches of 1 / 8 / 32, every shape forced in turn):
+    //   one WAVE per tile (render_wave_kernel) once the launch has several times more heavy tiles than the device has
+    //     workgroup slots -- then slots, not critical paths, set its duration, and single-wave workgroups give four times
+    //     as many (1080p Julia x32: 1.13 -> 0.88 ms; 4096^2 x8 +27 %; 8K Sierpinski x4 +16 %) -- from a load of 12 500
+    //     tiles for the Julia pipeline, 32 000 for the others, 30 000 for a lone frame (all its heavy tiles are one view's);
+    //   otherwise 256-thread workgroups (render_group_kernel), whose four waves take a tile's first, crowded rounds side
+    //     by side (a lone wave needs +30 % for the same tile): TWO tiles of the cost order per workgroup when the launch is
+    //     a batch with enough heavy tiles to pair (one tile's queue is short for most of its life, neighbours of the cost
+    //     order fill each other's waves: batched 1080p Julia 0.319 -> 0.281 ms; below 3 500 heavy tiles pairing only
+    //     halves the workgroups that can run side by side: 720p x8 at distance 5, 0.222 -> 0.188 ms with one) or a big
+    //     lone KIFS frame (1440p Sierpinski at distance 2: -11 %), else ONE.
+    // Not the bunny (four lanes per ray, 216 VGPRs: pairs just run longer); the generalised Julia pairs tiles only from
+    // 12 000 heavy tiles (1080p x32: 0.140 -> 0.125 ms per frame; x8: nothing, and its few, very long workgroups lost 7 %
+    // when paired on smaller launches) and keeps 256-thread workgroups throughout (one wave per tile: x32 0.150 ms, x8
+    // 0.31 against 0.22).
+    const int forced = knobs().group_tiles;
+    const bool julia = group_id == uint32_t(kifs::GROUP_JULIA);
+    const bool genjulia = group_id == uint32_t(kifs::GROUP_GENJULIA);
+    const bool kifs_scene = group_id == uint32_t(kifs::GROUP_KIFS);
+    const double wave_from = lone ? rules::WAVE_FROM_LONE : (julia ? rules::WAVE_FROM_JULIA : rules::WAVE_FROM_OTHER);
+    int shape = 1;
+    // (one wave per tile needs views to interleave: TWO frames of 4096^2 -- 19 600 heavy tiles, past WAVE_FROM_JULIA -- run
+    // 31.5 Gpixel/s that way against 42.8 with pairs, four 52.0 against 44.0: r04, profiles/r04/sweep_group_shapes.txt)
+    if (load >= wave_from && !genjulia && (count >= 3 || load >= rules::WAVE_FROM_LONE)) shape = 0;
+    else if (!lone && load >= (genjulia ? rules::PAIR_FROM_GENJULIA : kifs_scene ? rules::PAIR_FROM_BATCH_KIFS : rules::PAIR_FROM_BATCH))
+        shape = 2;
+    else if (lone && kifs_scene && load >= rules::PAIR_FROM_LONE_KIFS) shape = 2;
+    if (forced >= 0) shape = forced;
+    P.bunny_coop = 0;
+    if (bunny_scene) {  // its own rules: four lanes per ray (216 VGPRs) or four waves per 64 rays
+        const int coop = knobs().bunny_coop;  // (KIFS_BUNNY_COOP under KIFS_TUNING forces a form)
+        P.bunny_coop = coop >= 0 ? coop : (load >= rules::BUNNY_COOP_FROM ? 1 : load >= rules::BUNNY_W2LDS_FROM ? 2 : 0);
+        shape = P.bunny_coop ? 2 : forced >= 1 ? forced : (load >= rules::BUNNY_PAIR_FROM ? 2 : 1);
+        if (P.bunny_coop == 1 && P.round_steps == rules::ROUND_STEPS_OTHER && free_rounds) P.round_steps = rules::ROUND_STEPS_BUNNY_COOP;
+    }
+    P.group_tiles = shape;
+    if (shape == 0 && kifs_scene && !bunny_scene && P.round_steps == rules::ROUND_STEPS_OTHER && free_rounds)
+        P.round_steps = rules::ROUND_STEPS_KIFS_WAVE;
+}
+
+// What kifs_debug_last_* report of the launch P describes, whichever kind it is.
+static void report_shape(kifs_ctx* c, const kifs::FrameParams& P) {
+    const bool bunny = is_bunny(c), rounds = P.round_steps > 0;
+    c->last_round_steps = P.round_steps;
+    c->last_group_tiles = rounds ? P.group_tiles : -1;
+    c->last_bunny_form = bunny && rounds ? P.bunny_coop : -1;
+    c->last_kernel = P.geom ? KIFS_KERNEL_GEOMETRY : P.ssaa > 1 ? KIFS_KERNEL_SSAA
+                   : rounds ? (bunny ? (P.bunny_coop == 1 ? KIFS_KERNEL_BUNNY_COOP : KIFS_KERNEL_GROUP)
+                                     : (P.group_tiles == 0 ? KIFS_KERNEL_WAVE : KIFS_KERNEL_GROUP))
+                            : (bunny ? KIFS_KERNEL_BUNNY_QUAD : KIFS_KERNEL_BLOCK);
+}
+
+// The launch itself and what goes with every one: the profiling event pair around it, and the view table of a batch
+// beyond the kernel argument (ring slot `vs`) uploaded before it and marked in use after it.
+static int launch(kifs_ctx* c, hipStream_t stream, kifs::BatchParams& B, bool big, int vs) {
+    const bool timed = c->profiling && !c->prof_a.empty() && (c->prof_seen++ % uint64_t(c->prof_every)) == 0;
+    const size_t pslot = c->prof_count % (c->prof_a.empty() ? 1 : c->prof_a.size());
+    if (timed && !hip_ok(hipEventRecord(c->prof_a[pslot], stream), "record(profile start)")) return KIFS_ERR_RUNTIME;
+    if (big) {
+        if (!hip_ok(hipMemcpyAsync(c->d_views[vs], c->h_views[vs], sizeof(kifs::BatchView) * size_t(B.count), hipMemcpyHostToDevice, stream),
+                    "copy(view table)"))
+            return KIFS_ERR_RUNTIME;
+        B.table = c->d_views[vs];
+    }
+    if (!hip_ok(kifs::launch_render(B, c->options.fractal_group_id, c->options.primitive_id, stream), "render_kernel launch")) return KIFS_ERR_RUNTIME;
+    if (big) {
+        if (!hip_ok(hipEventRecord(c->views_used[vs], stream), "record(view table)")) return KIFS_ERR_RUNTIME;
+        c->views_busy[vs] = true;
+    }
+    if (timed) {
+        if (!hip_ok(hipEventRecord(c->prof_b[pslot], stream), "record(profile stop)")) return KIFS_ERR_RUNTIME;
+        ++c->prof_count;
+    }
+    return KIFS_OK;
+}
+
+int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras,
+                  uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
+                  const int* stripes, int n_stripes, int in_place, float* geom, size_t geom_pitch, size_t geom_stride) {
+    hip_ok(hipGetLastError(), "stale error before enqueue");
+    int st = check_arguments(c, count, cameras, outs, encode);
+    if (st != KIFS_OK) return st;
+    kifs::BatchParams B;
+    kifs::FrameParams& P = B.frame;
+    int rw, rh;
+    if ((st = fill_params(c, &P)) != KIFS_OK) return st;
+    if ((st = render_dims(c, &rw, &rh)) != KIFS_OK) return st;  // (the virtual screen of a supersampled launch)
+    B.count = count;
+    B.table = nullptr;
+    const int h = P.y1;  // the frame's height
+    st = set_destination(c, P, count, outs[0], pitch, y0, y1, encode, stripes != nullptr, geom, geom_pitch, geom_stride);
+    if (st != KIFS_OK) return st;  // (before a slot of the view ring is taken: a rejected call leaves no trace)
+    const bool big = count > kifs::MAX_BATCH_INLINE;
+    int vs = -1;
+    if (big && (st = take_view_slot(c, &vs)) != KIFS_OK) return st;
+    fill_views(c, P, big ? c->h_views[vs] : B.view, count, cameras, outs);
     if (y1 == y0) return KIFS_OK;
     const RowTable* rows = nullptr;
     if (stripes) {
@@ -547,237 +753,30 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     }
     TileTable* tt = tile_table(c, P.width, h, y0, y1, rows);
     if (!tt) return KIFS_ERR_RUNTIME;
-    // Temporal feedback on the tile order.  A launch can leave a cost per tile (the run time of
-    // the tile's slowest wave); a one-workgroup counting sort on the context's side stream turns
-    // those costs into a new order while the following launch is running, so the sort is off
-    // the critical path.  The longest rays sit at the fractal's silhouette, which no static
-    // order knows; with them first the frame ends when they do.  Tables:
-    //   d_order      read by the launches      d_order_alt   written by the sort, then swapped in
-    //   d_cost[0]    written by the first launch of a period, read by the sort
-    // Events order everything whichever streams the caller uses.  Off for small frames, where it
-    // does not pay for itself.
-    // KIFS frames gain from it only when they are large (8K: 2.58 -> 2.23 ms; 1080p: nothing).
-    const bool is_kifs = c->options.fractal_group_id == uint32_t(kifs::GROUP_KIFS);
-    // (the bunny's quad kernel records no costs)
-    const bool records_costs = !(is_kifs && c->options.primitive_id == uint32_t(kifs::PRIM_BUNNY));
-    const bool use_feedback = tt->feedback && tile_feedback_mode() != 0 && records_costs &&
-                              tt->count >= ((is_kifs && tile_feedback_mode() < 2) ? rules::FEEDBACK_MIN_TILES_KIFS : rules::FEEDBACK_MIN_TILES);
-    // The order is refreshed every FEEDBACK_PERIOD launches (views change slowly; the events the
-    // refresh needs cost a few microseconds each).  Within a period of launches k = 0..P-1:
-    //   k == 0: record costs, event;   k == 1: sort the costs of launch 0 on the side stream;
-    //   k == 2: adopt the new order (wait for the sort);   otherwise: a plain launch.
-    static const uint64_t FEEDBACK_PERIOD = [] {
-        const int v = tuning_knob("KIFS_FEEDBACK_PERIOD");
-        return uint64_t(v < 0 ? rules::FEEDBACK_PERIOD_LONE : v < 3 ? 3 : v);
-    }();
-    if (use_feedback && tt->last_stream && tt->last_stream != stream) {
-        // The caller moved to another stream: order this stream after the launches of the old
-        // one, so that the buffer rotation below keeps its "nobody still reads it" guarantee.
-        if (!hip_ok(hipEventRecord(tt->rendered[1], tt->last_stream), "record(stream change)") ||
-            !hip_ok(hipStreamWaitEvent(stream, tt->rendered[1], 0), "wait(stream change)"))
-            return KIFS_ERR_RUNTIME;
-    }
-    if (use_feedback) tt->last_stream = stream;
-    if (P.geom) {
-        // The geometry output: the plain launch's tile table, band, views and current order, one kernel form for every
-        // scene, whole rays.  Like a supersampled launch it neither records costs nor moves the sort, so a later plain
-        // launch of the same geometry finds the order where the plain launches left it.  A lone frame keeps the block
-        // kernel's residency cap.
-        P.tile_order = tt->d_order;
-        P.tile_count = tt->count;
-        P.tile_cost = nullptr;
-        P.counters = nullptr;
-        P.round_steps = 0;
-        const bool lone = count == 1 && c->frames_in_flight <= 1;
-        P.workgroups_per_cu = lone ? residency_for(P, c->options.fractal_group_id, disc_tiles(P, h, tt->count)) : 0;
-        c->last_kernel = KIFS_KERNEL_GEOMETRY;
-        c->last_round_steps = 0;
-        c->last_group_tiles = -1;
-        c->last_bunny_form = -1;
-        return launch(c, stream, B, big, vs);
-    }
-    if (P.ssaa > 1) {
-        // k x k supersampling: the output's tile table, stripes, band, views and current order, one kernel form for
-        // every scene.  Its tiles cost k^2 times theirs, so it neither records costs nor moves the sort: a later plain
-        // launch of the same geometry finds the order where the plain launches left it.
-        P.tile_order = tt->d_order;
-        P.tile_count = tt->count;
-        P.tile_cost = nullptr;
-        P.counters = nullptr;
-        P.round_steps = 0;
-        P.workgroups_per_cu = 0;
-        c->last_kernel = KIFS_KERNEL_SSAA;
-        c->last_round_steps = 0;
-        c->last_group_tiles = -1;
-        c->last_bunny_form = -1;
-        return launch(c, stream, B, big, vs);
-    }
-    // a batch is launched with the sort in its own stream and refreshes every third launch (its
-    // launches are long and its views move: an orbit; measured best for fixed and moving cameras;
-    // KIFS_BATCH_PERIOD overrides)
-    static const uint64_t BATCH_PERIOD = [] {
-        const int v = tuning_knob("KIFS_BATCH_PERIOD");
-        return uint64_t(v < 0 ? rules::FEEDBACK_PERIOD_BATCH : v < 2 ? 2 : v);
-    }();
-    const uint64_t period = count > 1 ? BATCH_PERIOD : FEEDBACK_PERIOD;
-    const uint64_t k = use_feedback ? tt->launches % period : 0;
-    // With several frames in flight (several contexts and streams on one device) the sort runs
-    // in the launch stream itself: streams share a handful of hardware queues, and an event wait
-    // parked in a queue also holds up whatever other context's launches sit behind it (measured:
-    // two contexts fell back to running one after the other).  The 10 us then hide behind the
-    // other frames' kernels.  A lone frame keeps the side stream: there nothing else can.
-    const bool inline_sort = c->frames_in_flight > 1 || count > 1;
-    if (use_feedback && tt->sort_pending && (inline_sort || k != 2)) {
-        // A side-stream sort from earlier launches still owns d_cost[0] and d_order_alt -- lone launches
-        // before a batch, or a period cut short when feedback was switched off in between (options
-        // changed to a pipeline without it and back).  Take its result before anything here records
-        // costs or sorts again: the sort reads cost[] twice and must not see it change.
-        if (!hip_ok(hipStreamWaitEvent(stream, tt->sorted, 0), "wait(sorted)")) return KIFS_ERR_RUNTIME;
-        std::swap(tt->d_order, tt->d_order_alt);
-        tt->sort_pending = false;
-    }
-    if (use_feedback && inline_sort && k == 1) {
-        const uint32_t tiles_x = uint32_t((P.width + kifs::TILE_W - 1) / kifs::TILE_W);
-        if (!hip_ok(kifs::launch_tile_order(tt->d_cost[0], tt->d_order_alt, tt->count, tiles_x, tt->cost_shift, stream),
-                    "tile_order_kernel launch"))
-            return KIFS_ERR_RUNTIME;
-        std::swap(tt->d_order, tt->d_order_alt);  // stream order: the sort precedes this launch
-    }
-    if (use_feedback && k == 2 && tt->sort_pending) {  // adopt the order the side stream prepared
-        if (!hip_ok(hipStreamWaitEvent(stream, tt->sorted, 0), "wait(sorted)")) return KIFS_ERR_RUNTIME;
-        std::swap(tt->d_order, tt->d_order_alt);
-        tt->sort_pending = false;
-    }
-    const bool record_costs = use_feedback && k == 0;
+    const uint32_t tiles_x = uint32_t((P.width + kifs::TILE_W - 1) / kifs::TILE_W);
+    const bool plain = !P.geom && P.ssaa <= 1;
+    Feedback feedback;
+    st = feedback_before(c, tt, stream, count, tiles_x, plain, &feedback);
+    if (st != KIFS_OK) return st;
     P.tile_order = tt->d_order;
     P.tile_count = tt->count;
-    P.tile_cost = record_costs ? tt->d_cost[0] : nullptr;
-    // The diagnostics buffer holds one record per wave of the screen kifs_debug_counters saw (counter_words).  A launch
-    // with more waves -- a larger screen set since, a batch -- runs as if diagnostics were off: nothing is reallocated
-    // here, an earlier enqueued launch may still be writing the buffer.
-    if (P.counters && 8ull + 16ull * uint64_t(tt->count) * uint64_t(count) > uint64_t(c->counter_words)) P.counters = nullptr;
-    if (P.counters) P.round_steps = 0;  // the per-wave diagnostics belong to the one-wave-per-block march
-    // ---- launch shape.  Everything below is decided from `load`: the launch's tiles that can hold rays
-    // with real work (the projected bounding sphere's tiles, all views), tools/cliff_sweep.py's x axis.
-    const uint32_t group_id = c->options.fractal_group_id;
-    const bool lone = count == 1 && c->frames_in_flight <= 1;
-    const bool bunny_scene = group_id == uint32_t(kifs::GROUP_KIFS) && c->options.primitive_id == uint32_t(kifs::PRIM_BUNNY);
-    const double heavy_tiles = disc_tiles(P, h, tt->count);
-    const double load = heavy_tiles * double(count);
-    // the residency cap serves a lone frame's latency; concurrent frames want every slot
-    P.workgroups_per_cu = lone ? residency_for(P, group_id, heavy_tiles) : 0;
-    // a residency-capped launch is a lone frame bound by its longest rays: re-queuing helps
-    // throughput, not that (1080p Julia: 0.143 ms without, 0.146 ms with)
-    if (P.workgroups_per_cu >= 1) P.round_steps = 0;
-    // (an uncapped lone Julia frame -- 4096^2 -- prefers longer rounds: 0.430 ms at 32 steps, 0.445 at 16)
-    if (P.round_steps == rules::ROUND_STEPS_JULIA && count == 1 && group_id == uint32_t(kifs::GROUP_JULIA) && P.max_iterations >= 64 &&
-        tuning_knob("KIFS_ROUND_STEPS") < 0)
-        P.round_steps = rules::ROUND_STEPS_LONE_JULIA;
-    // (nor does the lone bunny frame: 0.461 ms with the quad kernel, 0.670 ms in rounds; nor two of them)
-    if (bunny_scene && (count == 1 || (load < rules::BUNNY_ROUNDS_FROM && tuning_knob("KIFS_ROUND_STEPS") < 0))) P.round_steps = 0;
-    // nor does a launch too small to fill the device twice over (256x256 x 8 views = 2048
-    // workgroups: 0.038 ms without, 0.062 ms with)
-    if (uint64_t(tt->count) * uint64_t(count) < rules::REQUEUE_MIN_WORKGROUPS) P.round_steps = 0;
-    {   // Shape of the re-queuing path (profiles/r02/sweep_shapes.jsonl: 5 frame sizes x 4 camera
-        // distances x 2 scenes x batches of 1 / 8 / 32, every shape forced in turn):
-        //   one WAVE per tile (render_wave_kernel) once the launch has several times more heavy tiles
-        //     than the device has workgroup slots -- then slots, not critical paths, set its duration, and
-        //     single-wave workgroups give four times as many (1080p Julia x32: 1.13 -> 0.88 ms; 4096^2 x8
-        //     +27 %; 8K Sierpinski x4 +16 %) -- from a load of 12 500 tiles for the Julia pipeline, 32 000
-        //     for the others, 30 000 for a lone frame (all its heavy tiles are one view's);
-        //   otherwise 256-thread workgroups (render_group_kernel), whose four waves take a tile's first,
-        //     crowded rounds side by side (a lone wave needs +30 % for the same tile): TWO tiles of the cost
-        //     order per workgroup when the launch is a batch with enough heavy tiles to pair (one tile's
-        //     queue is short for most of its life, neighbours of the cost order fill each other's waves:
-        //     batched 1080p Julia 0.319 -> 0.281 ms; below 3 500 heavy tiles pairing only halves the
-        //     workgroups that can run side by side: 720p x8 at distance 5, 0.222 -> 0.188 ms with one) or a
-        //     big lone KIFS frame (1440p Sierpinski at distance 2: -11 %), else ONE.
-        // Not the bunny (four lanes per ray, 216 VGPRs: pairs just run longer); the generalised Julia pairs
-        // tiles only from 12 000 heavy tiles (1080p x32: 0.140 -> 0.125 ms per frame; x8: nothing, and its
-        // few, very long workgroups lost 7 % when paired on smaller launches) and keeps 256-thread
-        // workgroups throughout (one wave per tile: x32 0.150 ms, x8 0.31 against 0.22).
-        static const int forced = tuning_knob("KIFS_GROUP_TILES");
-        const bool julia = group_id == uint32_t(kifs::GROUP_JULIA);
-        const bool genjulia = group_id == uint32_t(kifs::GROUP_GENJULIA);
-        const bool kifs_scene = group_id == uint32_t(kifs::GROUP_KIFS);
-        const double wave_from = lone ? rules::WAVE_FROM_LONE : (julia ? rules::WAVE_FROM_JULIA : rules::WAVE_FROM_OTHER);
-        int shape = 1;
-        // (one wave per tile needs views to interleave: TWO frames of 4096^2 -- 19 600 heavy tiles, past WAVE_FROM_JULIA -- run
-        // 31.5 Gpixel/s that way against 42.8 with pairs, four 52.0 against 44.0: r04, profiles/r04/sweep_group_shapes.txt)
-        if (load >= wave_from && !genjulia && (count >= 3 || load >= rules::WAVE_FROM_LONE)) shape = 0;
-        else if (!lone && load >= (genjulia ? rules::PAIR_FROM_GENJULIA : kifs_scene ? rules::PAIR_FROM_BATCH_KIFS : rules::PAIR_FROM_BATCH))
-            shape = 2;
-        else if (lone && kifs_scene && load >= rules::PAIR_FROM_LONE_KIFS) shape = 2;
-        if (forced >= 0) shape = forced;
-        P.bunny_coop = 0;
-        if (bunny_scene) {  // its own rules: four lanes per ray (216 VGPRs) or four waves per 64 rays
-            static const int coop = tuning_knob("KIFS_BUNNY_COOP");
-            // (KIFS_BUNNY_COOP under KIFS_TUNING forces a form: 0 / 1 / 2, see FrameParams::bunny_coop)
-            P.bunny_coop = coop >= 0 ? std::min(coop, 2) : (load >= rules::BUNNY_COOP_FROM ? 1 : load >= rules::BUNNY_W2LDS_FROM ? 2 : 0);
-            shape = P.bunny_coop ? 2 : forced >= 1 ? forced : (load >= rules::BUNNY_PAIR_FROM ? 2 : 1);
-            if (P.bunny_coop == 1 && P.round_steps == rules::ROUND_STEPS_OTHER && tuning_knob("KIFS_ROUND_STEPS") < 0)
-                P.round_steps = rules::ROUND_STEPS_BUNNY_COOP;
-        }
-        P.group_tiles = shape;
-        if (shape == 0 && kifs_scene && !bunny_scene && P.round_steps == rules::ROUND_STEPS_OTHER && tuning_knob("KIFS_ROUND_STEPS") < 0)
-            P.round_steps = rules::ROUND_STEPS_KIFS_WAVE;
+    if (plain) {
+        P.tile_cost = feedback.record_costs ? tt->d_cost : nullptr;
+        choose_shape(c, P, count, h);
+    } else {
+        fixed_shape(c, P, count, h);
     }
-    if (record_costs) {
-        // render_kernel / render_group_kernel record run times in units of 1024 cycles; the stream kernel
-        // sums the march steps of a tile's long rays over the batch's views: scale to the sort's 1024 bins
-        tt->cost_shift = 0;
-    }
-    c->last_round_steps = P.round_steps;
-    c->last_group_tiles = P.round_steps > 0 ? P.group_tiles : -1;
-    c->last_bunny_form = bunny_scene && P.round_steps > 0 ? P.bunny_coop : -1;
-    c->last_kernel = P.round_steps > 0 ? (bunny_scene ? (P.bunny_coop == 1 ? KIFS_KERNEL_BUNNY_COOP : KIFS_KERNEL_GROUP)
-                                                      : (P.group_tiles == 0 ? KIFS_KERNEL_WAVE : KIFS_KERNEL_GROUP))
-                                       : (bunny_scene ? KIFS_KERNEL_BUNNY_QUAD : KIFS_KERNEL_BLOCK);
+    report_shape(c, P);
     st = launch(c, stream, B, big, vs);
-    if (st != KIFS_OK) return st;
-    if (!use_feedback) {  // no bookkeeping, no events: nothing depends on this launch
-        tt->launches = 0;  // (a pending side-stream sort stays pending: the next feedback launch waits for it)
-        return KIFS_OK;
-    }
-    tt->launches += 1;
-    if (record_costs) tt->costs_marked = false;
-    if (inline_sort) return KIFS_OK;
-    if (record_costs) {
-        // Launch k = 0 of the period wrote d_cost[0].  The previous sort (period before) read it
-        // and finished before that period's launch 2 started, i.e. long ago on this timeline.
-        if (!hip_ok(hipEventRecord(tt->rendered[0], stream), "record(render)")) return KIFS_ERR_RUNTIME;
-        tt->costs_marked = true;
-    } else if (k == 1) {
-        // The costs may come from a launch that sorts inline and records no event -- a batch, or frames_in_flight > 1,
-        // before this lone launch.  rendered[0] is then unrecorded or a period old, and a wait for it would let the sort
-        // read costs that launch is still writing: mark this point of the stream instead (it follows that launch).
-        if (!tt->costs_marked) {
-            if (!hip_ok(hipEventRecord(tt->rendered[0], stream), "record(render, late)")) return KIFS_ERR_RUNTIME;
-            tt->costs_marked = true;
-        }
-        // sort those costs into d_order_alt: the buffer last read by launches of the period
-        // before the previous adoption, all of which precede launch 0 of this period
-        if (!c->side_stream &&
-            !hip_ok(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking), "side stream"))
-            return KIFS_ERR_RUNTIME;
-        const uint32_t tiles_x = uint32_t((P.width + kifs::TILE_W - 1) / kifs::TILE_W);
-        if (!hip_ok(hipStreamWaitEvent(c->side_stream, tt->rendered[0], 0), "wait(render 0)") ||
-            !hip_ok(kifs::launch_tile_order(tt->d_cost[0], tt->d_order_alt, tt->count, tiles_x, tt->cost_shift,
-                                            c->side_stream), "tile_order_kernel launch") ||
-            !hip_ok(hipEventRecord(tt->sorted, c->side_stream), "record(sorted)"))
-            return KIFS_ERR_RUNTIME;
-        tt->sort_pending = true;
-    }
-    return KIFS_OK;
+    if (st != KIFS_OK || !plain) return st;
+    return feedback_after(c, tt, stream, tiles_x, feedback);
 }
 
-int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int y0, int y1,
-            int encode) {
+int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int y0, int y1, int encode) {
     if (!c->have_camera) return KIFS_ERR_UNCONFIGURED;
     if (!dev_out) return KIFS_ERR_BAD_ARG;
     return enqueue_batch(c, stream, 1, nullptr, &dev_out, pitch, y0, y1, encode);
 }
-
 
 bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what) {
     if (need <= have) return true;

@@ -18,7 +18,9 @@
 // (kifs_support_kernels.hip:115-125,184-187,211).  stub_fail_in(n): the n-th HIP call or launch from now on fails once
 // (hipErrorOutOfMemory / hipErrorLaunchFailure), for the error paths.  A hipFree under another device than the one that
 // was current at the hipMalloc aborts.  KIFS_STUB_TRACE=FILE writes one line per call (see trace() below): two builds of
-// the host code are compared call for call by running the driver on both and diffing the files.
+// the host code are compared call for call by running the driver on both and diffing the files.  A render launch's line
+// also says what the launch was told (its shape, which optional tables it got, which culls are on, which of the two order
+// buffers it read); stub_last_render() hands the same fields of the latest render launch to the driver.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
@@ -43,6 +45,8 @@ hipError_t g_last = hipSuccess;
 long g_fail_in = -1;  // countdown to an injected failure
 std::map<uintptr_t, size_t> g_device_mem, g_host_mem;
 std::map<uintptr_t, int> g_device_of;  // the device that was current at the hipMalloc
+std::map<uintptr_t, int> g_order_ordinal;  // allocations read as a tile order, in order of their first such launch
+int g_order_ordinals = 0;
 std::set<ihipStream_t*> g_streams;
 std::set<ihipEvent_t*> g_events;
 long g_calls = 0, g_launches = 0, g_device_syncs = 0;
@@ -78,6 +82,19 @@ bool inside(const std::map<uintptr_t, size_t>& m, const void* p, size_t bytes = 
     return a >= it->first && a + bytes <= it->first + it->second;
 }
 
+// Which allocation a launch reads its tile order from: an ordinal given at the allocation's first such launch (0: none).
+// Counted apart from the other allocations, so that d_order / d_order_alt keep their names when something else is
+// allocated or no longer is.
+int order_allocation_of(const void* p) {
+    auto it = g_device_mem.upper_bound(reinterpret_cast<uintptr_t>(p));
+    if (!p || it == g_device_mem.begin()) return 0;
+    --it;
+    if (reinterpret_cast<uintptr_t>(p) >= it->first + it->second) return 0;
+    int& ordinal = g_order_ordinal[it->first];
+    if (!ordinal) ordinal = ++g_order_ordinals;
+    return ordinal;
+}
+
 void need_device(const void* p, size_t bytes, const char* what) {
     if (bytes && !inside(g_device_mem, p, bytes)) {
         std::fprintf(stderr, "hip_stub: %s touches %zu bytes at %p outside every device allocation\n", what, bytes, p);
@@ -87,9 +104,22 @@ void need_device(const void* p, size_t bytes, const char* what) {
 
 }  // namespace
 
+// What the latest render launch was told (host_driver.cpp declares the same struct).
+struct StubRenderLaunch {
+    int count;
+    unsigned tile_count;
+    int round_steps, group_tiles, bunny_coop, workgroups_per_cu;
+    int tile_cost, counters, geom, stripe_rows, table;  // set or not
+    int ssaa, encode, y0, y1;
+    int cull, quick_cull, tile_cull;  // on or off
+    int order;                        // the allocation the tile order was read from (order_allocation_of)
+};
+static StubRenderLaunch g_last_render{};
+
 extern "C" {
 
 // ---- test hooks
+void stub_last_render(StubRenderLaunch* out) { *out = g_last_render; }
 void stub_fail_in(long n) { g_fail_in = n; }
 void stub_trace_mark(const char* what) { if (g_trace) std::fprintf(g_trace, "# %s\n", what); }
 long stub_calls() { return g_calls; }
@@ -136,6 +166,7 @@ hipError_t hipFree(void* p) {
         std::abort();
     }
     g_device_of.erase(it->first);
+    g_order_ordinal.erase(it->first);
     g_device_mem.erase(it);
     std::free(p);
     return hipSuccess;
@@ -265,9 +296,18 @@ uint32_t stub_pixel(const BatchView& v, int x, int y, uint32_t background) {
 
 hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t st) {
     ++g_launches;
-    trace("launch_render", st);
-    if (injected()) return fail(hipErrorLaunchFailure);
     const FrameParams& P = B.frame;
+    const StubRenderLaunch L = {B.count, P.tile_count, P.round_steps, P.group_tiles, P.bunny_coop, P.workgroups_per_cu,
+                                P.tile_cost != nullptr, P.counters != nullptr, P.geom != nullptr, P.stripe_rows != nullptr, B.table != nullptr,
+                                P.ssaa, P.encode, P.y0, P.y1, P.cull_n2 != 0.0f, P.quick_cull_n2 != 0.0f, P.tile_cull_beta != 0.0f,
+                                order_allocation_of(P.tile_order)};
+    g_last_render = L;
+    if (g_trace)
+        std::fprintf(g_trace, "launch_render dev=%d stream=%d count=%d tiles=%u rounds=%d group_tiles=%d bunny=%d per_cu=%d cost=%d counters=%d "
+                              "geom=%d stripes=%d table=%d ssaa=%d encode=%d y=%d..%d culls=%d%d%d order=%d\n", g_current, st ? st->ordinal : 0,
+                     L.count, L.tile_count, L.round_steps, L.group_tiles, L.bunny_coop, L.workgroups_per_cu, L.tile_cost, L.counters, L.geom,
+                     L.stripe_rows, L.table, L.ssaa, L.encode, L.y0, L.y1, L.cull, L.quick_cull, L.tile_cull, L.order);
+    if (injected()) return fail(hipErrorLaunchFailure);
     const int tiles_x = (P.width + TW - 1) / TW;
     // the tile table must name every tile of the launch exactly once
     std::vector<char> seen;
@@ -328,7 +368,7 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
 
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count, uint32_t tiles_x, uint32_t shift, hipStream_t st) {
     ++g_launches;
-    trace("launch_tile_order", st);
+    if (g_trace) std::fprintf(g_trace, "launch_tile_order dev=%d stream=%d tiles=%u tiles_x=%u shift=%u\n", g_current, st ? st->ordinal : 0, tile_count, tiles_x, shift);
     need_device(cost, size_t(tile_count) * 4, "tile_order: costs");
     need_device(order, size_t(tile_count) * 4, "tile_order: order");
     std::vector<std::pair<uint32_t, uint32_t>> keyed(tile_count);

@@ -4,9 +4,10 @@
 // test_gpu_api.py run on the GPU -- here what is checked is the HOST side: every frame gathered from four "devices"
 // must equal the frame one context renders (the stub's pixels depend on camera and frame coordinates only), one
 // long-lived context must keep rendering exact frames across evictions, feedback transitions, resizes and diagnostics
-// (context_lifecycle), nothing may
-// touch memory it does not own, every failure that is injected must leave the object usable, and after the last
+// (context_lifecycle), every launch-shape rule must pick what it picked when the table was written (launch_shapes),
+// nothing may touch memory it does not own, every failure that is injected must leave the object usable, and after the last
 // destroy the stub must hold no allocation, stream or event.  Prints "host_driver: N checks ok".
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +19,18 @@
 
 #include "../../include/kifs_hip.h"
 
+struct StubRenderLaunch {  // hip_stub.cpp: what the latest render launch was told
+    int count;
+    unsigned tile_count;
+    int round_steps, group_tiles, bunny_coop, workgroups_per_cu;
+    int tile_cost, counters, geom, stripe_rows, table;
+    int ssaa, encode, y0, y1;
+    int cull, quick_cull, tile_cull;
+    int order;
+};
+
 extern "C" {
+void stub_last_render(StubRenderLaunch* out);
 void stub_fail_in(long n);
 void stub_trace_mark(const char* what);
 long stub_launches();
@@ -191,6 +203,12 @@ void single_context(int w, int h) {
     for (int i = 0; i < 70; ++i) outs[size_t(i)] = frames + fb * i;
     CHECK(kifs_render_batch_async(c, nullptr, 5, cams.data(), outs.data(), size_t(w) * 4, 0, h, 1) == KIFS_OK);
     CHECK(std::memcmp(frames, want.data(), fb * 5) == 0);
+    {   // a big batch that is rejected takes no slot of the view ring (none exists yet: taking one would allocate it)
+        const long calls = stub_calls();
+        CHECK(kifs_render_batch_async(c, nullptr, 70, cams.data(), outs.data(), size_t(w) * 4, 0, h + 1, 1) == KIFS_ERR_BAD_ARG);
+        CHECK(kifs_render_batch_async(c, nullptr, 70, cams.data(), outs.data(), size_t(w) * 4 - 4, 0, h, 1) == KIFS_ERR_BAD_SIZE);
+        CHECK(stub_calls() == calls);
+    }
     for (int round = 0; round < 6; ++round) {
         std::memset(frames, 0xEE, fb * 70);
         CHECK(kifs_render_batch_async(c, nullptr, 70, cams.data(), outs.data(), size_t(w) * 4, 0, h, 1) == KIFS_OK);
@@ -783,6 +801,187 @@ void context_lifecycle() {
     kifs_destroy(c);
 }
 
+// ---- the launch-shape rules (namespace rules of kifs_schedule.cpp), from both sides of every threshold --------------
+// One context, no tuning knobs.  A case is a scene, a frame of tx x ty whole tiles, a camera distance, a number of views
+// and of frames in flight; after its launch the kernel, the round length, the tiles per workgroup, the bunny's form, the
+// residency cap, whether costs were recorded and which culls were on must equal the literals beside it.  THE LITERALS
+// WERE TAKEN FROM A RUN OF THIS SCENARIO AGAINST THE kifs_schedule.cpp OF COMMIT aa8491c, before that file's
+// enqueue_batch was split up; whoever changes a rule changes its line here on purpose, never by copying what the changed
+// code reports.  A camera at distance 0.5 is inside every scene's bounding sphere: the rules' `load` is then the exact
+// integer tiles x views, and a case can sit ON a threshold.  Where REQUEUE_MIN_WORKGROUPS (4096 workgroups) keeps such a
+// launch from having rounds at all, the camera stands outside and the pair of cases brackets the threshold within 5 %
+// (load = views x pi (H/2)^2 R^2 / (d^2 - R^2) / 256 for a frame of H rows, R = B + epsilon: disc_tiles(); at 1080 rows
+// 14315.4 / (d^2 - 4.0004) a view for the Julia set, 3579.2 / (d^2 - 1.0002) for the bunny).
+enum : int { HEATMAP = 1, EPS_ZERO = 2, DIAGNOSTICS = 4, GEOMETRY = 8, SSAA2 = 16, FAR_ORIGIN = 32, NAN_ORIGIN = 64, SKEWED = 128 };
+enum : int { JULIA = 1, GENJULIA = 2, KIFS = 0, SPHERE = 0, SIERPINSKI = 4, BUNNY = 5 };
+struct ShapeCase {
+    const char* what;
+    int group, prim, tx, ty;
+    float distance;
+    int views, in_flight, max_iterations, flags;
+    // expected: KifsKernel; FrameParams round_steps, group_tiles, bunny_coop, workgroups_per_cu; costs recorded; culls as
+    // three digits (bounding sphere, wave-level, tile-level)
+    int kernel, rounds, group_tiles, bunny, per_cu, costs, culls;
+};
+const float IN = 0.5f;
+const ShapeCase SHAPE_CASES[] = {
+    // REQUEUE_MIN_WORKGROUPS = 4096
+    {"requeue: lone, on the edge", JULIA, 0, 64, 64, IN, 1, 1, 256, 0, /**/ 1, 32, 1, 0, 0, 1, 111},
+    {"requeue: lone, one tile short", JULIA, 0, 63, 65, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 0, 1, 111},
+    {"requeue: 8 x 512", JULIA, 0, 16, 32, IN, 8, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 0, 111},
+    {"requeue: 8 x 511", JULIA, 0, 7, 73, IN, 8, 1, 256, 0, /**/ 0, 0, 2, 0, 0, 0, 111},
+    // max_iterations < 2 x rounds; the generalised Julia under 32 steps
+    {"steps: Julia 32", JULIA, 0, 16, 32, IN, 8, 1, 32, 0, /**/ 1, 16, 2, 0, 0, 0, 111},
+    {"steps: Julia 31", JULIA, 0, 16, 32, IN, 8, 1, 31, 0, /**/ 0, 0, 2, 0, 0, 0, 111},
+    {"steps: sphere 16", KIFS, SPHERE, 16, 32, IN, 8, 1, 16, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"steps: sphere 15", KIFS, SPHERE, 16, 32, IN, 8, 1, 15, 0, /**/ 0, 0, 1, 0, 0, 0, 111},
+    {"steps: gen-Julia 32", GENJULIA, 0, 16, 32, IN, 8, 1, 32, 0, /**/ 1, 16, 1, 0, 0, 0, 111},
+    {"steps: gen-Julia 31", GENJULIA, 0, 16, 32, IN, 8, 1, 31, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"steps: gen-Julia 16", GENJULIA, 0, 16, 32, IN, 8, 1, 16, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"steps: gen-Julia 15", GENJULIA, 0, 16, 32, IN, 8, 1, 15, 0, /**/ 0, 0, 1, 0, 0, 0, 111},
+    // heatmap, epsilon <= 0, diagnostics (a batch's records do not fit the buffer: it is dropped BEFORE it stops the rounds)
+    {"heatmap", JULIA, 0, 16, 32, IN, 8, 1, 256, HEATMAP, /**/ 0, 0, 2, 0, 0, 0, 100},
+    {"epsilon 0", JULIA, 0, 16, 32, IN, 8, 1, 256, EPS_ZERO, /**/ 0, 0, 2, 0, 0, 0, 111},
+    {"diagnostics: lone", JULIA, 0, 64, 64, IN, 1, 1, 256, DIAGNOSTICS, /**/ 0, 0, 1, 0, 0, 0, 111},
+    {"diagnostics: batch", JULIA, 0, 64, 64, IN, 2, 1, 256, DIAGNOSTICS, /**/ 1, 16, 2, 0, 0, 0, 111},
+    // ROUND_STEPS_LONE_JULIA: 64+ steps, uncapped, one view
+    {"lone Julia: 64 steps", JULIA, 0, 64, 64, IN, 1, 1, 64, 0, /**/ 1, 32, 1, 0, 0, 0, 111},
+    {"lone Julia: 63 steps", JULIA, 0, 64, 64, IN, 1, 1, 63, 0, /**/ 1, 16, 1, 0, 0, 1, 111},
+    {"lone Julia: two views", JULIA, 0, 64, 64, IN, 2, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 0, 111},
+    {"lone Julia: two frames in flight", JULIA, 0, 64, 64, IN, 1, 2, 256, 0, /**/ 1, 32, 2, 0, 0, 0, 111},
+    {"lone gen-Julia", GENJULIA, 0, 64, 64, IN, 1, 1, 256, 0, /**/ 1, 16, 1, 0, 0, 0, 111},
+    // RESIDENCY_ONE_PER_CU = 1024, RESIDENCY_TWO_PER_CU = 2048: lone Julia frames only
+    {"residency: 1024", JULIA, 0, 32, 32, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 1, 0, 111},
+    {"residency: 1025", JULIA, 0, 25, 41, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 2, 0, 111},
+    {"residency: 2048", JULIA, 0, 32, 64, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 2, 1, 111},
+    {"residency: 2049", JULIA, 0, 3, 683, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 0, 1, 111},
+    {"residency: 1024, two frames in flight", JULIA, 0, 32, 32, IN, 1, 2, 256, 0, /**/ 0, 0, 1, 0, 0, 0, 111},
+    {"residency: 1024, gen-Julia", GENJULIA, 0, 32, 32, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 0, 0, 111},
+    {"residency: 1024, sphere", KIFS, SPHERE, 32, 32, IN, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 0, 0, 111},
+    // (a capped launch has no rounds.  1080p = 60 x 135 tiles; heavy tiles: 2020 and 2078)
+    {"residency: 1080p, 1.4 % under 2048", JULIA, 0, 60, 135, 3.33f, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 2, 1, 111},
+    {"residency: 1080p, 1.5 % over 2048", JULIA, 0, 60, 135, 3.30f, 1, 1, 256, 0, /**/ 1, 32, 1, 0, 0, 0, 111},
+    {"residency: 1080p at distance 5", JULIA, 0, 60, 135, 5.0f, 1, 1, 256, 0, /**/ 0, 0, 1, 0, 1, 0, 111},
+    {"residency: 1080p at distance 5, two in flight", JULIA, 0, 60, 135, 5.0f, 1, 2, 256, 0, /**/ 1, 32, 1, 0, 0, 0, 111},
+    // WAVE_FROM_JULIA = 12500, with its `count >= 3 || load >= WAVE_FROM_LONE` clause
+    {"wave: Julia 4 x 3125", JULIA, 0, 25, 125, IN, 4, 1, 256, 0, /**/ 2, 16, 0, 0, 0, 1, 111},
+    {"wave: Julia 4 x 3124", JULIA, 0, 44, 71, IN, 4, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 1, 111},
+    {"wave: Julia 3 x 4167", JULIA, 0, 9, 463, IN, 3, 1, 256, 0, /**/ 2, 16, 0, 0, 0, 1, 111},
+    {"wave: Julia 2 x 6250", JULIA, 0, 50, 125, IN, 2, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 1, 111},
+    {"wave: Julia 2 x 15000", JULIA, 0, 100, 150, IN, 2, 1, 256, 0, /**/ 2, 16, 0, 0, 0, 1, 111},
+    {"wave: Julia 2 x 14999", JULIA, 0, 53, 283, IN, 2, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 1, 111},
+    // WAVE_FROM_OTHER = 32000 (KIFS on one wave per tile: rounds of 4); the generalised Julia never
+    {"wave: sphere 4 x 8000", KIFS, SPHERE, 80, 100, IN, 4, 1, 256, 0, /**/ 2, 4, 0, 0, 0, 0, 111},
+    {"wave: sphere 4 x 7999", KIFS, SPHERE, 19, 421, IN, 4, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"wave: gen-Julia 4 x 8000", GENJULIA, 0, 80, 100, IN, 4, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 1, 111},
+    // WAVE_FROM_LONE = 30000
+    {"wave: lone Julia 30000", JULIA, 0, 150, 200, IN, 1, 1, 256, 0, /**/ 2, 32, 0, 0, 0, 1, 111},
+    {"wave: lone Julia 29999", JULIA, 0, 131, 229, IN, 1, 1, 256, 0, /**/ 1, 32, 1, 0, 0, 1, 111},
+    {"wave: lone Sierpinski 30000", KIFS, SIERPINSKI, 150, 200, IN, 1, 1, 256, 0, /**/ 2, 4, 0, 0, 0, 0, 111},
+    {"wave: lone Sierpinski 29999", KIFS, SIERPINSKI, 131, 229, IN, 1, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"wave: Julia 30000, two in flight", JULIA, 0, 150, 200, IN, 1, 2, 256, 0, /**/ 2, 32, 0, 0, 0, 0, 111},
+    {"wave: Julia 29999, two in flight", JULIA, 0, 131, 229, IN, 1, 2, 256, 0, /**/ 1, 32, 2, 0, 0, 0, 111},
+    // PAIR_FROM_BATCH = 3500 (1080p x 8, load 3579 and 3423), PAIR_FROM_GENJULIA = 5000,
+    // PAIR_FROM_BATCH_KIFS = 7000, PAIR_FROM_LONE_KIFS = 12000
+    {"pair: Julia, 2.3 % over 3500", JULIA, 0, 60, 135, 6.00f, 8, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 1, 111},
+    {"pair: Julia, 2.2 % under 3500", JULIA, 0, 60, 135, 6.12f, 8, 1, 256, 0, /**/ 1, 16, 1, 0, 0, 0, 111},
+    {"pair: gen-Julia 8 x 625", GENJULIA, 0, 25, 25, IN, 8, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 0, 111},
+    {"pair: gen-Julia 8 x 624", GENJULIA, 0, 24, 26, IN, 8, 1, 256, 0, /**/ 1, 16, 1, 0, 0, 0, 111},
+    {"pair: sphere 8 x 875", KIFS, SPHERE, 25, 35, IN, 8, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"pair: sphere 8 x 874", KIFS, SPHERE, 23, 38, IN, 8, 1, 256, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"pair: lone Sierpinski 12000", KIFS, SIERPINSKI, 100, 120, IN, 1, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"pair: lone Sierpinski 11999", KIFS, SIERPINSKI, 13, 923, IN, 1, 1, 256, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"pair: Sierpinski 12000, two in flight", KIFS, SIERPINSKI, 100, 120, IN, 1, 2, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    // the bunny at 1080p: a lone frame takes the quad kernel; BUNNY_ROUNDS_FROM = 450 (load 465 and 437), BUNNY_PAIR_FROM = 1600
+    // (1637 and 1567), BUNNY_W2LDS_FROM = 2600 (2660 and 2545), BUNNY_COOP_FROM = 5000
+    {"bunny: lone", KIFS, BUNNY, 64, 64, IN, 1, 1, 256, 0, /**/ 3, 0, 2, 2, 0, 0, 111},
+    {"bunny: lone, two in flight", KIFS, BUNNY, 64, 64, IN, 1, 2, 256, 0, /**/ 3, 0, 2, 2, 0, 0, 111},
+    {"bunny: 3.3 % over 450", KIFS, BUNNY, 60, 135, 4.05f, 2, 1, 256, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"bunny: 2.9 % under 450", KIFS, BUNNY, 60, 135, 4.17f, 2, 1, 256, 0, /**/ 3, 0, 1, 0, 0, 0, 111},
+    {"bunny: 2.3 % over 1600", KIFS, BUNNY, 60, 135, 4.30f, 8, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"bunny: 2.1 % under 1600", KIFS, BUNNY, 60, 135, 4.39f, 8, 1, 256, 0, /**/ 1, 8, 1, 0, 0, 0, 111},
+    {"bunny: 2.3 % over 2600", KIFS, BUNNY, 60, 135, 3.43f, 8, 1, 256, 0, /**/ 1, 8, 2, 2, 0, 0, 111},
+    {"bunny: 2.1 % under 2600", KIFS, BUNNY, 60, 135, 3.50f, 8, 1, 256, 0, /**/ 1, 8, 2, 0, 0, 0, 111},
+    {"bunny: 8 x 625", KIFS, BUNNY, 25, 25, IN, 8, 1, 256, 0, /**/ 4, 4, 2, 1, 0, 0, 111},
+    {"bunny: 8 x 624", KIFS, BUNNY, 24, 26, IN, 8, 1, 256, 0, /**/ 1, 8, 2, 2, 0, 0, 111},
+    // the geometry and the supersampled launch: one tuple each, the geometry launch with the lone frame's residency
+    {"geometry: lone 1024", JULIA, 0, 32, 32, IN, 1, 1, 256, GEOMETRY, /**/ 6, 0, 1, 0, 1, 0, 111},
+    {"geometry: 1025", JULIA, 0, 25, 41, IN, 1, 1, 256, GEOMETRY, /**/ 6, 0, 1, 0, 2, 0, 111},
+    {"geometry: 1024, two in flight", JULIA, 0, 32, 32, IN, 1, 2, 256, GEOMETRY, /**/ 6, 0, 1, 0, 0, 0, 111},
+    {"geometry: lone 4096", JULIA, 0, 64, 64, IN, 1, 1, 256, GEOMETRY, /**/ 6, 0, 1, 0, 0, 0, 111},
+    {"supersampled: lone 1024", JULIA, 0, 32, 32, IN, 1, 1, 256, SSAA2, /**/ 5, 0, 1, 0, 0, 0, 111},
+    {"supersampled: lone 4096", JULIA, 0, 64, 64, IN, 1, 1, 256, SSAA2, /**/ 5, 0, 1, 0, 0, 0, 111},
+    {"supersampled: 8 x 512", JULIA, 0, 16, 32, IN, 8, 1, 256, SSAA2, /**/ 5, 0, 1, 0, 0, 0, 111},
+    // the culls: off for a far or NaN origin (every tile then counts as heavy), the tile-level one for a skewed matrix
+    {"culls: far origin", JULIA, 0, 32, 32, IN, 1, 1, 256, FAR_ORIGIN, /**/ 0, 0, 1, 0, 0, 0, 0},
+    {"culls: NaN origin", JULIA, 0, 32, 32, IN, 1, 1, 256, NAN_ORIGIN, /**/ 0, 0, 1, 0, 0, 0, 0},
+    {"culls: skewed matrix", JULIA, 0, 32, 32, IN, 1, 1, 256, SKEWED, /**/ 0, 0, 1, 0, 1, 0, 110},
+    {"culls: far origin in a batch", JULIA, 0, 60, 135, 6.12f, 8, 1, 256, FAR_ORIGIN, /**/ 2, 16, 0, 0, 0, 1, 0},
+    {"culls: 32 rows", JULIA, 0, 128, 4, IN, 8, 1, 256, 0, /**/ 1, 16, 2, 0, 0, 0, 110},
+};
+
+void launch_shapes() {
+    stub_trace_mark("launch_shapes");
+    int st = 0;
+    kifs_ctx* c = kifs_create(0, &st);
+    CHECK(c && st == KIFS_OK);
+    const size_t pixels = size_t(32 * 150) * (8 * 200);  // the largest frame of the table
+    uint8_t* frame = dev_alloc(pixels * 4);  // every view of a batch writes this one frame
+    float* geom = reinterpret_cast<float*>(dev_alloc(size_t(32 * 64) * (8 * 64) * 16));
+    for (const ShapeCase& k : SHAPE_CASES) {
+        const int w = 32 * k.tx, h = 8 * k.ty;
+        CHECK(size_t(w) * h <= pixels && size_t(w) * h * k.views <= 40u * 1000 * 1000);
+        KifsScreenUniform screen;
+        KifsOptionsUniform options;
+        KifsGuiData gui;
+        kifs_host_gui_default(&gui);
+        gui.fractal_group = uint32_t(k.group);
+        gui.primitive_shape = uint32_t(k.prim);
+        gui.max_iterations = uint32_t(k.max_iterations);
+        gui.is_heatmap = (k.flags & HEATMAP) ? 1 : 0;
+        if (k.flags & EPS_ZERO) gui.epsilon = 0.0f;
+        CHECK(kifs_host_screen(uint32_t(w), uint32_t(h), &screen) == KIFS_OK && kifs_host_options(&gui, &options) == KIFS_OK);
+        KifsCameraData cd;
+        kifs_host_camera_default(&cd);
+        cd.origin_distance = k.distance;
+        KifsCameraUniform cam;
+        CHECK(kifs_host_camera(&cd, &cam) == KIFS_OK);
+        if (k.flags & FAR_ORIGIN) cam.origin[1] = 2.0e15f;
+        if (k.flags & NAN_ORIGIN) cam.origin[2] = std::nanf("");
+        if (k.flags & SKEWED) cam.matrix[1][0] += 0.01f;
+        CHECK(kifs_set_screen(c, &screen) == KIFS_OK && kifs_set_options(c, &options) == KIFS_OK && kifs_set_camera(c, &cam) == KIFS_OK);
+        CHECK(kifs_set_frames_in_flight(c, k.in_flight) == KIFS_OK);
+        CHECK(kifs_set_supersampling(c, (k.flags & SSAA2) ? 2 : 1) == KIFS_OK);
+        unsigned long long head[8];
+        if (k.flags & DIAGNOSTICS) CHECK(kifs_debug_counters(c, 1, head) == KIFS_OK);
+        const std::vector<KifsCameraUniform> cams(size_t(k.views), cam);
+        const std::vector<uint8_t*> outs(size_t(k.views), frame);
+        if (k.flags & GEOMETRY)
+            CHECK(kifs_render_geometry_async(c, nullptr, 1, nullptr, outs.data(), size_t(w) * 4, geom, size_t(w) * 16, 0, 0, h, 1) == KIFS_OK);
+        else if (k.views == 1)
+            CHECK(kifs_render_async(c, nullptr, frame, size_t(w) * 4, 0, h, 1) == KIFS_OK);
+        else
+            CHECK(kifs_render_batch_async(c, nullptr, k.views, cams.data(), outs.data(), size_t(w) * 4, 0, h, 1) == KIFS_OK);
+        if (k.flags & DIAGNOSTICS) CHECK(kifs_debug_counters(c, 0, head) == KIFS_OK);
+        StubRenderLaunch got;
+        stub_last_render(&got);
+        const int culls = 100 * got.cull + 10 * got.quick_cull + got.tile_cull;
+        const bool same = kifs_debug_last_kernel(c) == k.kernel && got.round_steps == k.rounds && got.group_tiles == k.group_tiles &&
+                          got.bunny_coop == k.bunny && got.workgroups_per_cu == k.per_cu && got.tile_cost == k.costs && culls == k.culls;
+        if (!same)
+            std::fprintf(stderr, "launch_shapes: %s: kernel %d, rounds %d, group_tiles %d, bunny %d, per CU %d, costs %d, culls %03d\n", k.what,
+                         kifs_debug_last_kernel(c), got.round_steps, got.group_tiles, got.bunny_coop, got.workgroups_per_cu, got.tile_cost, culls);
+        CHECK(same);
+        // the report the library gives of the same launch
+        const bool rounds = got.round_steps > 0;
+        CHECK(got.count == k.views && got.tile_count == unsigned(k.tx * k.ty) && kifs_debug_last_round_steps(c) == got.round_steps);
+        CHECK(kifs_debug_last_group_tiles(c) == (rounds ? got.group_tiles : -1));
+        CHECK(kifs_debug_last_bunny_form(c) == (rounds && k.group == KIFS && k.prim == BUNNY ? got.bunny_coop : -1));
+    }
+    CHECK(hipFree(frame) == hipSuccess && hipFree(geom) == hipSuccess);
+    kifs_destroy(c);
+}
+
 }  // namespace
 
 int main() {
@@ -797,6 +996,7 @@ int main() {
     multi_pipeline(70, 37);
     injected_failures(100, 50);
     context_lifecycle();
+    launch_shapes();
     CHECK(stub_live_device_allocations() == 0);
     CHECK(stub_live_streams_and_events() == 0);
     std::printf("host_driver: %ld checks ok\n", g_checks);
