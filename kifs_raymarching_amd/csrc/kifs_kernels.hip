@@ -78,6 +78,198 @@ __global__ __launch_bounds__(BLOCK) void render_kernel(const BatchParams B) {
     store_tile(P, F.tile_x, F.tile_y, F.frame_y, s_tile, tid);
 }
 
+// ---- shading a hit list with the soft-shadow extension (include/kifs_hip.h): the secondary rays from a pool ----
+// A hit's secondary march is 1 to shadow_steps estimates long, so 64 of them side by side finish one by one and the
+// wave waits for the longest.  Instead the lanes take the secondary rays from a pool: pass 1 computes every hit's
+// normal and direct term, colours the hits that need no secondary ray and files the others (start point over the
+// pixel's cached direction, which nothing reads any more; pixel id and direct term over the hit list's slots already
+// consumed); pass 2 marches them with per-lane step counters, a lane that finishes its ray taking the next one of the
+// pool; pass 3 encodes.  Every ray's own sequence of operations is soft_shadow()'s (shadow_step): same pixels.
+// The queue kernels differ in where these things are, not in what is done with them.  A pool names its kernel's hit
+// list (pixel id and t per entry), per-pixel direction cache and staging tiles:
+template <uint32_t CAP>
+struct WavePool {  // render_wave_kernel: byte pixel ids (ly << 5 | lx), entry i at [CAP - 1 - i], one tile
+    uint8_t* hit_pix;
+    float* hit_val;
+    float (*dir)[CAP];
+    uint32_t (*tile)[TILE_W];
+    __device__ __forceinline__ static uint32_t slot(uint32_t i) { return CAP - 1u - i; }
+    __device__ __forceinline__ void set_pix(uint32_t k, uint32_t pix) const { hit_pix[slot(k)] = uint8_t(pix); }
+    __device__ __forceinline__ uint32_t& texel(uint32_t pix) const { return tile[pix >> 5][pix & 31u]; }
+};
+template <uint32_t CAP>
+struct GroupPool {  // render_group_kernel: pixel ids with the tile of the group (tile << 8 | ly << 5 | lx), entry i at [i]
+    uint32_t* hit_pix;
+    float* hit_val;
+    float (*dir)[CAP];
+    uint32_t (*tile)[TILE_H][TILE_W];
+    __device__ __forceinline__ static uint32_t slot(uint32_t i) { return i; }
+    __device__ __forceinline__ void set_pix(uint32_t k, uint32_t pix) const { hit_pix[slot(k)] = pix; }
+    __device__ __forceinline__ uint32_t& texel(uint32_t pix) const { return tile[pix >> 8][(pix >> 5) & 7u][pix & 31u]; }
+};
+
+// Pass 1, a lane's hit (pixel, t): its direct term, and where its secondary ray would start.
+template <int GROUP, int PRIM, class Pool>
+__device__ __forceinline__ float pooled_hit(const FrameParams& P, const Pool& pool, uint32_t pix, float t, V3& start) {
+    const V3 dir = V3{pool.dir[0][pix], pool.dir[1][pix], pool.dir[2][pix]};
+    const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
+    const V3 nrm = scene_normal<GROUP, PRIM>(P, p);
+    start = shadow_start(P, p, nrm);
+    return direct_term(nrm);
+}
+// ... filed as secondary ray k of the pool,
+template <class Pool>
+__device__ __forceinline__ void pooled_file(const Pool& pool, uint32_t k, uint32_t pix, float lit, V3 start) {
+    pool.set_pix(k, pix);
+    pool.hit_val[Pool::slot(k)] = lit;
+    pool.dir[0][pix] = start.x;
+    pool.dir[1][pix] = start.y;
+    pool.dir[2][pix] = start.z;
+}
+// ... or, passes 1 and 3, the pixel's colour from its final direct term.
+template <class Pool>
+__device__ __forceinline__ void pooled_colour(const FrameParams& P, const Pool& pool, uint32_t pix, float lit, bool srgb,
+                                              const float* s_srgb) {
+    pool.texel(pix) = encode_rgba(lit_colour(P, lit), srgb, s_srgb);
+}
+// Pass 2, a lane: the secondary ray it marches, if any.
+struct PooledLane {
+    bool busy = false;
+    uint32_t k = 0;  // the ray's slot
+    float lit = 0.0f;
+    ShadowRay ray{V3{0.0f, 0.0f, 0.0f}, 0.0f, 1.0f, 0};
+};
+template <class Pool>
+__device__ __forceinline__ void pooled_take(const FrameParams& P, const Pool& pool, PooledLane& l, uint32_t k) {
+    l.k = k;
+    const uint32_t pix = pool.hit_pix[Pool::slot(k)];
+    l.lit = pool.hit_val[Pool::slot(k)];
+    l.ray = shadow_ray_from(P, V3{pool.dir[0][pix], pool.dir[1][pix], pool.dir[2][pix]});
+    l.busy = true;
+}
+// One estimate for every busy lane (`lanes`: their mask); a ray that ends leaves the attenuated direct term in its slot.
+template <int GROUP, int PRIM, class Pool>
+__device__ __forceinline__ void pooled_step(const FrameParams& P, const Pool& pool, PooledLane& l, unsigned long long lanes) {
+    const float h = scene_sdf<GROUP, PRIM>(P, shadow_point(l.ray), lanes);
+    if (l.busy) {
+        if (shadow_step(P, h, l.ray)) {
+            pool.hit_val[Pool::slot(l.k)] = l.lit * l.ray.res;
+            l.busy = false;
+        }
+        ++l.ray.j;
+    }
+}
+
+// One wave and its tile (render_wave_kernel): counters in registers, nothing to wait for.
+template <int GROUP, int PRIM, uint32_t CAP>
+__device__ __forceinline__ void shade_hits_with_pooled_shadows(const FrameParams& P, uint32_t hits, uint32_t lane,
+                                                               const WavePool<CAP>& pool, bool srgb, const float* s_srgb) {
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t n_sh = 0;  // uniform
+    for (uint32_t i0 = 0; i0 < hits; i0 += 64u) {
+        const bool have = i0 + lane < hits;
+        uint32_t pix = 0;
+        float lit = 0.0f;
+        V3 start{0.0f, 0.0f, 0.0f};
+        if (have) {
+            pix = pool.hit_pix[pool.slot(i0 + lane)];
+            lit = pooled_hit<GROUP, PRIM>(P, pool, pix, pool.hit_val[pool.slot(i0 + lane)], start);
+        }
+        const bool secondary = have && (lit > 0.0f);
+        const unsigned long long ms = __builtin_amdgcn_ballot_w64(secondary);
+        // (slot k <= this hit's own: read above, by every lane, before anything is written)
+        if (secondary) pooled_file(pool, n_sh + uint32_t(__builtin_popcountll(ms & below)), pix, lit, start);
+        else if (have) pooled_colour(P, pool, pix, lit, srgb, s_srgb);  // no direct light: the colour is final
+        n_sh += uint32_t(__builtin_popcountll(ms));
+    }
+    // pass 2: the pool of secondary rays
+    {
+        uint32_t next = 0;  // uniform: rays handed out so far
+        PooledLane l;
+        for (;;) {
+            const unsigned long long idle = __builtin_amdgcn_ballot_w64(!l.busy);
+            const uint32_t mine = next + uint32_t(__builtin_popcountll(idle & below));
+            if (!l.busy && mine < n_sh) pooled_take(P, pool, l, mine);
+            next = min(n_sh, next + uint32_t(__builtin_popcountll(idle)));
+            const unsigned long long lanes = __builtin_amdgcn_ballot_w64(l.busy);
+            if (lanes == 0ull) break;
+            pooled_step<GROUP, PRIM>(P, pool, l, lanes);
+        }
+    }
+    // pass 3: their colours
+    for (uint32_t k0 = 0; k0 < n_sh; k0 += 64u) {
+        if (k0 + lane < n_sh)
+            pooled_colour(P, pool, pool.hit_pix[pool.slot(k0 + lane)], pool.hit_val[pool.slot(k0 + lane)], srgb, s_srgb);
+    }
+}
+
+// Four waves and the group's tiles (render_group_kernel): the pool is the workgroup's -- a barrier between reading a
+// chunk of 256 hits and filing its secondary rays over the hit list's consumed slots, an LDS cursor the four waves draw
+// from.  Same operations per ray: same pixels.
+template <int GROUP, int PRIM, uint32_t CAP>
+__device__ __forceinline__ void shade_group_hits_with_pooled_shadows(const FrameParams& P, uint32_t hits, int tid,
+                                                                     const GroupPool<CAP>& pool, bool srgb,
+                                                                     const float* s_srgb) {
+    __shared__ uint32_t sh_count, sh_next;
+    const int lane = tid & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (tid == 0) {
+        sh_count = 0;
+        sh_next = 0;
+    }
+    // pass 1: normals and direct terms; the hits that need no secondary ray get their colour
+    for (uint32_t i0 = 0; i0 < hits; i0 += uint32_t(BLOCK)) {
+        const uint32_t i = i0 + uint32_t(tid);
+        const bool have = i < hits;
+        const uint32_t pix = have ? pool.hit_pix[i] : 0u;
+        const float t = have ? pool.hit_val[i] : 0.0f;
+        __syncthreads();  // the chunk's entries are read (and the counters cleared) before any slot is filed over
+        float lit = 0.0f;
+        V3 start{0.0f, 0.0f, 0.0f};
+        if (have) lit = pooled_hit<GROUP, PRIM>(P, pool, pix, t, start);
+        const bool secondary = have && (lit > 0.0f);
+        const unsigned long long ms = __builtin_amdgcn_ballot_w64(secondary);
+        if (ms != 0ull) {
+            const int first = __builtin_ctzll(ms);
+            uint32_t base = 0;
+            if (lane == first) base = atomicAdd(&sh_count, uint32_t(__builtin_popcountll(ms)));
+            base = uint32_t(__builtin_amdgcn_readlane(int(base), first));
+            // (slot k <= the hits read so far: every one of them is in a register)
+            if (secondary) pooled_file(pool, base + uint32_t(__builtin_popcountll(ms & below)), pix, lit, start);
+        }
+        if (have && !secondary) pooled_colour(P, pool, pix, lit, srgb, s_srgb);
+    }
+    __syncthreads();
+    // pass 2: every lane marches a secondary ray of the pool and takes the next one when it ends
+    {
+        const uint32_t n_sh = sh_count;  // uniform
+        bool exhausted = false;
+        PooledLane l;
+        for (;;) {
+            const unsigned long long idle = __builtin_amdgcn_ballot_w64(!l.busy);
+            if (idle != 0ull && !exhausted) {
+                const int first = __builtin_ctzll(idle);
+                uint32_t base = 0;
+                if (lane == first) base = atomicAdd(&sh_next, uint32_t(__builtin_popcountll(idle)));
+                base = uint32_t(__builtin_amdgcn_readlane(int(base), first));
+                const uint32_t mine = base + uint32_t(__builtin_popcountll(idle & below));
+                if (!l.busy && mine < n_sh) pooled_take(P, pool, l, mine);
+                exhausted = base + uint32_t(__builtin_popcountll(idle)) >= n_sh;
+            }
+            const unsigned long long lanes = __builtin_amdgcn_ballot_w64(l.busy);
+            if (lanes == 0ull) break;
+            pooled_step<GROUP, PRIM>(P, pool, l, lanes);
+        }
+    }
+    __syncthreads();
+    // pass 3: their colours
+    const uint32_t n_sh = sh_count;
+    for (uint32_t k0 = 0; k0 < n_sh; k0 += uint32_t(BLOCK)) {
+        const uint32_t k = k0 + uint32_t(tid);
+        if (k < n_sh) pooled_colour(P, pool, pool.hit_pix[k], pool.hit_val[k], srgb, s_srgb);
+    }
+}
+
 // render_group_kernel<GROUP, PRIM, T>: the throughput path.  A workgroup renders T consecutive
 // entries of its view's tile order and RE-QUEUES its rays.
 //   Rays of one 8x8 block leave the march at very different steps (one wave per block: 54-66 % of
@@ -91,6 +283,37 @@ __global__ __launch_bounds__(BLOCK) void render_kernel(const BatchParams B) {
 //   A ray's own arithmetic is unchanged (t, and p = fma(t, dir, origin) rebuilt from it exactly as
 //   the march itself does), all rays of the workgroup make their k-th step in the same round (the
 //   step counter stays uniform), and pixels do not interact: same pixels as render_kernel.
+// Round 0's queue: the rays of the group's tiles that survive the culls.  Wave w -> 8x8 block w of each tile.
+// q_count, q_pix, q_t: the queue's counter and entries; s_dir: the per-pixel direction cache.
+template <int T, uint32_t CAP>
+__device__ __forceinline__ void group_round0(const FrameParams& P, const uint32_t* s_tiles, const int* s_rows, int lx, int ly,
+                                             int lane, uint32_t* q_count, uint32_t* q_pix, float* q_t, float (*s_dir)[CAP]) {
+    for (int j = 0; j < T; ++j) {
+        const uint32_t tile = s_tiles[j];  // uniform
+        if (tile == 0xffffffffu) break;
+        const int x = int(tile & 0xffffu) * TILE_W + lx;
+        const int y = s_rows[j] + ly;
+        const bool valid = (x < P.width) && (y < P.y1);
+        if (wave_is_culled(P, x, y, valid) || __ballot(valid) == 0ull) continue;  // wave-uniform
+        const V3 dir = ray_direction(P, x, y);
+        const bool alive = ray_sets_out(P, dir, valid, P.cull_n2 > 0.0f);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(alive);
+        if (m == 0ull) continue;
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(q_count, uint32_t(__builtin_popcountll(m)));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (alive) {
+            const uint32_t i = base + uint32_t(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
+            const uint32_t pix = (uint32_t(j) << 8) | (uint32_t(ly) << 5) | uint32_t(lx);
+            q_pix[i] = pix;
+            q_t[i] = 0.0f;
+            s_dir[0][pix] = dir.x;
+            s_dir[1][pix] = dir.y;
+            s_dir[2][pix] = dir.z;
+        }
+    }
+}
+
 template <int GROUP, int PRIM, int T, bool W2LDS = false>
 __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B) {
     constexpr uint32_t CAP = uint32_t(BLOCK) * T;  // every pixel of the group could be a live ray
@@ -154,32 +377,8 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     if constexpr (W2LDS) bunny_w2_stage(s_w2, tid);
     __syncthreads();
 
-    // ---- round 0's queue: the rays that survive the culls
-    for (int j = 0; j < T; ++j) {
-        const uint32_t tile = s_tiles[j];  // uniform
-        if (tile == 0xffffffffu) break;
-        const int x = int(tile & 0xffffu) * TILE_W + lx;
-        const int y = s_rows[j] + ly;
-        const bool valid = (x < P.width) && (y < P.y1);
-        if (wave_is_culled(P, x, y, valid) || __ballot(valid) == 0ull) continue;  // wave-uniform
-        const V3 dir = ray_direction(P, x, y);
-        bool alive = valid && (0 < P.max_iterations) && (0.0f < P.max_distance);
-        if (P.cull_n2 > 0.0f) alive = alive && !ray_never_inside(P, dir);
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(alive);
-        if (m == 0ull) continue;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&q_count[0], uint32_t(__builtin_popcountll(m)));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (alive) {
-            const uint32_t i = base + uint32_t(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
-            const uint32_t pix = (uint32_t(j) << 8) | (uint32_t(ly) << 5) | uint32_t(lx);
-            q_pix[0][i] = pix;
-            q_t[0][i] = 0.0f;
-            s_dir[0][pix] = dir.x;
-            s_dir[1][pix] = dir.y;
-            s_dir[2][pix] = dir.z;
-        }
-    }
+    // ---- round 0's queue
+    group_round0<T>(P, s_tiles, s_rows, lx, ly, lane, &q_count[0], q_pix[0], q_t[0], s_dir);
     __syncthreads();
 
     // ---- rounds
@@ -189,7 +388,6 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     for (uint32_t cur = 0, cnt = 0;; cur ^= 1u, cnt = (cnt + 1u) % 3u) {
         const uint32_t n = q_count[cnt];  // uniform
         if (n == 0u) break;
-        const uint32_t cnt_next = (cnt + 1u) % 3u;
         if (tid == 0) {  // the counters of the round after next
             q_count[(cnt + 2u) % 3u] = 0;
             q_ticket[(cnt + 2u) % 3u] = 0;
@@ -197,6 +395,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
         // (one chunk left: nothing more to merge, it is marched to the end -- see render_wave_kernel; not the
         // generalised Julia set, whose compiled march loses 5-10 % that way: 48 frames per launch 20.6 -> 19.6 Gpixel/s)
         const int limit = (GROUP != GROUP_GENJULIA && n <= RAYS) ? P.max_iterations : min(trips + P.round_steps, P.max_iterations);
+        const uint32_t cnt_next = (cnt + 1u) % 3u;
         for (;;) {
             uint32_t chunk = 0;
             if (lane == 0) chunk = atomicAdd(&q_ticket[cnt], 1u);
@@ -254,138 +453,23 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
         __syncthreads();  // the next queue and the hit list are complete
     }
 
-    // ---- shade the hits, 64 to a wave
+    // ---- shade the hits
     const uint32_t hits = h_count;  // uniform
+    const GroupPool<CAP> pool{h_pix, h_t, s_dir, s_tile};
+    bool pooled = false;  // the soft-shadow extension: its secondary rays from a pool (not the bunny)
     if constexpr (BUNNY) {
         if (hits != 0u && !weights_loaded) bunny_quad_load(W, lane & 3, s_w2);  // a wave that marched nothing shades too
+    } else {
+        pooled = P.soft_shadow != 0u && P.shadow_steps > 0;
+        // (the Julia pipeline's PRIM slot is its loop's variant: its SDF and normal do not depend on it)
+        if (pooled) shade_group_hits_with_pooled_shadows<GROUP, GROUP == GROUP_JULIA ? 0 : PRIM>(P, hits, tid, pool, srgb, s_srgb);
     }
-    bool shaded = false;
-    if constexpr (!BUNNY) {
-        // Soft shadows: the secondary rays from a pool, as in render_wave_kernel (shade_hits_with_pooled_shadows), the pool
-        // being the workgroup's: a barrier between reading a chunk of 256 hits and filing its secondary rays over the hit
-        // list's consumed slots, an LDS cursor the four waves draw from.  Same operations per ray: same pixels.
-        if (P.soft_shadow != 0u && P.shadow_steps > 0) {
-            shaded = true;
-            __shared__ uint32_t sh_count, sh_next;
-            constexpr int NPRIM = GROUP == GROUP_JULIA ? 0 : PRIM;  // (the Julia pipeline's PRIM slot is its loop's variant)
-            const unsigned long long below = (1ull << lane) - 1ull;
-            const V3 L = normalize(V3{1.0f, 1.0f, 1.0f});
-            const float off = 2.0f * P.epsilon;
-            if (tid == 0) {
-                sh_count = 0;
-                sh_next = 0;
-            }
-            // pass 1: normals and direct terms; the hits that need no secondary ray get their colour
-            for (uint32_t i0 = 0; i0 < hits; i0 += uint32_t(BLOCK)) {
-                const uint32_t i = i0 + uint32_t(tid);
-                const bool have = i < hits;
-                const uint32_t pix = have ? h_pix[i] : 0u;
-                const float t = have ? h_t[i] : 0.0f;
-                __syncthreads();  // the chunk's entries are read (and the counters cleared) before any slot is filed over
-                float lit = 0.0f;
-                V3 start{0.0f, 0.0f, 0.0f};
-                if (have) {
-                    const V3 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
-                    const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
-                    const V3 nrm = scene_normal<GROUP, NPRIM>(P, p);
-                    const float ndl = (nrm.x + nrm.y) + nrm.z;
-                    lit = clamp_(ndl, 0.0f, 1.0f);
-                    start = V3{fmaf_(off, nrm.x, p.x), fmaf_(off, nrm.y, p.y), fmaf_(off, nrm.z, p.z)};
-                }
-                const bool secondary = have && (lit > 0.0f);
-                const unsigned long long ms = __builtin_amdgcn_ballot_w64(secondary);
-                if (ms != 0ull) {
-                    const int first = __builtin_ctzll(ms);
-                    uint32_t base = 0;
-                    if (lane == first) base = atomicAdd(&sh_count, uint32_t(__builtin_popcountll(ms)));
-                    base = uint32_t(__builtin_amdgcn_readlane(int(base), first));
-                    if (secondary) {  // (slot k <= the hits read so far: every one of them is in a register)
-                        const uint32_t k = base + uint32_t(__builtin_popcountll(ms & below));
-                        h_pix[k] = pix;
-                        h_t[k] = lit;
-                        s_dir[0][pix] = start.x;
-                        s_dir[1][pix] = start.y;
-                        s_dir[2][pix] = start.z;
-                    }
-                }
-                if (have && !secondary) {
-                    const float diffuse = fmaf_(0.9f, lit, 0.1f);
-                    const V3 colour{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-                    s_tile[pix >> 8][(pix >> 5) & 7u][pix & 31u] = encode_rgba(colour, srgb, s_srgb);
-                }
-            }
-            __syncthreads();
-            // pass 2: every lane marches a secondary ray of the pool and takes the next one when it ends
-            {
-                const uint32_t n_sh = sh_count;  // uniform
-                bool busy = false, exhausted = false;
-                uint32_t k = 0;
-                int j = 0;
-                float lit = 0.0f, t = 0.0f, res = 1.0f;
-                V3 start{0.0f, 0.0f, 0.0f};
-                for (;;) {
-                    const unsigned long long idle = __builtin_amdgcn_ballot_w64(!busy);
-                    if (idle != 0ull && !exhausted) {
-                        const int first = __builtin_ctzll(idle);
-                        uint32_t base = 0;
-                        if (lane == first) base = atomicAdd(&sh_next, uint32_t(__builtin_popcountll(idle)));
-                        base = uint32_t(__builtin_amdgcn_readlane(int(base), first));
-                        const uint32_t mine = base + uint32_t(__builtin_popcountll(idle & below));
-                        if (!busy && mine < n_sh) {
-                            k = mine;
-                            const uint32_t pix = h_pix[k];
-                            lit = h_t[k];
-                            start = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
-                            t = P.shadow_t0;
-                            res = 1.0f;
-                            j = 0;
-                            busy = true;
-                        }
-                        exhausted = base + uint32_t(__builtin_popcountll(idle)) >= n_sh;
-                    }
-                    const unsigned long long lanes = __builtin_amdgcn_ballot_w64(busy);
-                    if (lanes == 0ull) break;
-                    const V3 q{fmaf_(t, L.x, start.x), fmaf_(t, L.y, start.y), fmaf_(t, L.z, start.z)};
-                    const float h = scene_sdf<GROUP, NPRIM>(P, q, lanes);
-                    if (busy) {
-                        bool done;
-                        if (h < P.epsilon) {
-                            res = 0.0f;
-                            done = true;
-                        } else {
-                            res = min_(res, (P.shadow_k * h) / t);
-                            t = t + h;
-                            done = (t > P.shadow_max_t) || !(j + 1 < P.shadow_steps);
-                            ++j;
-                        }
-                        if (done) {
-                            h_t[k] = lit * res;  // the attenuated direct term
-                            busy = false;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            // pass 3: their colours
-            const uint32_t n_sh = sh_count;
-            for (uint32_t k0 = 0; k0 < n_sh; k0 += uint32_t(BLOCK)) {
-                const uint32_t k = k0 + uint32_t(tid);
-                if (k < n_sh) {
-                    const uint32_t pix = h_pix[k];
-                    const float diffuse = fmaf_(0.9f, h_t[k], 0.1f);
-                    const V3 colour{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-                    s_tile[pix >> 8][(pix >> 5) & 7u][pix & 31u] = encode_rgba(colour, srgb, s_srgb);
-                }
-            }
-        }
-    }
-    for (uint32_t i0 = 0; !shaded && i0 < hits; i0 += uint32_t(BLOCK) / LPR) {
+    for (uint32_t i0 = 0; !pooled && i0 < hits; i0 += uint32_t(BLOCK) / LPR) {
         const uint32_t i = i0 + uint32_t(tid) / LPR;
         if (i < hits) {
-            const uint32_t pix = h_pix[i];
-            const float t = h_t[i];
-            const int hx = int(pix & 31u), hy = int((pix >> 5) & 7u);
-            const V3 dir = V3{s_dir[0][pix], s_dir[1][pix], s_dir[2][pix]};
+            const uint32_t pix = pool.hit_pix[i];
+            const float t = pool.hit_val[i];
+            const V3 dir = V3{pool.dir[0][pix], pool.dir[1][pix], pool.dir[2][pix]};
             const V3 p = (t == 0.0f) ? P.origin : ray_at(P, t, dir);
             V3 colour;
             if constexpr (BUNNY) {
@@ -396,118 +480,13 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
                 colour = shade_hit<GROUP, PRIM>(P, p);
             }
             const uint32_t rgba8 = encode_rgba(colour, srgb, s_srgb);
-            if ((uint32_t(tid) % LPR) == 0u) s_tile[pix >> 8][hy][hx] = rgba8;
+            if ((uint32_t(tid) % LPR) == 0u) pool.texel(pix) = rgba8;
         }
     }
     __syncthreads();
 
     // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's run time
     store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, t_start);
-}
-
-// Shading of a tile's hits with the soft-shadow extension (include/kifs_hip.h), for render_wave_kernel (every pipeline).
-// A hit's secondary march is 1 to shadow_steps estimates long, so 64 of them side by side finish one by one and the
-// wave waits for the longest.  Instead the lanes take the secondary rays from a pool: pass 1 computes every hit's
-// normal and direct term, colours the hits that need no secondary ray and files the others (start point over the
-// pixel's cached direction, which nothing reads any more; pixel id and direct term over the hit list's slots already
-// consumed); pass 2 marches them with per-lane step counters, a lane that finishes its ray taking the next one of the
-// pool; pass 3 encodes.  Every ray's own sequence of operations is soft_shadow()'s: same pixels.
-// hit_pix / hit_val: the hit list, entry i at [CAP - 1 - i] (pixel id, t); dir: the per-pixel direction cache.
-template <int GROUP, int PRIM, uint32_t CAP>
-__device__ __forceinline__ void shade_hits_with_pooled_shadows(const FrameParams& P, uint32_t hits, uint32_t lane, uint8_t* hit_pix,
-                                                               float* hit_val, float (*dir_cache)[CAP], uint32_t (*s_tile)[TILE_W],
-                                                               bool srgb, const float* s_srgb) {
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const V3 L = normalize(V3{1.0f, 1.0f, 1.0f});
-    const float off = 2.0f * P.epsilon;
-    uint32_t n_sh = 0;  // uniform
-    for (uint32_t i0 = 0; i0 < hits; i0 += 64u) {
-        const bool have = i0 + lane < hits;
-        uint32_t pix = 0;
-        float lit = 0.0f;
-        V3 start{0.0f, 0.0f, 0.0f};
-        if (have) {
-            pix = hit_pix[CAP - 1u - (i0 + lane)];
-            const float t = hit_val[CAP - 1u - (i0 + lane)];
-            const V3 dir = V3{dir_cache[0][pix], dir_cache[1][pix], dir_cache[2][pix]};
-            const V3 p = (t == 0.0f) ? P.origin
-                                     : V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y),
-                                          fmaf_(t, dir.z, P.origin.z)};
-            const V3 nrm = scene_normal<GROUP, PRIM>(P, p);
-            const float ndl = (nrm.x + nrm.y) + nrm.z;
-            lit = clamp_(ndl, 0.0f, 1.0f);
-            start = V3{fmaf_(off, nrm.x, p.x), fmaf_(off, nrm.y, p.y), fmaf_(off, nrm.z, p.z)};
-        }
-        const bool secondary = have && (lit > 0.0f);
-        const unsigned long long ms = __builtin_amdgcn_ballot_w64(secondary);
-        if (secondary) {  // (slot k <= this hit's own: read above, by every lane, before anything is written)
-            const uint32_t k = n_sh + uint32_t(__builtin_popcountll(ms & below));
-            hit_pix[CAP - 1u - k] = uint8_t(pix);
-            hit_val[CAP - 1u - k] = lit;
-            dir_cache[0][pix] = start.x;
-            dir_cache[1][pix] = start.y;
-            dir_cache[2][pix] = start.z;
-        } else if (have) {  // no direct light: the colour is final
-            const float diffuse = fmaf_(0.9f, lit, 0.1f);
-            const V3 colour{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-            s_tile[pix >> 5][pix & 31u] = encode_rgba(colour, srgb, s_srgb);
-        }
-        n_sh += uint32_t(__builtin_popcountll(ms));
-    }
-    // pass 2: the pool of secondary rays
-    {
-        uint32_t next = 0;  // uniform: rays handed out so far
-        bool busy = false;
-        uint32_t k = 0;
-        int j = 0;
-        float lit = 0.0f, t = 0.0f, res = 1.0f;
-        V3 start{0.0f, 0.0f, 0.0f};
-        for (;;) {
-            const unsigned long long idle = __builtin_amdgcn_ballot_w64(!busy);
-            const uint32_t mine = next + uint32_t(__builtin_popcountll(idle & below));
-            if (!busy && mine < n_sh) {
-                k = mine;
-                const uint32_t pix = hit_pix[CAP - 1u - k];
-                lit = hit_val[CAP - 1u - k];
-                start = V3{dir_cache[0][pix], dir_cache[1][pix], dir_cache[2][pix]};
-                t = P.shadow_t0;
-                res = 1.0f;
-                j = 0;
-                busy = true;
-            }
-            next = min(n_sh, next + uint32_t(__builtin_popcountll(idle)));
-            const unsigned long long lanes = __builtin_amdgcn_ballot_w64(busy);
-            if (lanes == 0ull) break;
-            const V3 q{fmaf_(t, L.x, start.x), fmaf_(t, L.y, start.y), fmaf_(t, L.z, start.z)};
-            const float h = scene_sdf<GROUP, PRIM>(P, q, lanes);
-            if (busy) {
-                bool done;
-                if (h < P.epsilon) {
-                    res = 0.0f;
-                    done = true;
-                } else {
-                    res = min_(res, (P.shadow_k * h) / t);
-                    t = t + h;
-                    done = (t > P.shadow_max_t) || !(j + 1 < P.shadow_steps);
-                    ++j;
-                }
-                if (done) {
-                    hit_val[CAP - 1u - k] = lit * res;  // the attenuated direct term
-                    busy = false;
-                }
-            }
-        }
-    }
-    // pass 3: their colours
-    for (uint32_t k0 = 0; k0 < n_sh; k0 += 64u) {
-        if (k0 + lane < n_sh) {
-            const uint32_t pix = hit_pix[CAP - 1u - (k0 + lane)];
-            const float lit = hit_val[CAP - 1u - (k0 + lane)];
-            const float diffuse = fmaf_(0.9f, lit, 0.1f);
-            const V3 colour{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-            s_tile[pix >> 5][pix & 31u] = encode_rgba(colour, srgb, s_srgb);
-        }
-    }
 }
 
 // render_wave_kernel<GROUP, PRIM>: the throughput path with ONE WAVE per workgroup and tile.
@@ -575,8 +554,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
         const bool valid = (x < P.width) && (y < P.y1);
         if (wave_is_culled(P, x, y, valid) || __ballot(valid) == 0ull) continue;  // wave-uniform
         const V3 dir = ray_direction(P, x, y);
-        bool alive = valid && (0 < P.max_iterations) && (0.0f < P.max_distance);
-        if (P.cull_n2 > 0.0f) alive = alive && !ray_never_inside(P, dir);
+        const bool alive = ray_sets_out(P, dir, valid, P.cull_n2 > 0.0f);
         const unsigned long long m = __builtin_amdgcn_ballot_w64(alive);
         if (alive) {
             const uint32_t i = n + uint32_t(__builtin_popcountll(m & below));
@@ -659,8 +637,8 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     if (P.soft_shadow != 0u && P.shadow_steps > 0) {  // secondary rays from a pool: see the function
         shaded = true;
         // (for the Julia pipeline the PRIM slot is the long-ray loop's variant: its SDF and normal do not depend on it)
-        shade_hits_with_pooled_shadows<GROUP, GROUP == GROUP_JULIA ? 0 : PRIM, CAP>(P, hits, lane, &q_pix[1][0], &q_t[1][0], s_dir, s_tile,
-                                                                                   srgb, s_srgb);
+        shade_hits_with_pooled_shadows<GROUP, GROUP == GROUP_JULIA ? 0 : PRIM>(P, hits, lane, WavePool<CAP>{&q_pix[1][0], &q_t[1][0], s_dir, s_tile},
+                                                                              srgb, s_srgb);
     }
     for (uint32_t i0 = 0; !shaded && i0 < hits; i0 += 64u) {
         if (i0 + lane < hits) {
@@ -709,6 +687,20 @@ unsigned residency_pad_bytes(int workgroups_per_cu) {
     }
 }
 
+// render_group_kernel for a launch: two tiles per workgroup (the last group of an odd table holds one) or one; W2LDS
+// exists for pairs only.
+template <int GROUP, int PRIM, bool W2LDS = false>
+static hipError_t launch_group(const BatchParams& B, hipStream_t stream) {
+    const FrameParams& P = B.frame;
+    if (W2LDS || P.group_tiles >= 2) {
+        hipLaunchKernelGGL((render_group_kernel<GROUP, PRIM, 2, W2LDS>), dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)),
+                           dim3(BLOCK), 0, stream, B);
+    } else if constexpr (!W2LDS) {
+        hipLaunchKernelGGL((render_group_kernel<GROUP, PRIM, 1>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), 0, stream, B);
+    }
+    return hipGetLastError();
+}
+
 // One pipeline's launch (dispatch_pipeline in kifs_render_common.hpp): which of its kernels, and the grid.
 template <int GROUP, int PRIM>
 static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
@@ -722,16 +714,7 @@ static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
                            residency_pad_bytes(0), stream, B);  // (the pad: KIFS_LDS_PAD under KIFS_TUNING, else 0)
         return hipGetLastError();
     }
-    if (P.round_steps > 0) {  // the throughput path: rays re-queued, one or two tiles per workgroup
-        if (P.group_tiles >= 2) {
-            hipLaunchKernelGGL((render_group_kernel<GROUP, LPRIM, 2>), dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)),
-                               dim3(BLOCK), 0, stream, B);
-        } else {
-            hipLaunchKernelGGL((render_group_kernel<GROUP, LPRIM, 1>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), 0,
-                               stream, B);
-        }
-        return hipGetLastError();
-    }
+    if (P.round_steps > 0) return launch_group<GROUP, LPRIM>(B, stream);  // the throughput path: rays re-queued, one or two tiles per workgroup
     hipLaunchKernelGGL((render_kernel<GROUP, LPRIM>), dim3(P.tile_count * uint32_t(B.count)), dim3(BLOCK), pad, stream, B);
     return hipGetLastError();
 }
@@ -739,21 +722,9 @@ static hipError_t launch_variant(const BatchParams& B, hipStream_t stream) {
 static hipError_t launch_bunny_quad(const BatchParams& B, hipStream_t stream) {
     const FrameParams& P = B.frame;
     if (P.round_steps > 0 && P.bunny_coop == 1) return launch_bunny_coop(B, stream);  // re-queued rays, four waves per 64 rays
-    if (P.round_steps > 0 && P.bunny_coop == 2) {  // four lanes per ray, layer 2 in LDS: three waves per SIMD (pairs of tiles only)
-        hipLaunchKernelGGL((render_group_kernel<GROUP_KIFS, PRIM_BUNNY, 2, true>),
-                           dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)), dim3(BLOCK), 0, stream, B);
-        return hipGetLastError();
-    }
-    if (P.round_steps > 0) {  // the throughput path: re-queued rays, four lanes per ray
-        if (P.group_tiles >= 2) {
-            hipLaunchKernelGGL((render_group_kernel<GROUP_KIFS, PRIM_BUNNY, 2>),
-                               dim3(((P.tile_count + 1u) / 2u) * uint32_t(B.count)), dim3(BLOCK), 0, stream, B);
-        } else {
-            hipLaunchKernelGGL((render_group_kernel<GROUP_KIFS, PRIM_BUNNY, 1>), dim3(P.tile_count * uint32_t(B.count)),
-                               dim3(BLOCK), 0, stream, B);
-        }
-        return hipGetLastError();
-    }
+    // four lanes per ray, layer 2 in LDS: three waves per SIMD (pairs of tiles only)
+    if (P.round_steps > 0 && P.bunny_coop == 2) return launch_group<GROUP_KIFS, PRIM_BUNNY, true>(B, stream);
+    if (P.round_steps > 0) return launch_group<GROUP_KIFS, PRIM_BUNNY>(B, stream);  // the throughput path: re-queued rays, four lanes per ray
     return launch_bunny_whole_rays(B, stream);
 }
 

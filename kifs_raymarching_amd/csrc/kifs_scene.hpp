@@ -492,33 +492,82 @@ KIFS_DEV V3 ray_direction(const FrameParams& P, int x, int y) {
     return normalize(d);
 }
 
-// ---- extension: soft shadows (not in the reference; see KifsExtensions) ------------------
-// Secondary march from the hit point towards the light, operation for operation as
-// specified in include/kifs_hip.h (KifsExtensions).  `lanes_hit` selects the lanes that take part; the loop leaves
-// when none of them is still marching.
+// ---- the lighting model: entry.wgsl:14-19 and the soft-shadow extension, stated once --------------
+// Every shading site of the library -- the whole-ray drivers below, the pooled shaders of kifs_kernels.hip -- is made
+// of these pieces, so the operations and their order exist in one place.
+// The direct term: dot(n, (1,1,1)) clamped; the light is not normalised (:17).
+KIFS_DEV float direct_term(V3 n) { return clamp_((n.x + n.y) + n.z, 0.0f, 1.0f); }
+// The colour of a hit whose (attenuated) direct term is `lit` (:18-19).
+KIFS_DEV V3 lit_colour(const FrameParams& P, float lit) {
+    const float diffuse = fmaf_(0.9f, lit, 0.1f);
+    return V3{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
+}
+// Heatmap mode: the loop counter at which the ray stopped, as a fraction of max_iterations (:27-29).
+KIFS_DEV V3 heatmap_colour(const FrameParams& P, int i_final) {
+    const float f = float(i_final) / float(P.max_iterations);
+    return V3{f * P.fractal_color.x, f * P.fractal_color.y, f * P.fractal_color.z};
+}
+
+// Extension: soft shadows (not in the reference; see KifsExtensions).  A secondary march from the hit point towards
+// the light, operation for operation as specified in include/kifs_hip.h.
+struct ShadowRay {
+    V3 start;    // the hit point lifted off the surface
+    float t;     // distance marched along the light direction
+    float res;   // the attenuation so far
+    int j;       // estimates taken
+};
+KIFS_DEV V3 shadow_start(const FrameParams& P, V3 p, V3 n) {
+    const float off = 2.0f * P.epsilon;
+    return V3{fmaf_(off, n.x, p.x), fmaf_(off, n.y, p.y), fmaf_(off, n.z, p.z)};
+}
+KIFS_DEV ShadowRay shadow_ray_from(const FrameParams& P, V3 start) { return ShadowRay{start, P.shadow_t0, 1.0f, 0}; }
+KIFS_DEV ShadowRay shadow_ray(const FrameParams& P, V3 p, V3 n) { return shadow_ray_from(P, shadow_start(P, p, n)); }
+// The position whose estimate the ray takes next.
+KIFS_DEV V3 shadow_point(const ShadowRay& s) {
+    const V3 L = normalize(V3{1.0f, 1.0f, 1.0f});
+    return V3{fmaf_(s.t, L.x, s.start.x), fmaf_(s.t, L.y, s.start.y), fmaf_(s.t, L.z, s.start.z)};
+}
+// One step with the estimate h at shadow_point(s); true when the ray is over (s.res is then its factor).  The caller
+// counts it (++s.j) where that suits its loop: a wave whose rays step together keeps the count in a scalar register.
+KIFS_DEV bool shadow_step(const FrameParams& P, float h, ShadowRay& s) {
+    if (h < P.epsilon) {
+        s.res = 0.0f;
+        return true;
+    }
+    s.res = min_(s.res, (P.shadow_k * h) / s.t);
+    s.t = s.t + h;
+    return (s.t > P.shadow_max_t) || !(s.j + 1 < P.shadow_steps);
+}
+// Whole secondary rays, one per lane.  `lanes_hit` selects the lanes that take part; the loop leaves when none of
+// them is still marching.
 template <class Sdf>
 KIFS_DEV float soft_shadow(const FrameParams& P, V3 p, V3 n, bool lanes_hit, Sdf sdf) {
-    const V3 L = normalize(V3{1.0f, 1.0f, 1.0f});
-    const float off = 2.0f * P.epsilon;
-    const V3 start{fmaf_(off, n.x, p.x), fmaf_(off, n.y, p.y), fmaf_(off, n.z, p.z)};
-    float res = 1.0f;
-    float t = P.shadow_t0;
+    ShadowRay s = shadow_ray(P, p, n);
     bool marching = lanes_hit && (0 < P.shadow_steps);
-    for (int j = 0; __builtin_amdgcn_ballot_w64(marching) != 0ull; ++j) {
-        if (marching) {
-            const V3 q{fmaf_(t, L.x, start.x), fmaf_(t, L.y, start.y), fmaf_(t, L.z, start.z)};
-            const float h = sdf(q, ~0ull);
-            if (h < P.epsilon) {
-                res = 0.0f;
-                marching = false;
-            } else {
-                res = min_(res, (P.shadow_k * h) / t);
-                t = t + h;
-                marching = !(t > P.shadow_max_t) && (j + 1 < P.shadow_steps);
-            }
-        }
+    for (; __builtin_amdgcn_ballot_w64(marching) != 0ull; ++s.j) {
+        if (marching) marching = !shadow_step(P, sdf(shadow_point(s), ~0ull), s);
     }
-    return res;
+    return s.res;
+}
+
+// Colour of a hit at p, soft shadows if enabled.  `sdf(p, lanes)`: the scene's estimate (lanes = whose value is used);
+// `normal(p)`: its normal.  n_out, when given, receives the normal the shading used (the geometry output's).
+template <class Sdf, class Normal>
+KIFS_DEV V3 generic_shade(const FrameParams& P, V3 p, Sdf sdf, Normal normal, V3* n_out = nullptr) {
+    const V3 n = normal(p);
+    if (n_out) *n_out = n;
+    float lit = direct_term(n);
+    // (a lane whose direct term is not positive marches no secondary ray: its factor is 1 and 0 * 1 = 0)
+    if (__builtin_expect(P.soft_shadow != 0u, 0)) lit = lit * soft_shadow(P, p, n, lit > 0.0f, sdf);
+    return lit_colour(P, lit);
+}
+// The same for pipeline <GROUP, PRIM> (Julia: julia.wgsl:29-56 for the normal; its PRIM slot is not a primitive).
+template <int GROUP, int PRIM>
+KIFS_DEV V3 shade_hit(const FrameParams& P, V3 p, V3* n_out = nullptr) {
+    constexpr int NPRIM = GROUP == GROUP_JULIA ? 0 : PRIM;
+    return generic_shade(
+        P, p, [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, NPRIM>(P, q, lanes); },
+        [&](V3 q) { return scene_normal<GROUP, NPRIM>(P, q); }, n_out);
 }
 
 // ---- the long-ray loop: every live lane inside the bounding sphere -------------------------
@@ -934,6 +983,29 @@ KIFS_DEV void march_priority(int trips) {
     else __builtin_amdgcn_s_setprio(1);
 }
 
+// Whether a ray sets out at all: inside the frame, with a step to make and room to make it in, and -- `cull`,
+// wave-uniform: the bounding-sphere cull is on -- not passing the sphere by.  Every scene's estimate obeys
+// d(p) >= |p| - B, so outside the sphere of radius R = B + epsilon it exceeds epsilon (Julia: length(p) - 2,
+// julia.wgsl:8-9) and a ray that never enters can never satisfy `d < epsilon`: its pixel is background whatever else
+// the loop does (only the heatmap's step count would notice, so heatmap frames march every ray).  The test keeps a
+// 10 % margin on R^2, orders of magnitude above the rounding of p = fma(t, dir, origin) for any t < max_distance.
+KIFS_DEV bool ray_sets_out(const FrameParams& P, V3 dir, bool valid, bool cull) {
+    bool live = valid && (0 < P.max_iterations) && (0.0f < P.max_distance);
+    if (cull) live = live && !ray_never_inside(P, dir);
+    return live;
+}
+KIFS_DEV bool whole_ray_sets_out(const FrameParams& P, V3 dir, bool valid) {
+    return ray_sets_out(P, dir, valid, P.is_heatmap == 0u && P.cull_n2 > 0.0f);
+}
+// The colour of a finished whole ray (entry.wgsl:26-31): `shade()` is the colour of its hit.
+template <class Shade>
+KIFS_DEV V3 whole_ray_colour(const FrameParams& P, bool hit, int i_final, Shade shade) {
+    V3 colour = P.background_color;
+    if (hit) colour = shade();
+    if (P.is_heatmap) colour = heatmap_colour(P, i_final);
+    return colour;
+}
+
 struct JuliaDiag {  // diagnostics of one wave's march (SGPRs)
     int fast_steps = 0, fast_entries = 0, general_steps = 0;
     unsigned long long fast_ticks = 0;
@@ -1001,19 +1073,6 @@ KIFS_DEV void julia_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& hi
     }
 }
 
-// Colour of a Julia hit at p (entry.wgsl:14-19 with julia.wgsl:29-56), soft shadows if enabled.
-// n_out, when given, receives the normal the shading used (the geometry output's).
-KIFS_DEV V3 julia_shade(const FrameParams& P, V3 p, V3* n_out = nullptr) {
-    V3 n = julia_normal(P, p);
-    if (n_out) *n_out = n;
-    float ndl = (n.x + n.y) + n.z;
-    float lit = clamp_(ndl, 0.0f, 1.0f);
-    if (__builtin_expect(P.soft_shadow != 0u, 0))
-        lit = lit * soft_shadow(P, p, n, lit > 0.0f, [&](V3 q, unsigned long long) { return julia_sdf(P, q); });
-    float diffuse = fmaf_(0.9f, lit, 0.1f);
-    return V3{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-}
-
 // A whole ray per lane, start to finish (heatmap mode, diagnostics, and the building block the
 // re-queuing kernel path is checked against).
 template <bool SHORT_DIVSQRT>
@@ -1023,13 +1082,7 @@ KIFS_DEV V3 raymarch_julia(const FrameParams& P, V3 dir, bool valid, int& steps)
     bool hit = false;
     int trips = 0;     // == the loop counter i of entry.wgsl:11 for every marching lane
     int i_final = 0;
-    bool marching = valid && (0 < P.max_iterations) && (t < P.max_distance);
-    // Bounding-sphere cull.  Outside the sphere of radius R = 2 + epsilon the estimate is
-    // length(p) - 2 > epsilon (julia.wgsl:8-9), so a ray that never enters the sphere can never
-    // satisfy `d < epsilon`: its pixel is background whatever else the loop does (only the
-    // heatmap's step count would notice).  The test keeps a 10 % margin on R^2, orders of
-    // magnitude above the rounding of p = fma(t, dir, origin) for any t < max_distance.
-    if (P.is_heatmap == 0u && P.cull_n2 > 0.0f) marching = marching && !ray_never_inside(P, dir);
+    bool marching = whole_ray_sets_out(P, dir, valid);
     JuliaDiag diag;
     const bool stamp = P.counters != nullptr;
     const unsigned long long wave_t0 = stamp ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -1048,13 +1101,7 @@ KIFS_DEV V3 raymarch_julia(const FrameParams& P, V3 dir, bool valid, int& steps)
             rec[3] = (unsigned long long)diag.general_steps;
         }
     }
-    V3 colour = P.background_color;
-    if (hit) colour = julia_shade(P, p);
-    if (P.is_heatmap) {
-        float f = float(i_final) / float(P.max_iterations);
-        colour = V3{f * P.fractal_color.x, f * P.fractal_color.y, f * P.fractal_color.z};
-    }
-    return colour;
+    return whole_ray_colour(P, hit, i_final, [&] { return shade_hit<GROUP_JULIA, 0>(P, p); });
 }
 
 // `sdf(p, lanes)`: the scene's estimate (lanes = whose value is used); `normal(p)`: its normal.
@@ -1066,7 +1113,7 @@ KIFS_DEV V3 raymarch_julia(const FrameParams& P, V3 dir, bool valid, int& steps)
 template <bool AGE_PRIORITY = false, class Sdf>
 KIFS_DEV void generic_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& hit, bool& marching,
                            int& trips, int& i_final, int limit, Sdf sdf) {
-    // Bounding-sphere culls (see raymarch_julia and fill_params): every scene's estimate obeys
+    // Bounding-sphere culls (see ray_sets_out and fill_params): every scene's estimate obeys
     // d(p) >= |p| - B, so a lane outside R = B + epsilon and moving away can never satisfy
     // `d < epsilon`.  Not in heatmap mode.
     const bool cull = (P.is_heatmap == 0u) && (P.cull_n2 > 0.0f);  // wave-uniform
@@ -1102,19 +1149,6 @@ KIFS_DEV void generic_loop(const FrameParams& P, V3 dir, float& t, V3& p, bool& 
     }
 }
 
-// Colour of a hit at p (entry.wgsl:14-19), soft shadows if enabled.  n_out: as julia_shade's.
-template <class Sdf, class Normal>
-KIFS_DEV V3 generic_shade(const FrameParams& P, V3 p, Sdf sdf, Normal normal, V3* n_out = nullptr) {
-    V3 n = normal(p);
-    if (n_out) *n_out = n;
-    float ndl = (n.x + n.y) + n.z;  // dot(n, (1,1,1)): the light is not normalised (:17)
-    float lit = clamp_(ndl, 0.0f, 1.0f);
-    // (a lane whose direct term is not positive marches no secondary ray: its factor is 1 and 0 * 1 = 0)
-    if (__builtin_expect(P.soft_shadow != 0u, 0)) lit = lit * soft_shadow(P, p, n, lit > 0.0f, sdf);
-    float diffuse = fmaf_(0.9f, lit, 0.1f);
-    return V3{diffuse * P.fractal_color.x, diffuse * P.fractal_color.y, diffuse * P.fractal_color.z};
-}
-
 // A whole ray per lane, start to finish.
 template <class Sdf, class Normal>
 KIFS_DEV V3 raymarch_with(const FrameParams& P, V3 dir, bool valid, int& steps, Sdf sdf, Normal normal) {
@@ -1125,18 +1159,11 @@ KIFS_DEV V3 raymarch_with(const FrameParams& P, V3 dir, bool valid, int& steps, 
     // entry.wgsl:11 is the wave-uniform trip count (an SGPR); a lane records it when it stops.
     int trips = 0;
     int i_final = 0;
-    bool marching = valid && (0 < P.max_iterations) && (t < P.max_distance);
-    if ((P.is_heatmap == 0u) && (P.cull_n2 > 0.0f)) marching = marching && !ray_never_inside(P, dir);
+    bool marching = whole_ray_sets_out(P, dir, valid);
     generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, sdf);
     __builtin_amdgcn_s_setprio(0);
     steps = trips;
-    V3 colour = P.background_color;
-    if (hit) colour = generic_shade(P, p, sdf, normal);
-    if (P.is_heatmap) {
-        float f = float(i_final) / float(P.max_iterations);
-        colour = V3{f * P.fractal_color.x, f * P.fractal_color.y, f * P.fractal_color.z};
-    }
-    return colour;
+    return whole_ray_colour(P, hit, i_final, [&] { return generic_shade(P, p, sdf, normal); });
 }
 
 template <int GROUP, int PRIM>
@@ -1166,15 +1193,6 @@ KIFS_DEV void march_round(const FrameParams& P, V3 dir, float& t, V3& p, bool& h
     }
 }
 
-template <int GROUP, int PRIM>
-KIFS_DEV V3 shade_hit(const FrameParams& P, V3 p, V3* n_out = nullptr) {
-    if constexpr (GROUP == GROUP_JULIA) return julia_shade(P, p, n_out);
-    else
-        return generic_shade(
-            P, p, [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); },
-            [&](V3 q) { return scene_normal<GROUP, PRIM>(P, q); }, n_out);
-}
-
 // raymarch<GROUP, PRIM> for the geometry output (kifs_geometry_kernels.hip): the same whole ray per lane, handing out
 // what the march and the shading held -- whether the loop broke at d < epsilon, the ray parameter t at the break (the
 // tested position is fma(t, dir, origin), or the origin itself with t = 0 on the first step) and the normal the
@@ -1186,8 +1204,7 @@ KIFS_DEV V3 raymarch_geometry(const FrameParams& P, V3 dir, bool valid, bool& hi
     hit = false;
     int trips = 0;
     int i_final = 0;
-    bool marching = valid && (0 < P.max_iterations) && (t < P.max_distance);
-    if (P.is_heatmap == 0u && P.cull_n2 > 0.0f) marching = marching && !ray_never_inside(P, dir);
+    bool marching = whole_ray_sets_out(P, dir, valid);
     if constexpr (GROUP == GROUP_JULIA) {
         JuliaDiag diag;
         julia_loop<(PRIM & 1) != 0, false>(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, diag);
@@ -1196,16 +1213,10 @@ KIFS_DEV V3 raymarch_geometry(const FrameParams& P, V3 dir, bool valid, bool& hi
                      [&](V3 q, unsigned long long lanes) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });
     }
     __builtin_amdgcn_s_setprio(0);
-    V3 colour = P.background_color;
-    if (hit) {
-        colour = shade_hit<GROUP, PRIM>(P, p, &n);
+    return whole_ray_colour(P, hit, i_final, [&] {
         t_hit = t;
-    }
-    if (P.is_heatmap) {
-        float f = float(i_final) / float(P.max_iterations);
-        colour = V3{f * P.fractal_color.x, f * P.fractal_color.y, f * P.fractal_color.z};
-    }
-    return colour;
+        return shade_hit<GROUP, PRIM>(P, p, &n);
+    });
 }
 
 }  // namespace kifs

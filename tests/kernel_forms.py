@@ -73,8 +73,12 @@ SCENES = {
     "box": Scene(KIFS, 2, encodes=(1,)),
     "torus_shadow": Scene(KIFS, 3, iters=(24, 10, 6), shadow=True, encodes=(0,)),
     "sierpinski": Scene(KIFS, 4, iters=(24, 10, 7), encodes=(1,)),      # an odd number of folds
+    # the two estimates that read the `lanes` mask the pooled soft-shadow shader hands them (the fold loop, the
+    # generalised Julia step), and the bunny shaded through soft_shadow
+    "sierpinski_shadow": Scene(KIFS, 4, iters=(24, 10, 7), shadow=True, encodes=(1,)),
     "unknown": Scene(KIFS, UNKNOWN, encodes=(0,)),
     "bunny": Scene(KIFS, BUNNY, max_iterations=61, encodes=(1, 0)),
+    "bunny_shadow": Scene(KIFS, BUNNY, max_iterations=61, shadow=True, encodes=(1,)),
     # the four builds of the Julia long-ray loop: bit 1 = the doubled orbit trip, bit 0 = sdf_iters <= 24
     "julia_v0": Scene(JULIA, max_iterations=131, iters=(25, 6, 10), constant=INELIGIBLE_C, encodes=(0,)),
     "julia_v1": Scene(JULIA, max_iterations=131, iters=(24, 6, 10), constant=INELIGIBLE_C, encodes=(1,)),
@@ -82,6 +86,8 @@ SCENES = {
     "julia_v3": Scene(JULIA, max_iterations=131, iters=(24, 6, 10), constant=ELIGIBLE_C, encodes=(1, 0)),
     "genjulia": Scene(GENJULIA, max_iterations=29, iters=(5, 3, 10), power=3.5, constant=(-0.3, 0.5, 0.3, 0.1),
                       encodes=(1,)),
+    "genjulia_shadow": Scene(GENJULIA, max_iterations=29, iters=(5, 3, 10), power=3.5, constant=(-0.3, 0.5, 0.3, 0.1),
+                             shadow=True, encodes=(0,)),
     # max_iterations exactly 2 x round_steps: the smallest march that is still re-queued
     "sphere_2steps": Scene(KIFS, 0, max_iterations=2, encodes=(1,)),
     "sphere_6steps": Scene(KIFS, 0, max_iterations=6, encodes=(0,)),
@@ -165,8 +171,8 @@ def instantiation(observed, scene):
 
 
 # ---- child configurations ----------------------------------------------------------------------------------------
-NON_BUNNY = ("sphere", "cylinder", "box", "torus_shadow", "sierpinski", "unknown",
-             "julia_v0", "julia_v1", "julia_v2_shadow", "julia_v3", "genjulia")
+NON_BUNNY = ("sphere", "cylinder", "box", "torus_shadow", "sierpinski", "sierpinski_shadow", "unknown",
+             "julia_v0", "julia_v1", "julia_v2_shadow", "julia_v3", "genjulia", "genjulia_shadow")
 
 
 @dataclass(frozen=True)
@@ -186,9 +192,9 @@ CONFIGS = {
     "group2": Config({"KIFS_GROUP_TILES": 2}, NON_BUNNY, _EXTRAS),
     "wave": Config({"KIFS_GROUP_TILES": 0}, NON_BUNNY, _EXTRAS),
     "bunny_t1": Config({"KIFS_BUNNY_COOP": 0, "KIFS_GROUP_TILES": 1, "KIFS_ROUND_STEPS": 8}, ("bunny",), _BUNNY_EXTRAS, 300),
-    "bunny_t2": Config({"KIFS_BUNNY_COOP": 0, "KIFS_GROUP_TILES": 2, "KIFS_ROUND_STEPS": 8}, ("bunny",), _BUNNY_EXTRAS, 300),
+    "bunny_t2": Config({"KIFS_BUNNY_COOP": 0, "KIFS_GROUP_TILES": 2, "KIFS_ROUND_STEPS": 8}, ("bunny", "bunny_shadow"), _BUNNY_EXTRAS, 300),
     "bunny_w2lds": Config({"KIFS_BUNNY_COOP": 2, "KIFS_ROUND_STEPS": 8}, ("bunny",), _BUNNY_EXTRAS, 300),
-    "bunny_coop": Config({"KIFS_BUNNY_COOP": 1, "KIFS_ROUND_STEPS": 4}, ("bunny",), _BUNNY_EXTRAS, 300),
+    "bunny_coop": Config({"KIFS_BUNNY_COOP": 1, "KIFS_ROUND_STEPS": 4}, ("bunny", "bunny_shadow"), _BUNNY_EXTRAS, 300),
 }
 for _rs, _boundary in ((1, "sphere_2steps"), (3, "sphere_6steps")):
     for _form, _tiles in (("group1", 1), ("group2", 2), ("wave", 0)):

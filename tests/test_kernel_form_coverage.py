@@ -5,6 +5,7 @@ checked for consistency with the launch plan the GPU test renders.  CPU only (hi
 import re
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 import kernel_forms as F
@@ -87,3 +88,33 @@ def test_julia_variants_and_encodes():
 def test_child_environment_drops_every_kifs_variable():
     env = F.child_env({"PATH": "/bin", "KIFS_GROUP_TILES": "2", "KIFS_DEBUG": "1", "KIFS_TUNING": "0"}, "group1")
     assert env == {"PATH": "/bin", "KIFS_TUNING": "1", "KIFS_GROUP_TILES": "1"}
+
+
+SHADOW_SCENES = [s for s, v in F.SCENES.items() if v.shadow]
+
+
+@pytest.mark.parametrize("scene", SHADOW_SCENES)
+def test_shadow_scene_has_occluded_and_unoccluded_hits(scene, oracle, kifs):
+    """A `*_shadow` scene cannot pass vacuously: over the table's cameras the oracle's frame with the soft-shadow
+    extension differs from its frame without it in some hit pixel (a secondary ray met the fractal) and equals it in
+    some hit pixel (one did not, or none was cast).  From the oracle alone."""
+    K, O = kifs, oracle
+    assert scene.endswith("_shadow") and len(SHADOW_SCENES) == 5
+    s, ub, ext = F.SCENES[scene], K.uniform_bytes, F.extensions(scene)
+
+    def frame(cam, shadow):
+        return O.render(O.from_bytes(O.Screen, ub(K.ScreenData(*F.FRAME).into_buffer_data())),
+                        O.from_bytes(O.Camera, ub(F.camera(K, scene, cam).into_buffer_data())),
+                        O.from_bytes(O.Options, ub(F.options(K, scene))), O.iters(*s.iters), encode=s.encodes[0],
+                        ext=O.Ext(1, ext["shadow_steps"], ext["shadow_k"], ext["shadow_t0"], ext["shadow_max_t"])
+                        if shadow else None)
+
+    background = frame(len(F.CAMERAS) - 1, False)[0, 0]  # a corner of the far view
+    differ = equal = 0
+    for cam in range(len(F.CAMERAS)):
+        plain, shadowed = frame(cam, False), frame(cam, True)
+        hit = (plain != background).any(-1)
+        changed = (plain != shadowed).any(-1)
+        differ += int(np.count_nonzero(hit & changed))
+        equal += int(np.count_nonzero(hit & ~changed))
+    assert differ > 0 and equal > 0, (scene, differ, equal)
