@@ -239,6 +239,50 @@ int kifs_render_geometry_async(kifs_ctx* ctx, void* hip_stream, int count,
                                float* dev_geometry, size_t geometry_pitch_bytes, size_t geometry_stride_bytes,
                                int y0, int y1, int encode);
 
+/* ---- extension: adaptive anti-aliasing -- supersample only the pixels on an edge -----------------
+ * NOT part of the reference.  kifs_set_supersampling pays k^2 rays for every pixel; nine tenths of a frame of these
+ * scenes are flat background or smooth surface, where a second sample changes nothing.  This call renders the frame
+ * once with its geometry (kifs_render_geometry_async's texels, kept in memory the context owns), marks the pixels whose
+ * geometry differs from a neighbour's and gives only those the k x k resolve.  Whole frames only.
+ *   frames    frame i is rendered with cameras[i] into dev_outs_rgba8[i] (rows pitch_bytes apart, pitch_bytes >= 4 W and
+ *             a multiple of 4); cameras == NULL with count == 1: the context's camera.  1 <= count <= KIFS_MAX_BATCH; a
+ *             large batch may run as several launches over the same scratch memory.  Stream, ordering and
+ *             kifs_order_after as the other async renders.
+ *   texel     g(p) = (n, t): the texel kifs_render_geometry_async defines for pixel p.  hit(p): t's bit pattern is not
+ *             0x7f800000.
+ *   pair      for p and a 4-neighbour q INSIDE the frame, (x +- 1, y) or (x, y +- 1) -- neighbours outside it do not
+ *             exist -- in f32 without fma: d = (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z;
+ *             pair(p, q) = hit(p) != hit(q), or both hit and ( !(d >= normal_cos) or
+ *             fabsf(t_p - t_q) > depth_rel * fminf(t_p, t_q) ).  E(p) = the OR of pair(p, q) over p's neighbours.  The
+ *             rule is symmetric: a background pixel beside a hit is an edge pixel too.
+ *   output    where E(p) is false the pixel holds exactly the bytes kifs_render_batch_async writes; where it is true,
+ *             exactly the bytes a render with kifs_set_supersampling(ctx, factor) writes for it: the same virtual
+ *             k W x k H screen, sample order, division by k^2 and encode; heatmap frames resolve heatmap colours, soft
+ *             shadows apply per sample.  The mask always comes from the primary ray's geometry.  Bytes of a row beyond
+ *             4 W are not touched.
+ *   counts    dev_edge_counts, when not NULL, points to `count` words of device memory: word i receives the number of
+ *             edge pixels of frame i, valid once the stream has reached that point.
+ *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: a null ctx, dev_outs_rgba8 or aa; a factor
+ *             outside 2 .. KIFS_MAX_SUPERSAMPLING; a NaN normal_cos; a NaN or negative depth_rel; the context's own
+ *             supersampling factor above 1; a bad pitch.  KIFS_ERR_BAD_SIZE: k W or k H above 65536.
+ *             KIFS_ERR_RUNTIME is no refusal: a HIP call failed after work was enqueued, and the destinations and the
+ *             counts are undefined.
+ *   streams   the scratch memory belongs to the context: a call on another stream than the context's previous adaptive
+ *             call is ordered after that call by the library (an event behind its last pass), so calls of one context
+ *             may alternate between streams without caller-side ordering; they then run one after the other.
+ *   no bands  bands, row shards and kifs_multi_* have no adaptive form: the mask of a band's first and last row needs
+ *             rows outside the band.
+ *   launch    like a geometry launch the call neither records tile costs nor advances the tile-order sort;
+ *             kifs_debug_last_kernel reports KIFS_KERNEL_ADAPTIVE. */
+typedef struct KifsAdaptiveAA {
+    int32_t factor;    /* k: 2 .. KIFS_MAX_SUPERSAMPLING */
+    float normal_cos;  /* two hits whose normals' dot product is not >= this are an edge */
+    float depth_rel;   /* two hits with |t_p - t_q| > depth_rel * min(t_p, t_q) are an edge; >= 0, +inf allowed */
+} KifsAdaptiveAA;
+int kifs_render_adaptive_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                               uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsAdaptiveAA* aa,
+                               uint32_t* dev_edge_counts /* may be NULL */, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);
@@ -491,7 +535,8 @@ enum KifsKernel {
     KIFS_KERNEL_BUNNY_QUAD = 3,  /* render_bunny_quad_kernel: whole rays, four lanes per pixel */
     KIFS_KERNEL_BUNNY_COOP = 4,  /* render_bunny_coop_kernel: rays re-queued, four waves per 64 rays */
     KIFS_KERNEL_SSAA = 5,        /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
-    KIFS_KERNEL_GEOMETRY = 6     /* geom::render_kernel: colour plus the geometry plane (kifs_render_geometry_async) */
+    KIFS_KERNEL_GEOMETRY = 6,    /* geom::render_kernel: colour plus the geometry plane (kifs_render_geometry_async) */
+    KIFS_KERNEL_ADAPTIVE = 7     /* adaptive::render_kernel: the edge pixels' k x k resolve (kifs_render_adaptive_async) */
 };
 int kifs_debug_last_kernel(kifs_ctx* ctx);
 /* The bunny's throughput form in the context's latest launch: 0 = four lanes per ray with every weight in VGPRs, 1 = four

@@ -41,6 +41,10 @@ class ExtensionsC(C.Structure):  # KifsExtensions
                 ("shadow_t0", C.c_float), ("shadow_max_t", C.c_float)]
 
 
+class AdaptiveAAC(C.Structure):  # KifsAdaptiveAA
+    _fields_ = [("factor", C.c_int32), ("normal_cos", C.c_float), ("depth_rel", C.c_float)]
+
+
 class GuiDataC(C.Structure):  # KifsGuiData
     _fields_ = [("max_iterations", C.c_uint32), ("max_distance", C.c_float),
                 ("epsilon", C.c_float), ("fractal_color", C.c_uint8 * 3),
@@ -93,6 +97,8 @@ SIGNATURES = {
                                           _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_render_geometry_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_render_adaptive_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                             _P(AdaptiveAAC), C.c_void_p, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

@@ -107,6 +107,11 @@ void kifs_destroy(kifs_ctx* c) {
         if (c->h_views[i]) (void)hipHostFree(c->h_views[i]);
     }
     if (c->d_scratch) (void)hipFree(c->d_scratch);
+    if (c->adaptive_done) {
+        (void)hipEventSynchronize(c->adaptive_done);
+        (void)hipEventDestroy(c->adaptive_done);
+    }
+    if (c->d_adaptive) (void)hipFree(c->d_adaptive);
     if (c->d_srgb) (void)hipFree(c->d_srgb);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);

@@ -4,6 +4,7 @@
 //   kifs_schedule.cpp  one launch: parameters, tile tables, tile-order feedback, launch shape (enqueue_batch)
 //   kifs_shards.cpp    row shards and sparse shards (the multi-GPU partition's per-device entry points)
 //   kifs_multi.cpp     one process driving several devices (kifs_multi_*)
+//   kifs_adaptive_kernels.hip  adaptive anti-aliasing: its entry point beside its kernels
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -58,6 +59,10 @@ struct kifs_ctx {
     float* d_srgb = nullptr;       // 256 thresholds
     uint8_t* d_scratch = nullptr;  // frame staging for host destinations
     size_t scratch_bytes = 0;
+    uint8_t* d_adaptive = nullptr;  // kifs_render_adaptive_async: geometry planes, edge queues and edge counters
+    size_t adaptive_bytes = 0;
+    hipEvent_t adaptive_done = nullptr;     // recorded behind the latest adaptive call's last pass
+    hipStream_t adaptive_stream = nullptr;  // and the stream it ran on: a call on another stream waits for the event
     KifsScreenUniform screen{};
     KifsCameraUniform camera{};
     KifsOptionsUniform options{};
@@ -116,6 +121,10 @@ int frame_dims(const kifs_ctx* c, int* w, int* h);
 // frame_dims for a render: with k x k supersampling the virtual k W x k H screen must meet the same limit (BAD_SIZE)
 int render_dims(const kifs_ctx* c, int* w, int* h);
 int fill_params(const kifs_ctx* c, kifs::FrameParams* P);
+// The views of a launch (cameras NULL: the context's camera) into `views`, and what they decide for all of it: P's
+// camera is view 0's, and the culls go when a view does not meet what they assume.
+void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
+                uint8_t* const* outs);
 bool is_device_pointer(const void* p);
 void free_table(TileTable& t);
 // Device image of a stripe list, cached by content.  Stripes must be ascending and inside the frame.

@@ -461,8 +461,8 @@ static int take_view_slot(kifs_ctx* c, int* slot) {
 
 // The views, and what they decide for the whole launch: P's camera is view 0's, and the culls go when a view does not
 // meet what they assume.
-static void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
-                       uint8_t* const* outs) {
+void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
+                uint8_t* const* outs) {
     bool far_origin = false;  // a view whose origin is not within 1e15 of the scene: no culls for this launch
     for (int i = 0; i < count; ++i) {
         const KifsCameraUniform& cam = cameras ? cameras[i] : c->camera;

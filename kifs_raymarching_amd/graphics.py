@@ -22,7 +22,7 @@ from . import _lib
 MAX_BATCH = 512  # KIFS_MAX_BATCH of include/kifs_hip.h
 SPARSE_RECORD_BYTES = 1040  # KIFS_SPARSE_RECORD_BYTES
 STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
-from ._lib import (CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, OptionsUniform,
+from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -409,6 +409,54 @@ class GraphicState:
             torch.cuda.synchronize(colour.device)
         return colour[0], geometry[0]
 
+    # ---- adaptive anti-aliasing (kifs_render_adaptive_async): the k x k resolve for the edge pixels only
+    def render_adaptive_batch(self, cameras=None, k: int = 2, normal_cos: float = 0.9, depth_rel: float = 0.05, stream=None,
+                              encode: int = ENCODE_SRGB, colour=None, edge_counts=None):
+        """len(cameras) <= MAX_BATCH whole frames (cameras None: one frame with the context's camera), each rendered
+        once with its geometry; the pixels whose hit / miss, normal (dot product below `normal_cos`) or depth (relative
+        difference above `depth_rel`) differs from a 4-neighbour's get the k x k supersampled resolve, every other pixel
+        stays the plain frame's.  Returns (colour, edge_counts): a uint8 (count, H, W, 4) and an int32
+        (count,) torch tensor on this context's device -- the number of pixels supersampled per frame.  `colour`, `edge_counts`:
+        contiguous destination tensors of those shapes to reuse.  Enqueued on `stream` like render_async; the caller
+        synchronises before reading.  A tensor this method allocates is written on the launch stream, which torch's
+        allocator does not know of: keep the returned tensors alive until the launch has run (or pass your own), as with
+        render_geometry_batch's planes."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        n = 1 if cameras is None else len(cameras)
+        if not 1 <= n <= MAX_BATCH:
+            raise ValueError(f"render_adaptive_batch: 1..{MAX_BATCH} frames")
+        dev = torch.device("cuda", self.device)
+        if colour is None:
+            colour = torch.empty((n, h, w, 4), dtype=torch.uint8, device=dev)
+        if tuple(colour.shape) != (n, h, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_adaptive_batch: colour uint8 ({n}, {h}, {w}, 4), contiguous")
+        counts = torch.empty((n,), dtype=torch.int32, device=dev) if edge_counts is None else edge_counts
+        if tuple(counts.shape) != (n,) or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError(f"render_adaptive_batch: edge_counts int32 ({n},), contiguous")
+        stream = self._stream_handle(stream, "render_adaptive_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        base, frame_bytes = _device_pointer(colour), h * w * 4
+        ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+        aa = AdaptiveAAC(int(k), float(normal_cos), float(depth_rel))
+        self._order_after_producer(colour, stream)
+        check(lib.kifs_render_adaptive_async(self._ctx, stream, n, cams, ptrs, w * 4, C.byref(aa), _device_pointer(counts),
+                                             encode), "render_adaptive")
+        return colour, counts
+
+    def render_adaptive(self, k: int = 2, normal_cos: float = 0.9, depth_rel: float = 0.05, encode: int = ENCODE_SRGB,
+                        stream=None):
+        """The context's frame with adaptive anti-aliasing, synchronously: (colour uint8 H x W x 4 torch tensor on this
+        context's device, number of pixels supersampled)."""
+        import torch
+        colour, counts = self.render_adaptive_batch(None, k=k, normal_cos=normal_cos, depth_rel=depth_rel, stream=stream,
+                                                    encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0], int(counts[0].item())
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -564,7 +612,7 @@ class GraphicState:
         return int(lib.kifs_debug_last_group_tiles(self._ctx))
 
     KERNEL_NAMES = ("render_kernel", "render_group_kernel", "render_wave_kernel", "render_bunny_quad_kernel",
-                    "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel")
+                    "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel", "render_adaptive_kernel")
 
     def debug_last_kernel(self) -> str:
         """Name of the render kernel the latest launch used ("" before the first)."""

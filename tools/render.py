@@ -3,6 +3,7 @@
 
     python tools/render.py cfg2_julia_1080p out.png
     python tools/render.py cfg2_julia_1080p out.png --aa 3          # 3 x 3 supersampled
+    python tools/render.py cfg2_julia_1080p out.png --aa-adaptive 3 # 3 x 3 supersampling for the edge pixels only
     python tools/render.py cfg2_julia_1080p out.png --geometry out.npz --depth-png depth.png   # + normal and hit distance
     python tools/render.py cfg5_sierpinski_8k_orbit frames/orbit_%03d.png --frames 0 30 60 --scale 0.25
 """
@@ -22,6 +23,14 @@ ap.add_argument("--frames", type=int, nargs="*", default=None, help="orbit frame
 ap.add_argument("--scale", type=float, default=1.0, help="resolution scale")
 ap.add_argument("--heatmap", action="store_true")
 ap.add_argument("--aa", type=int, default=1, metavar="K", help="K x K supersampled anti-aliasing (1..4; 1 = off)")
+ap.add_argument("--aa-adaptive", type=int, default=0, metavar="K",
+                help="adaptive anti-aliasing (kifs_render_adaptive_async): K x K samples (2..4) for the pixels whose geometry "
+                     "differs from a neighbour's, the plain pixel elsewhere; prints the share supersampled; not with --aa, "
+                     "--geometry or --frames")
+ap.add_argument("--aa-normal-cos", type=float, default=0.9, metavar="X",
+                help="with --aa-adaptive: neighbouring hits whose normals' dot product is below X are an edge")
+ap.add_argument("--aa-depth-rel", type=float, default=0.05, metavar="Y",
+                help="with --aa-adaptive: neighbouring hits whose distances differ by more than Y of the nearer one are an edge")
 ap.add_argument("--geometry", metavar="OUT.npz", default=None,
                 help="also write the frame's geometry plane (kifs_render_geometry_async): arrays rgba (H, W, 4) uint8, "
                      "normal (H, W, 3) float32 and t (H, W) float32, +inf where the ray missed; not with --aa or --frames")
@@ -30,6 +39,8 @@ ap.add_argument("--depth-png", metavar="OUT.png", default=None,
 args = ap.parse_args()
 if args.geometry and (args.aa != 1 or args.frames is not None):
     ap.error("--geometry renders one frame without supersampling")
+if args.aa_adaptive and (args.aa != 1 or args.geometry or args.frames is not None):
+    ap.error("--aa-adaptive renders one frame, without --aa or --geometry")
 if args.depth_png and not args.geometry:
     ap.error("--depth-png goes with --geometry")
 w = WORKLOADS[args.workload]
@@ -57,6 +68,12 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                 lo, hi = float(t[hit].min()), float(t[hit].max())
                 grey[hit] = (255.0 - 215.0 * (t[hit] - lo) / max(hi - lo, 1e-30)).astype(np.uint8)
             write_png(args.depth_png, np.dstack([grey, grey, grey, np.full_like(grey, 255)]))
+    elif args.aa_adaptive:
+        colour, edges = gs.render_adaptive(k=args.aa_adaptive, normal_cos=args.aa_normal_cos, depth_rel=args.aa_depth_rel)
+        write_png(args.out, colour.cpu().numpy())
+        pixels = screen.width * screen.height
+        print(f"{args.out}: {screen.width}x{screen.height}, {edges} of {pixels} pixels supersampled "
+              f"{args.aa_adaptive}x{args.aa_adaptive} ({100.0 * edges / pixels:.2f} %)")
     elif args.frames is None:
         write_png(args.out, gs.render())
         print(f"{args.out}: {screen.width}x{screen.height}, kernel {gs.last_kernel_ms():.3f} ms")
