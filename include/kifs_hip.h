@@ -283,6 +283,44 @@ int kifs_render_adaptive_async(kifs_ctx* ctx, void* hip_stream, int count, const
                                uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsAdaptiveAA* aa,
                                uint32_t* dev_edge_counts /* may be NULL */, int encode);
 
+/* ---- extension: animated batches -- per-frame Julia constant, power and colours in one launch -----
+ * NOT part of the reference (it renders the GUI's current options, one frame per draw: graphics.rs:304-325).
+ * kifs_render_batch_async varies the camera only; the sequence made most often with these scenes is a MORPH -- the
+ * constant, the power or the colours change from frame to frame (the sliders of GuiData.constant, .power,
+ * .fractal_color, .background_color).  This call renders such a sequence as one launch, the long rays of all its frames
+ * side by side.
+ *   frames    frame i is rendered into dev_outs_rgba8[i] with cameras[i] (cameras == NULL: the context's camera for every
+ *             frame) and options[i]: `count` option images, one per frame, never NULL.  Screen, iteration counts and
+ *             extensions are the context's.  Rows [y0, y1), pitch_bytes, encode, stream and kifs_order_after as
+ *             kifs_render_batch_async.  1 <= count <= KIFS_MAX_BATCH.
+ *   context   the context's own options are neither read nor changed and need not have been set.  The screen must be
+ *             set; the camera only when cameras == NULL.
+ *   varying   constant, power, fractal_color and background_color may differ from frame to frame.  max_iterations,
+ *             max_distance, epsilon, is_heatmap, fractal_group_id and primitive_id must be bit-identical to options[0]'s
+ *             in every frame (a sequence shares one pipeline and one march budget): otherwise KIFS_ERR_BAD_ARG.  Padding
+ *             words are ignored.
+ *   output    frame i holds exactly the bytes kifs_render_async writes for those rows after kifs_set_camera(cameras[i])
+ *             and kifs_set_options(options[i]), for every pipeline, heatmap frames and soft shadows included.  Bytes of a
+ *             row beyond 4 W are not touched.
+ *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: a null ctx, options or dev_outs_rgba8; a
+ *             null or misaligned destination; count out of range; a bad encode or band; a fractal_group_id above 2; frames
+ *             that differ where they may not; the context's supersampling factor above 1 (out of scope, as for the
+ *             geometry output).  KIFS_ERR_BAD_SIZE: a bad pitch.  KIFS_ERR_UNCONFIGURED: no screen, or no camera with
+ *             cameras == NULL.
+ *   tables    the frames' scenes reach the kernel through a device table: a ring of KIFS_ANIMATION_RING tables per
+ *             context, each rewritten only once the launch that read it is over -- a call that finds its table busy
+ *             (more than KIFS_ANIMATION_RING calls ahead of the device) waits for that launch on the host.
+ *   launch    like a geometry launch the call neither records tile costs nor advances the tile-order sort;
+ *             kifs_debug_last_kernel reports KIFS_KERNEL_ANIMATION, kifs_debug_last_round_steps 0,
+ *             kifs_debug_last_group_tiles and kifs_debug_last_bunny_form -1.
+ *   no shards row shards and kifs_multi_* have no animated form. */
+#define KIFS_ANIMATION_RING 4
+int kifs_render_animation_async(kifs_ctx* ctx, void* hip_stream, int count,
+                                const KifsCameraUniform* cameras,   /* NULL: the context's camera for every frame */
+                                const KifsOptionsUniform* options,  /* count images, one per frame; not NULL */
+                                uint8_t* const* dev_outs_rgba8, size_t pitch_bytes,
+                                int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);
@@ -536,7 +574,8 @@ enum KifsKernel {
     KIFS_KERNEL_BUNNY_COOP = 4,  /* render_bunny_coop_kernel: rays re-queued, four waves per 64 rays */
     KIFS_KERNEL_SSAA = 5,        /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
     KIFS_KERNEL_GEOMETRY = 6,    /* geom::render_kernel: colour plus the geometry plane (kifs_render_geometry_async) */
-    KIFS_KERNEL_ADAPTIVE = 7     /* adaptive::render_kernel: the edge pixels' k x k resolve (kifs_render_adaptive_async) */
+    KIFS_KERNEL_ADAPTIVE = 7,    /* adaptive::render_kernel: the edge pixels' k x k resolve (kifs_render_adaptive_async) */
+    KIFS_KERNEL_ANIMATION = 8    /* anim::render_kernel: a scene per view (kifs_render_animation_async) */
 };
 int kifs_debug_last_kernel(kifs_ctx* ctx);
 /* The bunny's throughput form in the context's latest launch: 0 = four lanes per ray with every weight in VGPRs, 1 = four

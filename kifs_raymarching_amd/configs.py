@@ -6,7 +6,9 @@ sRGB 200 via the reference's /256 conversion, black background, sRGB colour targ
 `iters` = (sdf_iters, normal_iters, fold_iters); the reference constants are (100, 10, 10).
 """
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
+
+import numpy as np
 
 from .graphics import CameraData, FractalGroup, GuiData, PrimitiveShape, ScreenData
 
@@ -84,3 +86,34 @@ def orbit_camera(workload: Workload, frame: int) -> CameraData:
     frames = max(workload.frames, 120)
     return CameraData(origin_distance=base.origin_distance, min_distance=base.min_distance,
                       phi=2.0 * math.pi * frame / frames, theta=base.theta)
+
+
+# what the frames of one animated launch must share (kifs_render_animation_async: one pipeline, one march budget)
+MORPH_FIXED = ("max_iterations", "max_distance", "epsilon", "is_heatmap", "fractal_group", "primitive_shape")
+
+
+def morph_options(gui_a: GuiData, gui_b: GuiData, n: int) -> list:
+    """The `n` option sets of a morph from `gui_a` to `gui_b` for GraphicState.render_animation: frame i has
+    constant and power a + (b - a) * t_i, t_i = i / (n - 1), every operation in f32 (the difference, t_i, the product,
+    the sum); frame 0 is a's values exactly and frame n - 1 b's.  The colours are a's.  ValueError when a field the
+    frames of one launch must share differs between the two."""
+    if n < 1:
+        raise ValueError("morph_options: at least one frame")
+    for name in MORPH_FIXED:
+        if getattr(gui_a, name) != getattr(gui_b, name):
+            raise ValueError(f"morph_options: {name} may not vary within a sequence "
+                             f"({getattr(gui_a, name)!r} against {getattr(gui_b, name)!r})")
+    f32 = np.float32
+    a = np.array(tuple(gui_a.constant) + (gui_a.power,), dtype=f32)
+    b = np.array(tuple(gui_b.constant) + (gui_b.power,), dtype=f32)
+    frames = []
+    for i in range(n):
+        if i == 0:
+            v = a
+        elif i == n - 1:
+            v = b
+        else:
+            t = f32(i) / f32(n - 1)
+            v = a + (b - a) * t
+        frames.append(replace(gui_a, constant=tuple(float(x) for x in v[:4]), power=float(v[4])))
+    return frames

@@ -106,6 +106,14 @@ void kifs_destroy(kifs_ctx* c) {
         if (c->d_views[i]) (void)hipFree(c->d_views[i]);
         if (c->h_views[i]) (void)hipHostFree(c->h_views[i]);
     }
+    for (int i = 0; i < kifs_ctx::SCENE_RING; ++i) {
+        if (c->scenes_used[i]) {
+            (void)hipEventSynchronize(c->scenes_used[i]);
+            (void)hipEventDestroy(c->scenes_used[i]);
+        }
+        if (c->d_scenes[i]) (void)hipFree(c->d_scenes[i]);
+        if (c->h_scenes[i]) (void)hipHostFree(c->h_scenes[i]);
+    }
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->adaptive_done) {
         (void)hipEventSynchronize(c->adaptive_done);

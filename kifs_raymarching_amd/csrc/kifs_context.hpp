@@ -5,6 +5,7 @@
 //   kifs_shards.cpp    row shards and sparse shards (the multi-GPU partition's per-device entry points)
 //   kifs_multi.cpp     one process driving several devices (kifs_multi_*)
 //   kifs_adaptive_kernels.hip  adaptive anti-aliasing: its entry point beside its kernels
+//   kifs_animation_kernels.hip  animated batches: its entry point beside its kernel
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -94,6 +95,15 @@ struct kifs_ctx {
     hipEvent_t views_used[VIEW_RING] = {};
     bool views_busy[VIEW_RING] = {};
     int view_slot = 0;
+    // Scene tables of kifs_render_animation_async (anim::SceneView records, kifs_animation_kernels.hip): the same kind of
+    // ring -- device table, pinned host image, event behind the launch that read it -- one slot per call.
+    static constexpr int SCENE_RING = 4;
+    static constexpr size_t SCENE_SLOT_BYTES = size_t(64) * size_t(kifs::MAX_BATCH);
+    void* d_scenes[SCENE_RING] = {};
+    void* h_scenes[SCENE_RING] = {};
+    hipEvent_t scenes_used[SCENE_RING] = {};
+    bool scenes_busy[SCENE_RING] = {};
+    int scene_slot = 0;
 };
 
 namespace kifs {
@@ -125,6 +135,8 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P);
 // camera is view 0's, and the culls go when a view does not meet what they assume.
 void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
                 uint8_t* const* outs);
+// The next slot of the view-table ring (batches beyond MAX_BATCH_INLINE), free to be rewritten when the call returns.
+int take_view_slot(kifs_ctx* c, int* slot);
 bool is_device_pointer(const void* p);
 void free_table(TileTable& t);
 // Device image of a stripe list, cached by content.  Stripes must be ascending and inside the frame.

@@ -443,7 +443,7 @@ static int check_arguments(const kifs_ctx* c, int count, const KifsCameraUniform
 }
 
 // A batch beyond the kernel argument's room: the views go through a device table, the next slot of the ring.
-static int take_view_slot(kifs_ctx* c, int* slot) {
+int take_view_slot(kifs_ctx* c, int* slot) {
     const int vs = *slot = c->view_slot;
     c->view_slot = (vs + 1) % kifs_ctx::VIEW_RING;
     if (!c->d_views[vs]) {

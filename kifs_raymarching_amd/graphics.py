@@ -22,6 +22,7 @@ from . import _lib
 MAX_BATCH = 512  # KIFS_MAX_BATCH of include/kifs_hip.h
 SPARSE_RECORD_BYTES = 1040  # KIFS_SPARSE_RECORD_BYTES
 STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
+ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, OptionsUniform,
                    ScreenUniform, check, lib)
 
@@ -156,6 +157,15 @@ def camera_array(cameras):
         return cameras
     return (CameraUniform * len(cameras))(*[c.into_buffer_data() if hasattr(c, "into_buffer_data") else c
                                             for c in cameras])
+
+
+def options_array(options):
+    """A C array of OptionsUniform images from GuiData objects / uniform images (render_animation takes it in place of
+    the list)."""
+    if isinstance(options, C.Array):
+        return options
+    return (OptionsUniform * len(options))(*[o.into_buffer_data() if hasattr(o, "into_buffer_data") else o
+                                             for o in options])
 
 
 def _device_pointer(obj):
@@ -457,6 +467,40 @@ class GraphicState:
             torch.cuda.synchronize(colour.device)
         return colour[0], int(counts[0].item())
 
+    # ---- animated batches (kifs_render_animation_async): per-frame constant, power and colours in one launch
+    def render_animation(self, options, cameras=None, outs=None, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB,
+                         stream=None):
+        """One launch for len(options) <= MAX_BATCH frames of a morph: frame i is rendered with options[i] (GuiData or
+        an OptionsUniform image; an options_array is taken as it is) and cameras[i] (cameras None: the context's camera
+        for every frame).  constant, power, fractal_color and background_color may differ between the frames;
+        everything else of the options must be frame 0's (KifsError BAD_ARG otherwise).  The context's own options are
+        neither used nor changed.  Returns the frames as one uint8 (count, rows, W, 4) torch tensor on this context's
+        device; `outs`: a contiguous destination tensor of that shape to reuse.  Enqueued on `stream` like render_async
+        and ordered after torch's current stream; the caller synchronises before reading, and keeps a tensor this
+        method allocated alive until the launch has run (as with render_geometry_batch's planes)."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        opts = options_array(options)
+        n = len(opts)
+        if not 1 <= n <= MAX_BATCH:
+            raise ValueError(f"render_animation: 1..{MAX_BATCH} frames")
+        if cameras is not None and len(cameras) != n:
+            raise ValueError(f"render_animation: {n} option images for {len(cameras)} cameras")
+        if outs is None:
+            outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
+            raise ValueError(f"render_animation: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+        stream = self._stream_handle(stream, "render_animation")
+        cams = None if cameras is None else camera_array(cameras)
+        base, frame_bytes = _device_pointer(outs), rows * w * 4
+        ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+        self._order_after_producer(outs, stream)
+        check(lib.kifs_render_animation_async(self._ctx, stream, n, cams, opts, ptrs, w * 4, y0, y1, encode),
+              "render_animation")
+        return outs
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -612,7 +656,8 @@ class GraphicState:
         return int(lib.kifs_debug_last_group_tiles(self._ctx))
 
     KERNEL_NAMES = ("render_kernel", "render_group_kernel", "render_wave_kernel", "render_bunny_quad_kernel",
-                    "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel", "render_adaptive_kernel")
+                    "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel", "render_adaptive_kernel",
+                    "render_animation_kernel")
 
     def debug_last_kernel(self) -> str:
         """Name of the render kernel the latest launch used ("" before the first)."""

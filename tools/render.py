@@ -6,6 +6,7 @@
     python tools/render.py cfg2_julia_1080p out.png --aa-adaptive 3 # 3 x 3 supersampling for the edge pixels only
     python tools/render.py cfg2_julia_1080p out.png --geometry out.npz --depth-png depth.png   # + normal and hit distance
     python tools/render.py cfg5_sierpinski_8k_orbit frames/orbit_%03d.png --frames 0 30 60 --scale 0.25
+    python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48   # out_000.png .. out_047.png
 """
 import argparse
 import sys
@@ -13,13 +14,17 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
-from kifs_raymarching_amd.configs import WORKLOADS, orbit_camera  # noqa: E402
+from kifs_raymarching_amd.configs import WORKLOADS, morph_options, orbit_camera  # noqa: E402
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("workload", choices=sorted(WORKLOADS))
 ap.add_argument("out")
-ap.add_argument("--frames", type=int, nargs="*", default=None, help="orbit frame indices (out needs %%d)")
+ap.add_argument("--frames", type=int, nargs="*", default=None,
+                help="orbit frame indices (out needs %%d); with --morph-to: one number, the frames of the morph")
+ap.add_argument("--morph-to", metavar="R,I,J,K", default=None,
+                help="a morph of the constant from the workload's to this quaternion, --frames N frames in launches of up to "
+                     "512 (kifs_render_animation_async), written to OUT_000.png ..; not with --aa, --aa-adaptive or --geometry")
 ap.add_argument("--scale", type=float, default=1.0, help="resolution scale")
 ap.add_argument("--heatmap", action="store_true")
 ap.add_argument("--aa", type=int, default=1, metavar="K", help="K x K supersampled anti-aliasing (1..4; 1 = off)")
@@ -43,6 +48,18 @@ if args.aa_adaptive and (args.aa != 1 or args.geometry or args.frames is not Non
     ap.error("--aa-adaptive renders one frame, without --aa or --geometry")
 if args.depth_png and not args.geometry:
     ap.error("--depth-png goes with --geometry")
+morph_to = None
+if args.morph_to is not None:
+    try:
+        morph_to = tuple(float(x) for x in args.morph_to.split(","))
+    except ValueError:
+        morph_to = ()
+    if len(morph_to) != 4:
+        ap.error("--morph-to takes four numbers R,I,J,K")
+    if args.aa != 1 or args.aa_adaptive or args.geometry:
+        ap.error("--morph-to renders plain frames, without --aa, --aa-adaptive or --geometry")
+    if args.frames is None or len(args.frames) != 1 or args.frames[0] < 1:
+        ap.error("--morph-to needs --frames N, the number of frames (at least 1)")
 w = WORKLOADS[args.workload]
 screen = K.ScreenData(max(1, int(w.screen.width * args.scale)), max(1, int(w.screen.height * args.scale)))
 gui = w.gui
@@ -74,6 +91,17 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
         pixels = screen.width * screen.height
         print(f"{args.out}: {screen.width}x{screen.height}, {edges} of {pixels} pixels supersampled "
               f"{args.aa_adaptive}x{args.aa_adaptive} ({100.0 * edges / pixels:.2f} %)")
+    elif morph_to is not None:
+        n = args.frames[0]
+        guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n)
+        out = Path(args.out)
+        for first in range(0, n, K.MAX_BATCH):
+            frames = gs.render_animation(guis[first:first + K.MAX_BATCH])
+            gs.synchronize()
+            for i, frame in enumerate(frames.cpu().numpy(), start=first):
+                write_png(str(out.with_name(f"{out.stem}_{i:03d}{out.suffix}")), frame)
+        print(f"{out.with_name(out.stem + '_000' + out.suffix)} .. : {n} frames of {screen.width}x{screen.height}, constant "
+              f"{tuple(gui.constant)} -> {morph_to}")
     elif args.frames is None:
         write_png(args.out, gs.render())
         print(f"{args.out}: {screen.width}x{screen.height}, kernel {gs.last_kernel_ms():.3f} ms")
