@@ -515,7 +515,11 @@ double kifs_last_kernel_ms(kifs_ctx* ctx);
  * render kernel (after any stream waits), kept in a ring of the latest 4096 launches;
  * enable = n > 1 times only every n-th launch (an event pair costs a few microseconds).
  * kifs_profile_read synchronises, reports how many launches were timed and their mean,
- * minimum and maximum kernel duration in ms, and clears the ring. */
+ * minimum and maximum kernel duration in ms, and clears the ring.  Timed are the launches of
+ * kifs_render, kifs_render_async, kifs_render_batch_async, kifs_render_shard_async and
+ * kifs_render_geometry_async, and of kifs_render_adaptive_async its first pass only (the plain frame
+ * with its geometry; neither the classification nor the resolve of the edge pixels); a launch of
+ * kifs_render_animation_async is not timed and does not count towards every n-th. */
 int kifs_set_profiling(kifs_ctx* ctx, int enable);
 int kifs_profile_read(kifs_ctx* ctx, int* launches, double* mean_ms, double* min_ms, double* max_ms);
 

@@ -1,17 +1,26 @@
 """Seeded walks over the state of one long-lived context (tests/test_gpu_context_lifecycle.py::test_seeded_walk).
 
-plan(seed) is a pure function of the seed: a list of 60 operations, each a tuple (kind, argument).  The GPU test replays
+plan(seed) is a pure function of the seed: a list of 72 operations, each a tuple (kind, argument).  The GPU test replays
 it on one GraphicState and checks every render; tests/test_context_walk_plan.py (CPU) replays it on the model below --
 the context's eight tile-table slots, least recently used replaced (kifs_schedule.cpp, tile_table) -- and asserts what a
 walk must cover.  Nothing here touches the library.
+
+Besides the plain launches (bands, batches, shards, geometry) a walk holds the two entry points with state of their own
+between launches: "adaptive" (kifs_render_adaptive_async: the scratch block and its event / stream pair) and
+"animation3" / "animation66" (kifs_render_animation_async: the scene-table ring, the view-table ring it shares with
+"batch66", its own stream rule on the tile table).  Frame j of an animated launch uses camera batch_cameras(camera, n)[j]
+and the option image morph_of(that camera) of the context's options, so that a launch's frames differ in scene as well
+as in view and still need no more than four references per context state.
 """
 import random
 
 SIZES = ((1024, 512), (330, 149), (64, 40), (1056, 516), (200, 135))  # 2048 tiles (feedback), ragged, tiny, 33 x 65, small
 N_CAMERAS, N_OPTIONS, N_ITERS, N_BANDS, N_STREAMS = 4, 3, 2, 12, 3
+N_MORPHS = 3  # option images per option set: 0 the set itself, 1 and 2 with other constant, power and colours
 TABLE_SLOTS = 8  # MAX_TILE_TABLES of kifs_context.hpp
-STEPS = 60
-SEEDS = (4, 16, 39)
+VIEW_RING = 4    # kifs_ctx::VIEW_RING: the view tables of launches beyond 64 views
+STEPS = 72
+SEEDS = (16, 2039, 2360)
 
 # kind -> (weight, arguments to draw from); the renders outweigh the state changes so that the set of distinct
 # (scene, camera, size) references stays small
@@ -29,13 +38,30 @@ OPS = {
     "shard": (3, (0, 1, 2)),      # the rank of three whose stripes are rendered
     "geometry": (3, (0,)),
     "stream": (2, range(N_STREAMS)),  # 0: the context's stream, 1 / 2: caller streams
+    "adaptive": (3, (2, 3)),          # k; the thresholds are adaptive_reference.DEFAULT
+    "animation3": (3, (-1, 2, 7)),    # -1: the whole frame, else the band band_rows(h, argument)
+    "animation66": (2, (0,)),         # the whole frame, 66 frames: beyond MAX_BATCH_INLINE
 }
-RENDERS = ("band", "batch3", "batch66", "shard", "geometry")
+RENDERS = ("band", "batch3", "batch66", "shard", "geometry", "adaptive", "animation3", "animation66")
+ONE_SAMPLE_ONLY = ("geometry", "adaptive", "animation3", "animation66")  # refused by the API while supersampling > 1
+STATEFUL = ("adaptive", "animation3", "animation66")                     # entry points with state of their own
+ANIMATED = {"animation3": 3, "animation66": 66}                          # kind -> frames
+VIEW_RING_USERS = ("batch66", "animation66")
+
+
+def morph_of(camera_index):
+    """The option image an animated launch gives the frame of this camera."""
+    return camera_index % N_MORPHS
 
 
 def band_rows(height, i):
     """Band i of 12: a quarter of the frame starting at sixteenths, neither end on a tile row for most heights."""
     return (i * height) // 16, ((i + 4) * height) // 16 + (1 if i % 2 else 0)
+
+
+def animation_rows(height, arg):
+    """The rows of an "animation3" launch: the whole frame for -1, else band `arg`."""
+    return (0, height) if arg < 0 else band_rows(height, arg)
 
 
 def shard_stripes(height, rank):
@@ -51,8 +77,8 @@ def plan(seed):
     while len(ops) < STEPS:
         kind = rng.choices(kinds, weights)[0]
         arg = rng.choice(list(OPS[kind][1]))
-        if kind == "geometry" and supersampling > 1:
-            continue  # refused by the API: a resolved pixel has no single hit
+        if kind in ONE_SAMPLE_ONLY and supersampling > 1:
+            continue  # refused by the API: a resolved pixel has no single hit, and the newer calls take one sample
         if kind == "supersampling":
             supersampling = arg
         ops.append((kind, arg))
@@ -77,7 +103,9 @@ def batch_cameras(camera, n):
 
 def replay(ops):
     """The tile-table geometries a plan visits: yields (op index, key, event) for every render, event one of "hit",
-    "fill" (an empty slot), "evict" and "return" (a miss on a geometry this walk has evicted before: also an eviction)."""
+    "fill" (an empty slot), "evict" and "return" (a miss on a geometry this walk has evicted before: also an eviction).
+    An animated band takes the table of the plain band of its rows; an adaptive call's first pass and a whole-frame
+    animated launch take the full frame's."""
     size = SIZES[0]
     slots, clock, evicted = {}, 0, set()
     for i, (kind, arg) in enumerate(ops):
@@ -86,7 +114,7 @@ def replay(ops):
         if kind not in RENDERS:
             continue
         w, h = size
-        if kind == "band":
+        if kind == "band" or (kind == "animation3" and arg >= 0):
             key = (w, h) + band_rows(h, arg) + (None,)
         elif kind == "shard":
             key = (w, h, 0, h, shard_stripes(h, arg))
@@ -107,6 +135,15 @@ def replay(ops):
 
 
 def coverage(ops):
+    """What a plan exercises: launches per kind, evictions and returns of the table model, per entry point with state of
+    its own the launches made while the walk's stream is a caller's (1 or 2), and whether a slot of the view-table ring
+    passes from one entry point to the other: some user of the ring and the user VIEW_RING later, which takes the same
+    slot, are a "batch66" and an "animation66" in either order (so that window of VIEW_RING + 1 users holds both)."""
     events = [e for _, _, e in replay(ops)]
     kinds = {k: sum(1 for kind, _ in ops if kind == k) for k in OPS}
-    return {"kinds": kinds, "evictions": events.count("evict") + events.count("return"), "returns": events.count("return")}
+    renders = list(trace(ops))
+    on_caller_stream = {k: sum(1 for _, kind, _, st in renders if kind == k and st["stream"] in (1, 2)) for k in STATEFUL}
+    users = [kind for _, kind, _, _ in renders if kind in VIEW_RING_USERS]
+    shared = any(users[i] != users[i + VIEW_RING] for i in range(len(users) - VIEW_RING))
+    return {"kinds": kinds, "evictions": events.count("evict") + events.count("return"), "returns": events.count("return"),
+            "on_caller_stream": on_caller_stream, "view_ring_shared": shared}

@@ -1,22 +1,53 @@
-"""One long-lived context against the oracle across state changes: what kifs_schedule.cpp keeps BETWEEN launches.
+"""One long-lived context against the oracle across state changes: what the library keeps BETWEEN launches.
 
 A kifs_ctx caches eight tile tables (least recently used replaced, the device drained first), runs a per-table state
 machine for the tile-order feedback (launches % period, a side-stream sort, a double-buffered order), and owns the
-diagnostics buffer and the profiling ring.  Every test here opens its own GraphicState, so that it knows the context's
-whole history, enqueues a sequence of launches without synchronising in between (each launch has a sentinel-filled
-destination of its own), and only then compares every band byte for byte with the oracle.  Supersampled and geometry
-launches are compared with the same call on a fresh context: test_gpu_ssaa.py and test_gpu_geometry.py hold those
-kernels to the oracle.
+diagnostics buffer and the profiling ring (kifs_schedule.cpp).  The two newer entry points add state of their own:
+kifs_render_adaptive_async a scratch block that grows, whose planes, queues and counters sit at offsets that follow the
+call's count and the screen, and an event / stream pair that orders calls across streams; its first pass is a geometry
+launch through enqueue_batch.  kifs_render_animation_async a ring of four scene tables, a share in the ring of four view
+tables of every launch beyond 64 views, the context's options replaced by frame 0's for the length of a call, and a
+stream rule of its own that writes the tile table's last_stream, which belongs to the feedback.
 
-Oracle frames are whole frames, cached per (options, iters, extensions, camera, size) for the module and never written
-to; a band's reference is a slice of its frame (a pixel depends on its frame coordinates only).
+Every test here opens its own GraphicState, so that it knows the context's whole history, enqueues a sequence of
+launches without synchronising in between (each launch has a sentinel-filled destination of its own), and only then
+compares every band byte for byte with the oracle.  Every frame of an animated launch is compared with the oracle too:
+frame j has camera batch_cameras(camera, n)[j] and the option image context_walk.morph_of(that camera) of the context's
+option set (_morph), on the context's or a caller's stream.  Supersampled, geometry and adaptive launches are compared
+with the same call on a fresh context (test_gpu_ssaa.py, test_gpu_geometry.py and test_gpu_adaptive.py hold those
+kernels to the oracle); an adaptive call is anchored to the oracle besides, without the code under test: with n the edge
+count it reports, 0 < pixels that differ from the oracle's plain frame <= n < W * H, and on screens up to 330 x 149
+without extensions its bytes and its count are those of adaptive_reference.expected_frame, the model built from the
+unmodified oracle.  (0 < holds for the oracle alone only if some edge pixel's resolve differs from its one-sample bytes:
+checked on the CPU with the model for the three option sets, the four cameras and both iteration counts at 64 x 40,
+200 x 135 and 330 x 149, k = 2 and 3 -- between 68 and 2324 pixels differ, the sphere heatmap's 68 to 320 included, so
+no scene needs 0 <=.)
+
+What is covered since the adaptive and animated launches joined: both in the seeded walks, on caller streams, between
+feedback launches, evictions, resizes and batches beyond 64 views (tests/context_walk.py); both at every phase of the lone
+period on the smallest frame with feedback, an animated launch also on a caller's stream between lone launches on the
+context's (test_transition_at_every_phase); the view-table ring passed between batches and animated launches
+(test_view_ring_shared_between_entry_points); the scratch block across sizes, counts and streams
+(test_adaptive_scratch_across_sizes_and_counts); and both with the diagnostics buffer and the profiling ring switched on
+(test_diagnostics_buffer).
+
+Oracle frames are whole frames, cached per (size, camera, options, iters, extensions, option image) for the module and
+never written to; a band's reference is a slice of its frame (a pixel depends on its frame coordinates only).  CPU cost
+of the references in seconds of wall time, the oracle on its default threads, over four runs of which some shared the
+host with other work: the module's oracle frames were 56 (10.3 Mpixel, 0.7 to 2.2 s) before the newer launches joined and
+are 88 (20.9 Mpixel) with them; the 57 of them that the older tests did not need (15.0 Mpixel) take 1.2 to 3.3 s, and the
+14 adaptive-model frames (0.32 Mpixel; the three of 330 x 149 about 0.4 s each) 2.0 to 6.3 s, nearly all of it the
+per-sample calls into the oracle.  That is 3 to 10 s of new references for the module, of which the 330 x 149 models are
+1.2 s: they do not dominate, and the model's ceiling stays at 330 x 149.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import adaptive_reference as AR
 import context_walk as W
+from geometry_cases import Raw
 from helpers import oracle_uniforms
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +55,9 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 0xEE
 FULL = (1024, 512)   # 32 x 64 = 2048 tiles: the >= edge of FEEDBACK_MIN_TILES
 ITERS = ((12, 10, 10), (10, 6, 8))
+MODEL_UP_TO = (330, 149)  # the largest screen an adaptive call is also held to adaptive_reference.expected_frame on
+EDGE_SENTINEL = 0x5A5A5A5A
+HOLD_PASSES = 384  # _hold_back: 9.4 ms of GPU time per 128 passes as measured on the MI355X, 0.7 ms of host time to enqueue them
 SHADOWS = dict(soft_shadow=True, shadow_steps=16, shadow_k=8.0, shadow_t0=0.02, shadow_max_t=10.0)
 
 
@@ -38,22 +72,60 @@ def _options(K):
             K.GuiData(primitive_shape=PS.Sphere, is_heatmap=True, max_iterations=64)]
 
 
+def _morph(K, gui, m):
+    """Option image m of W.N_MORPHS of an option set: 0 the set's own image; 1 and 2 with fixed offsets on constant,
+    power and both colours -- what the frames of an animated launch may differ in -- and junk in the padding words, which
+    the contract ignores.  Everything else stays bit-identical."""
+    from kifs_raymarching_amd._lib import OptionsUniform
+    u = OptionsUniform.from_buffer_copy(K.uniform_bytes(gui.into_buffer_data()))
+    if m:
+        for ch, step in enumerate((0.07, -0.05, 0.03, -0.04)):
+            u.constant[ch] += np.float32(step * m)
+        u.power = np.float32(u.power + 0.75 * m)
+        for ch in range(3):
+            u.fractal_color[ch] -= np.float32(0.09 * m * (ch + 1))
+            u.background_color[ch] += np.float32(0.04 * m * (ch + 1))
+        u._padding1, u._padding2, u._padding3 = 0xdead0000 + m, 17 * m, 0xffffffff - m
+    return u
+
+
+def _modelled(size, ext):
+    return size[0] <= MODEL_UP_TO[0] and size[1] <= MODEL_UP_TO[1] and not ext
+
+
 class Refs:
-    """The module's oracle frames, on the device, read-only."""
+    """The module's oracle frames and adaptive-model frames, on the device, read-only."""
 
     def __init__(self, K, O):
         self.K, self.O, self.cams, self.opts, self.frames = K, O, _cameras(K), _options(K), {}
+        self.morphs = [[_morph(K, g, m) for m in range(W.N_MORPHS)] for g in self.opts]
+        self.geoms, self.means, self.models = {}, {}, {}
 
-    def frame(self, size, cam, options=0, iters=0, ext=0):
+    def frame(self, size, cam, options=0, iters=0, ext=0, morph=0):
         import torch
-        key = (size, cam, options, iters, ext)
+        key = (size, cam, options, iters, ext, morph)
         if key not in self.frames:
             K, O = self.K, self.O
-            s, c, o = oracle_uniforms(O, K, (K.ScreenData(*size), self.cams[cam], self.opts[options]))
+            gui = Raw(self.morphs[options][morph]) if morph else self.opts[options]
+            s, c, o = oracle_uniforms(O, K, (K.ScreenData(*size), self.cams[cam], gui))
             e = O.Ext(1, SHADOWS["shadow_steps"], SHADOWS["shadow_k"], SHADOWS["shadow_t0"], SHADOWS["shadow_max_t"]) if ext else None
             kw = dict(ext=e) if ext else {}
             self.frames[key] = torch.from_numpy(O.render(s, c, o, O.iters(*ITERS[iters]), **kw)).to("cuda:0")
         return self.frames[key]
+
+    def adaptive(self, size, cam, options, iters, k):
+        """(frame, edge count) of adaptive_reference.expected_frame at the default thresholds, extensions off."""
+        import torch
+        key = (size, cam, options, iters, k)
+        if key not in self.models:
+            K, O = self.K, self.O
+            scene = (K.ScreenData(*size), self.cams[cam], self.opts[options], ITERS[iters])
+            if key[:4] not in self.geoms:
+                self.geoms[key[:4]] = AR.geometry(O, K, *scene)
+            frame, mask = AR.expected_frame(O, K, *scene, k, *AR.DEFAULT, geom=self.geoms[key[:4]],
+                                            means=self.means.setdefault(key[:4], {}))
+            self.models[key] = (torch.from_numpy(frame).to("cuda:0"), int(mask.sum()))
+        return self.models[key]
 
 
 @pytest.fixture(scope="module")
@@ -73,7 +145,7 @@ class Ctx:
         self.gs.update_options(refs.opts[options])
         self.gs.set_iters(*ITERS[iters])
         self.gs.set_camera(refs.cams[0])
-        self.pending, self.log, self.kernels = [], [], []
+        self.pending, self.log, self.kernels, self.checks = [], [], [], []
 
     def close(self):
         self.gs.close()
@@ -93,9 +165,9 @@ class Ctx:
         self.state["options"] = i
         self.log.append(("options", i))
 
-    def want(self, cam, y0, y1):
+    def want(self, cam, y0, y1, morph=0):
         st = self.state
-        return self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"])[y0:y1]
+        return self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"], morph)[y0:y1]
 
     def dest(self, rows, n=None):
         w = self.state["size"][0]
@@ -124,6 +196,58 @@ class Ctx:
         for i, c in enumerate(cams):
             self.pending.append((outs[i], self.want(c, y0, y1), len(self.log)))
 
+    def animation(self, n, y0=0, y1=None, stream=None, shift=0, what=None):
+        """An animated launch of n frames: frame j has camera batch_cameras(camera, n)[j] and the option image
+        (morph_of(that camera) + shift) % N_MORPHS of the context's options.  Every frame against the oracle."""
+        y1 = self.state["size"][1] if y1 is None else y1
+        cams = W.batch_cameras(self.state["camera"], n)
+        morphs = [(W.morph_of(cam) + shift) % W.N_MORPHS for cam in cams]
+        images = self.refs.morphs[self.state["options"]]
+        outs = self.dest(y1 - y0, n)
+        self.gs.render_animation([images[m] for m in morphs], cameras=[self.refs.cams[cam] for cam in cams], outs=outs, y0=y0, y1=y1,
+                                 stream=stream)
+        self.log.append(what or ("animation", n, y0, y1, shift, "caller stream" if stream is not None else "context stream"))
+        for j, (cam, m) in enumerate(zip(cams, morphs)):
+            self.pending.append((outs[j], self.want(cam, y0, y1, m), len(self.log)))
+        return outs
+
+    def adaptive(self, k, count=None, stream=None, fresh=None, what=None):
+        """An adaptive call at the default thresholds: the context's camera (count None) or the cameras
+        batch_cameras(camera, count).  Frame and edge count against the same call on `fresh` (a context configured
+        alike, without history) when there is one, and against adaptive_reference's model when the screen is at most
+        MODEL_UP_TO and the extensions are off.  Anchored to the oracle's plain frame whatever the size: with n the edge
+        count read back, 0 < pixels that differ from it <= n < W * H."""
+        torch, st = self.torch, self.state
+        (w, h), cam0 = st["size"], st["camera"]
+        cams = [cam0] if count is None else W.batch_cameras(cam0, count)
+        uniforms = None if count is None else [self.refs.cams[cam] for cam in cams]
+        colour = self.dest(h, len(cams))
+        counts = torch.full((len(cams),), EDGE_SENTINEL, dtype=torch.int32, device="cuda:0")
+        self.gs.render_adaptive_batch(uniforms, k=k, normal_cos=AR.DEFAULT[0], depth_rel=AR.DEFAULT[1], stream=stream, colour=colour,
+                                      edge_counts=counts)
+        self.log.append(what or ("adaptive", k, count, (w, h), "caller stream" if stream is not None else "context stream"))
+        upto = len(self.log)
+        if fresh is not None:
+            want_c = self.dest(h, len(cams))
+            want_n = torch.full((len(cams),), EDGE_SENTINEL, dtype=torch.int32, device="cuda:0")
+            fresh.render_adaptive_batch(uniforms, k=k, normal_cos=AR.DEFAULT[0], depth_rel=AR.DEFAULT[1], colour=want_c, edge_counts=want_n)
+            self.pending.append((colour, want_c, upto))
+            self.pending.append((counts.view(1, -1, 1), want_n.view(1, -1, 1), upto))
+        modelled = _modelled((w, h), st["ext"])
+        for j, cam in enumerate(cams):
+            plain = self.want(cam, 0, h)
+            if modelled:
+                frame, edges = self.refs.adaptive((w, h), cam, st["options"], st["iters"], k)
+                self.pending.append((colour[j], frame, upto))
+                self.pending.append((counts[j].view(1, 1, 1), torch.tensor([[[edges]]], dtype=torch.int32, device="cuda:0"), upto))
+
+            def anchored(j=j, plain=plain):
+                n, differ = int(counts[j]), int((colour[j] != plain).any(-1).sum())
+                assert 0 < differ <= n < w * h, \
+                    f"{differ} pixels off the oracle's plain frame, {n} edge pixels of {w * h}, after {self.log[:upto]}"
+            self.checks.append(anchored)
+        return colour, counts
+
     def expect(self, out, want, what):
         self.log.append(what)
         self.pending.append((out, want, len(self.log)))
@@ -136,7 +260,9 @@ class Ctx:
             if not self.torch.equal(out, want):
                 bad = int((out != want).any(-1).sum())
                 raise AssertionError(f"{bad} pixels differ after {self.log[:upto]}")
-        self.pending = []
+        for check in self.checks:  # (what needs a value read back: the adaptive calls' anchors)
+            check()
+        self.pending, self.checks = [], []
 
     def other_band(self, n):
         """The n-th of a supply of distinct bands, none the full frame: 8 rows from row 8 (n % 60), then longer ones."""
@@ -163,6 +289,22 @@ def ctx(kifs, refs):
     yield make
     for c in made:
         c.close()
+
+
+def _hold_back(torch, passes=HOLD_PASSES):
+    """HOLD_PASSES element-wise passes over 256 MiB on torch's current stream: about 28 ms of GPU time (9.4 ms measured
+    for 128 passes), enqueued in about 2 ms -- longer than the first launches behind it, ring tables allocated on first use
+    included, take to enqueue.  Every launch's stream is ordered after that stream (the wrapper's rule for torch
+    destinations), so the launches enqueued next pile up behind it instead of running as they arrive.  That lasts as long
+    as the host is not made to wait: from the fifth user of a ring on, take_view_slot and take_scene_slot block the host
+    on the slot's event (hipEventSynchronize), until this work and the slot's previous launch are over, and a scratch
+    block that grows is freed, which drains the device.  So it is the first four users of each ring, and the calls up to
+    the first growth, that are enqueued before any of them runs.  Returns the tensor, to be kept until the launches have
+    run."""
+    x = torch.zeros(1 << 26, dtype=torch.float32, device="cuda:0")
+    for _ in range(passes):
+        x.add_(1.0)
+    return x
 
 
 def _fresh_order(K, size):
@@ -202,17 +344,26 @@ def test_eviction_round_trip(k, ctx, kifs):
     c.permutation()
 
 
-TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504")
+TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504",
+               "adaptive", "animation3", "animation70", "animation_caller_stream")
 
 
 @pytest.mark.parametrize("k", range(4))
 @pytest.mark.parametrize("transition", TRANSITIONS)
 def test_transition_at_every_phase(transition, k, ctx, kifs):
     """k lone launches bring the full-frame table to phase k of its period; then one transition the comments of
-    enqueue_batch call out, then six more lone launches.  Everything equals the oracle, the order table stays a
+    enqueue_batch call out -- or an adaptive call or animated launches, which keep state of their own and pass through the
+    full frame's tile table --, then six more lone launches.  Everything equals the oracle, the order table stays a
     permutation, and the lone launches before and after run the same kernel."""
     import torch
     c = ctx()
+    for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch: the lone launches', then the animated ones'
+        c.refs.frame(FULL, cam)
+        if transition.startswith("animation"):
+            for shift in range(W.N_MORPHS if transition == "animation_caller_stream" else 1):
+                c.refs.frame(FULL, cam, morph=(W.morph_of(cam) + shift) % W.N_MORPHS)
+    if transition == "sphere":
+        c.refs.frame(FULL, 1, options=2)
     for i in range(k):
         c.lone(cam=i % 4, record_kernel=True)
     if transition == "batch3":
@@ -257,6 +408,26 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
         c.options(0)
     elif transition == "band504":
         c.lone(1, 0, 504)  # 63 tile rows, 2016 tiles: a geometry without feedback
+    elif transition == "adaptive":
+        before = c.gs.debug_get_tile_order()
+        with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[1], gui_data=c.refs.opts[0]) as fresh:
+            fresh.set_iters(*ITERS[0])
+            c.camera(1)
+            c.adaptive(2, fresh=fresh)  # pass A: a geometry launch on the full frame's table
+            fresh.synchronize()
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)
+    elif transition in ("animation3", "animation70", "animation_caller_stream"):
+        before = c.gs.debug_get_tile_order()
+        c.camera(1)
+        if transition == "animation_caller_stream":
+            s = torch.cuda.Stream()
+            c.animation(3, stream=s)
+            c.animation(3, stream=s, shift=1)
+        else:
+            c.animation(int(transition[9:]))
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)  # neither the sort nor the order has moved
+        if transition == "animation_caller_stream":
+            c.animation(3, stream=s, shift=2)  # and one that the lone launches below follow without a wait in between
     for i in range(6):
         c.lone(cam=(i + 1) % 4, record_kernel=True)
     c.verify()
@@ -317,19 +488,23 @@ def test_resize_sequence(ctx, kifs):
 
 @pytest.mark.parametrize("seed", W.SEEDS)
 def test_seeded_walk(seed, ctx, kifs):
-    """60 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
-    checked, and a failure prints the plan up to it."""
+    """72 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
+    checked, and a failure prints the plan up to it.  Adaptive calls and animated launches run on the walk's current
+    stream like every other render: every animated frame against the oracle, an adaptive call as Ctx.adaptive says."""
     import torch
     ops = W.plan(seed)
     c = ctx()
     streams = [None, torch.cuda.Stream(), torch.cuda.Stream()]
     fresh = kifs.GraphicState(0)   # the reference for supersampled and geometry launches: configured alike, no history
     try:
-        for _, kind, _, st in W.trace(ops):  # every oracle frame before the first launch
+        for _, kind, arg, st in W.trace(ops):  # every oracle and model frame before the first launch
             if st["supersampling"] == 1:
-                n = {"batch3": 3, "batch66": 66}.get(kind, 1)
+                n = {"batch3": 3, "batch66": 66, **W.ANIMATED}.get(kind, 1)
+                scene = (W.SIZES[st["size"]], st["options"], st["iters"])
                 for cam in set(W.batch_cameras(st["camera"], n)):
-                    c.refs.frame(W.SIZES[st["size"]], cam, st["options"], st["iters"], st["extensions"])
+                    c.refs.frame(scene[0], cam, *scene[1:], st["extensions"], W.morph_of(cam) if kind in W.ANIMATED else 0)
+                if kind == "adaptive" and _modelled(scene[0], st["extensions"]):
+                    c.refs.adaptive(scene[0], st["camera"], *scene[1:], arg)
         state = dict(size=0, camera=0, options=0, iters=0, extensions=0, supersampling=1, frames_in_flight=1, stream=0)
 
         def mirror(g):
@@ -364,7 +539,7 @@ def test_seeded_walk(seed, ctx, kifs):
             cam0 = state["camera"]
             what = (i, kind, arg, dict(state))
             exact = state["supersampling"] == 1  # else: against the same call on the fresh context
-            if not exact or kind == "geometry":
+            if not exact or kind in ("geometry", "adaptive"):
                 mirror(fresh)
             if kind == "band" or kind in ("batch3", "batch66"):
                 n = {"band": 1, "batch3": 3, "batch66": 66}[kind]
@@ -396,6 +571,11 @@ def test_seeded_walk(seed, ctx, kifs):
                     fresh.render_shard_async([want[0]], [c.refs.cams[cam0]], stripes)
                     want = want[0]
                 c.expect(out[0], want, what)
+            elif kind in W.ANIMATED:
+                c.animation(W.ANIMATED[kind], *W.animation_rows(h, arg if kind == "animation3" else -1), stream=stream, what=what)
+            elif kind == "adaptive":
+                fresh.set_camera(c.refs.cams[cam0])
+                c.adaptive(arg, stream=stream, fresh=fresh, what=what)
             else:  # geometry: colour and texels against the fresh context, colour against the oracle too
                 fresh.set_camera(c.refs.cams[cam0])
                 want_c, want_g = fresh.render_geometry()
@@ -409,14 +589,77 @@ def test_seeded_walk(seed, ctx, kifs):
         fresh.close()
 
 
+@pytest.mark.parametrize("size", [(64, 40), (330, 149)])
+def test_view_ring_shared_between_entry_points(size, ctx):
+    """Batches of 70 views and animated launches of 70 frames in turn, six rounds without a wait; rounds 1 and 4 hold two
+    batches, so that the users of the four view tables (host::take_view_slot) run B A B B A B A B A B B A B A and a slot
+    passes from a batch to an animated launch and back (user n and user n + 4 share one): fourteen users of the view
+    tables, six of the four scene tables.  The context's camera moves between the launches, so that no two tables of one
+    kind in flight hold the same views or scenes, two of the animated launches run on a caller's stream, and the first four
+    users of each ring queue up behind work that holds the streams back (_hold_back).  Every frame of every launch against
+    the oracle: 4 cameras x 3 option images.  64 x 40 is the size this needs; at 330 x 149, added because it costs a tenth
+    of a second, a launch is long enough to be still reading its tables when a launch on the other stream is let go."""
+    import torch
+    c = ctx(size=size)
+    for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch
+        for m in range(W.N_MORPHS):
+            c.refs.frame(size, cam, morph=m)
+    s = torch.cuda.Stream()
+    held = _hold_back(torch)
+    for i in range(6):
+        c.camera((3 * i) % W.N_CAMERAS)
+        c.batch(70)
+        if i in (1, 4):
+            c.camera((3 * i + 1) % W.N_CAMERAS)
+            c.batch(70)
+        c.animation(70, stream=s if i in (1, 4) else None, shift=i)
+    c.verify()
+    del held
+
+
+def test_adaptive_scratch_across_sizes_and_counts(ctx):
+    """Adaptive calls of 1, 5, 1 and 3 frames at 200 x 135, 64 x 40, 330 x 149 and 200 x 135 on one context and two streams
+    in turn, an animated launch and a batch of three between each pair, nothing waited for by the test: the offsets of the
+    planes, the queues and the counters in the scratch block move with every call.  The block grows at the third and the
+    fourth call, and growing frees it, which drains the device: there the calls are checked for the new block and its
+    offsets.  The second call fits the first's block, and is enqueued on the other stream while the first is still held
+    back (_hold_back): that hand-over alone rests on the context's event (adaptive_done).  Every frame and edge count
+    against adaptive_reference's model, k = 2 and 3."""
+    import torch
+    calls = ((200, 135), 1, 2), ((64, 40), 5, 3), ((330, 149), 1, 2), ((200, 135), 3, 3)  # size, frames, k
+    c = ctx(size=calls[0][0])
+    for n, (size, count, k) in enumerate(calls):  # every reference before the first launch
+        for cam in set(W.batch_cameras(n, count)):
+            c.refs.adaptive(size, cam, 0, 0, k)
+        for cam in range(W.N_CAMERAS):
+            c.refs.frame(size, cam, morph=W.morph_of(cam))
+            c.refs.frame(size, cam)
+    streams = [torch.cuda.Stream(), None]
+    held = _hold_back(torch)
+    for n, (size, count, k) in enumerate(calls):
+        c.screen(size)
+        c.camera(n)
+        c.adaptive(k, count=count, stream=streams[n % 2])
+        if n < len(calls) - 1:
+            c.animation(3, stream=streams[(n + 1) % 2])
+            c.batch(3)
+    c.verify()
+    del held
+
+
 def test_diagnostics_buffer(ctx, kifs):
     """kifs_debug_counters sizes the per-wave record buffer for the screen of the call; a launch with more waves than it
-    holds (a batch, a larger screen set since) runs as a normal launch without diagnostics.  Then the profiling ring."""
+    holds (a batch, a larger screen set since) runs as a normal launch without diagnostics, and so do an animated launch
+    and an adaptive call (what they leave in the records is not defined).  Then the profiling ring, which those two leave
+    consistent."""
     from kifs_raymarching_amd._lib import lib
     small, tiles = (330, 149), 11 * 19
     c = ctx(size=small)
     gs = c.gs
+    c.refs.adaptive(small, 1, 0, 0, 2)  # (the references of the first calls before the first launch)
     plain = c.lone(cam=1)
+    animated = c.animation(3)
+    resolved, edges = c.adaptive(2)
     c.verify()
     out8 = (C.c_uint64 * 8)()
     zero = lambda: lib.kifs_debug_counters(gs._ctx, 1, out8)
@@ -428,6 +671,12 @@ def test_diagnostics_buffer(ctx, kifs):
     c.verify()
     assert c.torch.equal(counted, plain)   # pixels with counters on == pixels with counters off
     assert gs.debug_wave_records().any()
+    assert zero() == 0
+    animated_on = c.animation(3)           # the two newer entry points with counters on: the same pixels, the same buffer
+    resolved_on, edges_on = c.adaptive(2)
+    c.verify()
+    assert c.torch.equal(animated_on, animated) and c.torch.equal(resolved_on, resolved) and c.torch.equal(edges_on, edges)
+    assert gs.debug_wave_records().shape == (4 * tiles, 4)
     assert zero() == 0
     c.lone(2, 16, 56)                      # a band of five tile rows: 55 workgroups
     c.verify()
@@ -459,6 +708,16 @@ def test_diagnostics_buffer(ctx, kifs):
         c.lone(cam=i % 4)
     launches, mean, lo, hi = gs.profile_read()
     assert launches == 4 and 0 < lo <= mean <= hi, (launches, mean, lo, hi)
+    assert gs.profile_read()[0] == 0
+    # An animated launch is not timed and an adaptive call's first pass is (include/kifs_hip.h, kifs_set_profiling): only
+    # that the ring stays consistent is asserted here.
+    gs.set_profiling(1)
+    c.camera(1)
+    c.animation(3)
+    c.adaptive(2)
+    c.lone(cam=2)
+    launches, mean, lo, hi = gs.profile_read()
+    assert launches >= 0 and (launches == 0 or lo <= mean <= hi), (launches, mean, lo, hi)
     assert gs.profile_read()[0] == 0
     gs.set_profiling(0)
     c.verify()
