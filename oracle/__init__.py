@@ -95,6 +95,8 @@ def lib():
                                        u8p, C.c_size_t, P(Stats), P(C.c_uint16)]),
         "kor_shade_pixel": (C.c_int, [P(Screen), P(Camera), P(Options), P(Iters), i32, i32,
                                       P(f32)]),
+        "kor_shade_pixel_ext": (C.c_int, [P(Screen), P(Camera), P(Options), P(Iters), P(Ext), i32, i32,
+                                          P(f32)]),
         "kor_scene_sdf": (f32, [P(Options), P(Iters), P(f32)]),
         "kor_get_normal": (None, [P(Options), P(Iters), P(f32), P(f32)]),
         "kor_ray_direction": (None, [P(Screen), P(Camera), i32, i32, P(f32)]),

@@ -696,8 +696,14 @@ int kor_march_trace(const KorScreen* screen, const KorCamera* camera, const KorO
 
 int kor_shade_pixel(const KorScreen* screen, const KorCamera* camera, const KorOptions* options,
                     const KorIters* iters, int x, int y, float rgba[4]) {
+    return kor_shade_pixel_ext(screen, camera, options, iters, NULL, x, y, rgba);
+}
+
+int kor_shade_pixel_ext(const KorScreen* screen, const KorCamera* camera, const KorOptions* options,
+                        const KorIters* iters, const KorExt* ext, int x, int y, float rgba[4]) {
     Scene s;
     scene_init(&s, screen, camera, options, iters);
+    if (ext) s.ext = *ext;
     return raymarch(&s, ray_direction(&s, x, y), rgba, NULL);
 }
 

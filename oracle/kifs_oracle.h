@@ -120,6 +120,9 @@ int kor_march_trace(const KorScreen* screen, const KorCamera* camera, const KorO
 /* Linear (pre-encode) colour of one pixel; rgba[4] f32.  Returns loop counter i. */
 int kor_shade_pixel(const KorScreen* screen, const KorCamera* camera, const KorOptions* options,
                     const KorIters* iters, int x, int y, float rgba[4]);
+/* kor_shade_pixel with the extension block (ext == NULL: identical to kor_shade_pixel): the colour kor_render_ext encodes. */
+int kor_shade_pixel_ext(const KorScreen* screen, const KorCamera* camera, const KorOptions* options,
+                        const KorIters* iters, const KorExt* ext, int x, int y, float rgba[4]);
 
 /* ---- pieces, for known-answer tests --------------------------------------- */
 float kor_scene_sdf(const KorOptions* options, const KorIters* iters, const float p[3]);

@@ -15,16 +15,17 @@ def virtual_screen(O, screen, k):
     return O.Screen(float(k) * screen.width, float(k) * screen.height, screen.aspect_ratio)
 
 
-def linear_frame(O, screen, camera, options, it):
-    """(H, W, 3) float32: the oracle's linear colour of every pixel of `screen` (kor_shade_pixel; ctypes releases the
-    GIL, so the rows run on a few threads)."""
+def linear_frame(O, screen, camera, options, it, ext=None):
+    """(H, W, 3) float32: the oracle's linear colour of every pixel of `screen` (kor_shade_pixel_ext, `ext` an O.Ext for
+    the soft-shadow extension or None; ctypes releases the GIL, so the rows run on a few threads)."""
     w, h = int(screen.width), int(screen.height)
-    fn = O.lib().kor_shade_pixel
+    fn = O.lib().kor_shade_pixel_ext
+    ext = C.byref(ext) if ext is not None else None
     out = np.zeros((h, w, 3), dtype=np.float32)
 
     def row(y):
         rgba = (C.c_float * 4)()
-        args = (C.byref(screen), C.byref(camera), C.byref(options), C.byref(it))
+        args = (C.byref(screen), C.byref(camera), C.byref(options), C.byref(it), ext)
         for x in range(w):
             fn(*args, x, y, rgba)
             out[y, x] = rgba[:3]
@@ -56,14 +57,14 @@ def encode(O, colour, encode_mode):
     return out
 
 
-def linear_samples(O, K, screen, camera, gui, iters, k):
+def linear_samples(O, K, screen, camera, gui, iters, k, ext=None):
     """The virtual frame's linear colours for product-side scene objects (ScreenData, CameraData, GuiData or an
     OptionsUniform image)."""
     s, c, o = oracle_uniforms(O, K, (screen, camera, gui))
-    return linear_frame(O, virtual_screen(O, s, k), c, o, O.iters(*iters))
+    return linear_frame(O, virtual_screen(O, s, k), c, o, O.iters(*iters), ext)
 
 
-def aa_frame(O, K, screen, camera, gui, iters, k, encode_mode=1, lin=None):
+def aa_frame(O, K, screen, camera, gui, iters, k, encode_mode=1, lin=None, ext=None):
     if lin is None:
-        lin = linear_samples(O, K, screen, camera, gui, iters, k)
+        lin = linear_samples(O, K, screen, camera, gui, iters, k, ext)
     return encode(O, resolve(lin, k), encode_mode)

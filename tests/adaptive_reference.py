@@ -9,7 +9,7 @@ import numpy as np
 
 import aa_reference as AA
 import geometry_reference as GR
-from helpers import oracle_frame, oracle_uniforms
+from helpers import oracle_uniforms
 
 MISS_T = 0x7f800000
 SILHOUETTE = (-2.0, float("inf"))  # thresholds no two hits can fail: only hit against miss is an edge
@@ -41,11 +41,13 @@ def edge_mask(geom, normal_cos, depth_rel):
     return e
 
 
-def resolved_pixels(O, K, screen, camera, gui, iters, k, pixels):
-    """(N, 3) float32: the contract's mean of the k^2 linear samples of each (y, x) of `pixels` (N, 2)."""
+def resolved_pixels(O, K, screen, camera, gui, iters, k, pixels, ext=None):
+    """(N, 3) float32: the contract's mean of the k^2 linear samples of each (y, x) of `pixels` (N, 2); `ext`: an O.Ext
+    for the soft-shadow extension or None."""
     s, c, o = oracle_uniforms(O, K, (screen, camera, gui))
     virt, it = AA.virtual_screen(O, s, k), O.iters(*iters)
-    fn = O.lib().kor_shade_pixel
+    fn = O.lib().kor_shade_pixel_ext
+    e = C.byref(ext) if ext is not None else None
     out = np.zeros((len(pixels), 3), dtype=np.float32)
 
     def one(n):
@@ -54,7 +56,7 @@ def resolved_pixels(O, K, screen, camera, gui, iters, k, pixels):
         acc = None
         for j in range(k):
             for i in range(k):
-                fn(C.byref(virt), C.byref(c), C.byref(o), C.byref(it), k * x + i, k * y + j, rgba)
+                fn(C.byref(virt), C.byref(c), C.byref(o), C.byref(it), e, k * x + i, k * y + j, rgba)
                 v = np.array(rgba[:3], dtype=np.float32)
                 acc = v if acc is None else (acc + v).astype(np.float32)  # as aa_reference.resolve: s = 0 first
         out[n] = (acc / np.float32(k * k)).astype(np.float32)
@@ -68,10 +70,12 @@ def geometry(O, K, screen, camera, gui, iters):
     return GR.geometry_frame(O, K, screen, camera, gui, iters)[0]
 
 
-def expected_frame(O, K, screen, camera, gui, iters, k, normal_cos, depth_rel, encode=1, geom=None, means=None):
+def expected_frame(O, K, screen, camera, gui, iters, k, normal_cos, depth_rel, encode=1, geom=None, means=None, ext=None):
     """(frame (H, W, 4) uint8, mask (H, W) bool).  `geom`: the scene's geometry plane when the caller has it; `means`:
-    a dict the resolved means of this (scene, k, mask) are kept in across encodes."""
-    frame = oracle_frame(O, K, screen, camera, gui, iters, encode=encode).copy()
+    a dict the resolved means of this (scene, k, mask) are kept in across encodes; `ext`: an O.Ext -- the soft-shadow
+    extension changes the colours on and off the mask, never the mask (the geometry is the primary ray's)."""
+    s, c, o = oracle_uniforms(O, K, (screen, camera, gui))
+    frame = O.render(s, c, o, O.iters(*iters), encode=encode, ext=ext).copy()
     if geom is None:
         geom = geometry(O, K, screen, camera, gui, iters)
     mask = edge_mask(geom, normal_cos, depth_rel)
@@ -79,7 +83,7 @@ def expected_frame(O, K, screen, camera, gui, iters, k, normal_cos, depth_rel, e
     if len(pixels):
         key = (k, mask.tobytes())
         if means is None or key not in means:
-            lin = resolved_pixels(O, K, screen, camera, gui, iters, k, pixels)
+            lin = resolved_pixels(O, K, screen, camera, gui, iters, k, pixels, ext)
             if means is not None:
                 means[key] = lin
         else:

@@ -344,6 +344,26 @@ SSAA_FORMS = {
 }
 
 
+# geom::, adaptive:: and anim::render_kernel<G, P>, chosen by dispatch_pipeline<2>(group, primitive, sdf_iters <= 24): each
+# is claimed by the geometry_cases.PIPELINES name that reaches it in test_every_pipeline_bit_exact of
+# tests/test_gpu_geometry.py, test_gpu_adaptive.py and test_gpu_animation.py (and in the seeded scenes of
+# tests/extension_fuzz_cases.py, which take the same names).  adaptive::classify_kernel is no render form -- it reads a
+# geometry plane and marches nothing -- and stays out of the table.
+_EXTENSION_PIPELINES = {(0, 0): "sphere", (0, 1): "cylinder", (0, 2): "box", (0, 3): "torus", (0, 4): "sierpinski",
+                        (0, 5): "bunny", (0, 6): "unknown_id", (1, 0): "julia_25", (1, 1): "julia_24", (2, 0): "genjulia"}
+
+
+def _extension_forms(namespace, params):
+    return {f"void kifs::{namespace}::render_kernel<{g}, {p}>({params})": name for (g, p), name in _EXTENSION_PIPELINES.items()}
+
+
+GEOMETRY_FORMS = _extension_forms("geom", "kifs::BatchParams")
+ADAPTIVE_FORMS = _extension_forms("adaptive", "kifs::adaptive::Params")
+ANIMATION_FORMS = _extension_forms("anim", "kifs::anim::Params")
+EXTENSION_FORMS = {"test_gpu_geometry.py": GEOMETRY_FORMS, "test_gpu_adaptive.py": ADAPTIVE_FORMS,
+                   "test_gpu_animation.py": ANIMATION_FORMS}
+
+
 def short(name):
     """`void kifs::render_group_kernel<0, 2, 1, false>(kifs::BatchParams)` -> `render_group_kernel<0,2,1,false>`."""
     return name.split("(")[0].replace("void ", "").replace("kifs::", "").replace(" ", "")

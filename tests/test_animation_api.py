@@ -1,6 +1,6 @@
 """Animated batches (kifs_render_animation_async), the parts a machine without a GPU can check: the ABI surface, the
 Python and CLI surface, configs.morph_options against a NumPy f32 model, and that hipcc compiled anim::render_kernel
-for every pipeline under a name the kernel-form table's pattern does not claim."""
+for every pipeline, each instantiation with a claim in the kernel-form table."""
 import ctypes as C
 import re
 import subprocess
@@ -106,12 +106,13 @@ def test_morph_options_refuses_a_field_that_may_not_vary(field, other, kifs):
     assert len(morph_options(a, replace(a, power=5.0, fractal_color=(1, 1, 1)), 4)) == 4
 
 
-def test_every_pipeline_is_compiled_and_stays_out_of_the_form_table():
+def test_every_pipeline_is_compiled_and_claimed_in_the_form_table():
     from geometry_cases import PIPELINES
     names = [n for n in kernel_report() if "kifs::anim::render_kernel<" in n]
     got = sorted(re.search(r"render_kernel<(\d+), (\d+)>", n).groups() for n in names)
     # the ten pipelines of the geometry cases: two Julia variants, the generalised Julia set, six primitives, PRIM_OTHER
     want = sorted([("1", "0"), ("1", "1"), ("2", "0")] + [("0", str(p)) for p in range(7)])
     assert got == want and len(names) == len(PIPELINES) == 10, names
+    from kernel_forms import ANIMATION_FORMS
     from test_kernel_form_coverage import RENDER  # the form table's own pattern
-    assert not [n for n in names if RENDER.search(n)]
+    assert all(RENDER.search(n) for n in names) and sorted(names) == sorted(ANIMATION_FORMS)

@@ -41,11 +41,12 @@ def test_render_tool_offers_geometry(kifs):
     assert "--geometry" in p.stdout
 
 
-def test_every_pipeline_is_compiled_and_stays_out_of_the_form_table():
+def test_every_pipeline_is_compiled_and_claimed_in_the_form_table():
     names = [n for n in kernel_report() if "kifs::geom::render_kernel<" in n]
     got = sorted(re.search(r"render_kernel<(\d+), (\d+)>", n).groups() for n in names)
     want = sorted([("1", "0"), ("1", "1"), ("2", "0")] + [("0", str(p)) for p in range(7)])
     # ten: what launch_ssaa covers -- two Julia variants, the generalised Julia set, six primitives, PRIM_OTHER
     assert got == want and len(names) == 10, names
+    from kernel_forms import GEOMETRY_FORMS
     from test_kernel_form_coverage import RENDER  # the form table's own pattern
-    assert not [n for n in names if RENDER.search(n)]
+    assert all(RENDER.search(n) for n in names) and sorted(names) == sorted(GEOMETRY_FORMS)

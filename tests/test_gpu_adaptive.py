@@ -2,13 +2,17 @@
 edge mask the frame is the oracle's plain frame, on it the oracle's k x k resolve, and the edge count is the mask's
 (tests/adaptive_reference.py, held to the oracle by tests/test_adaptive_reference.py).  No tolerance anywhere.  Frames
 are 74 x 45 -- ragged tiles, 74 % 32 = 10 and 45 % 8 = 5 -- and every destination is pre-filled with a sentinel so that
-a missing store shows."""
+a missing store shows.  The seeded scenes of tests/extension_fuzz_cases.py run the same comparison at frames narrower than
+one classify row of 64 pixels and lower than 4 k rows, from cameras inside, on and just outside the bounding sphere, with
+four kinds of thresholds, lone and in batches."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import adaptive_reference as AR
+import extension_fuzz_cases as X
+import extension_fuzz_support as S
 from geometry_cases import PIPELINES, Raw, cases
 from helpers import oracle_frame, oracle_uniforms
 
@@ -385,3 +389,34 @@ def test_calls_of_one_context_on_two_streams(kifs):
             colour, edge = run(order)
             for i in range(2):
                 assert (colour[i] == want[i]).all() and edge[i] == counts[i], (order, i)
+
+
+@pytest.mark.parametrize("index", range(X.N))
+def test_fuzz_scene_bit_exact(index, ags, kifs, oracle):
+    """A seeded scene at k = 2 + index % 3 and its thresholds, lone; every third one also as a 3-view batch that mixes
+    camera families, with a count per view.  Every fourth scene runs with soft shadows, against the oracle's frame and
+    resolve with the extension (kor_shade_pixel_ext): bit for bit like the rest."""
+    scene = X.scenes(kifs)[index]
+    name, family, screen, cam, gui, iters, encode = scene
+    w, h, k, th = screen.width, screen.height, X.supersampling(index), X.thresholds(index)
+    what = f"{S.describe(index, scene)}; k {k}, thresholds {th}"
+    shadow = S.shadow_of(oracle, kifs, index)
+    pitch = 4 * w + (40 if index % 2 else 0)
+    launches = [None] + ([X.batch_cameras(kifs, index, scene, 0xada)] if X.has_batch(index) else [])
+    S.setup(ags, screen, cam, gui, iters, shadow=shadow)
+    try:
+        results = []
+        for cams in launches:
+            results.append(_call(ags, kifs, k=k, th=th, cams=cams, count=1 if cams is None else len(cams), encode=encode,
+                                 pitch=pitch))
+            assert ags.debug_last_kernel() == "render_adaptive_kernel", what
+    finally:
+        ags.set_extensions(soft_shadow=False)
+    for cams, (st, got, counts) in zip(launches, results):
+        assert st == 0, what
+        assert (got[:, :, 4 * w:] == SENT).all(), f"{what}: the padding of the rows"
+        for v, c in enumerate([cam] if cams is None else cams):
+            want, mask = AR.expected_frame(oracle, kifs, screen, c, gui, iters, k, th[0], th[1], encode,
+                                           geom=S.geometry(oracle, kifs, index)[0] if v == 0 else None,
+                                           ext=X.oracle_ext(oracle, shadow))
+            _check(got[v], counts[v], want, mask, f"{what}; view {v} of {len(got)} ({c})")

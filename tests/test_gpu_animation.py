@@ -3,12 +3,16 @@ launch whose frames differ in constant, power, colours and camera equals the con
 kifs_set_camera / kifs_set_options with that frame's values, and the oracle's frame for them -- for every pipeline and
 both encodes.  No tolerance: both sides run the contract's operation sequence.  Frames are 230 x 147 (width no multiple of
 32, height no multiple of 8) unless a case says otherwise, and every destination is pre-filled with a sentinel so that a
-missing or a stray store shows."""
+missing or a stray store shows.  The seeded scenes of tests/extension_fuzz_cases.py run launches of 2, 5 and 9 small
+frames whose cameras mix positions inside, on and outside the bounding sphere and whose constants include exact and negative
+zeros."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import extension_fuzz_cases as X
+import extension_fuzz_support as S
 from geometry_cases import PIPELINES, Raw, cases
 from helpers import oracle_frame
 
@@ -400,3 +404,34 @@ def test_a_context_without_options_or_camera(ags, kifs):
         assert lib.kifs_render_async(ctx, None, one.data_ptr(), 160, 0, 24, 1) == UNCONFIGURED
     finally:
         lib.kifs_destroy(ctx)
+
+
+@pytest.mark.parametrize("index", range(X.N))
+def test_fuzz_sequence_bit_exact(index, ags, kifs, oracle):
+    """A seeded scene's launch of 2, 5 or 9 frames, each with its own constant, power, colours and camera family: every
+    frame is the oracle's for that frame's options, and one of them the bytes of update_options + render."""
+    scene = X.scenes(kifs)[index]
+    name, _, _, cam, gui, iters, encode = scene
+    screen, frames, lone = X.animation(kifs, index, scene)
+    w, h = screen.width, screen.height
+    what = f"{S.describe(index, scene)}; {len(frames)} frames of {w} x {h}"
+    shadow = S.shadow_of(oracle, kifs, index)
+    cams = [c for c, _ in frames]
+    options = [_image(kifs, g) for _, g in frames]
+    S.setup(ags, screen, cam, gui, iters, shadow=shadow)
+    try:
+        st, dest = _call(ags, kifs, options, cams=cams, encode=encode, pitch=4 * w + 32)
+        assert st == 0, what
+        assert _hooks(ags) == (ANIMATION_KERNEL, "render_animation_kernel", 0, -1, -1), what
+        alone = _lone(ags, cams[lone], options[lone], encode=encode)
+    finally:
+        ags.set_extensions(soft_shadow=False)
+    got, padding = _pixels(dest, w)
+    assert (padding == SENT).all(), f"{what}: the padding of the rows"
+    for f, (c, g) in enumerate(frames):
+        want = S.expected_colour(oracle, kifs, screen, c, Raw(options[f]), iters, encode, shadow)
+        bad = (got[f] != want).any(-1)
+        assert not bad.any(), (f"{what}; frame {f} ({c}, {X.options_of(g)}): {S.first(bad)}: got {got[f][bad][0]}, "
+                               f"want {want[bad][0]}")
+    bad = (got[lone] != alone).any(-1)
+    assert not bad.any(), f"{what}; frame {lone} against update_options + render: {S.first(bad)}"

@@ -3,12 +3,16 @@ pipeline and both encodes the colour plane equals kifs_render's bytes and the or
 (n.x, n.y, n.z, t) equals the CPU restatement of the contract (tests/geometry_reference.c, held to the oracle by
 tests/test_geometry_reference.py).  f32 planes are compared by bit pattern, any NaN equal to any NaN; no tolerance: both
 sides run the contract's operation sequence.  Frames are a few hundred pixels a side, width no multiple of 32, height no
-multiple of 8, and every destination is pre-filled with a sentinel so that a missing store shows."""
+multiple of 8, and every destination is pre-filled with a sentinel so that a missing store shows.  The seeded scenes of
+tests/extension_fuzz_cases.py run the same comparison at small ragged sizes from cameras inside, on and just outside the
+bounding sphere, lone and in batches that mix them."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import extension_fuzz_cases as X
+import extension_fuzz_support as S
 import geometry_reference as GR
 from geometry_cases import PIPELINES, Raw, cases
 from helpers import oracle_frame, oracle_uniforms
@@ -40,9 +44,10 @@ def _setup(g, screen, cam, gui, iters):
     g.set_supersampling(1)
 
 
-def _call(g, kifs, cams=None, count=1, y0=0, y1=None, encode=1, gpitch=None, gstride=None, misalign=0):
+def _call(g, kifs, cams=None, count=1, y0=0, y1=None, encode=1, gpitch=None, gstride=None, misalign=0, cpad=0):
     """The raw entry point on sentinel-filled destinations: (status, colour (count, rows, W, 4) uint8,
-    geometry (count, rows, gpitch / 4) float32 -- whole rows, padding included)."""
+    geometry (count, rows, gpitch / 4) float32 -- whole rows, padding included).  `cpad`: bytes of padding after every
+    colour row (and 64 after every frame's last row), asserted to hold the sentinel still."""
     import torch
     from kifs_raymarching_amd._lib import lib
     w, h = g.screen_data.width, g.screen_data.height
@@ -50,13 +55,14 @@ def _call(g, kifs, cams=None, count=1, y0=0, y1=None, encode=1, gpitch=None, gst
     rows = y1 - y0
     gpitch = 16 * w if gpitch is None else gpitch
     gstride = rows * gpitch if gstride is None else gstride
-    colour = torch.full((count, rows, w, 4), SENT_U8, dtype=torch.uint8, device="cuda:0")
+    cpitch = 4 * w + cpad
+    colour = torch.full((count, rows * cpitch + (64 if cpad else 0)), SENT_U8, dtype=torch.uint8, device="cuda:0")
     floats = max(count * gstride, rows * gpitch) // 4 + 8
     plane = torch.full((floats,), float(SENT_F32), dtype=torch.float32, device="cuda:0")
     torch.cuda.synchronize()
     ptrs = (C.c_void_p * count)(*[colour[i].data_ptr() for i in range(count)])
     arr = None if cams is None else kifs.camera_array(cams)
-    st = lib.kifs_render_geometry_async(g._ctx, None, count, arr, ptrs, w * 4, plane.data_ptr() + misalign, gpitch, gstride,
+    st = lib.kifs_render_geometry_async(g._ctx, None, count, arr, ptrs, cpitch, plane.data_ptr() + misalign, gpitch, gstride,
                                         y0, y1, encode)
     assert lib.kifs_synchronize(g._ctx) == 0
     host = plane.cpu().numpy()
@@ -64,7 +70,10 @@ def _call(g, kifs, cams=None, count=1, y0=0, y1=None, encode=1, gpitch=None, gst
     if st == 0:
         geom = np.stack([host[i * gstride // 4: i * gstride // 4 + rows * gpitch // 4].reshape(rows, gpitch // 4)
                          for i in range(count)])
-    return st, colour.cpu().numpy(), geom, host
+    chost = colour.cpu().numpy()
+    crows = chost[:, :rows * cpitch].reshape(count, rows, cpitch)
+    assert (crows[:, :, 4 * w:] == SENT_U8).all() and (chost[:, rows * cpitch:] == SENT_U8).all(), "a colour store outside the frame"
+    return st, np.ascontiguousarray(crows[:, :, :4 * w]).reshape(count, rows, w, 4), geom, host
 
 
 def _texels(geom_rows, w):
@@ -274,3 +283,50 @@ def test_no_side_effects_on_the_plain_path(kifs, oracle):
         assert hit.any() and not hit.all()
         after = g.render()
         assert (after == frames[0]).all() and g.debug_last_kernel() == kernel != "render_geometry_kernel"
+
+
+def _fuzz_band(index, h):
+    """A band of the frame with neither end a multiple of 8 (frames are at least 9 rows high)."""
+    rng = X.scene_rng(index, 0x6e0)
+    y0 = int(rng.integers(1, min(8, h - 1)))
+    y1 = int(rng.choice([y for y in range(y0 + 1, h + 1) if y % 8]))
+    return y0, y1
+
+
+@pytest.mark.parametrize("index", range(X.N))
+def test_fuzz_scene_bit_exact(index, ggs, kifs, oracle):
+    """A seeded scene, lone; every third one also as a 3-view batch that mixes camera families, every second of those as a
+    band into a padded geometry pitch.  With soft shadows only the colour changes."""
+    scene = X.scenes(kifs)[index]
+    name, family, screen, cam, gui, iters, encode = scene
+    what = S.describe(index, scene)
+    w, h = screen.width, screen.height
+    shadow = S.shadow_of(oracle, kifs, index)
+    launches = [(None, 0, h, None)]
+    if X.has_batch(index):
+        band = X.has_band(index)
+        launches.append((X.batch_cameras(kifs, index, scene, 0x6e0), *(_fuzz_band(index, h) if band else (0, h)),
+                         16 * w + 48 if band else None))
+    S.setup(ggs, screen, cam, gui, iters, shadow=shadow)
+    try:
+        results = []
+        for cams, y0, y1, gpitch in launches:
+            results.append(_call(ggs, kifs, cams=cams, count=1 if cams is None else len(cams), y0=y0, y1=y1, encode=encode,
+                                 gpitch=gpitch, cpad=24))
+            assert ggs.debug_last_kernel() == "render_geometry_kernel", what
+    finally:
+        ggs.set_extensions(soft_shadow=False)
+    for (cams, y0, y1, gpitch), (st, colour, geom, host) in zip(launches, results):
+        assert st == 0, what
+        rows, gpitch = y1 - y0, 16 * w if gpitch is None else gpitch
+        for v, c in enumerate([cam] if cams is None else cams):
+            view = f"{what}; view {v} of {len(colour)} ({c}), rows {y0}..{y1}"
+            bad = (colour[v] != S.expected_colour(oracle, kifs, screen, c, gui, iters, encode, shadow, y0, y1)).any(-1)
+            assert not bad.any(), f"{view}: colour: {S.first(bad)}"
+            # the texels never depend on the extension: the reference marches without it
+            want = S.geometry(oracle, kifs, index)[0][y0:y1] if v == 0 else \
+                GR.geometry_frame(oracle, kifs, screen, c, gui, iters, y0, y1)[0]
+            bad = ~GR.same_bits(_texels(geom[v], w), want)
+            assert not bad.any(), f"{view}: texels: {S.first(bad)}, got {_texels(geom[v], w)[bad][0]!r}, want {want[bad][0]!r}"
+            assert (geom[v][:, 4 * w:] == SENT_F32).all(), f"{view}: the padding of the rows"
+        assert (host[len(colour) * rows * gpitch // 4:] == SENT_F32).all(), f"{what}: past the last plane"

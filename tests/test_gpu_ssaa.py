@@ -1,7 +1,8 @@
 """k x k supersampled anti-aliasing on the GPU (kifs_set_supersampling, kifs_ssaa_kernels.hip): bit-exact against the
 oracle's resolve of the virtual frame (tests/aa_reference.py) for every pipeline, k = 2..4 and both encodes; every
 render entry point (lone frame, band, batch, batch through the device view table, packed and in-place shards,
-kifs_multi) gives the lone frame's bytes; k = 1 is the plain path; the size limit of the virtual screen.  These tests use
+kifs_multi) gives the lone frame's bytes; k = 1 is the plain path; the size limit of the virtual screen; the seeded scenes
+of tests/extension_fuzz_cases.py, lone and in batches, from cameras inside, on and just outside the bounding sphere.  These tests use
 their own contexts: the session's `gs` stays at k = 1."""
 import ctypes as C
 
@@ -9,6 +10,8 @@ import numpy as np
 import pytest
 
 import aa_reference as AA
+import extension_fuzz_cases as X
+import extension_fuzz_support as S
 from helpers import diff_report, oracle_frame
 
 pytestmark = pytest.mark.gpu
@@ -281,3 +284,60 @@ def test_virtual_screen_beyond_the_limit(kifs):
             assert lib.kifs_render_async(g._ctx, None, dev.data_ptr(), W * 4, 0, H, 1) == 0
             lib.kifs_synchronize(g._ctx)
             assert not bool((dev == 7).all())
+
+
+FUZZ_SENT = 0xA5  # (alpha is 255 in every pixel a kernel stores)
+
+
+def _fuzz_check(got, want, what):
+    bad = (got != want).any(-1)
+    assert not bad.any(), f"{what}: {S.first(bad)}: got {got[bad][0]}, want {want[bad][0]}"
+
+
+@pytest.mark.parametrize("index", range(X.N))
+def test_fuzz_scene_bit_exact(index, ags, kifs, oracle):
+    """A seeded scene at k = 2 + index % 3 through `render`; every third one also as a 3-view batch that mixes camera
+    families; then k = 1 again: the plain frame.  Every fourth scene runs with soft shadows, against the oracle's resolve of
+    samples shaded with the extension (kor_shade_pixel_ext): bit for bit like the rest."""
+    import torch
+    scene = X.scenes(kifs)[index]
+    name, family, screen, cam, gui, iters, encode = scene
+    what = S.describe(index, scene)
+    w, h, k = screen.width, screen.height, X.supersampling(index)
+    shadow = S.shadow_of(oracle, kifs, index)
+    cams = [cam] + (X.batch_cameras(kifs, index, scene, 0x55a) if X.has_batch(index) else [])
+    pitch = 4 * w + 32
+    dest = torch.full((len(cams), h * pitch + 64), FUZZ_SENT, dtype=torch.uint8, device="cuda:0")
+    plain = torch.full((h * pitch + 64,), FUZZ_SENT, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    S.setup(ags, screen, cam, gui, iters, k=k, shadow=shadow)
+    try:
+        ags.render(out=dest[0], encode=encode, pitch_bytes=pitch)
+        assert ags.debug_last_kernel() == "render_ssaa_kernel", what
+        if len(cams) > 1:
+            stream = torch.cuda.Stream()
+            ags.render_batch_async([dest[v] for v in range(1, 4)], cams[1:], stream=stream, encode=encode, pitch_bytes=pitch)
+            stream.synchronize()
+            assert ags.debug_last_kernel() == "render_ssaa_kernel", what
+        ags.set_supersampling(1)
+        ags.render(out=plain, encode=encode, pitch_bytes=pitch)
+        assert ags.debug_last_kernel() != "render_ssaa_kernel", what
+        ags.synchronize()
+    finally:
+        ags.set_supersampling(1)
+        ags.set_extensions(soft_shadow=False)
+    host = dest.cpu().numpy()
+    rows = host[:, :h * pitch].reshape(len(cams), h, pitch)
+    assert (rows[:, :, 4 * w:] == FUZZ_SENT).all() and (host[:, h * pitch:] == FUZZ_SENT).all(), f"{what}: a store outside the frame"
+    for v, c in enumerate(cams):
+        view = f"{what}; k {k}, {'lone' if v == 0 else f'batch view {v - 1}'} ({c})"
+        got = rows[v][:, :4 * w].reshape(h, w, 4)
+        if v == 1:  # the batch's first view has the lone frame's camera: the same bytes, already compared
+            bad = (got != rows[0][:, :4 * w].reshape(h, w, 4)).any(-1)
+            assert not bad.any(), f"{view}: not the lone frame: {S.first(bad)}"
+            continue
+        _fuzz_check(got, AA.aa_frame(oracle, kifs, screen, c, gui, iters, k, encode, ext=X.oracle_ext(oracle, shadow)), view)
+    got = plain.cpu().numpy()
+    assert (got[h * pitch:] == FUZZ_SENT).all() and (got[:h * pitch].reshape(h, pitch)[:, 4 * w:] == FUZZ_SENT).all(), what
+    _fuzz_check(got[:h * pitch].reshape(h, pitch)[:, :4 * w].reshape(h, w, 4),
+                S.expected_colour(oracle, kifs, screen, cam, gui, iters, encode, shadow), f"{what}; back at k 1")

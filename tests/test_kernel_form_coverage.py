@@ -11,13 +11,15 @@ import pytest
 import kernel_forms as F
 from kernel_report import kernel_report
 
-RENDER = re.compile(r"\bkifs::(ssaa::)?render\w*_kernel\b")
+RENDER = re.compile(r"\bkifs::((ssaa|geom|adaptive|anim)::)?render\w*_kernel\b")  # (not adaptive::classify_kernel: no render form)
 
 
 def test_table_equals_the_compiled_render_instantiations():
     compiled = {n for n in kernel_report() if RENDER.search(n)}
-    table = set(F.RENDER_FORMS) | set(F.SSAA_FORMS)
-    assert not set(F.RENDER_FORMS) & set(F.SSAA_FORMS)
+    tables = [F.RENDER_FORMS, F.SSAA_FORMS, F.GEOMETRY_FORMS, F.ADAPTIVE_FORMS, F.ANIMATION_FORMS]
+    table = set().union(*tables)
+    assert len(table) == sum(len(t) for t in tables)  # no instantiation in two tables
+    assert not any("classify" in n for n in table) and any("adaptive::classify_kernel" in n for n in kernel_report())
     assert sorted(compiled - table) == [], "compiled, but no recipe in tests/kernel_forms.py"
     assert sorted(table - compiled) == [], "a recipe for an instantiation that is no longer compiled"
 
@@ -29,6 +31,27 @@ def test_ssaa_claims_name_cases_of_the_ssaa_test():
     assert m, "the parameter list of test_aa_frame_bit_exact"
     cases = set(re.findall(r'"([^"]+)"', m.group(1)))
     assert cases and set(F.SSAA_FORMS.values()) <= cases, sorted(set(F.SSAA_FORMS.values()) - cases)
+
+
+@pytest.mark.parametrize("file", sorted(F.EXTENSION_FORMS))
+def test_extension_claims_name_cases_of_the_extension_tests(file, kifs):
+    """test_every_pipeline_bit_exact of the file runs every name of geometry_cases.PIPELINES, each claim names one of them,
+    and the ten claims of a table name ten different pipelines: the (GROUP, PRIM) pair in the instantiation's name is the
+    one dispatch_pipeline takes for that pipeline's scene in geometry_cases.cases."""
+    from geometry_cases import PIPELINES, cases
+    text = (Path(__file__).resolve().parent / file).read_text()
+    assert re.search(r"^from geometry_cases import [^\n]*\bPIPELINES\b", text, re.M)
+    assert re.search(r'@pytest\.mark\.parametrize\("name", PIPELINES\)\s*\n(?:@pytest\.mark\.parametrize\([^\n]*\n)*'
+                     r'def test_every_pipeline_bit_exact\(', text), "the parameter list of test_every_pipeline_bit_exact"
+    forms = F.EXTENSION_FORMS[file]
+    assert len(forms) == 10 and sorted(forms.values()) == sorted(PIPELINES)
+    scenes = cases(kifs, 64, 48)
+    for name, pipeline in forms.items():
+        _, _, gui, iters = scenes[pipeline]
+        u = gui.into_buffer_data()
+        group, prim = int(u.fractal_group_id), int(u.primitive_id)
+        pair = (1, int(iters[0] <= 24)) if group == F.JULIA else (2, 0) if group == F.GENJULIA else (0, min(prim, F.PRIM_OTHER))
+        assert re.search(r"render_kernel<(\d+), (\d+)>", name).groups() == tuple(str(v) for v in pair), (name, pipeline)
 
 
 @pytest.mark.parametrize("name", list(F.RENDER_FORMS))
