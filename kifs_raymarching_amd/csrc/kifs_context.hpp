@@ -4,8 +4,8 @@
 //   kifs_schedule.cpp  one launch: parameters, tile tables, tile-order feedback, launch shape (enqueue_batch)
 //   kifs_shards.cpp    row shards and sparse shards (the multi-GPU partition's per-device entry points)
 //   kifs_multi.cpp     one process driving several devices (kifs_multi_*)
-//   kifs_adaptive_kernels.hip  adaptive anti-aliasing: its entry point beside its kernels
-//   kifs_animation_kernels.hip  animated batches: its entry point beside its kernel
+//   kifs_adaptive.cpp  adaptive anti-aliasing (kifs_render_adaptive_async): scratch block, rounds, the three passes
+//   kifs_animation.cpp animated batches (kifs_render_animation_async): the scene-table ring, one launch
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -95,7 +95,7 @@ struct kifs_ctx {
     hipEvent_t views_used[VIEW_RING] = {};
     bool views_busy[VIEW_RING] = {};
     int view_slot = 0;
-    // Scene tables of kifs_render_animation_async (anim::SceneView records, kifs_animation_kernels.hip): the same kind of
+    // Scene tables of kifs_render_animation_async (anim::SceneView records, kifs_params.hpp): the same kind of
     // ring -- device table, pinned host image, event behind the launch that read it -- one slot per call.
     static constexpr int SCENE_RING = 4;
     static constexpr size_t SCENE_SLOT_BYTES = size_t(64) * size_t(kifs::MAX_BATCH);
@@ -105,6 +105,8 @@ struct kifs_ctx {
     bool scenes_busy[SCENE_RING] = {};
     int scene_slot = 0;
 };
+static_assert(sizeof(kifs::anim::SceneView) * size_t(kifs::MAX_BATCH) == kifs_ctx::SCENE_SLOT_BYTES, "a ring slot holds MAX_BATCH records");
+static_assert(kifs_ctx::SCENE_RING == KIFS_ANIMATION_RING, "header and context agree on the ring's depth");
 
 namespace kifs {
 namespace host {

@@ -1,4 +1,5 @@
-// kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip, kifs_support_kernels.hip).
+// kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
+// kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,17 @@ namespace kifs {
 
 hipError_t launch_render(const BatchParams& B, uint32_t group, uint32_t primitive,
                          hipStream_t stream);
+// Adaptive anti-aliasing (kifs_adaptive_kernels.hip; the host side is kifs_adaptive.cpp).  Pass B: the edge pixels of
+// `count` planes of `stride_texels` texels each (rows of `width`) by the pair rule, appended to view i's queue at
+// queues + i * stride_texels and counted in counts[i] (zero beforehand).  Pass C: the queued pixels' k x k resolves,
+// `groups_per_view` workgroups per view.
+hipError_t launch_adaptive_classify(const float* planes, uint32_t stride_texels, int width, int height, int count,
+                                    float normal_cos, float depth_rel, uint32_t* queues, uint32_t* counts, hipStream_t stream);
+hipError_t launch_adaptive_render(const adaptive::Params& A, uint32_t group, uint32_t primitive, uint32_t groups_per_view,
+                                  hipStream_t stream);
+// Animated batches (kifs_animation_kernels.hip; the host side is kifs_animation.cpp): launch_render's whole-ray form
+// with view i's scene record laid over the frame constants.
+hipError_t launch_animation_render(const anim::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

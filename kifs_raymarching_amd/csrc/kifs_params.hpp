@@ -120,4 +120,44 @@ struct BatchParams {
 };
 static_assert(sizeof(BatchParams) <= 4096, "the kernel argument is limited to 4 KB");
 
+namespace adaptive {
+
+// The argument of adaptive::render_kernel (pass C of kifs_render_adaptive_async, kifs_adaptive_kernels.hip): the launch's
+// frame constants and views as every render kernel takes them (frame.ssaa = k, frame.out / view[i].out = the
+// destinations pass A wrote), and the queues pass B filled.
+struct Params {
+    BatchParams B;
+    const uint32_t* queues;  // view i's entries at queues + i * capacity
+    const uint32_t* counts;  // view i's number of entries
+    uint32_t capacity;
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace adaptive
+
+namespace anim {
+
+// What may differ between the frames of an animated launch (kifs_render_animation_async, kifs_animation_kernels.hip)
+// besides the camera: frame i's values of the FrameParams fields of the same names, background_rgba encoded on the host
+// as set_destination encodes the plain launch's.  One record is four 16-byte rows; the table is indexed by view.
+struct alignas(16) SceneView {
+    V4 c;
+    float power;
+    V3 fractal_color;
+    V3 background_color;
+    uint32_t background_rgba;
+    uint32_t pad[4];
+};
+static_assert(sizeof(SceneView) == 64, "a scene record is 64 bytes");
+// (that a ring slot of the context holds MAX_BATCH of them is asserted beside kifs_ctx, kifs_context.hpp)
+
+// The kernel argument: the launch's frame constants and views as every render kernel takes them, and the scene table.
+struct Params {
+    BatchParams B;
+    const SceneView* scenes;  // view i's record at scenes + i (device memory)
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace anim
+
 }  // namespace kifs

@@ -446,13 +446,12 @@ static int check_arguments(const kifs_ctx* c, int count, const KifsCameraUniform
 int take_view_slot(kifs_ctx* c, int* slot) {
     const int vs = *slot = c->view_slot;
     c->view_slot = (vs + 1) % kifs_ctx::VIEW_RING;
-    if (!c->d_views[vs]) {
-        const size_t bytes = sizeof(kifs::BatchView) * size_t(kifs::MAX_BATCH);
-        if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_views[vs]), bytes), "hipMalloc(view table)") ||
-            !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_views[vs]), bytes, hipHostMallocDefault), "hipHostMalloc(view table)") ||
-            !hip_ok(hipEventCreateWithFlags(&c->views_used[vs], hipEventDisableTiming), "hipEventCreate(view table)"))
-            return KIFS_ERR_RUNTIME;
-    }
+    // (each part on its own: a slot that a failed allocation left half made is completed when the ring comes round to it)
+    const size_t bytes = sizeof(kifs::BatchView) * size_t(kifs::MAX_BATCH);
+    if ((!c->d_views[vs] && !hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_views[vs]), bytes), "hipMalloc(view table)")) ||
+        (!c->h_views[vs] && !hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_views[vs]), bytes, hipHostMallocDefault), "hipHostMalloc(view table)")) ||
+        (!c->views_used[vs] && !hip_ok(hipEventCreateWithFlags(&c->views_used[vs], hipEventDisableTiming), "hipEventCreate(view table)")))
+        return KIFS_ERR_RUNTIME;
     // the launch that last read this slot (four big launches ago) must be over before its images change
     if (c->views_busy[vs] && !hip_ok(hipEventSynchronize(c->views_used[vs]), "wait(view table)")) return KIFS_ERR_RUNTIME;
     c->views_busy[vs] = false;

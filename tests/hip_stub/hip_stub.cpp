@@ -1,6 +1,7 @@
 // hip_stub.cpp -- TEST INFRASTRUCTURE, never shipped: a synchronous in-memory stand-in for the HIP runtime calls and
 // the kernel launchers that the HOST side of the library uses (kifs_api.cpp, kifs_schedule.cpp, kifs_shards.cpp,
-// kifs_multi.cpp, kifs_host.cpp), so that those 2 500 lines of slot / stream / event / buffer bookkeeping can run under
+// kifs_multi.cpp, kifs_host.cpp, kifs_adaptive.cpp, kifs_animation.cpp), so that those 2 700 lines of slot / stream /
+// event / buffer bookkeeping can run under
 // AddressSanitizer and UndefinedBehaviorSanitizer on a box without a GPU (the GPU pool does not
 // offer sanitizers).  `make -C kifs_raymarching_amd/csrc asan` links it with the sanitised host objects into
 // build/kifs_host_asan; tests/test_host_sanitizers.py runs that.
@@ -21,8 +22,15 @@
 // the host code are compared call for call by running the driver on both and diffing the files.  A render launch's line
 // also says what the launch was told (its shape, which optional tables it got, which culls are on, which of the two order
 // buffers it read); stub_last_render() hands the same fields of the latest render launch to the driver.
+// The adaptive passes: the geometry texel is (x, y, origin.x, t) with t = +inf where the pixel pattern holds the
+// background, so a frame has hits and misses; the classify stand-in applies the header's pair rule to those texels and
+// fills the queues and counts; the adaptive render overwrites every queued pixel with a pattern of camera, frame
+// coordinates and k.  The animation render is the render pattern with every non-background pixel also a function of the
+// view's scene record.  A frame of more than SAMPLE_ABOVE pixels (no scenario but the 4096 x 4096 adaptive one has
+// such a frame) gets only a bounded sample of its tiles written and classified: see stub_sampled_tile.
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -49,7 +57,10 @@ std::map<uintptr_t, int> g_order_ordinal;  // allocations read as a tile order, 
 int g_order_ordinals = 0;
 std::set<ihipStream_t*> g_streams;
 std::set<ihipEvent_t*> g_events;
-long g_calls = 0, g_launches = 0, g_device_syncs = 0;
+long g_calls = 0, g_launches = 0, g_device_syncs = 0, g_stream_waits = 0, g_event_syncs = 0;
+long g_device_frees = 0;
+std::map<int, long> g_waits_on, g_syncs_on;  // per event ordinal
+std::vector<int> g_adaptive_rounds;  // the view count of every adaptive render launch since the driver last asked
 
 hipError_t fail(hipError_t e) { g_last = e; return e; }
 
@@ -125,6 +136,24 @@ void stub_trace_mark(const char* what) { if (g_trace) std::fprintf(g_trace, "# %
 long stub_calls() { return g_calls; }
 long stub_launches() { return g_launches; }
 long stub_device_synchronizes() { return g_device_syncs; }
+long stub_stream_waits() { return g_stream_waits; }
+long stub_event_synchronizes() { return g_event_syncs; }
+long stub_device_frees() { return g_device_frees; }
+int stub_events_created() { return g_event_ordinals; }  // the ordinal of the newest event
+long stub_stream_waits_on(int event_ordinal) { return g_waits_on[event_ordinal]; }
+long stub_event_synchronizes_on(int event_ordinal) { return g_syncs_on[event_ordinal]; }
+int stub_has_device_allocation_of(size_t bytes) {
+    for (const auto& a : g_device_mem)
+        if (a.second == bytes) return 1;
+    return 0;
+}
+// The view counts of the adaptive render launches since the last call, oldest first; returns how many there were.
+int stub_adaptive_rounds(int* out, int max) {
+    const int n = int(g_adaptive_rounds.size());
+    for (int i = 0; i < n && i < max; ++i) out[i] = g_adaptive_rounds[size_t(i)];
+    g_adaptive_rounds.clear();
+    return n;
+}
 size_t stub_live_device_allocations() { return g_device_mem.size(); }
 size_t stub_live_streams_and_events() { return g_streams.size() + g_events.size() + g_host_mem.size(); }
 
@@ -137,6 +166,13 @@ hipError_t hipSetDevice(int d) {
     return hipSuccess;
 }
 hipError_t hipDeviceSynchronize(void) { trace("hipDeviceSynchronize"); ++g_device_syncs; return hipSuccess; }
+hipError_t hipDeviceGetAttribute(int* value, hipDeviceAttribute_t attr, int device) {
+    trace("hipDeviceGetAttribute");
+    if (injected()) return fail(hipErrorInvalidDevice);
+    if (attr != hipDeviceAttributeMultiprocessorCount || device < 0 || device >= g_devices) return fail(hipErrorInvalidValue);
+    *value = 256;
+    return hipSuccess;
+}
 hipError_t hipDeviceCanAccessPeer(int* can, int a, int b) { *can = a != b; return hipSuccess; }
 hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
 hipError_t hipGetLastError(void) { hipError_t e = g_last; g_last = hipSuccess; return e; }
@@ -168,6 +204,7 @@ hipError_t hipFree(void* p) {
     g_device_of.erase(it->first);
     g_order_ordinal.erase(it->first);
     g_device_mem.erase(it);
+    ++g_device_frees;
     std::free(p);
     return hipSuccess;
 }
@@ -237,6 +274,8 @@ hipError_t hipStreamSynchronize(hipStream_t s) { if (s && !g_streams.count(s)) s
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
     if ((s && !g_streams.count(s)) || !g_events.count(e)) std::abort();  // a destroyed stream or event
     trace("hipStreamWaitEvent", s, e);
+    ++g_stream_waits;
+    ++g_waits_on[e->ordinal];
     if (!e->recorded) {  // HIP takes this for a wait that is already over: whoever meant to order two streams has not
         std::fprintf(stderr, "hip_stub: hipStreamWaitEvent on an event that was never recorded\n");
         std::abort();
@@ -264,7 +303,7 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     e->recorded = true;
     return hipSuccess;
 }
-hipError_t hipEventSynchronize(hipEvent_t e) { if (!g_events.count(e)) std::abort(); trace("hipEventSynchronize", nullptr, e); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { if (!g_events.count(e)) std::abort(); trace("hipEventSynchronize", nullptr, e); ++g_event_syncs; ++g_syncs_on[e->ordinal]; return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t e) { if (!g_events.count(e)) std::abort(); trace("hipEventQuery", nullptr, e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
     if (!g_events.count(a) || !g_events.count(b)) std::abort();
@@ -286,13 +325,46 @@ uint32_t bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
 
 // The stand-in for a pixel's colour: a function of the camera and the pixel's frame coordinates.  A quarter of the
 // 32 x 8 tiles hold something, the rest is background (so the sparse gather has both kinds).
+uint32_t stub_key(const BatchView& v) {
+    return bits(v.origin.x) * 2654435761u ^ bits(v.origin.y) * 40503u ^ bits(v.origin.z) * 69069u ^ bits(v.m1.x);
+}
+bool stub_hit(uint32_t key, int x, int y) { return (((unsigned(x) >> 5) + 3u * (unsigned(y) >> 3) + (key >> 7)) & 3u) == 0u; }
 uint32_t stub_pixel(const BatchView& v, int x, int y, uint32_t background) {
-    const uint32_t key = bits(v.origin.x) * 2654435761u ^ bits(v.origin.y) * 40503u ^ bits(v.origin.z) * 69069u ^ bits(v.m1.x);
-    if ((((unsigned(x) >> 5) + 3u * (unsigned(y) >> 3) + (key >> 7)) & 3u) != 0u) return background;
+    const uint32_t key = stub_key(v);
+    if (!stub_hit(key, x, y)) return background;
     uint32_t c = (unsigned(x) * 73856093u ^ unsigned(y) * 19349663u ^ key) | 0xff000000u;
     return c == background ? c ^ 1u : c;
 }
+// The geometry texel's t: a hit where the pixel pattern holds something, a miss (+inf) where it holds the background.
+float stub_depth(const BatchView& v, int x, int y) {
+    return stub_hit(stub_key(v), x, y) ? v.origin.z + 0.25f * float((x + 2 * y) & 3) : INFINITY;
+}
+// What the adaptive render writes over an edge pixel: the camera, the frame coordinates and k.
+uint32_t stub_adaptive_pixel(const BatchView& v, int x, int y, int k) {
+    return (unsigned(x) * 2246822519u ^ unsigned(y) * 3266489917u ^ stub_key(v) * 668265263u ^ unsigned(k) * 374761393u) | 0xff000000u;
+}
+// What an animated frame's scene adds to every pixel that is not background: all of the record but its padding.
+uint32_t stub_scene_key(const anim::SceneView& s) {
+    const float f[11] = {s.c.x, s.c.y, s.c.z, s.c.w, s.power, s.fractal_color.x, s.fractal_color.y, s.fractal_color.z,
+                         s.background_color.x, s.background_color.y, s.background_color.z};
+    uint32_t k = 2166136261u;
+    for (float v : f) k = (k ^ bits(v)) * 16777619u;
+    return k & 0x00ffffffu;
+}
+// A frame of more than SAMPLE_ABOVE pixels is too much per-pixel work under the sanitizers: the render and classify
+// stand-ins then check the extents of everything they would touch through need_device as always, but write and
+// classify only the tiles of this sample (every 32nd tile column and the one beside it, every 64th tile row, and the
+// last of each: every camera's pattern then has hits, misses and a border between them in it), and a
+// neighbour outside the sample does not exist for the pair rule.  The driver's model does the same.
+constexpr size_t SAMPLE_ABOVE = size_t(1) << 23;
+bool stub_sampled_tile(int tiles_x, int tiles_y, int tx, int tj) {
+    return (tx % 32 <= 1 || tx == tiles_x - 1) && (tj % 64 == 0 || tj == tiles_y - 1);
+}
 }  // namespace
+
+namespace {
+void stub_render(const BatchParams& B, const anim::SceneView* scenes);
+}
 
 hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t st) {
     ++g_launches;
@@ -308,12 +380,34 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
                      L.count, L.tile_count, L.round_steps, L.group_tiles, L.bunny_coop, L.workgroups_per_cu, L.tile_cost, L.counters, L.geom,
                      L.stripe_rows, L.table, L.ssaa, L.encode, L.y0, L.y1, L.cull, L.quick_cull, L.tile_cull, L.order);
     if (injected()) return fail(hipErrorLaunchFailure);
-    const int tiles_x = (P.width + TW - 1) / TW;
+    stub_render(B, nullptr);
+    return hipSuccess;
+}
+
+namespace {
+// The pixels, texels, wave records and tile costs of a render launch; `scenes` non-null: an animated one.
+void stub_render(const BatchParams& B, const anim::SceneView* scenes) {
+    const FrameParams& P = B.frame;
+    const int tiles_x = (P.width + TW - 1) / TW, tiles_y = (P.y1 - P.y0 + TH - 1) / TH;
+    const bool sample = !P.stripe_rows && size_t(P.width) * size_t(P.y1 - P.y0) > SAMPLE_ABOVE;
     // the tile table must name every tile of the launch exactly once
     std::vector<char> seen;
     for (int f = 0; f < B.count; ++f) {
+        if (B.table) need_device(B.table + f, sizeof(BatchView), "render: a view of the table");
         const BatchView& v = B.table ? B.table[f] : B.view[f];
         uint32_t* out = v.out;
+        uint32_t background = P.background_rgba, scene_key = 0;
+        if (scenes) {
+            need_device(scenes + f, sizeof(anim::SceneView), "render: a scene record");
+            background = scenes[f].background_rgba;
+            scene_key = stub_scene_key(scenes[f]);
+        }
+        if (sample) {  // (what the tiles left out would have touched)
+            const size_t rows = size_t(P.y1 - P.y0);
+            need_device(out + (P.out_frame_rows ? size_t(P.y0) * P.pitch_words : 0), ((rows - 1) * P.pitch_words + size_t(P.width)) * 4, "render: a view's rows");
+            if (P.geom)
+                need_device(P.geom + 4 * size_t(f) * P.geom_stride_texels, ((rows - 1) * P.geom_pitch_texels + size_t(P.width)) * 16, "render: a view's plane");
+        }
         seen.assign(size_t(P.tile_count), 0);
         need_device(P.tile_order, size_t(P.tile_count) * 4, "render: tile order");
         for (uint32_t i = 0; i < P.tile_count; ++i) {
@@ -322,6 +416,7 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
             const size_t flat = size_t(tj) * size_t(tiles_x) + tx;
             if (flat >= seen.size() || seen[flat]) { std::fprintf(stderr, "hip_stub: the tile table is not a permutation\n"); std::abort(); }
             seen[flat] = 1;
+            if (sample && !stub_sampled_tile(tiles_x, tiles_y, int(tx), int(tj))) continue;
             int base;
             if (P.stripe_rows) {
                 need_device(P.stripe_rows + tj, 4, "render: stripe table");
@@ -337,11 +432,12 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
                 need_device(out + row * P.pitch_words + x0, size_t(x1 - x0) * 4, "render: a tile row's pixels");
                 for (int x = x0; x < x1; ++x) {
                     uint32_t* dst = out + row * P.pitch_words + x;
-                    *dst = stub_pixel(v, x, y, P.background_rgba);
+                    *dst = stub_pixel(v, x, y, background);
+                    if (scenes && *dst != background) *dst ^= scene_key;
                     if (P.geom) {  // the geometry plane: rows of a band packed, one plane per view (kifs_geometry_kernels.hip:62-66)
                         float* texel = P.geom + 4 * (size_t(f) * P.geom_stride_texels + (size_t(TH) * tj + size_t(r)) * P.geom_pitch_texels + size_t(x));
                         need_device(texel, 16, "render: a geometry texel");
-                        const float value[4] = {float(x), float(y), v.origin.x, v.origin.z};
+                        const float value[4] = {float(x), float(y), v.origin.x, stub_depth(v, x, y)};
                         std::memcpy(texel, value, sizeof value);
                     }
                 }
@@ -362,6 +458,105 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
     if (P.tile_cost) {  // the feedback's per-tile costs: something the sort can chew on
         need_device(P.tile_cost, size_t(P.tile_count) * 4, "render: tile costs");
         for (uint32_t i = 0; i < P.tile_count; ++i) P.tile_cost[i] = (i * 2654435761u) >> 20;
+    }
+}
+
+// The pair rule of include/kifs_hip.h ("pair") on two texels (n.x, n.y, n.z, t), f32.
+bool stub_pair(const float* p, const float* q, float normal_cos, float depth_rel) {
+    const bool hp = bits(p[3]) != 0x7f800000u, hq = bits(q[3]) != 0x7f800000u;
+    if (hp != hq) return true;
+    if (!hp) return false;
+    const float d = (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2];
+    return !(d >= normal_cos) || std::fabs(p[3] - q[3]) > depth_rel * std::fmin(p[3], q[3]);
+}
+}  // namespace
+
+hipError_t launch_animation_render(const anim::Params& A, uint32_t, uint32_t, hipStream_t st) {
+    ++g_launches;
+    const FrameParams& P = A.B.frame;
+    if (g_trace)
+        std::fprintf(g_trace, "launch_animation_render dev=%d stream=%d count=%d tiles=%u table=%d encode=%d y=%d..%d order=%d\n", g_current,
+                     st ? st->ordinal : 0, A.B.count, P.tile_count, A.B.table != nullptr, P.encode, P.y0, P.y1, order_allocation_of(P.tile_order));
+    if (injected()) return fail(hipErrorLaunchFailure);
+    if (P.tile_cost || P.counters || P.geom || P.stripe_rows || P.round_steps != 0) {
+        std::fprintf(stderr, "hip_stub: an animated launch with costs, diagnostics, a plane, stripes or rounds\n");
+        std::abort();
+    }
+    stub_render(A.B, A.scenes);
+    return hipSuccess;
+}
+
+hipError_t launch_adaptive_classify(const float* planes, uint32_t stride_texels, int width, int height, int count, float normal_cos,
+                                    float depth_rel, uint32_t* queues, uint32_t* counts, hipStream_t st) {
+    ++g_launches;
+    if (g_trace)
+        std::fprintf(g_trace, "launch_adaptive_classify dev=%d stream=%d count=%d width=%d height=%d stride=%u\n", g_current, st ? st->ordinal : 0,
+                     count, width, height, stride_texels);
+    if (injected()) return fail(hipErrorLaunchFailure);
+    const uint32_t capacity = stride_texels;  // (as the real launcher hands it to the kernel)
+    const int tiles_x = (width + TW - 1) / TW, tiles_y = (height + TH - 1) / TH;
+    const bool sample = size_t(width) * size_t(height) > SAMPLE_ABOVE;
+    for (int view = 0; view < count; ++view) {
+        const float* plane = planes + 4 * size_t(view) * stride_texels;
+        uint32_t* queue = queues + size_t(view) * capacity;
+        need_device(plane, size_t(width) * size_t(height) * 16, "classify: a view's plane");
+        need_device(queue, size_t(capacity) * 4, "classify: a view's queue");
+        need_device(counts + view, 4, "classify: a view's count");
+        if (counts[view] != 0) { std::fprintf(stderr, "hip_stub: classify: the edge count was not cleared\n"); std::abort(); }
+        // the block's layout as kifs_adaptive.cpp states it: planes | queues | counters of THIS launch's views, nothing between
+        if (static_cast<const void*>(queues) != planes + 4 * size_t(count) * stride_texels || counts != queues + size_t(count) * capacity) {
+            std::fprintf(stderr, "hip_stub: classify: the scratch block is not planes | queues | counters of %d views\n", count);
+            std::abort();
+        }
+        const auto exists = [&](int x, int y) {
+            return x >= 0 && y >= 0 && x < width && y < height && (!sample || stub_sampled_tile(tiles_x, tiles_y, x / TW, y / TH));
+        };
+        const auto texel = [&](int x, int y) { return plane + 4 * (size_t(y) * size_t(width) + size_t(x)); };
+        uint32_t n = 0;
+        for (int tj = 0; tj < tiles_y; ++tj)
+            for (int tx = 0; tx < tiles_x; ++tx) {
+                if (sample && !stub_sampled_tile(tiles_x, tiles_y, tx, tj)) continue;
+                for (int y = tj * TH; y < std::min(height, tj * TH + TH); ++y)
+                    for (int x = tx * TW; x < std::min(width, tx * TW + TW); ++x) {
+                        const float* p = texel(x, y);
+                        const int nb[4][2] = {{x - 1, y}, {x + 1, y}, {x, y - 1}, {x, y + 1}};
+                        bool edge = false;
+                        for (const auto& q : nb) edge = edge || (exists(q[0], q[1]) && stub_pair(p, texel(q[0], q[1]), normal_cos, depth_rel));
+                        if (!edge) continue;
+                        if (n >= capacity) { std::fprintf(stderr, "hip_stub: classify: view %d's queue is full\n", view); std::abort(); }
+                        queue[n++] = uint32_t(x) | (uint32_t(y) << 16);
+                    }
+            }
+        counts[view] = n;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_adaptive_render(const adaptive::Params& A, uint32_t, uint32_t, uint32_t groups_per_view, hipStream_t st) {
+    ++g_launches;
+    const FrameParams& P = A.B.frame;
+    if (g_trace)
+        std::fprintf(g_trace, "launch_adaptive_render dev=%d stream=%d count=%d ssaa=%d groups=%u capacity=%u encode=%d\n", g_current,
+                     st ? st->ordinal : 0, A.B.count, P.ssaa, groups_per_view, A.capacity, P.encode);
+    g_adaptive_rounds.push_back(A.B.count);
+    if (injected()) return fail(hipErrorLaunchFailure);
+    if (A.B.table || A.B.count < 1 || A.B.count > MAX_BATCH_INLINE || groups_per_view < 1) {
+        std::fprintf(stderr, "hip_stub: an adaptive render launch of %d views, table %p, %u groups per view\n", A.B.count, (const void*)A.B.table, groups_per_view);
+        std::abort();
+    }
+    for (int f = 0; f < A.B.count; ++f) {
+        const BatchView& v = A.B.view[f];
+        need_device(A.counts + f, 4, "adaptive render: a view's count");
+        const uint32_t n = std::min(A.counts[f], A.capacity);
+        const uint32_t* queue = A.queues + size_t(f) * A.capacity;
+        need_device(queue, size_t(n) * 4, "adaptive render: a view's queue");
+        for (uint32_t e = 0; e < n; ++e) {
+            const int x = int(queue[e] & 0xffffu), y = int(queue[e] >> 16);
+            if (x >= P.width || y >= P.y1) { std::fprintf(stderr, "hip_stub: adaptive render: entry (%d, %d) outside the frame\n", x, y); std::abort(); }
+            uint32_t* dst = v.out + size_t(y) * P.pitch_words + size_t(x);
+            need_device(dst, 4, "adaptive render: a pixel");
+            *dst = stub_adaptive_pixel(v, x, y, P.ssaa);
+        }
     }
     return hipSuccess;
 }

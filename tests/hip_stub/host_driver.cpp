@@ -6,7 +6,10 @@
 // long-lived context must keep rendering exact frames across evictions, feedback transitions, resizes and diagnostics
 // (context_lifecycle), every launch-shape rule must pick what it picked when the table was written (launch_shapes),
 // nothing may touch memory it does not own, every failure that is injected must leave the object usable, and after the last
-// destroy the stub must hold no allocation, stream or event.  Prints "host_driver: N checks ok".
+// destroy the stub must hold no allocation, stream or event.  The adaptive and the animated entry points
+// (kifs_adaptive.cpp, kifs_animation.cpp; tests/test_gpu_adaptive.py, test_gpu_animation.py) come last, so that the
+// call trace of everything before them stays what it was: their frames are compared with the stand-in's patterns as
+// this file restates them (namespace model).  Prints "host_driver: N checks ok".
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -38,6 +41,14 @@ long stub_calls();
 long stub_device_synchronizes();
 size_t stub_live_device_allocations();
 size_t stub_live_streams_and_events();
+long stub_stream_waits();
+long stub_event_synchronizes();
+long stub_device_frees();
+int stub_events_created();
+long stub_stream_waits_on(int event_ordinal);
+long stub_event_synchronizes_on(int event_ordinal);
+int stub_has_device_allocation_of(size_t bytes);
+int stub_adaptive_rounds(int* out, int max);
 }
 
 static long g_checks = 0;
@@ -982,6 +993,693 @@ void launch_shapes() {
     kifs_destroy(c);
 }
 
+
+// ---- the adaptive and the animated entry points ----------------------------------------------------------------------
+// What the stand-in's launchers write, restated from its documentation (hip_stub.cpp: stub_key, stub_hit, stub_depth,
+// stub_adaptive_pixel, stub_scene_key, stub_sampled_tile): the driver computes every expected frame from these alone.
+namespace model {
+
+uint32_t fbits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+uint32_t key(const KifsCameraUniform& c) {
+    return fbits(c.origin[0]) * 2654435761u ^ fbits(c.origin[1]) * 40503u ^ fbits(c.origin[2]) * 69069u ^ fbits(c.matrix[1][0]);
+}
+bool hit(uint32_t k, int x, int y) { return (((unsigned(x) >> 5) + 3u * (unsigned(y) >> 3) + (k >> 7)) & 3u) == 0u; }
+struct Texel { float nx, ny, nz, t; };
+Texel texel(const KifsCameraUniform& c, int x, int y) {
+    return Texel{float(x), float(y), c.origin[0], hit(key(c), x, y) ? c.origin[2] + 0.25f * float((x + 2 * y) & 3) : INFINITY};
+}
+// include/kifs_hip.h, "pair"
+bool pair(const Texel& p, const Texel& q, const KifsAdaptiveAA& aa) {
+    const bool hp = fbits(p.t) != 0x7f800000u, hq = fbits(q.t) != 0x7f800000u;
+    if (hp != hq) return true;
+    if (!hp) return false;
+    const float d = (p.nx * q.nx + p.ny * q.ny) + p.nz * q.nz;
+    return !(d >= aa.normal_cos) || std::fabs(p.t - q.t) > aa.depth_rel * std::fmin(p.t, q.t);
+}
+uint32_t adaptive_pixel(const KifsCameraUniform& c, int x, int y, int k) {
+    return (unsigned(x) * 2246822519u ^ unsigned(y) * 3266489917u ^ key(c) * 668265263u ^ unsigned(k) * 374761393u) | 0xff000000u;
+}
+uint32_t scene_key(const KifsOptionsUniform& o) {
+    const float f[11] = {o.constant[0], o.constant[1], o.constant[2], o.constant[3], o.power, o.fractal_color[0], o.fractal_color[1],
+                         o.fractal_color[2], o.background_color[0], o.background_color[1], o.background_color[2]};
+    uint32_t k = 2166136261u;
+    for (float v : f) k = (k ^ fbits(v)) * 16777619u;
+    return k & 0x00ffffffu;
+}
+// A frame of more than 2^23 pixels: the stand-in writes and classifies this sample of its 32 x 8 tiles only, and a
+// neighbour outside the sample does not exist.
+bool sampled(int w, int h, int x, int y) {
+    if (size_t(w) * size_t(h) <= (size_t(1) << 23)) return true;
+    const int tiles_x = (w + 31) / 32, tiles_y = (h + 7) / 8, tx = x / 32, tj = y / 8;
+    return (tx % 32 <= 1 || tx == tiles_x - 1) && (tj % 64 == 0 || tj == tiles_y - 1);
+}
+bool edge(const KifsCameraUniform& c, int w, int h, int x, int y, const KifsAdaptiveAA& aa) {
+    const Texel p = texel(c, x, y);
+    const int nb[4][2] = {{x - 1, y}, {x + 1, y}, {x, y - 1}, {x, y + 1}};
+    for (const auto& q : nb)
+        if (q[0] >= 0 && q[1] >= 0 && q[0] < w && q[1] < h && sampled(w, h, q[0], q[1]) && pair(p, texel(c, q[0], q[1]), aa)) return true;
+    return false;
+}
+
+}  // namespace model
+
+// The plain frames of (camera i, options i) as one context renders them one by one, into host memory.
+std::vector<uint8_t> plain_frames(const Scene& s, const std::vector<KifsCameraUniform>& cams, const std::vector<KifsOptionsUniform>& opts, int encode) {
+    int st = 0;
+    kifs_ctx* c = kifs_create(0, &st);
+    CHECK(c && st == KIFS_OK && kifs_set_screen(c, &s.screen) == KIFS_OK);
+    const size_t fb = size_t(s.w) * s.h * 4;
+    std::vector<uint8_t> out(fb * cams.size());
+    for (size_t i = 0; i < cams.size(); ++i) {
+        CHECK(kifs_set_camera(c, &cams[i]) == KIFS_OK && kifs_set_options(c, &opts[i % opts.size()]) == KIFS_OK);
+        CHECK(kifs_render(c, out.data() + i * fb, size_t(s.w) * 4, 0, s.h, encode) == KIFS_OK);
+    }
+    kifs_destroy(c);
+    return out;
+}
+
+// The frames kifs_render_adaptive_async owes for `cams`: the plain frame with every edge pixel replaced; counts[i] = frame
+// i's edge pixels.  (A frame above the sampling threshold: only model::sampled pixels mean anything.)
+std::vector<uint8_t> adaptive_frames(const Scene& s, const std::vector<KifsCameraUniform>& cams, const KifsAdaptiveAA& aa, int encode,
+                                     std::vector<uint32_t>* counts) {
+    std::vector<uint8_t> want = plain_frames(s, cams, {s.options}, encode);
+    const size_t fb = size_t(s.w) * s.h * 4;
+    counts->assign(cams.size(), 0u);
+    for (size_t i = 0; i < cams.size(); ++i)
+        for (int y = 0; y < s.h; ++y)
+            for (int x = 0; x < s.w; ++x) {
+                if (!model::edge(cams[i], s.w, s.h, x, y, aa)) continue;
+                const uint32_t px = model::adaptive_pixel(cams[i], x, y, aa.factor);
+                std::memcpy(want.data() + i * fb + (size_t(y) * s.w + size_t(x)) * 4, &px, 4);
+                ++(*counts)[i];
+            }
+    return want;
+}
+
+// Rows of `w` pixels, `pitch` bytes apart, equal to the packed frame `want`, and the bytes between them still 0xEE.
+bool rows_equal(const uint8_t* dev, size_t pitch, const uint8_t* want, int w, int y0, int y1) {
+    for (int y = y0; y < y1; ++y) {
+        if (std::memcmp(dev + size_t(y - y0) * pitch, want + size_t(y) * w * 4, size_t(w) * 4) != 0) return false;
+        for (size_t b = size_t(w) * 4; b < pitch; ++b)
+            if (dev[size_t(y - y0) * pitch + b] != 0xEE) return false;
+    }
+    return true;
+}
+
+kifs_ctx* context_for(const Scene& s, const KifsCameraUniform* cam, bool options = true, int device = 0) {
+    int st = 0;
+    kifs_ctx* c = kifs_create(device, &st);
+    CHECK(c && st == KIFS_OK && kifs_set_screen(c, &s.screen) == KIFS_OK);
+    if (options) CHECK(kifs_set_options(c, &s.options) == KIFS_OK);
+    if (cam) CHECK(kifs_set_camera(c, cam) == KIFS_OK);
+    return c;
+}
+
+// One adaptive call of `count` frames (first camera cams[first]; lone: cameras NULL, the context's camera must be
+// cams[first]) into sentinel-filled device frames `pitch` apart in rows, with or without counts.  Returns the status; on
+// KIFS_OK with `want` given, every frame, every byte between the rows and every count has been compared.
+struct AdaptiveCall {
+    const Scene& s;
+    const std::vector<KifsCameraUniform>& cams;
+    KifsAdaptiveAA aa;
+    int encode = 1;
+    size_t pad = 0;  // bytes between rows
+    uint8_t* dev = nullptr;       // room for cams.size() frames of the padded pitch
+    uint32_t* dev_counts = nullptr;  // cams.size() + 2 words: a sentinel before and behind
+
+    size_t pitch() const { return size_t(s.w) * 4 + pad; }
+    size_t frame_bytes() const { return pitch() * size_t(s.h); }
+    void alloc() {
+        dev = dev_alloc(frame_bytes() * cams.size());
+        dev_counts = reinterpret_cast<uint32_t*>(dev_alloc((cams.size() + 2) * 4));
+    }
+    void release() { CHECK(hipFree(dev) == hipSuccess && hipFree(dev_counts) == hipSuccess); }
+    int run(kifs_ctx* c, hipStream_t stream, int first, int count, bool lone, bool with_counts, const std::vector<uint8_t>* want,
+            const std::vector<uint32_t>* want_counts) {
+        std::vector<uint8_t*> outs(static_cast<size_t>(count));
+        for (int i = 0; i < count; ++i) outs[size_t(i)] = dev + frame_bytes() * size_t(i);
+        std::memset(dev, 0xEE, frame_bytes() * size_t(count));
+        std::memset(dev_counts, 0xEE, (cams.size() + 2) * 4);
+        const int st = kifs_render_adaptive_async(c, stream, count, lone ? nullptr : cams.data() + first, outs.data(), pitch(), &aa,
+                                                  with_counts ? dev_counts + 1 : nullptr, encode);
+        if (st != KIFS_OK || !want) return st;
+        const size_t fb = size_t(s.w) * s.h * 4;
+        for (int i = 0; i < count; ++i) CHECK(rows_equal(outs[size_t(i)], pitch(), want->data() + fb * size_t(first + i), s.w, 0, s.h));
+        CHECK(dev_counts[0] == 0xEEEEEEEEu);
+        for (int i = 0; i < count; ++i) CHECK(dev_counts[1 + i] == (with_counts ? (*want_counts)[size_t(first + i)] : 0xEEEEEEEEu));
+        CHECK(dev_counts[1 + count] == 0xEEEEEEEEu);
+        CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ADAPTIVE);
+        return st;
+    }
+};
+
+// The view counts of the adaptive render launches since the last question.
+std::vector<int> adaptive_rounds() {
+    int r[16];
+    const int n = stub_adaptive_rounds(r, 16);
+    return std::vector<int>(r, r + std::min(n, 16));  // (more than 16: nobody compares such a run)
+}
+
+void adaptive_batches(int w, int h) {
+    stub_trace_mark("adaptive_batches");
+    const Scene s = scene(w, h, 40);
+    const auto cams = cameras(70, 5);
+    const size_t pixels = size_t(w) * h;
+    // two hits' normals (x, y, origin.x): an edge inside a circle about the frame's corner; depths 0.25 .. 0.75 apart
+    AdaptiveCall A{s, cams, KifsAdaptiveAA{2, 0.35f * float(w) * float(w), 0.1f}};
+    std::vector<uint32_t> counts;
+    const auto want = adaptive_frames(s, cams, A.aa, 1, &counts);
+    {   // the mask is neither empty nor everything, and it differs between the views
+        size_t total = 0;
+        for (uint32_t n : counts) { CHECK(n > 0 && n < pixels); total += n; }
+        CHECK(total != counts[0] * counts.size());
+        CHECK(want != single_frames(s, cams));
+    }
+    A.alloc();
+    kifs_ctx* c = context_for(s, &cams[0]);
+    (void)adaptive_rounds();
+    // the lone frame of the context's camera, without and with its count; batches within and beyond the kernel argument
+    CHECK(A.run(c, nullptr, 0, 1, true, false, &want, &counts) == KIFS_OK);
+    CHECK(A.run(c, nullptr, 0, 1, true, true, &want, &counts) == KIFS_OK);
+    CHECK(A.run(c, nullptr, 2, 3, false, true, &want, &counts) == KIFS_OK);
+    CHECK(A.run(c, nullptr, 2, 3, false, false, &want, &counts) == KIFS_OK);
+    CHECK(adaptive_rounds() == (std::vector<int>{1, 1, 3, 3}));
+    CHECK(A.run(c, nullptr, 0, 70, false, true, &want, &counts) == KIFS_OK);  // two rounds: the second's counts at + 35
+    CHECK(adaptive_rounds() == (std::vector<int>{35, 35}));
+    CHECK(A.run(c, nullptr, 0, 70, false, false, &want, &counts) == KIFS_OK);
+    CHECK(A.run(c, nullptr, 3, 67, false, true, &want, &counts) == KIFS_OK);  // rounds of unequal size over one block
+    CHECK(adaptive_rounds() == (std::vector<int>{35, 35, 34, 33}));
+    CHECK(A.run(c, nullptr, 1, 64, false, true, &want, &counts) == KIFS_OK && A.run(c, nullptr, 1, 65, false, true, &want, &counts) == KIFS_OK);
+    CHECK(adaptive_rounds() == (std::vector<int>{64, 33, 32}));
+    A.release();
+    // a padded pitch, the other encoding, another factor and thresholds at which only hit against miss is an edge
+    AdaptiveCall B{s, cams, KifsAdaptiveAA{3, -INFINITY, INFINITY}, 0, 48};
+    const std::vector<KifsCameraUniform> few(cams.begin(), cams.begin() + 4);
+    const auto want_b = adaptive_frames(s, few, B.aa, 0, &counts);
+    B.alloc();
+    CHECK(B.run(c, nullptr, 0, 4, false, true, &want_b, &counts) == KIFS_OK);
+    CHECK(B.run(c, nullptr, 0, 1, true, true, &want_b, &counts) == KIFS_OK);
+    B.release();
+    kifs_destroy(c);
+}
+
+// The scratch block over sizes and counts that shrink and grow: freed and allocated anew exactly when a call needs more
+// than every call before it, and then of exactly the bytes the layout asks for.
+void adaptive_scratch() {
+    stub_trace_mark("adaptive_scratch");
+    const auto cams = cameras(6, 9);
+    const int calls[][3] = {{64, 40, 1}, {333, 211, 3}, {64, 40, 5}, {333, 211, 3}, {340, 211, 3}, {64, 8, 6}, {333, 211, 6}, {340, 211, 1}};
+    kifs_ctx* c = context_for(scene(64, 40, 40), &cams[0]);
+    size_t have = 0;
+    for (const auto& k : calls) {
+        const Scene s = scene(k[0], k[1], 40);
+        CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
+        AdaptiveCall A{s, cams, KifsAdaptiveAA{2, 5000.0f, 0.1f}};
+        std::vector<uint32_t> counts;
+        const auto want = adaptive_frames(s, cams, A.aa, 1, &counts);
+        A.alloc();
+        const size_t need = size_t(k[2]) * (size_t(k[0]) * size_t(k[1]) * 20 + 4);
+        const long frees = stub_device_frees(), syncs = stub_device_synchronizes();
+        CHECK(A.run(c, nullptr, 0, k[2], false, true, &want, &counts) == KIFS_OK);
+        CHECK(stub_device_frees() - frees == (need > have && have > 0 ? 1 : 0));
+        CHECK(stub_device_synchronizes() == syncs);  // (hipFree itself waits for the launches that use the block)
+        if (need > have) have = need;
+        CHECK(stub_has_device_allocation_of(have));
+        A.release();
+    }
+    kifs_destroy(c);
+    CHECK(!stub_has_device_allocation_of(have));
+}
+
+// Calls of one context on two streams and its own: the library waits for the previous call's event exactly when the
+// stream is another one than that call's.
+void adaptive_streams() {
+    stub_trace_mark("adaptive_streams");
+    const Scene s = scene(100, 50, 40);
+    const auto cams = cameras(3, 1);
+    AdaptiveCall A{s, cams, KifsAdaptiveAA{2, 5000.0f, 0.1f}};
+    std::vector<uint32_t> counts;
+    const auto want = adaptive_frames(s, cams, A.aa, 1, &counts);
+    A.alloc();
+    kifs_ctx* c = context_for(s, &cams[0]);
+    hipStream_t a = nullptr, b = nullptr;
+    CHECK(hipStreamCreateWithFlags(&a, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&b, hipStreamNonBlocking) == hipSuccess);
+    CHECK(A.run(c, a, 0, 3, false, true, &want, &counts) == KIFS_OK);
+    const int done = stub_events_created();  // (the call's last act was to create and record adaptive_done)
+    CHECK(stub_stream_waits_on(done) == 0);
+    hipStream_t order[] = {a, b, b, a, nullptr, nullptr, b, a, a};
+    hipStream_t previous = a;
+    long waits = 0;
+    for (hipStream_t st : order) {
+        CHECK(A.run(c, st, 0, 3, false, true, &want, &counts) == KIFS_OK);
+        if (st != previous) ++waits;
+        CHECK(stub_stream_waits_on(done) == waits);
+        previous = st;
+    }
+    kifs_destroy(c);
+    CHECK(hipStreamDestroy(a) == hipSuccess && hipStreamDestroy(b) == hipSuccess);
+    A.release();
+}
+
+// A round count that the 2 GiB cap on the scratch block decides: 4096 x 4096, 20 bytes a pixel and view -- six views fit,
+// seven take two rounds of 4 and 3.  (Above the stand-in's sampling threshold: model::sampled.)
+void adaptive_scratch_cap() {
+    stub_trace_mark("adaptive_scratch_cap");
+    const int w = 4096, h = 4096, views = 7;
+    const Scene s = scene(w, h, 40);
+    const auto cams = cameras(views, 2);
+    const KifsAdaptiveAA aa{2, 3.0e6f, 0.1f};
+    const size_t fb = size_t(w) * h * 4;
+    uint8_t* dev = dev_alloc(fb * views);
+    uint32_t* dev_counts = reinterpret_cast<uint32_t*>(dev_alloc((views + 2) * 4));
+    std::memset(dev_counts, 0xEE, (views + 2) * 4);
+    std::vector<uint8_t*> outs(views);
+    for (int i = 0; i < views; ++i) outs[size_t(i)] = dev + fb * size_t(i);
+    kifs_ctx* c = context_for(s, &cams[0]);
+    (void)adaptive_rounds();
+    CHECK(kifs_render_adaptive_async(c, nullptr, views, cams.data(), outs.data(), size_t(w) * 4, &aa, dev_counts + 1, 1) == KIFS_OK);
+    CHECK(adaptive_rounds() == (std::vector<int>{4, 3}));
+    CHECK(stub_has_device_allocation_of(size_t(4) * (size_t(w) * h * 20 + 4)));
+    CHECK(dev_counts[0] == 0xEEEEEEEEu && dev_counts[views + 1] == 0xEEEEEEEEu);
+    // the sample of every frame against the plain frame of a second context and the model's mask
+    kifs_ctx* plain = context_for(s, &cams[0]);
+    uint8_t* one = dev_alloc(fb);
+    for (int i = 0; i < views; ++i) {
+        CHECK(kifs_set_camera(plain, &cams[size_t(i)]) == KIFS_OK && kifs_render_async(plain, nullptr, one, size_t(w) * 4, 0, h, 1) == KIFS_OK);
+        uint32_t edges = 0;
+        bool same = true;
+        for (int y = 0; y < h; ++y) {
+            if (!model::sampled(w, h, 0, y)) { y |= 7; continue; }  // (tile column 0 is in the sample wherever the tile row is)
+            for (int x = 0; x < w; ++x) {
+                if (!model::sampled(w, h, x, y)) { x |= 31; continue; }
+                uint32_t px;
+                std::memcpy(&px, one + (size_t(y) * w + size_t(x)) * 4, 4);
+                if (model::edge(cams[size_t(i)], w, h, x, y, aa)) { px = model::adaptive_pixel(cams[size_t(i)], x, y, aa.factor); ++edges; }
+                same = same && std::memcmp(&px, outs[size_t(i)] + (size_t(y) * w + size_t(x)) * 4, 4) == 0;
+            }
+        }
+        CHECK(same && edges > 0 && dev_counts[1 + i] == edges);
+    }
+    kifs_destroy(plain);
+    kifs_destroy(c);
+    CHECK(hipFree(one) == hipSuccess && hipFree(dev) == hipSuccess && hipFree(dev_counts) == hipSuccess);
+}
+
+// Every refusal of include/kifs_hip.h for the adaptive call: the status, no HIP call, no launch, nothing written.
+void adaptive_refusals() {
+    stub_trace_mark("adaptive_refusals");
+    const Scene s = scene(100, 50, 40);
+    const auto cams = cameras(3, 1);
+    const size_t pitch = size_t(s.w) * 4, fb = pitch * s.h;
+    uint8_t* dev = dev_alloc(fb * 3);
+    uint32_t* dev_counts = reinterpret_cast<uint32_t*>(dev_alloc(12));
+    std::memset(dev, 0xEE, fb * 3);
+    std::memset(dev_counts, 0xEE, 12);
+    uint8_t* outs[3] = {dev, dev + fb, dev + 2 * fb};
+    kifs_ctx* c = context_for(s, &cams[0]);
+    const KifsAdaptiveAA good{2, 0.9f, 0.1f};
+    auto call = [&](kifs_ctx* ctx, int count, const KifsCameraUniform* cm, uint8_t* const* o, size_t p, const KifsAdaptiveAA* aa, int encode) {
+        const long calls = stub_calls(), launches = stub_launches();  // a refused call makes no HIP call and launches nothing
+        const int st = kifs_render_adaptive_async(ctx, nullptr, count, cm, o, p, aa, dev_counts, encode);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() == launches);
+        return st;
+    };
+    CHECK(call(nullptr, 3, cams.data(), outs, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), nullptr, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), outs, pitch, nullptr, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, nullptr, outs, pitch, &good, 1) == KIFS_ERR_BAD_ARG);  // the context's camera is one frame's
+    CHECK(call(c, 0, cams.data(), outs, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 513, cams.data(), outs, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    for (int factor : {-1, 0, 1, KIFS_MAX_SUPERSAMPLING + 1}) {
+        const KifsAdaptiveAA aa{factor, 0.9f, 0.1f};
+        CHECK(call(c, 3, cams.data(), outs, pitch, &aa, 1) == KIFS_ERR_BAD_ARG);
+    }
+    const KifsAdaptiveAA nan_cos{2, std::nanf(""), 0.1f}, nan_depth{2, 0.9f, std::nanf("")}, neg_depth{2, 0.9f, -0.5f};
+    CHECK(call(c, 3, cams.data(), outs, pitch, &nan_cos, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), outs, pitch, &nan_depth, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), outs, pitch, &neg_depth, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), outs, pitch, &good, 2) == KIFS_ERR_BAD_ARG);
+    uint8_t* null_out[3] = {dev, nullptr, dev}, *odd_out[3] = {dev, dev + 2, dev};
+    CHECK(call(c, 3, cams.data(), null_out, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), odd_out, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), outs, pitch - 4, &good, 1) == KIFS_ERR_BAD_ARG);  // a bad pitch: short, unaligned
+    CHECK(call(c, 3, cams.data(), outs, pitch + 2, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(kifs_set_supersampling(c, 2) == KIFS_OK);
+    CHECK(call(c, 3, cams.data(), outs, pitch, &good, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(kifs_set_supersampling(c, 1) == KIFS_OK);
+    {   // k W above 65536
+        const Scene wide = scene(16400, 8, 40);
+        CHECK(kifs_set_screen(c, &wide.screen) == KIFS_OK);
+        const KifsAdaptiveAA four{4, 0.9f, 0.1f}, five{5, 0.9f, 0.1f};
+        CHECK(KIFS_MAX_SUPERSAMPLING < 5 || call(c, 1, cams.data(), outs, size_t(16400) * 4, &five, 1) == KIFS_ERR_BAD_SIZE);
+        CHECK(KIFS_MAX_SUPERSAMPLING < 4 || call(c, 1, cams.data(), outs, size_t(16400) * 4, &four, 1) == KIFS_ERR_BAD_SIZE);
+        const Scene tall = scene(8, 16400, 40);
+        CHECK(kifs_set_screen(c, &tall.screen) == KIFS_OK);
+        CHECK(KIFS_MAX_SUPERSAMPLING < 4 || call(c, 1, cams.data(), outs, 32, &four, 1) == KIFS_ERR_BAD_SIZE);
+        CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
+    }
+    {   // unconfigured: no options, no camera
+        kifs_ctx* bare = context_for(s, nullptr, false);
+        CHECK(call(bare, 3, cams.data(), outs, pitch, &good, 1) == KIFS_ERR_UNCONFIGURED);
+        CHECK(kifs_set_options(bare, &s.options) == KIFS_OK);
+        CHECK(call(bare, 1, nullptr, outs, pitch, &good, 1) == KIFS_ERR_UNCONFIGURED);
+        kifs_destroy(bare);
+    }
+    for (size_t i = 0; i < fb * 3; ++i)
+        if (dev[i] != 0xEE) CHECK(false);
+    CHECK(dev_counts[0] == 0xEEEEEEEEu && dev_counts[2] == 0xEEEEEEEEu);
+    kifs_destroy(c);
+    CHECK(hipFree(dev) == hipSuccess && hipFree(dev_counts) == hipSuccess);
+}
+
+// ---- animated batches
+// Frame i's options: the constant, the power and both colours move, the pipeline and the march budget stay.
+std::vector<KifsOptionsUniform> morph(const KifsOptionsUniform& base, int n, int first) {
+    std::vector<KifsOptionsUniform> out(static_cast<size_t>(n), base);
+    for (int i = 0; i < n; ++i) {
+        KifsOptionsUniform& o = out[size_t(i)];
+        const float t = float(first + i);
+        o.constant[0] += 0.01f * t;
+        o.constant[3] -= 0.02f * t;
+        o.power = 2.0f + 0.125f * float((first + i) % 9);
+        o.fractal_color[1] = 0.1f + 0.01f * t;
+        o.background_color[0] = 0.002f * t;
+        o.background_color[2] = 0.5f - 0.004f * t;
+    }
+    return out;
+}
+
+// The frames kifs_render_animation_async owes: frame i as a plain render with (cams[i], opts[i]) writes it, every pixel
+// that is not background also a function of opts[i]'s scene.
+std::vector<uint8_t> animation_frames(const Scene& s, const std::vector<KifsCameraUniform>& cams, const std::vector<KifsOptionsUniform>& opts, int encode) {
+    std::vector<uint8_t> want = plain_frames(s, cams, opts, encode);
+    const size_t fb = size_t(s.w) * s.h * 4;
+    for (size_t i = 0; i < cams.size(); ++i) {
+        const uint32_t k = model::key(cams[i]), sk = model::scene_key(opts[i % opts.size()]);
+        for (int y = 0; y < s.h; ++y)
+            for (int x = 0; x < s.w; ++x) {
+                if (!model::hit(k, x, y)) continue;
+                uint32_t px;
+                uint8_t* at = want.data() + i * fb + (size_t(y) * s.w + size_t(x)) * 4;
+                std::memcpy(&px, at, 4);
+                px ^= sk;
+                std::memcpy(at, &px, 4);
+            }
+    }
+    return want;
+}
+
+struct AnimationCall {
+    const Scene& s;
+    const std::vector<KifsCameraUniform>& cams;
+    const std::vector<KifsOptionsUniform>& opts;
+    int encode = 1;
+    size_t pad = 0;
+    uint8_t* dev = nullptr;
+
+    size_t pitch() const { return size_t(s.w) * 4 + pad; }
+    size_t frame_bytes() const { return pitch() * size_t(s.h); }
+    void alloc() { dev = dev_alloc(frame_bytes() * cams.size() + 64); }
+    void release() { CHECK(hipFree(dev) == hipSuccess); }
+    // `shared_camera`: cameras NULL, every frame with the context's camera (which must be cams[first] = ... = the same)
+    int run(kifs_ctx* c, hipStream_t stream, int first, int count, int y0, int y1, bool shared_camera, const std::vector<uint8_t>* want) {
+        std::vector<uint8_t*> outs(static_cast<size_t>(count));
+        const size_t band = pitch() * size_t(y1 - y0);
+        for (int i = 0; i < count; ++i) outs[size_t(i)] = dev + band * size_t(i);
+        std::memset(dev, 0xEE, frame_bytes() * cams.size() + 64);
+        const int st = kifs_render_animation_async(c, stream, count, shared_camera ? nullptr : cams.data() + first, opts.data() + first,
+                                                   outs.data(), pitch(), y0, y1, encode);
+        if (st != KIFS_OK || !want) return st;
+        const size_t fb = size_t(s.w) * s.h * 4;
+        for (int i = 0; i < count; ++i) CHECK(rows_equal(outs[size_t(i)], pitch(), want->data() + fb * size_t(first + i), s.w, y0, y1));
+        for (size_t b = band * size_t(count); b < band * size_t(count) + 64; ++b) CHECK(dev[b] == 0xEE);
+        if (y1 > y0) CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ANIMATION && kifs_debug_last_round_steps(c) == 0);
+        return st;
+    }
+};
+
+void animation_batches(int w, int h) {
+    stub_trace_mark("animation_batches");
+    const Scene s = scene(w, h, 40);
+    const auto cams = cameras(70, 7);
+    const auto opts = morph(s.options, 70, 0);
+    AnimationCall A{s, cams, opts};
+    const auto want = animation_frames(s, cams, opts, 1);
+    CHECK(want != plain_frames(s, cams, opts, 1));
+    A.alloc();
+    // a context that never had kifs_set_options: it has none afterwards either
+    kifs_ctx* c = context_for(s, nullptr, false);
+    uint8_t* plain = dev_alloc(size_t(w) * h * 4);
+    for (int count : {1, 5, 70}) {
+        CHECK(A.run(c, nullptr, 0, count, 0, h, false, &want) == KIFS_OK);
+        CHECK(A.run(c, nullptr, 70 - count, count, 0, h, false, &want) == KIFS_OK);
+    }
+    CHECK(A.run(c, nullptr, 0, 1, 0, h, true, nullptr) == KIFS_ERR_UNCONFIGURED);  // no camera yet
+    CHECK(kifs_set_camera(c, &cams[4]) == KIFS_OK);
+    CHECK(kifs_render_async(c, nullptr, plain, size_t(w) * 4, 0, h, 1) == KIFS_ERR_UNCONFIGURED);
+    {   // the context's camera for every frame
+        const std::vector<KifsCameraUniform> same(70, cams[4]);
+        AnimationCall S{s, same, opts};
+        const auto want_same = animation_frames(s, same, opts, 1);
+        S.alloc();
+        for (int count : {1, 5, 70}) CHECK(S.run(c, nullptr, 3, std::min(count, 67), 0, h, true, &want_same) == KIFS_OK);
+        S.release();
+    }
+    CHECK(kifs_render_async(c, nullptr, plain, size_t(w) * 4, 0, h, 1) == KIFS_ERR_UNCONFIGURED);
+    // with options of its own: a plain frame before and after a call with other options is that of its own
+    const Scene other = scene(w, h, 200);
+    CHECK(kifs_set_options(c, &other.options) == KIFS_OK);
+    const auto own = single_frames(other, {cams[4]});
+    CHECK(own != single_frames(s, {cams[4]}));
+    CHECK(kifs_render_async(c, nullptr, plain, size_t(w) * 4, 0, h, 1) == KIFS_OK && equal_dev(plain, own));
+    CHECK(A.run(c, nullptr, 10, 5, 0, h, false, &want) == KIFS_OK);
+    CHECK(kifs_render_async(c, nullptr, plain, size_t(w) * 4, 0, h, 1) == KIFS_OK && equal_dev(plain, own));
+    CHECK(A.run(c, nullptr, 0, 70, 0, h, false, &want) == KIFS_OK);
+    CHECK(kifs_render_async(c, nullptr, plain, size_t(w) * 4, 0, h, 1) == KIFS_OK && equal_dev(plain, own));
+    A.release();
+    // bands with a padded pitch, the other encoding; an empty band enqueues nothing
+    AnimationCall B{s, cams, opts, 0, 80};
+    const auto want_b = animation_frames(s, cams, opts, 0);
+    B.alloc();
+    for (int count : {1, 5, 70}) {
+        CHECK(B.run(c, nullptr, 70 - count, count, h / 3, h - 3, false, &want_b) == KIFS_OK);
+        CHECK(B.run(c, nullptr, 0, count, 0, std::min(h, 9), false, &want_b) == KIFS_OK);
+        const long calls = stub_calls(), launches = stub_launches();
+        CHECK(B.run(c, nullptr, 0, count, h / 2, h / 2, false, &want_b) == KIFS_OK);
+        CHECK(stub_launches() == launches && stub_calls() == calls);
+    }
+    B.release();
+    CHECK(hipFree(plain) == hipSuccess);
+    kifs_destroy(c);
+}
+
+// The rings: a call waits on the host for the launch that read its scene table four calls ago, not sooner; the view
+// ring is the one kifs_render_batch_async uses; a call on another stream than the tile table's follows it once.
+void animation_rings() {
+    stub_trace_mark("animation_rings");
+    const Scene s = scene(100, 50, 40);
+    const auto cams = cameras(70, 7);
+    const auto opts = morph(s.options, 70, 3);
+    AnimationCall A{s, cams, opts};
+    const auto want = animation_frames(s, cams, opts, 1);
+    const auto want_plain = single_frames(s, cams);
+    A.alloc();
+    kifs_ctx* c = context_for(s, &cams[0]);
+    const size_t fb = size_t(s.w) * s.h * 4;
+    uint8_t* frames = dev_alloc(fb * 70);
+    std::vector<uint8_t*> outs(70);
+    for (int i = 0; i < 70; ++i) outs[size_t(i)] = frames + fb * size_t(i);
+    CHECK(kifs_render_async(c, nullptr, frames, size_t(s.w) * 4, 0, s.h, 1) == KIFS_OK);  // (the tile table and its events exist)
+    // six calls, no wait between them: slots 0..3 new, then slot 0's event, then slot 1's
+    int slot_event[KIFS_ANIMATION_RING];
+    for (int k = 0; k < 6; ++k) {
+        const int events = stub_events_created();
+        const long syncs = stub_event_synchronizes();
+        CHECK(A.run(c, nullptr, k, 5, 0, s.h, false, &want) == KIFS_OK);
+        if (k < KIFS_ANIMATION_RING) {
+            CHECK(stub_events_created() == events + 1 && stub_event_synchronizes() == syncs);
+            slot_event[k] = events + 1;
+        } else {
+            CHECK(stub_events_created() == events && stub_event_synchronizes() == syncs + 1);
+            CHECK(stub_event_synchronizes_on(slot_event[k - KIFS_ANIMATION_RING]) == 1);
+        }
+    }
+    // animated calls of 70 frames between batches of 70: one view ring, every slot waited for before it is rewritten
+    for (int k = 0; k < 10; ++k) {
+        const long syncs = stub_event_synchronizes();
+        if (k % 3 == 1) {
+            std::memset(frames, 0xEE, fb * 70);
+            CHECK(kifs_render_batch_async(c, nullptr, 70, cams.data(), outs.data(), size_t(s.w) * 4, 0, s.h, 1) == KIFS_OK);
+            CHECK(equal_dev(frames, want_plain));
+            CHECK(stub_event_synchronizes() - syncs == (k >= 4 ? 1 : 0));  // its view slot's previous launch
+        } else {
+            CHECK(A.run(c, nullptr, 0, 70, 0, s.h, false, &want) == KIFS_OK);
+            CHECK(stub_event_synchronizes() - syncs == (k >= 4 ? 2 : 1));  // the scene slot's, and the view slot's
+        }
+    }
+    // the caller's stream after the context's, and back: one record on the stream left and one wait, once per change
+    hipStream_t caller = nullptr;
+    CHECK(hipStreamCreateWithFlags(&caller, hipStreamNonBlocking) == hipSuccess);
+    hipStream_t order[] = {nullptr, caller, caller, nullptr, nullptr, caller};
+    hipStream_t previous = nullptr;
+    CHECK(A.run(c, nullptr, 0, 5, 0, s.h, false, &want) == KIFS_OK);
+    for (hipStream_t st : order) {
+        const long waits = stub_stream_waits();
+        CHECK(A.run(c, st, 0, 5, 0, s.h, false, &want) == KIFS_OK);
+        CHECK(stub_stream_waits() - waits == (st != previous ? 1 : 0));
+        previous = st;
+    }
+    CHECK(hipStreamDestroy(caller) == hipSuccess);
+    kifs_destroy(c);
+    CHECK(hipFree(frames) == hipSuccess);
+    A.release();
+}
+
+void animation_refusals() {
+    stub_trace_mark("animation_refusals");
+    const Scene s = scene(100, 50, 40);
+    const auto cams = cameras(3, 1);
+    auto opts = morph(s.options, 3, 0);
+    const size_t pitch = size_t(s.w) * 4, fb = pitch * s.h;
+    uint8_t* dev = dev_alloc(fb * 3);
+    std::memset(dev, 0xEE, fb * 3);
+    uint8_t* outs[3] = {dev, dev + fb, dev + 2 * fb};
+    kifs_ctx* c = context_for(s, &cams[0]);
+    auto call = [&](kifs_ctx* ctx, int count, const KifsCameraUniform* cm, const KifsOptionsUniform* o, uint8_t* const* out, size_t p, int y0, int y1,
+                    int encode) {
+        const long calls = stub_calls(), launches = stub_launches();  // a refused call makes no HIP call and launches nothing
+        const int st = kifs_render_animation_async(ctx, nullptr, count, cm, o, out, p, y0, y1, encode);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() == launches);
+        return st;
+    };
+    CHECK(call(nullptr, 3, cams.data(), opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), nullptr, outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), nullptr, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    uint8_t* null_out[3] = {dev, nullptr, dev}, *odd_out[3] = {dev, dev, dev + 1};
+    CHECK(call(c, 3, cams.data(), opts.data(), null_out, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), odd_out, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 0, cams.data(), opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 513, cams.data(), opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch, 0, s.h, 2) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch, -1, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch, 0, s.h + 1, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch, 9, 8, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch - 4, 0, s.h, 1) == KIFS_ERR_BAD_SIZE);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch + 2, 0, s.h, 1) == KIFS_ERR_BAD_SIZE);
+    {   // a pipeline that does not exist; frames that differ where they may not -- by bit pattern, padding apart
+        auto o = opts;
+        for (auto& f : o) f.fractal_group_id = 3;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts; o[2].max_iterations += 1;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts; o[1].max_distance *= 2.0f;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts; o[1].is_heatmap = 1;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts; o[2].fractal_group_id = 2;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts; o[2].primitive_id = 3;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+        o = opts;
+        for (auto& f : o) f.epsilon = 0.0f;
+        o[1].epsilon = -0.0f;
+        CHECK(call(c, 3, cams.data(), o.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    }
+    CHECK(kifs_set_supersampling(c, 2) == KIFS_OK);
+    CHECK(call(c, 3, cams.data(), opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_BAD_ARG);
+    CHECK(kifs_set_supersampling(c, 1) == KIFS_OK);
+    {   // no camera with cameras NULL; no screen
+        kifs_ctx* bare = context_for(s, nullptr, false);
+        CHECK(call(bare, 3, nullptr, opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_UNCONFIGURED);
+        kifs_destroy(bare);
+        int st = 0;
+        bare = kifs_create(0, &st);
+        CHECK(bare && call(bare, 3, cams.data(), opts.data(), outs, pitch, 0, s.h, 1) == KIFS_ERR_UNCONFIGURED);
+        kifs_destroy(bare);
+    }
+    for (size_t i = 0; i < fb * 3; ++i)
+        if (dev[i] != 0xEE) CHECK(false);
+    // junk in the padding words is no difference: accepted, and the frames are those of the clean images
+    auto junk = opts;
+    junk[1]._padding1 = 0xdeadbeefu;
+    junk[2]._padding2 = 0x12345678u;
+    junk[0]._padding3 = 0xffffffffu;
+    AnimationCall A{s, cams, junk};
+    const auto want = animation_frames(s, cams, opts, 1);
+    A.alloc();
+    CHECK(A.run(c, nullptr, 0, 3, 0, s.h, false, &want) == KIFS_OK);
+    A.release();
+    kifs_destroy(c);
+    CHECK(hipFree(dev) == hipSuccess);
+}
+
+// Every HIP call and launch of an adaptive call of 70 views and of animated calls of 5 and of 70 frames fails once, in
+// turn, on a fresh context and on a warm one (scratch, rings and tables allocated): the call reports KIFS_ERR_RUNTIME or
+// absorbs the failure; KIFS_ANIMATION_RING + 1 more calls of its kind and a batch of 70 each return a status -- the rings
+// come round to whatever slot the failure left half made -- and from the first that succeeds on every frame is exact;
+// the destroy leaves nothing behind.
+void extension_injected_failures(int w, int h) {
+    stub_trace_mark("extension_injected_failures");
+    const Scene s = scene(w, h, 10);
+    const auto cams = cameras(70, 13);
+    const auto opts = morph(s.options, 70, 1);
+    AdaptiveCall A{s, cams, KifsAdaptiveAA{2, 5000.0f, 0.1f}};
+    AnimationCall M{s, cams, opts};
+    std::vector<uint32_t> counts;
+    const auto want_adaptive = adaptive_frames(s, cams, A.aa, 1, &counts);
+    const auto want_animation = animation_frames(s, cams, opts, 1);
+    const auto want_plain = single_frames(s, cams);
+    A.alloc();
+    M.alloc();
+    const size_t fb = size_t(w) * h * 4;
+    uint8_t* frames = dev_alloc(fb * 70);
+    std::vector<uint8_t*> outs(70);
+    for (int i = 0; i < 70; ++i) outs[size_t(i)] = frames + fb * size_t(i);
+    const size_t own_allocations = stub_live_device_allocations(), own_handles = stub_live_streams_and_events();
+    for (int kind = 0; kind < 3; ++kind) {  // adaptive 70, animated 5, animated 70
+        auto call = [&](kifs_ctx* c) {
+            return kind == 0 ? A.run(c, nullptr, 0, 70, false, true, &want_adaptive, &counts)
+                             : M.run(c, nullptr, 0, kind == 1 ? 5 : 70, 0, h, false, &want_animation);
+        };
+        for (int warm = 0; warm < 2; ++warm) {
+            int failed = 0;
+            for (long n = 1; n < 400; ++n) {
+                kifs_ctx* c = context_for(s, &cams[0]);
+                if (warm)
+                    for (int k = 0; k < KIFS_ANIMATION_RING; ++k) CHECK(call(c) == KIFS_OK);
+                const long before = stub_calls();
+                stub_fail_in(n);
+                const int st = call(c);  // (KIFS_OK: the frames have been compared)
+                const bool reached = stub_calls() - before >= n;
+                stub_fail_in(-1);
+                CHECK(st == KIFS_OK || st == KIFS_ERR_RUNTIME);
+                if (st != KIFS_OK) ++failed;
+                bool ok_seen = false;
+                for (int k = 0; k < KIFS_ANIMATION_RING + 2; ++k) {
+                    int again;
+                    if (k == 2) {
+                        std::memset(frames, 0xEE, fb * 70);
+                        again = kifs_render_batch_async(c, nullptr, 70, cams.data(), outs.data(), size_t(w) * 4, 0, h, 1);
+                        if (again == KIFS_OK) CHECK(equal_dev(frames, want_plain));
+                    } else {
+                        again = call(c);
+                    }
+                    CHECK(again == KIFS_OK || (again == KIFS_ERR_RUNTIME && !ok_seen));
+                    ok_seen = ok_seen || again == KIFS_OK;
+                }
+                CHECK(ok_seen);
+                kifs_destroy(c);
+                CHECK(stub_live_device_allocations() == own_allocations && stub_live_streams_and_events() == own_handles);
+                if (!reached) break;
+            }
+            CHECK(failed >= 3);  // (a warm animated call of 5 frames: the copy, the launch, the record)
+        }
+    }
+    CHECK(hipFree(frames) == hipSuccess);
+    M.release();
+    A.release();
+}
+
 }  // namespace
 
 int main() {
@@ -997,6 +1695,17 @@ int main() {
     injected_failures(100, 50);
     context_lifecycle();
     launch_shapes();
+    adaptive_batches(333, 211);  // neither dimension a multiple of the 32 x 8 tile
+    adaptive_batches(96, 20);  // (every camera sees a tile that holds something)
+    adaptive_scratch();
+    adaptive_streams();
+    adaptive_scratch_cap();
+    adaptive_refusals();
+    animation_batches(333, 211);
+    animation_batches(64, 8);
+    animation_rings();
+    animation_refusals();
+    extension_injected_failures(100, 50);
     CHECK(stub_live_device_allocations() == 0);
     CHECK(stub_live_streams_and_events() == 0);
     std::printf("host_driver: %ld checks ok\n", g_checks);

@@ -246,6 +246,51 @@ def test_batch_beyond_the_inline_views(ags, kifs):
         assert st1 == 0 and (got[i] == lone[0]).all() and counts[i] == c1[0], i
 
 
+def test_rounds_under_the_scratch_cap(kifs):
+    """Seven 4096 x 4096 views: at 20 bytes a pixel and view only six fit the 2 GiB cap on the scratch block, so the call
+    runs as two rounds of 4 and 3 views over one block of 1.25 GiB -- the smallest shape at which the cap, not the kernel
+    argument's 64 views, decides the rounds and leaves them uneven (below 1.68 Mpixel a view it never binds).  Every frame
+    and count equals the same view's lone call on a second context, on the device; one frame of the second round is the
+    plain batch frame wherever the model's mask of its own geometry plane is false, and its count is that mask's.  No
+    oracle frame at this size."""
+    import torch
+    w = h = 4096
+    views = 7
+    screen, _, gui, iters = cases(kifs, w, h)["julia_24"]
+    cams = [kifs.CameraData(origin_distance=2.3 + 0.2 * i, phi=0.55 * i, theta=0.12 * (i - 3)) for i in range(views)]
+    th = AR.DEFAULT
+    with kifs.GraphicState(0, screen_data=screen, camera_data=cams[0], gui_data=gui) as g, \
+            kifs.GraphicState(0, screen_data=screen, camera_data=cams[0], gui_data=gui) as lone:
+        g.set_iters(*iters)
+        lone.set_iters(*iters)
+        colour = torch.full((views, h, w, 4), SENT, dtype=torch.uint8, device="cuda:0")
+        counts = torch.full((views,), SENT_COUNT, dtype=torch.int32, device="cuda:0")
+        one = torch.full((1, h, w, 4), SENT, dtype=torch.uint8, device="cuda:0")
+        count1 = torch.full((1,), SENT_COUNT, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        g.render_adaptive_batch(cams, k=2, normal_cos=th[0], depth_rel=th[1], colour=colour, edge_counts=counts)
+        g.synchronize()
+        assert g.debug_last_kernel() == "render_adaptive_kernel"
+        got_counts = counts.cpu().numpy()
+        assert got_counts.min() > 0 and len(set(got_counts.tolist())) == views
+        for i, cam in enumerate(cams):
+            lone.set_camera(cam)
+            lone.render_adaptive_batch(None, k=2, normal_cos=th[0], depth_rel=th[1], colour=one, edge_counts=count1)
+            lone.synchronize()
+            assert torch.equal(colour[i], one[0]), f"view {i}: {int((colour[i] != one[0]).any(-1).sum())} pixels differ"
+            assert int(got_counts[i]) == int(count1.item()), i
+        # view 5, the second round's second: its plain pixels, and its count against the mask
+        v = 5
+        _, geometry = lone.render_geometry_batch([cams[v]])
+        plain = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda:0")
+        lone.render_batch_async([plain], [cams[v]])
+        lone.synchronize()
+        mask = torch.from_numpy(AR.edge_mask(geometry[0].cpu().numpy(), *th)).to("cuda:0")
+        assert int(mask.sum().item()) == int(got_counts[v])
+        differs = (colour[v] != plain).any(-1)
+        assert not (differs & ~mask).any() and (differs & mask).any()
+
+
 def test_padded_pitch_is_left_alone(ags, kifs, oracle):
     scene = cases(kifs, W, H)["torus"]
     _setup(ags, *scene)

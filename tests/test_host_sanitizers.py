@@ -1,10 +1,11 @@
-"""The host side of the library (kifs_api / kifs_schedule / kifs_shards / kifs_multi / kifs_host: 2 500 lines of slot,
-stream, event and buffer bookkeeping) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU: `make asan`
-compiles those five files as plain C++ with -fsanitize=address,undefined and links them with tests/hip_stub/ -- a
-synchronous in-memory stand-in for the HIP runtime API and the kernel launchers (test infrastructure; the product has no
-CPU path) -- into a driver that replays the multi-device, shard, sparse and batch scenarios of the GPU tests, injects a
-failure into every HIP call of a submit / wait cycle in turn, and finally asks the stand-in whether any allocation,
-stream or event is still alive.  VERDICT r03 weak 12 / item 8a; the GPU pool offers no sanitizers."""
+"""The host side of the library (kifs_api / kifs_schedule / kifs_shards / kifs_multi / kifs_host / kifs_adaptive /
+kifs_animation: 2 700 lines of slot, stream, event and buffer bookkeeping) under AddressSanitizer +
+UndefinedBehaviorSanitizer, on the CPU: `make asan` compiles those seven files as plain C++ with
+-fsanitize=address,undefined and links them with tests/hip_stub/ -- a synchronous in-memory stand-in for the HIP runtime
+API and the kernel launchers (test infrastructure; the product has no CPU path) -- into a driver that replays the
+multi-device, shard, sparse, batch, adaptive and animation scenarios of the GPU tests, injects a failure into every HIP
+call of a submit / wait cycle in turn, and finally asks the stand-in whether any allocation, stream or event is still
+alive.  VERDICT r03 weak 12 / item 8a; the GPU pool offers no sanitizers."""
 import subprocess
 from pathlib import Path
 
