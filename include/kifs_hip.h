@@ -321,6 +321,48 @@ int kifs_render_animation_async(kifs_ctx* ctx, void* hip_stream, int count,
                                 uint8_t* const* dev_outs_rgba8, size_t pitch_bytes,
                                 int y0, int y1, int encode);
 
+/* ---- extension: accumulated frames -- motion blur, depth of field and temporal anti-aliasing in one launch -----
+ * NOT part of the reference (every frame it draws is an instantaneous pinhole exposure: entry.wgsl:49-59).  A film made
+ * of these sequences wants motion blur over the shutter interval, depth of field from a finite lens, a morph without
+ * temporal aliasing.  All three are one operation: the average of several SUB-FRAMES that differ in camera, scene or
+ * both, taken in linear colour before the encode -- which no caller can do from encoded RGBA8 bytes.
+ *   sub-frames  output frame i, 0 <= i < count, has sub-frames s = 0 .. samples-1; sub-frame s is view v = i * samples + s.
+ *             Its colour c_s(p) is the linear colour fs_main returns for pixel p with cameras[v] and options[v]
+ *             (options == NULL: the context's options for every view).  Screen, iteration counts and extensions are the
+ *             context's; heatmap colours and soft shadows apply per sub-frame.  These are exactly the values a plain
+ *             render encodes.  The context's own camera is neither used nor changed.
+ *   resolve   per channel in f32, without fma: acc = c_0(p); acc = acc + c_s(p) for s = 1 .. samples-1, in that order;
+ *             mean = acc / float(samples), correctly rounded; then the frame's encoder (sRGB or UNORM; alpha 255), into
+ *             dev_outs_rgba8[i].
+ *   single    samples = 1 gives the bytes of kifs_render_batch_async exactly.
+ *   misses    a sub-frame whose ray misses contributes its own background_color; rays dropped by any cull are misses.  A
+ *             pixel that every sub-frame misses is the same formula applied to the backgrounds -- not the encoded
+ *             background pixel: three equal f32 values summed and divided by 3 need not give the value back, and the
+ *             sub-frames' backgrounds may differ.
+ *   limits    1 <= samples <= KIFS_MAX_ACCUMULATE, 1 <= count, count * samples <= KIFS_MAX_BATCH.
+ *   varying   as kifs_render_animation_async, over all count * samples images: constant, power, fractal_color and
+ *             background_color may differ; max_iterations, max_distance, epsilon, is_heatmap, fractal_group_id and
+ *             primitive_id must be bit-identical to options[0]'s in every image.  Padding words are ignored.
+ *   bands     rows [y0, y1), pitch_bytes, encode, stream and kifs_order_after as kifs_render_batch_async: a band is
+ *             bit-identical to the same rows of the whole frame; bytes of a row beyond 4 W are not touched.
+ *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: a null ctx, cameras or dev_outs_rgba8; a
+ *             null or misaligned destination; samples outside 1 .. KIFS_MAX_ACCUMULATE; count below 1 or count * samples
+ *             above KIFS_MAX_BATCH; a bad encode or band; a fractal_group_id above 2; images that differ where they may
+ *             not; the context's supersampling factor above 1 (out of scope, as for the other extensions).
+ *             KIFS_ERR_BAD_SIZE: a bad pitch.  KIFS_ERR_UNCONFIGURED: no screen, or no options with options == NULL.
+ *   tables    the views' scenes travel through the ring of kifs_render_animation_async's tables (KIFS_ANIMATION_RING
+ *             per context, shared by both calls), with the context's scene in every record when options == NULL.
+ *   launch    like an animated launch the call neither records tile costs nor advances the tile-order sort and is not
+ *             timed by kifs_set_profiling; kifs_debug_last_kernel reports KIFS_KERNEL_ACCUMULATE,
+ *             kifs_debug_last_round_steps 0, kifs_debug_last_group_tiles and kifs_debug_last_bunny_form -1.
+ *   no shards row shards, the geometry output, adaptive anti-aliasing and kifs_multi_* have no accumulated form. */
+#define KIFS_MAX_ACCUMULATE 64
+int kifs_render_accumulate_async(kifs_ctx* ctx, void* hip_stream, int count, int samples,
+                                 const KifsCameraUniform* cameras,   /* count * samples images; not NULL */
+                                 const KifsOptionsUniform* options,  /* count * samples images, or NULL: the context's options */
+                                 uint8_t* const* dev_outs_rgba8,     /* count destinations */
+                                 size_t pitch_bytes, int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);
@@ -519,7 +561,7 @@ double kifs_last_kernel_ms(kifs_ctx* ctx);
  * kifs_render, kifs_render_async, kifs_render_batch_async, kifs_render_shard_async and
  * kifs_render_geometry_async, and of kifs_render_adaptive_async its first pass only (the plain frame
  * with its geometry; neither the classification nor the resolve of the edge pixels); a launch of
- * kifs_render_animation_async is not timed and does not count towards every n-th. */
+ * kifs_render_animation_async or kifs_render_accumulate_async is not timed and does not count towards every n-th. */
 int kifs_set_profiling(kifs_ctx* ctx, int enable);
 int kifs_profile_read(kifs_ctx* ctx, int* launches, double* mean_ms, double* min_ms, double* max_ms);
 
@@ -579,7 +621,8 @@ enum KifsKernel {
     KIFS_KERNEL_SSAA = 5,        /* ssaa::render_kernel: k x k supersampling (kifs_set_supersampling), every pipeline */
     KIFS_KERNEL_GEOMETRY = 6,    /* geom::render_kernel: colour plus the geometry plane (kifs_render_geometry_async) */
     KIFS_KERNEL_ADAPTIVE = 7,    /* adaptive::render_kernel: the edge pixels' k x k resolve (kifs_render_adaptive_async) */
-    KIFS_KERNEL_ANIMATION = 8    /* anim::render_kernel: a scene per view (kifs_render_animation_async) */
+    KIFS_KERNEL_ANIMATION = 8,   /* anim::render_kernel: a scene per view (kifs_render_animation_async) */
+    KIFS_KERNEL_ACCUMULATE = 9   /* accum::render_kernel: the mean of a frame's sub-frames (kifs_render_accumulate_async) */
 };
 int kifs_debug_last_kernel(kifs_ctx* ctx);
 /* The bunny's throughput form in the context's latest launch: 0 = four lanes per ray with every weight in VGPRs, 1 = four

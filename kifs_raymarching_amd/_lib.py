@@ -101,6 +101,8 @@ SIGNATURES = {
                                              _P(AdaptiveAAC), C.c_void_p, C.c_int]),
     "kifs_render_animation_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(OptionsUniform), _P(C.c_void_p),
                                               C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_render_accumulate_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
+                                               _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

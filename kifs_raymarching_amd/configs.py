@@ -117,3 +117,70 @@ def morph_options(gui_a: GuiData, gui_b: GuiData, n: int) -> list:
             v = a + (b - a) * t
         frames.append(replace(gui_a, constant=tuple(float(x) for x in v[:4]), power=float(v[4])))
     return frames
+
+
+def shutter_cameras(workload_or_orbit, frame: int, samples: int, shutter: float = 0.5) -> list:
+    """The `samples` sub-frame cameras of orbit frame `frame` for GraphicState.render_accumulate (motion blur): the
+    shutter is open for `shutter` x the angle between two frames of the orbit, centred on the frame, and sub-frame s
+    sits in the middle of the s-th of `samples` equal parts of that interval:
+        phi_s = phi + step * ((s + 0.5) / samples - 0.5),  phi = f32(2 pi frame / frames),  step = f32(shutter) * f32(2 pi / frames),
+    every operation after those roundings in f32.  One sample is orbit_camera(frame)'s f32 angle itself, whatever the
+    shutter.  `workload_or_orbit`: a Workload (its camera and max(frames, 120) frames per turn, as orbit_camera) or a
+    (CameraData, frames per turn) pair."""
+    if samples < 1:
+        raise ValueError("shutter_cameras: at least one sub-frame")
+    if isinstance(workload_or_orbit, Workload):
+        base, frames = workload_or_orbit.camera, max(workload_or_orbit.frames, 120)
+    else:
+        base, frames = workload_or_orbit
+    f32 = np.float32
+    phi = f32(2.0 * math.pi * frame / frames)
+    step = f32(shutter) * f32(2.0 * math.pi / frames)
+    cams = []
+    for s in range(samples):
+        t = (f32(s) + f32(0.5)) / f32(samples) - f32(0.5)
+        cams.append(CameraData(origin_distance=base.origin_distance, min_distance=base.min_distance,
+                               phi=float(phi + step * t), theta=base.theta))
+    return cams
+
+
+LENS_GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))  # the turn between two points of lens_points
+
+
+def lens_points(aperture: float, samples: int) -> np.ndarray:
+    """The fixed point set of lens_cameras, (samples, 2) float32 offsets (a, b) in the lens plane: Vogel's spiral over
+    the disc of radius `aperture` -- point s at radius aperture * sqrt(s / samples) and angle s * LENS_GOLDEN_ANGLE
+    (radius and angle in f64, the offsets r cos, r sin rounded to f32).  Point 0 is the lens' centre: the pinhole."""
+    pts = np.zeros((samples, 2), dtype=np.float32)
+    for s in range(samples):
+        r, a = aperture * math.sqrt(s / samples), s * LENS_GOLDEN_ANGLE
+        pts[s] = (r * math.cos(a), r * math.sin(a))
+    return pts
+
+
+def lens_cameras(camera_data: CameraData, aperture: float, focus_distance: float, samples: int):
+    """The `samples` sub-frame cameras of a thin lens for GraphicState.render_accumulate (depth of field), as a C array
+    of raw CameraUniform images (graphics.camera_array takes it as it is).  With the pinhole image's origin o and
+    matrix columns m0, m1, m2 (pixel (ux, uy) looks along ux m1 - uy m2 - m0: entry.wgsl:49-59), sub-frame s moves the
+    origin by lens_points' (a, b) in the lens plane and re-aims the forward axis at the focus point:
+        o_s = o + (a m1 + b m2),   m0_s = m0 + (a m1 + b m2) / focus_distance,   m1, m2 unchanged,
+    every operation in f32, the sum in brackets first.  Every pixel's ray then still passes through the point the
+    pinhole's ray reaches on the plane `focus_distance` in front of the camera: that plane stays sharp, everything else
+    is spread over the lens.  (m0_s is deliberately not renormalised: the shear is what keeps the plane of focus a plane.)
+    Sub-frame 0 is the pinhole image itself."""
+    from .graphics import CameraUniform
+    if samples < 1 or not focus_distance > 0.0:
+        raise ValueError("lens_cameras: at least one sub-frame and a positive focus distance")
+    f32 = np.float32
+    base = camera_data.into_buffer_data() if hasattr(camera_data, "into_buffer_data") else camera_data
+    o = np.array(base.origin[:], dtype=f32)
+    m = [np.array(base.matrix[c][:3], dtype=f32) for c in range(3)]
+    out = (CameraUniform * samples)()
+    for s, (a, b) in enumerate(lens_points(aperture, samples)):
+        shift = a * m[1] + b * m[2]
+        o_s, m0_s = o + shift, m[0] + shift / f32(focus_distance)
+        u = out[s]
+        u.origin[:] = [float(v) for v in o_s]
+        for c, col in enumerate((m0_s, m[1], m[2])):
+            u.matrix[c][:] = [float(v) for v in col] + [0.0]
+    return out

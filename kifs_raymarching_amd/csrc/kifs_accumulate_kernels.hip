@@ -1,0 +1,158 @@
+// kifs_accumulate_kernels.hip -- accumulated frames (kifs_render_accumulate_async, include/kifs_hip.h): every output
+// frame is the mean of `samples` sub-frames that differ in camera, scene or both -- motion blur over a shutter interval,
+// depth of field from a finite lens, the temporal anti-aliasing of a morph.  The mean is taken in linear colour, before
+// the encode, and only a kernel holds that colour (kifs_ssaa_kernels.hip); no sub-frame ever reaches memory.
+//
+//   accum::render_kernel<GROUP, PRIM>  256 threads per 8 x 8 OUTPUT block and output frame: four workgroups share an
+//                                      entry of the launch's tile order, one per 8-column block of the 32 x 8 tile.
+//                                      Wave w marches sub-frames w, w + 4, .. of the block as whole rays, 64 lanes = the
+//                                      block's 64 pixels, under the wave-level cull of that sub-frame's camera, and leaves
+//                                      each lane's linear colour in LDS at [s][channel][lane].  After a barrier wave 0 adds
+//                                      a pixel's sub-frames in the contract's order, divides, encodes and stores.
+// Why not the supersampling kernel's shape (a lane marches all of its samples one after another): a launch is as long as
+// its longest rays, and that shape makes a lone frame's critical ray `samples` rays long.  Here the
+// sub-frames of a block run side by side on four waves, and the blocks of every output frame side by side on the device.
+// (Measured: min(samples, 16) waves per workgroup, a wave per sub-frame up to 16, left the lone frame of 16 sub-frames
+// where it was and cost six frames of eight 14 %: DESIGN 5.11.)
+// No atomics and no sums across workgroups: the order of the additions is the contract's.
+// A view of the launch is a SUB-FRAME: view f * samples + s, with its camera (inline up to MAX_BATCH_INLINE views,
+// through the view-table ring beyond) and its scene record (anim::SceneView, always present: the host fills the table
+// with the context's scene when the caller gives no options).  Both are read with scalar loads: the view index is
+// wave-uniform and made so explicitly (readfirstlane of the wave's number).
+// LDS: samples * 768 bytes of dynamic memory (48 KB at 64 sub-frames) beside the 1 KB sRGB table; lanes access
+// consecutive words, no bank conflicts.  Stores: one 4-byte pixel per lane, eight 32-byte row segments per instruction,
+// under the guards of a ragged frame edge and a band's last row.
+// The entry point's host side is kifs_accumulate.cpp; it reaches the kernel through launch_accumulate_render at the end
+// of this file (kifs_internal.hpp).
+#include "kifs_render_common.hpp"
+
+namespace kifs {
+namespace accum {
+
+constexpr int BLOCK_W = 8;                         // an output block: 8 x 8 pixels, one lane each
+constexpr uint32_t BLOCKS = TILE_W / BLOCK_W;      // blocks per entry of the tile order
+constexpr uint32_t WAVES = BLOCK / 64;             // sub-frames in flight per workgroup
+constexpr uint32_t SLOT = 3 * 64;                  // floats per sub-frame in LDS: [channel][lane]
+
+// View `view`'s scene over its frame constants, as anim::overlay_scene lays it (the encoded background is not used: a
+// pixel every sub-frame misses is still the mean of the backgrounds, encoded like any other).
+__device__ __forceinline__ void overlay_scene(FrameParams& P, const anim::SceneView* scenes, uint32_t view) {
+    typedef const anim::SceneView __attribute__((address_space(4))) * ConstScene;
+    const ConstScene s = (ConstScene)(scenes + view);
+    P.c = V4{s->c.x, s->c.y, s->c.z, s->c.w};
+    P.power = s->power;
+    P.fractal_color = V3{s->fractal_color.x, s->fractal_color.y, s->fractal_color.z};
+    P.background_color = V3{s->background_color.x, s->background_color.y, s->background_color.z};
+}
+
+// The kernel argument again, through a pointer the compiler cannot see through: inside the sub-frame loop every frame
+// constant is then loaded where the march uses it (scalar loads from the argument segment, a few hundred bytes per ray
+// march) instead of all of them being held in SGPRs across the loop beside the Julia march's pinned s74-s97 -- which
+// cost 36 parked SGPRs, two spilled VGPRs and a private segment.
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+__device__ __forceinline__ const Params& reloaded(ConstParams& kp) {
+    asm volatile("" : "+s"(kp));
+    return *(const Params*)kp;
+}
+
+// (amdgpu_waves_per_eu: as ssaa::render_kernel, whose sample loop this one's sub-frame loop resembles)
+template <int GROUP, int PRIM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void render_kernel(const Params A) {
+    __shared__ float s_srgb[256];
+    extern __shared__ float s_colour[];  // [samples][3][64]
+
+    ConstParams kp = (ConstParams)__builtin_amdgcn_kernarg_segment_ptr();  // = &A
+    int tid = threadIdx.x;
+    const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(tid >> 6));  // uniform, and known to be
+    const uint32_t frames = uint32_t(A.frames), samples = uint32_t(A.samples);
+    // workgroup b works on output frame b % frames, so the long rays of every frame start at t = 0 (launch_slot)
+    const uint32_t frame = frames > 1 ? blockIdx.x % frames : 0u;
+    const uint32_t index = frames > 1 ? blockIdx.x / frames : blockIdx.x;
+    if (A.B.frame.encode == 1) s_srgb[tid] = A.B.frame.srgb_table[tid];
+    const uint32_t tile = A.B.frame.tile_order[index / BLOCKS];
+    const int block_x = int(tile & 0xffffu) * TILE_W + BLOCK_W * int(index % BLOCKS);
+    if (block_x >= A.B.frame.width) return;  // uniform: a block beyond the frame's right edge (before any barrier)
+    const int tile_y = int(tile >> 16) * TILE_H;
+    const int frame_y = tile_frame_row(A.B.frame, tile >> 16);
+
+    for (uint32_t s = wave; s < samples; s += WAVES) {  // scalar
+        const Params& L = reloaded(kp);
+        asm volatile("" : "+v"(tid));  // (and the lane's pixel from its number: one VGPR across the march, not four)
+        const uint32_t lane = uint32_t(tid) & 63u;
+        const int x = block_x + int(lane & 7u), y = frame_y + int(lane >> 3);
+        const uint32_t view = frame * samples + s;
+        FrameParams P = batch_frame(L.B, view);
+        overlay_scene(P, L.scenes, view);
+        const bool valid = (x < P.width) && (y < P.y1);
+        V3 c = P.background_color;  // a ray the cull drops is a miss
+        if (!wave_is_culled(P, x, y, valid)) {  // wave-uniform
+            int steps = 0;
+            const V3 dir = ray_direction(P, x, y);
+            c = raymarch<GROUP, PRIM>(P, dir, valid, steps);
+        }
+        float* const slot = s_colour + s * SLOT + lane;
+        slot[0] = c.x;
+        slot[64] = c.y;
+        slot[128] = c.z;
+    }
+    __syncthreads();  // every sub-frame's colours and s_srgb visible
+    if (wave != 0u) return;
+
+    // The resolve of the contract, per channel in f32: acc = c_0, then acc + c_s in order (-ffp-contract=off: no fma),
+    // mean = acc / samples correctly rounded, then the frame's encoder.
+    const uint32_t lane = uint32_t(tid) & 63u;
+    const float* at = s_colour + lane;
+    V3 acc{at[0], at[64], at[128]};
+    for (uint32_t s = 1; s < samples; ++s) {
+        at += SLOT;
+        acc = V3{acc.x + at[0], acc.y + at[64], acc.z + at[128]};
+    }
+    const float n = float(samples);
+    const FrameParams& C = reloaded(kp).B.frame;  // what every view shares
+    const uint32_t rgba = encode_rgba(V3{acc.x / n, acc.y / n, acc.z / n}, C.encode == 1, s_srgb);
+    const int ly = int(lane >> 3);
+    const int x = block_x + int(lane & 7u), y = frame_y + ly;
+    if (x < C.width && y < C.y1) {
+        uint32_t* const out = batch_frame(reloaded(kp).B, frame * samples).out;  // (every sub-frame of a frame carries it)
+        out[out_row(C, y, tile_y + ly) * C.pitch_words + uint32_t(x)] = rgba;
+    }
+}
+
+// From 63 sub-frames the dynamic LDS and the 1 KB sRGB table together pass the default limit of 48 KB: the kernel then opts
+// in, once per instantiation and device, as ensure_dynamic_lds does for the residency pad (kifs_render_common.hpp).
+template <int GROUP, int PRIM>
+static hipError_t ensure_lds(unsigned dynamic_bytes) {
+    if (dynamic_bytes + 256u * unsigned(sizeof(float)) <= 48u * 1024u) return hipSuccess;
+    static std::atomic<bool> opted_in[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
+        hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        if (attr != hipSuccess) return attr;
+        if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+
+template <int GROUP, int PRIM>
+static hipError_t launch(const Params& A, hipStream_t stream) {
+    const unsigned lds = unsigned(A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
+    if (hipError_t e = ensure_lds<GROUP, PRIM>(lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), dim3(A.B.frame.tile_count * BLOCKS * uint32_t(A.frames)), dim3(BLOCK), lds,
+                       stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace accum
+
+hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream) {
+    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
+    // Julia: the short divide / square root by sdf_iters; the doubled orbit trip is the throughput kernels' only.
+    // The bunny: per-lane bunny_sdf -- slow, correct.
+    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
+        return accum::launch<decltype(g)::value, decltype(prim)::value>(A, stream);
+    });
+}
+
+}  // namespace kifs

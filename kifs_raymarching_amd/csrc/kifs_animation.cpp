@@ -11,7 +11,7 @@ namespace anim {
 
 // The fields every frame of a launch shares: one pipeline, one march budget.  Bit patterns, not values: -0.0f is not 0.0f
 // and a NaN equals itself here.  Padding words are not looked at.
-static bool same_pipeline(const KifsOptionsUniform& a, const KifsOptionsUniform& b) {
+bool same_pipeline(const KifsOptionsUniform& a, const KifsOptionsUniform& b) {
     return a.max_iterations == b.max_iterations && std::memcmp(&a.max_distance, &b.max_distance, sizeof(float)) == 0 &&
            std::memcmp(&a.epsilon, &b.epsilon, sizeof(float)) == 0 && a.is_heatmap == b.is_heatmap &&
            a.fractal_group_id == b.fractal_group_id && a.primitive_id == b.primitive_id;
@@ -36,27 +36,9 @@ static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras,
     return KIFS_OK;
 }
 
-// The launch's frame constants come from fill_params, which reads the context's options: for the length of a call the
-// context holds frame 0's image in their place and gets its own back at the end, set or not.
-struct OptionsOfFrame0 {
-    kifs_ctx* c;
-    KifsOptionsUniform saved;
-    bool had;
-    OptionsOfFrame0(kifs_ctx* ctx, const KifsOptionsUniform& first) : c(ctx), saved(ctx->options), had(ctx->have_options) {
-        c->options = first;
-        c->have_options = true;
-    }
-    ~OptionsOfFrame0() {
-        c->options = saved;
-        c->have_options = had;
-    }
-    OptionsOfFrame0(const OptionsOfFrame0&) = delete;
-    OptionsOfFrame0& operator=(const OptionsOfFrame0&) = delete;
-};
-
 // The next slot of the scene-table ring, as take_view_slot takes one of the view tables: allocated on first use, and
 // rewritten only after the launch that last read it is over.
-static int take_scene_slot(kifs_ctx* c, int* slot) {
+int take_scene_slot(kifs_ctx* c, int* slot) {
     const int ss = *slot = c->scene_slot;
     c->scene_slot = (ss + 1) % kifs_ctx::SCENE_RING;
     // (each part on its own: a slot that a failed allocation left half made is completed when the ring comes round to it)
@@ -73,7 +55,7 @@ static int take_scene_slot(kifs_ctx* c, int* slot) {
 // A launch on another stream than the tile table's feedback launches follows them, as a geometry launch does
 // (feedback_before in kifs_schedule.cpp): the sort rotates the order's two buffers on the understanding that nobody still
 // reads the one it writes.  Nothing else of the feedback is touched: no costs, no step of the sort.
-static int follow_stream_change(TileTable* tt, hipStream_t stream) {
+int follow_stream_change(TileTable* tt, hipStream_t stream) {
     if (tt->last_stream && tt->last_stream != stream &&
         (!host::hip_ok(hipEventRecord(tt->stream_left, tt->last_stream), "record(stream change)") ||
          !host::hip_ok(hipStreamWaitEvent(stream, tt->stream_left, 0), "wait(stream change)")))

@@ -6,6 +6,7 @@
 //   kifs_multi.cpp     one process driving several devices (kifs_multi_*)
 //   kifs_adaptive.cpp  adaptive anti-aliasing (kifs_render_adaptive_async): scratch block, rounds, the three passes
 //   kifs_animation.cpp animated batches (kifs_render_animation_async): the scene-table ring, one launch
+//   kifs_accumulate.cpp accumulated frames (kifs_render_accumulate_async): sub-frames as views of one launch
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -161,4 +162,34 @@ int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int
 bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what);
 
 }  // namespace host
+
+// What kifs_animation.cpp shares with kifs_accumulate.cpp: both launches carry a scene per view through the scene-table ring.
+namespace anim {
+
+// The fields every view of a launch shares (one pipeline, one march budget), compared as bit patterns.
+bool same_pipeline(const KifsOptionsUniform& a, const KifsOptionsUniform& b);
+// The next slot of the scene-table ring, free to be rewritten when the call returns.
+int take_scene_slot(kifs_ctx* c, int* slot);
+// A launch on another stream than the tile table's feedback launches follows them.
+int follow_stream_change(TileTable* tt, hipStream_t stream);
+
+// The launch's frame constants come from fill_params, which reads the context's options: for the length of a call the
+// context holds frame 0's image in their place and gets its own back at the end, set or not.
+struct OptionsOfFrame0 {
+    kifs_ctx* c;
+    KifsOptionsUniform saved;
+    bool had;
+    OptionsOfFrame0(kifs_ctx* ctx, const KifsOptionsUniform& first) : c(ctx), saved(ctx->options), had(ctx->have_options) {
+        c->options = first;
+        c->have_options = true;
+    }
+    ~OptionsOfFrame0() {
+        c->options = saved;
+        c->have_options = had;
+    }
+    OptionsOfFrame0(const OptionsOfFrame0&) = delete;
+    OptionsOfFrame0& operator=(const OptionsOfFrame0&) = delete;
+};
+
+}  // namespace anim
 }  // namespace kifs

@@ -1,5 +1,5 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
-// kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip).
+// kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,9 @@ hipError_t launch_adaptive_render(const adaptive::Params& A, uint32_t group, uin
 // Animated batches (kifs_animation_kernels.hip; the host side is kifs_animation.cpp): launch_render's whole-ray form
 // with view i's scene record laid over the frame constants.
 hipError_t launch_animation_render(const anim::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Accumulated frames (kifs_accumulate_kernels.hip; the host side is kifs_accumulate.cpp): every output frame the mean of
+// its sub-frames' linear colours, one workgroup per 8 x 8 output block and output frame.
+hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

@@ -160,4 +160,18 @@ static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
 
 }  // namespace anim
 
+namespace accum {
+
+// The argument of accum::render_kernel (kifs_render_accumulate_async, kifs_accumulate_kernels.hip): the launch's frame
+// constants as every render kernel takes them; its VIEWS are the sub-frames -- B.count = frames * samples, view
+// f * samples + s is sub-frame s of output frame f and carries that frame's destination -- and a scene record per view.
+struct Params {
+    BatchParams B;
+    const anim::SceneView* scenes;  // view v's record at scenes + v (device memory)
+    int frames, samples;            // output frames; sub-frames per output frame, 1..KIFS_MAX_ACCUMULATE
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace accum
+
 }  // namespace kifs

@@ -23,6 +23,7 @@ MAX_BATCH = 512  # KIFS_MAX_BATCH of include/kifs_hip.h
 SPARSE_RECORD_BYTES = 1040  # KIFS_SPARSE_RECORD_BYTES
 STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
+MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
 from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, OptionsUniform,
                    ScreenUniform, check, lib)
 
@@ -501,6 +502,44 @@ class GraphicState:
               "render_animation")
         return outs
 
+    # ---- accumulated frames (kifs_render_accumulate_async): every frame the linear-colour mean of its sub-frames
+    def render_accumulate(self, cameras, samples, options=None, outs=None, y0: int = 0, y1: int = None,
+                          encode: int = ENCODE_SRGB, stream=None):
+        """One launch for len(cameras) / samples output frames, each the mean of `samples` sub-frames taken in linear
+        colour before the encode: motion blur (configs.shutter_cameras), depth of field (configs.lens_cameras), a morph
+        without temporal aliasing (per-sub-frame options).  Sub-frame s of frame i is cameras[i * samples + s] (CameraData
+        or CameraUniform images; a camera_array is taken as it is) with options[i * samples + s] (GuiData or
+        OptionsUniform images, as render_animation takes them; None: the context's options for all of them).
+        1 <= samples <= MAX_ACCUMULATE and len(cameras) <= MAX_BATCH.  Returns the frames as one uint8
+        (count, rows, W, 4) torch tensor on this context's device; `outs`: a contiguous destination tensor of that shape
+        to reuse.  Enqueued on `stream` like render_async and ordered after torch's current stream; the caller
+        synchronises before reading, and keeps a tensor this method allocated alive until the launch has run."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        samples = int(samples)
+        cams = camera_array(cameras)
+        views = len(cams)
+        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
+            raise ValueError(f"render_accumulate: 1..{MAX_ACCUMULATE} samples per frame, count * samples cameras, at most "
+                             f"{MAX_BATCH} of them")
+        n = views // samples
+        opts = None if options is None else options_array(options)
+        if opts is not None and len(opts) != views:
+            raise ValueError(f"render_accumulate: {len(opts)} option images for {views} cameras")
+        if outs is None:
+            outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
+            raise ValueError(f"render_accumulate: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+        stream = self._stream_handle(stream, "render_accumulate")
+        base, frame_bytes = _device_pointer(outs), rows * w * 4
+        ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+        self._order_after_producer(outs, stream)
+        check(lib.kifs_render_accumulate_async(self._ctx, stream, n, samples, cams, opts, ptrs, w * 4, y0, y1, encode),
+              "render_accumulate")
+        return outs
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -657,7 +696,7 @@ class GraphicState:
 
     KERNEL_NAMES = ("render_kernel", "render_group_kernel", "render_wave_kernel", "render_bunny_quad_kernel",
                     "render_bunny_coop_kernel", "render_ssaa_kernel", "render_geometry_kernel", "render_adaptive_kernel",
-                    "render_animation_kernel")
+                    "render_animation_kernel", "render_accumulate_kernel")
 
     def debug_last_kernel(self) -> str:
         """Name of the render kernel the latest launch used ("" before the first)."""

@@ -7,6 +7,9 @@
     python tools/render.py cfg2_julia_1080p out.png --geometry out.npz --depth-png depth.png   # + normal and hit distance
     python tools/render.py cfg5_sierpinski_8k_orbit frames/orbit_%03d.png --frames 0 30 60 --scale 0.25
     python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48   # out_000.png .. out_047.png
+    python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --shutter 0.5   # motion blur
+    python tools/render.py cfg2_julia_1080p out.png --dof 0.05,3.2 --samples 32                # depth of field
+    python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --motion-blur 8   # a blurred morph
 """
 import argparse
 import sys
@@ -14,7 +17,7 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
-from kifs_raymarching_amd.configs import WORKLOADS, morph_options, orbit_camera  # noqa: E402
+from kifs_raymarching_amd.configs import WORKLOADS, lens_cameras, morph_options, orbit_camera, shutter_cameras  # noqa: E402
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -41,7 +44,35 @@ ap.add_argument("--geometry", metavar="OUT.npz", default=None,
                      "normal (H, W, 3) float32 and t (H, W) float32, +inf where the ray missed; not with --aa or --frames")
 ap.add_argument("--depth-png", metavar="OUT.png", default=None,
                 help="with --geometry: t as a grey image for a quick look (nearest hit white, misses black)")
+ap.add_argument("--motion-blur", type=int, default=0, metavar="S",
+                help="accumulated frames (kifs_render_accumulate_async): every orbit frame of --frames is the linear-colour mean "
+                     "of S sub-frames (1..64) spread over the shutter interval; with --morph-to: every frame of the morph the "
+                     "mean of S steps of it (per-sub-frame options); not with --aa, --aa-adaptive or --geometry")
+ap.add_argument("--shutter", type=float, default=0.5, metavar="F",
+                help="with --motion-blur on orbit frames: the shutter is open for F x the angle between two frames")
+ap.add_argument("--dof", metavar="APERTURE,FOCUS", default=None,
+                help="depth of field: the mean of --samples S sub-frames whose cameras sit on a lens of radius APERTURE and "
+                     "share the plane at distance FOCUS; one frame, or the orbit frames of --frames; not with --motion-blur, "
+                     "--morph-to, --aa, --aa-adaptive or --geometry")
+ap.add_argument("--samples", type=int, default=16, metavar="S", help="with --dof: sub-frames per frame (1..64)")
 args = ap.parse_args()
+dof = None
+if args.dof is not None:
+    try:
+        dof = tuple(float(x) for x in args.dof.split(","))
+    except ValueError:
+        dof = ()
+    if len(dof) != 2 or not dof[1] > 0.0:
+        ap.error("--dof takes two numbers APERTURE,FOCUS with a positive focus distance")
+    if args.motion_blur or args.morph_to is not None:
+        ap.error("--dof goes without --motion-blur and --morph-to")
+accumulate = args.motion_blur or (args.samples if dof else 0)
+if (args.motion_blur or dof) and not 1 <= accumulate <= K.MAX_ACCUMULATE:
+    ap.error(f"1..{K.MAX_ACCUMULATE} sub-frames per frame")
+if accumulate and (args.aa != 1 or args.aa_adaptive or args.geometry):
+    ap.error("--motion-blur and --dof render without --aa, --aa-adaptive or --geometry")
+if args.motion_blur and args.morph_to is None and not args.frames:
+    ap.error("--motion-blur needs the orbit frames of --frames (or --morph-to)")
 if args.geometry and (args.aa != 1 or args.frames is not None):
     ap.error("--geometry renders one frame without supersampling")
 if args.aa_adaptive and (args.aa != 1 or args.geometry or args.frames is not None):
@@ -91,6 +122,40 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
         pixels = screen.width * screen.height
         print(f"{args.out}: {screen.width}x{screen.height}, {edges} of {pixels} pixels supersampled "
               f"{args.aa_adaptive}x{args.aa_adaptive} ({100.0 * edges / pixels:.2f} %)")
+    elif morph_to is not None and args.motion_blur:
+        # frame i of the morph is the mean of steps i S .. i S + S - 1 of a morph of n S steps
+        n, S = args.frames[0], args.motion_blur
+        guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n * S)
+        out = Path(args.out)
+        per_call = max(1, K.MAX_BATCH // S)
+        for first in range(0, n, per_call):
+            sub = guis[first * S:(first + per_call) * S]
+            frames = gs.render_accumulate([w.camera] * len(sub), S, options=sub)
+            gs.synchronize()
+            for i, frame in enumerate(frames.cpu().numpy(), start=first):
+                write_png(str(out.with_name(f"{out.stem}_{i:03d}{out.suffix}")), frame)
+        print(f"{out.with_name(out.stem + '_000' + out.suffix)} .. : {n} frames of {screen.width}x{screen.height}, each the mean "
+              f"of {S} steps, constant {tuple(gui.constant)} -> {morph_to}")
+    elif accumulate:
+        # motion blur over the orbit's frames, or depth of field for one frame / the orbit's frames
+        S = accumulate
+        indices = args.frames if args.frames is not None else [None]
+        per_call = max(1, K.MAX_BATCH // S)
+        for first in range(0, len(indices), per_call):
+            part = indices[first:first + per_call]
+            cams = []
+            for k in part:
+                if dof:
+                    cams.extend(lens_cameras(w.camera if k is None else orbit_camera(w, k), dof[0], dof[1], S))
+                else:
+                    cams.extend(c.into_buffer_data() for c in shutter_cameras(w, k, S, args.shutter))
+            frames = gs.render_accumulate(cams, S)
+            gs.synchronize()
+            for k, frame in zip(part, frames.cpu().numpy()):
+                path = args.out if k is None else args.out % k
+                write_png(path, frame)
+                print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
+                      + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})"))
     elif morph_to is not None:
         n = args.frames[0]
         guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n)
