@@ -691,6 +691,19 @@ void kifs_host_rotation_matrix(int axis, float radians, float m_colmajor[9]); /*
 void kifs_host_mat3_mul(const float a[9], const float b[9], float out[9]);    /* math.rs:326-353 */
 void kifs_host_mat3_vec(const float a[9], const float v[3], float out[3]);    /* math.rs:355-367 */
 
+/* The host model of the power-2 Julia pipeline's culls (no device needed).
+ * kifs_host_julia_cull_radius: the certified radius rho of the set for this constant -- every point with |p| >= rho has
+ * an estimate of at least *bound (may be NULL) >= 16 epsilon + 2^-14, so a ray whose closest approach to the origin is
+ * >= rho never hits -- or 0 when there is none (|c| too large, a NaN, epsilon or max_distance out of range).
+ * kifs_host_cull_thresholds: what a launch of `count` views of these uniforms would run with,
+ *   out[0] cull_n2 (per-ray cull, squared radius; 0 = off)   out[1] quick_cull_n2 (wave-level exit)
+ *   out[2] tile_cull_sqrtk, out[3] tile_cull_beta (tile-level exit; beta 0 = off)
+ *   out[4] 1.1 (B + epsilon)^2 of the scene's bounding radius B: the sphere the launch-shape rules are written in.
+ * KIFS_TUNING=1 KIFS_JULIA_CERT_CULL=0 keeps the Julia culls on the bounding sphere (A/B runs, tests). */
+double kifs_host_julia_cull_radius(const float constant[4], float epsilon, float max_distance, int sdf_iters, double* bound);
+int kifs_host_cull_thresholds(const KifsScreenUniform* screen, const KifsOptionsUniform* options, int sdf_iters,
+                              const KifsCameraUniform* cameras, int count, float out[5]);
+
 #ifdef __cplusplus
 }
 #endif

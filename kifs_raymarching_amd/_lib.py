@@ -169,6 +169,8 @@ SIGNATURES = {
     "kifs_host_rotation_matrix": (None, [C.c_int, C.c_float, _f32p]),
     "kifs_host_mat3_mul": (None, [_f32p, _f32p, _f32p]),
     "kifs_host_mat3_vec": (None, [_f32p, _f32p, _f32p]),
+    "kifs_host_julia_cull_radius": (C.c_double, [_f32p, C.c_float, C.c_float, C.c_int, _P(C.c_double)]),
+    "kifs_host_cull_thresholds": (C.c_int, [_P(ScreenUniform), _P(OptionsUniform), C.c_int, _P(CameraUniform), C.c_int, _f32p]),
 }
 
 

@@ -56,6 +56,7 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
     P.round_steps = 0;
     P.workgroups_per_cu = 0;
     P.orbit_x2 = 0;
+    if (options) host::julia_culls_of_frames(c, P, options, views);  // (fill_params certified view 0's constant alone)
     if (y1 == y0) return KIFS_OK;
 
     const bool big = views > MAX_BATCH_INLINE;

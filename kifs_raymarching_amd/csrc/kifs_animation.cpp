@@ -84,6 +84,7 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraU
     P.round_steps = 0;
     P.workgroups_per_cu = 0;
     P.orbit_x2 = 0;
+    host::julia_culls_of_frames(c, P, options, count);  // (fill_params certified frame 0's constant alone)
     if (y1 == y0) return KIFS_OK;
 
     const bool big = count > MAX_BATCH_INLINE;

@@ -134,6 +134,13 @@ int frame_dims(const kifs_ctx* c, int* w, int* h);
 // frame_dims for a render: with k x k supersampling the virtual k W x k H screen must meet the same limit (BAD_SIZE)
 int render_dims(const kifs_ctx* c, int* w, int* h);
 int fill_params(const kifs_ctx* c, kifs::FrameParams* P);
+// The certified radius of the power-2 Julia set for these options, 0: none; `bound` (may be null) receives the lower bound
+// of the estimate beyond it.  julia_culls(): the cull thresholds of a Julia launch from the radius its frames share
+// (fill_params does it for the context's options; a launch with options per frame calls julia_culls_of_frames after it).
+double julia_cull_radius(const float c[4], float epsilon, float max_distance, int sdf_iters, double* bound);
+bool takes_julia_culls(const kifs::FrameParams& P, uint32_t group);
+void julia_culls(kifs::FrameParams& P, double rho, bool tile);
+void julia_culls_of_frames(const kifs_ctx* c, kifs::FrameParams& P, const KifsOptionsUniform* options, int count);
 // The views of a launch (cameras NULL: the context's camera) into `views`, and what they decide for all of it: P's
 // camera is view 0's, and the culls go when a view does not meet what they assume.
 void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,

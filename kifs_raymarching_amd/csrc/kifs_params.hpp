@@ -30,7 +30,8 @@ struct FrameParams {
     // exactly `dot(p,p) > bound_n2` because correctly rounded sqrt is monotone.
     float bound_n2;
     int orbit_blocks, orbit_rem;        // sdf_iters = 6 * orbit_blocks + orbit_rem
-    // (2 + epsilon)^2 * 1.1 for the bounding-sphere culls (0 disables them: NaN/odd epsilon)
+    // (2 + epsilon)^2 * 1.1 for the bounding-sphere culls (0 disables them: NaN/odd epsilon); the power-2 Julia set
+    // with a certified radius rho: (1 + 2^-6) rho^2 (fill_params)
     float cull_n2;
     // Smallest f32 v with sqrt(v) >= max_distance: `length(pos) < max_distance` (kifs.wgsl:72)
     // is exactly `dot(pos,pos) < fold_n2_stop`.
@@ -98,6 +99,10 @@ struct FrameParams {
     // would not fit the kernel argument and would move every kernel's view loads).
     float* geom;
     uint32_t geom_pitch_texels, geom_stride_texels;
+    // Host-side, not read by the kernels: 1.1 (B + epsilon)^2 of the scene's bounding radius B (0: culls off) -- what
+    // cull_n2 holds unless a certified radius of the Julia set replaced it (julia_cull_radius() in kifs_schedule.cpp).
+    // The launch-shape rules (disc_tiles, residency_for) were swept in this sphere's units and keep reading it.
+    float shape_n2;
 };
 
 // A launch renders a batch of up to MAX_BATCH frames that share screen, options and tile

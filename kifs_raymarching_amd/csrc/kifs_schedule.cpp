@@ -62,13 +62,14 @@ constexpr double BUNNY_W2LDS_FROM = 2600.0;   // pairs with layer 2 of the netwo
 constexpr double BUNNY_COOP_FROM = 5000.0;    // four waves per 64 rays (same file: x28 43.9 against 49.0 for the form above, x32 48.4 / 49.1, x40 55.0 / 50.0, x48 58.0 / 50.0)
 }  // namespace rules
 
-// Tuning overrides (KIFS_ROUND_STEPS, KIFS_GROUP_TILES, KIFS_BUNNY_COOP, KIFS_TILE_FEEDBACK, KIFS_FEEDBACK_PERIOD,
-// KIFS_BATCH_PERIOD; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as well: they exist
+// Tuning overrides (KIFS_ROUND_STEPS, KIFS_GROUP_TILES, KIFS_BUNNY_COOP, KIFS_TILE_FEEDBACK, KIFS_JULIA_CERT_CULL,
+// KIFS_FEEDBACK_PERIOD, KIFS_BATCH_PERIOD; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as well: they exist
 // for tools/sweep_kernels.sh and friends, not for production hosts.  Read once per process, clamped here.
 struct Knobs {
     int round_steps, group_tiles;        // -1: not set
     int bunny_coop;                      // -1, or a form 0 / 1 / 2 (FrameParams::bunny_coop)
     int tile_feedback;                   // 0 = never, 1 (default) = per pipeline thresholds, 2 = every frame of 2048+ tiles
+    int julia_cert_cull;                 // 0: the Julia culls stay on the patch sphere (julia_culls); -1 / other: certified radius
     uint64_t period_lone, period_batch;  // launches between two refreshes of the tile order
 };
 static const Knobs& knobs() {
@@ -80,7 +81,7 @@ static const Knobs& knobs() {
         };
         const int coop = knob("KIFS_BUNNY_COOP"), mode = knob("KIFS_TILE_FEEDBACK");
         const int lone = knob("KIFS_FEEDBACK_PERIOD"), batch = knob("KIFS_BATCH_PERIOD");
-        return Knobs{knob("KIFS_ROUND_STEPS"), knob("KIFS_GROUP_TILES"), std::min(coop, 2), mode >= 0 ? mode : 1,
+        return Knobs{knob("KIFS_ROUND_STEPS"), knob("KIFS_GROUP_TILES"), std::min(coop, 2), mode >= 0 ? mode : 1, knob("KIFS_JULIA_CERT_CULL"),
                      uint64_t(lone < 0 ? rules::FEEDBACK_PERIOD_LONE : lone < 3 ? 3 : lone),
                      uint64_t(batch < 0 ? rules::FEEDBACK_PERIOD_BATCH : batch < 2 ? 2 : batch)};
     }();
@@ -157,6 +158,140 @@ static bool orbit_x2_eligible(const kifs::FrameParams& P) {
     return P.max_distance > 0.0f && P.max_distance <= far && P.bound_n2 > 0.0f && P.bound_n2 <= far;
 }
 
+// ---- a certified radius of the power-2 Julia set --------------------------------------------------------------
+// The patch sphere of julia.wgsl:8-9 has radius 2; the set is much smaller.  For the estimate
+//   q_0 = (p, 0.1), q_{k+1} = q_k^2 + c, dqs = prod_{k<n} 4 |q_k|^2, d = 0.25 ln|q_n|^2 sqrt(|q_n|^2 / dqs)
+// (n: the trip at which |q|^2 > max_distance, or sdf_iters) the quaternion norm is multiplicative, so
+// |q_{k+1}| >= |q_k|^2 - |c|.  With a = sqrt(rho^2 + 0.01) and a^2 - |c| > a (rho beyond the escape radius), L_0 = a,
+// L_{k+1} = L_k^2 - |c|, every point with |p| >= rho has |q_k| >= L_k, growing;
+//   g_k = |q_k| / prod_{j<k} 2 |q_j|  obeys  g_{k+1} >= g_k (1 - |c| / |q_k|^2) / 2,  and
+//   ln|q_n| >= 2^n G,  G = ln(a^2 - |c|) - ln a,
+// hence for every n:  d = ln|q_n| g_n / 2  >=  D(rho) = a G P / 2,  P = prod_{k<sdf_iters} (1 - |c| / L_k^2),
+// increasing in rho.  A ray whose closest approach to the origin is >= rho samples only points with |p| >= rho: outside
+// the patch sphere d = |p| - 2 > epsilon as ever, in the shell d >= D(rho) > epsilon.  It never hits.  DESIGN section 4
+// has the float-error argument behind the margins: D(rho) >= 16 epsilon + 2^-14, nothing overflows in f32.
+struct JuliaBound {
+    double D;   // the lower bound of the estimate over |p| >= rho; <= 0: rho is not beyond the escape radius
+    int trips;  // n_max: trips until L_k^2 > max_distance, at most sdf_iters
+};
+static JuliaBound julia_bound(double rho, double cn, double max_distance, int sdf_iters) {
+    const double a = std::sqrt(rho * rho + 0.01);
+    if (!(a * a - cn > a)) return {0.0, 0};
+    const double G = std::log(a * a - cn) - std::log(a);
+    double L = a, P = 1.0;
+    int trips = sdf_iters;
+    for (int k = 0; k < sdf_iters; ++k) {
+        if (k >= 1 && trips == sdf_iters && L * L > max_distance) trips = k;
+        if (L > 1.0e150) break;  // every further factor is 1 in double
+        P *= 1.0 - cn / (L * L);
+        L = L * L - cn;
+    }
+    return {0.5 * a * G * P, trips};
+}
+
+static double julia_cull_radius_uncached(const float c[4], float epsilon, float max_distance, int sdf_iters, double* bound);
+// The smallest radius the certificate holds for, by bisection on [escape radius, 2 + epsilon] in double; 0: none
+// (|c| too large for the shell, a NaN, a huge epsilon or max_distance).  `bound`, when given, receives D(rho).
+double julia_cull_radius(const float c[4], float epsilon, float max_distance, int sdf_iters, double* bound) {
+    // (asked again with every launch: the latest answer is kept, per thread)
+    struct Asked { float c[4], epsilon, max_distance; int sdf_iters; };
+    thread_local Asked last{};
+    thread_local double last_rho = -1.0, last_bound = 0.0;
+    const Asked now{{c[0], c[1], c[2], c[3]}, epsilon, max_distance, sdf_iters};
+    if (last_rho >= 0.0 && std::memcmp(&last, &now, sizeof now) == 0) {
+        if (bound) *bound = last_bound;
+        return last_rho;
+    }
+    double D = 0.0;
+    const double rho = julia_cull_radius_uncached(c, epsilon, max_distance, sdf_iters, &D);
+    last = now;
+    last_rho = rho;
+    last_bound = D;
+    if (bound) *bound = D;
+    return rho;
+}
+static double julia_cull_radius_uncached(const float c[4], float epsilon, float max_distance, int sdf_iters, double* bound) {
+    *bound = 0.0;
+    double cc = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        if (!(std::fabs(c[i]) <= 0x1p10f)) return 0.0;  // (also NaN)
+        cc += double(c[i]) * double(c[i]);
+    }
+    // fill_params' `sane` for the Julia patch (B = 2)
+    const float R = 2.0f + epsilon;
+    if (!(R > 0.5f && R < 1.0e6f && epsilon >= 0.0f && max_distance < 1.0e15f) || sdf_iters < 0) return 0.0;
+    const double cn = std::sqrt(cc), eps = double(epsilon), md = double(max_distance), top = 2.0 + eps;
+    const double need = 16.0 * eps + 0x1p-14, room = 0x1p100;
+    const auto holds = [&](double rho) {
+        const JuliaBound b = julia_bound(rho, cn, md, sdf_iters);
+        if (!(b.D >= need)) return false;
+        // f32 range: dqs <= max(4 max_distance, 4 |q_0|^2)^n_max and the last |q|^2 <= (max_distance + |c|)^2
+        const double factor = std::max(4.0 * md, 4.0 * (top * top + 0.01));
+        return b.trips * std::log2(factor) <= 100.0 && (md + cn) * (md + cn) <= room;
+    };
+    if (!holds(top)) return 0.0;
+    const double a_esc = 0.5 * (1.0 + std::sqrt(1.0 + 4.0 * cn));
+    double lo = std::sqrt(std::max(a_esc * a_esc - 0.01, 0.0)), hi = top;  // holds(lo) is false: D(lo) = 0
+    if (!(lo < hi)) return 0.0;
+    for (int i = 0; i < 36; ++i) {  // to 2^-36 of the shell: a launch with a constant per frame asks once per frame
+        const double mid = 0.5 * (lo + hi);
+        (holds(mid) ? hi : lo) = mid;
+    }
+    *bound = julia_bound(hi, cn, md, sdf_iters).D;
+    return hi;
+}
+
+// The cull thresholds: cull_n2 for the per-ray culls, the wave-level quick exit's sphere (0: off), and its tile-level
+// form (render_wave_kernel): for an orthonormal camera matrix |d| >= 1 and two pixel
+// centres of a 32 x 8 tile are at most (31, 7) pixels = (31, 7) * 2 / height apart in uv, so a
+// ray of the tile and the ray through the tile's centre differ by at most
+// asin(|(31, 7)| / height) <= 1.05 * 31.8 / height radians (the ratio is below 0.5 from 64 rows);
+// 34 / height leaves 2 % for the matrix check's tolerance.  fill_views() switches it off when
+// a view's matrix is not orthonormal (`tile` false: it has).
+static void set_culls(kifs::FrameParams& P, float cull_n2, float quick_n2, bool tile) {
+    P.cull_n2 = cull_n2;
+    P.quick_cull_n2 = quick_n2;
+    P.tile_cull_sqrtk = std::sqrt(quick_n2);
+    P.tile_cull_beta = (tile && quick_n2 > 0.0f && P.height >= 64.0f) ? 34.0f / P.height : 0.0f;
+}
+
+// The thresholds of a launch of the power-2 Julia pipeline whose culls are on (not its heatmap), from the certified
+// radius `rho` its frames share (any rho' >= a frame's own is valid for it; 0: none): (1 + 2^-6) rho^2 for the culls, and
+// the quick exits keep their ratio to it, 1.2 / 1.1 -- wave_is_culled and tile_is_culled argue with that room, not
+// with the radius.  Without a radius, or with KIFS_JULIA_CERT_CULL=0 under KIFS_TUNING=1: the patch sphere's,
+// 1.1 and 1.2 (2 + epsilon)^2.  `tile`: the tile-level exit is allowed.
+void julia_culls(kifs::FrameParams& P, double rho, bool tile) {
+    const float R = 2.0f + P.epsilon;
+    float cull = 1.1f * R * R, quick = 1.2f * R * R;
+    if (rho > 0.0 && knobs().julia_cert_cull != 0) {
+        const float r = float(rho);
+        cull = (1.0f + 0x1p-6f) * r * r;
+        quick = cull * (1.2f / 1.1f);
+    }
+    set_culls(P, cull, P.max_iterations > 0 ? quick : 0.0f, tile);
+}
+// Whether julia_culls() applies to the launch P describes: the Julia pipeline with its culls on.
+bool takes_julia_culls(const kifs::FrameParams& P, uint32_t group) {
+    return group == uint32_t(kifs::GROUP_JULIA) && !P.is_heatmap && P.shape_n2 > 0.0f;
+}
+
+// A launch whose frames bring their own options (one pipeline, one epsilon and march budget: anim::same_pipeline): the
+// largest of the frames' radii serves them all; the patch sphere if one of them has none.  After fill_params, before
+// fill_views.
+void julia_culls_of_frames(const kifs_ctx* c, kifs::FrameParams& P, const KifsOptionsUniform* options, int count) {
+    if (!takes_julia_culls(P, options[0].fractal_group_id)) return;
+    double rho = 0.0;
+    for (int i = 0; i < count; ++i) {
+        const double r = julia_cull_radius(options[i].constant, P.epsilon, P.max_distance, c->sdf_iters, nullptr);
+        if (!(r > 0.0)) {
+            rho = 0.0;
+            break;
+        }
+        rho = std::max(rho, r);
+    }
+    julia_culls(P, rho, true);
+}
+
 int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
     int w, h;
     int st = frame_dims(c, &w, &h);
@@ -210,18 +345,13 @@ int fill_params(const kifs_ctx* c, kifs::FrameParams* P) {
         // (max_distance below 1e15 -- the GUI's range ends at 1e4 -- and, per view, an origin within 1e15 of the
         // scene: fill_views; the long-ray loop's square root of |p|^2 relies on |p|^2 being finite then)
         const bool sane = B > 0.0f && R > 0.5f && R < 1.0e6f && o.epsilon >= 0.0f && o.max_distance < 1.0e15f;
-        P->cull_n2 = sane ? 1.1f * R * R : 0.0f;
+        P->shape_n2 = sane ? 1.1f * R * R : 0.0f;
         // the wave-level quick exit uses a sphere 9 % larger again; like the culls, not in heatmap mode
-        P->quick_cull_n2 = (sane && !o.is_heatmap && o.max_iterations > 0) ? 1.2f * R * R : 0.0f;
+        set_culls(*P, P->shape_n2, (sane && !o.is_heatmap && o.max_iterations > 0) ? 1.2f * R * R : 0.0f, true);
         P->inv_height = 1.0f / c->screen.height;
-        // Tile-level form (render_wave_kernel): for an orthonormal camera matrix |d| >= 1 and two pixel
-        // centres of a 32 x 8 tile are at most (31, 7) pixels = (31, 7) * 2 / height apart in uv, so a
-        // ray of the tile and the ray through the tile's centre differ by at most
-        // asin(|(31, 7)| / height) <= 1.05 * 31.8 / height radians (the ratio is below 0.5 from 64 rows);
-        // 34 / height leaves 2 % for the matrix check's tolerance.  fill_views() switches it off when
-        // a view's matrix is not orthonormal.
-        P->tile_cull_sqrtk = std::sqrt(P->quick_cull_n2);
-        P->tile_cull_beta = (P->quick_cull_n2 > 0.0f && c->screen.height >= 64.0f) ? 34.0f / c->screen.height : 0.0f;
+        // the power-2 Julia set: a certified radius inside the patch sphere, when there is one
+        if (takes_julia_culls(*P, o.fractal_group_id))
+            julia_culls(*P, julia_cull_radius(o.constant, o.epsilon, o.max_distance, c->sdf_iters, nullptr), true);
     }
     {   // Ray re-queuing (render_group_kernel): rounds of this many march steps -- 16 for the Julia
         // pipelines (generalised Julia: 1080p lone 0.882 -> 0.869 ms, x8 +2.7 %, x48 +1 % over rounds of 8),
@@ -378,7 +508,7 @@ TileTable* tile_table(kifs_ctx* c, int width, int height, int y0, int y1, const 
 // size together, where tile counts and pixel counts do not.
 double disc_tiles(const kifs::FrameParams& P, int frame_height, uint32_t tile_count) {
     if (P.cull_n2 <= 0.0f || P.is_heatmap) return double(tile_count);
-    const double R2 = double(P.cull_n2) / 1.1;  // (B + epsilon)^2
+    const double R2 = double(P.shape_n2) / 1.1;  // (B + epsilon)^2: the bounding sphere, whatever radius the culls stand on
     const double d2 = double(P.origin.x) * P.origin.x + double(P.origin.y) * P.origin.y +
                       double(P.origin.z) * P.origin.z;
     const double frame_px = double(P.width) * double(frame_height);
@@ -463,6 +593,9 @@ int take_view_slot(kifs_ctx* c, int* slot) {
 void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views, int count, const KifsCameraUniform* cameras,
                 uint8_t* const* outs) {
     bool far_origin = false;  // a view whose origin is not within 1e15 of the scene: no culls for this launch
+    // a view beyond 32 from the scene: oo - b^2 of ray_never_inside cancels too much for the certified radius's margin of
+    // 2^-6; the patch sphere's 10 % serves the launch
+    bool distant_origin = false;
     for (int i = 0; i < count; ++i) {
         const KifsCameraUniform& cam = cameras ? cameras[i] : c->camera;
         kifs::BatchView& v = views[i];
@@ -473,6 +606,8 @@ void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views,
         v.out = reinterpret_cast<uint32_t*>(outs[i]);
         if (!(double(v.origin.x) * v.origin.x + double(v.origin.y) * v.origin.y + double(v.origin.z) * v.origin.z < 1.0e30))
             far_origin = true;  // (also NaN)
+        if (double(v.origin.x) * v.origin.x + double(v.origin.y) * v.origin.y + double(v.origin.z) * v.origin.z > 1024.0)
+            distant_origin = true;
         if (P.tile_cull_beta > 0.0f) {  // the tile-level cull's angle bound assumes an orthonormal matrix
             const kifs::V3* m[3] = {&v.m0, &v.m1, &v.m2};
             for (int a = 0; a < 3; ++a)
@@ -482,7 +617,9 @@ void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views,
                 }
         }
     }
-    if (far_origin) P.cull_n2 = P.quick_cull_n2 = P.tile_cull_beta = 0.0f;
+    if (distant_origin && P.cull_n2 > 0.0f && P.cull_n2 != P.shape_n2)  // (only julia_culls makes the two differ)
+        julia_culls(P, 0.0, P.tile_cull_beta > 0.0f);
+    if (far_origin) P.cull_n2 = P.quick_cull_n2 = P.tile_cull_beta = P.shape_n2 = 0.0f;
     P.origin = views[0].origin;
     P.m0 = views[0].m0;
     P.m1 = views[0].m1;
@@ -608,6 +745,17 @@ static int feedback_after(kifs_ctx* c, TileTable* tt, hipStream_t stream, uint32
     return KIFS_OK;
 }
 
+// A residency-capped lone Julia frame keeps the patch sphere's culls.  With one workgroup per CU the certified radius made
+// the 1080p frame at distance 5 LONGER, 0.152 -> 0.172 ms (fixed view 0.142 -> 0.173), although it marches half the rays
+// and no wave can take more steps: the same library, KIFS_JULIA_CERT_CULL on / off, with or without the tile-order
+// feedback; at two workgroups per CU and uncapped the smaller sphere is 1 - 2 % ahead (profiles/r11/README.md).  The cap
+// exists so that the frame's long waves run undisturbed; what the smaller sphere changes is what their neighbours do
+// meanwhile -- half as many tiles march, so the other CUs turn to the launch's 7 800 empty tiles early.  Not explained
+// further; the residency rule was fitted to the patch sphere's load and is re-fitted with the other shape rules.
+static void capped_frame_culls(kifs::FrameParams& P) {
+    if (P.workgroups_per_cu >= 1 && P.cull_n2 > 0.0f && P.cull_n2 != P.shape_n2) julia_culls(P, 0.0, P.tile_cull_beta > 0.0f);
+}
+
 // The shape of a geometry or supersampled launch: one kernel form for every scene, whole rays, no costs, no diagnostics.
 // A lone geometry frame keeps the block kernel's residency cap.
 static void fixed_shape(const kifs_ctx* c, kifs::FrameParams& P, int count, int frame_height) {
@@ -616,6 +764,7 @@ static void fixed_shape(const kifs_ctx* c, kifs::FrameParams& P, int count, int 
     P.round_steps = 0;
     const bool lone = count == 1 && c->frames_in_flight <= 1;
     P.workgroups_per_cu = (P.geom && lone) ? residency_for(P, c->options.fractal_group_id, disc_tiles(P, frame_height, P.tile_count)) : 0;
+    capped_frame_culls(P);
 }
 
 // The shape of a plain launch.  Everything is decided from `load`: the launch's tiles that can hold rays with real work
@@ -634,6 +783,7 @@ static void choose_shape(const kifs_ctx* c, kifs::FrameParams& P, int count, int
     const double load = heavy_tiles * double(count);
     // the residency cap serves a lone frame's latency; concurrent frames want every slot
     P.workgroups_per_cu = lone ? residency_for(P, group_id, heavy_tiles) : 0;
+    capped_frame_culls(P);
     // a residency-capped launch is a lone frame bound by its longest rays: re-queuing helps throughput, not that (1080p
     // Julia: 0.143 ms without, 0.146 ms with)
     if (P.workgroups_per_cu >= 1) P.round_steps = 0;
@@ -789,3 +939,32 @@ bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what) {
 
 }  // namespace host
 }  // namespace kifs
+
+// ---- C ABI: the host model of the culls, GPU-free (include/kifs_hip.h) -------------------------------------------
+extern "C" double kifs_host_julia_cull_radius(const float constant[4], float epsilon, float max_distance, int sdf_iters,
+                                              double* bound) {
+    if (bound) *bound = 0.0;
+    if (!constant) return 0.0;
+    return kifs::host::julia_cull_radius(constant, epsilon, max_distance, sdf_iters, bound);
+}
+
+extern "C" int kifs_host_cull_thresholds(const KifsScreenUniform* screen, const KifsOptionsUniform* options, int sdf_iters,
+                                         const KifsCameraUniform* cameras, int count, float out[5]) {
+    if (!screen || !options || !cameras || !out || sdf_iters < 0 || count < 1 || count > kifs::MAX_BATCH) return KIFS_ERR_BAD_ARG;
+    kifs_ctx c;  // (plain data until something is rendered: no device behind it)
+    c.screen = *screen;
+    c.options = *options;
+    c.camera = cameras[0];
+    c.sdf_iters = sdf_iters;
+    kifs::FrameParams P;
+    if (const int st = kifs::host::fill_params(&c, &P); st != KIFS_OK) return st;
+    std::vector<kifs::BatchView> views(static_cast<size_t>(count));
+    std::vector<uint8_t*> outs(static_cast<size_t>(count), nullptr);
+    kifs::host::fill_views(&c, P, views.data(), count, cameras, outs.data());
+    out[0] = P.cull_n2;
+    out[1] = P.quick_cull_n2;
+    out[2] = P.tile_cull_sqrtk;
+    out[3] = P.tile_cull_beta;
+    out[4] = P.shape_n2;
+    return KIFS_OK;
+}
