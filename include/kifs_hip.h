@@ -304,8 +304,9 @@ int kifs_render_adaptive_async(kifs_ctx* ctx, void* hip_stream, int count, const
  *             row beyond 4 W are not touched.
  *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: a null ctx, options or dev_outs_rgba8; a
  *             null or misaligned destination; count out of range; a bad encode or band; a fractal_group_id above 2; frames
- *             that differ where they may not; the context's supersampling factor above 1 (out of scope, as for the
- *             geometry output).  KIFS_ERR_BAD_SIZE: a bad pitch.  KIFS_ERR_UNCONFIGURED: no screen, or no camera with
+ *             that differ where they may not; the context's supersampling factor above 1 (an anti-aliased morph is
+ *             kifs_render_accumulate_jittered_async's whole-grid form).  KIFS_ERR_BAD_SIZE: a bad pitch.
+ *             KIFS_ERR_UNCONFIGURED: no screen, or no camera with
  *             cameras == NULL.
  *   tables    the frames' scenes reach the kernel through a device table: a ring of KIFS_ANIMATION_RING tables per
  *             context, each rewritten only once the launch that read it is over -- a call that finds its table busy
@@ -348,8 +349,8 @@ int kifs_render_animation_async(kifs_ctx* ctx, void* hip_stream, int count,
  *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: a null ctx, cameras or dev_outs_rgba8; a
  *             null or misaligned destination; samples outside 1 .. KIFS_MAX_ACCUMULATE; count below 1 or count * samples
  *             above KIFS_MAX_BATCH; a bad encode or band; a fractal_group_id above 2; images that differ where they may
- *             not; the context's supersampling factor above 1 (out of scope, as for the other extensions).
- *             KIFS_ERR_BAD_SIZE: a bad pitch.  KIFS_ERR_UNCONFIGURED: no screen, or no options with options == NULL.
+ *             not; the context's supersampling factor above 1 (sub-frames that also anti-alias are
+ *             kifs_render_accumulate_jittered_async's, below).  KIFS_ERR_BAD_SIZE: a bad pitch.  KIFS_ERR_UNCONFIGURED: no screen, or no options with options == NULL.
  *   tables    the views' scenes travel through the ring of kifs_render_animation_async's tables (KIFS_ANIMATION_RING
  *             per context, shared by both calls), with the context's scene in every record when options == NULL.
  *   launch    like an animated launch the call neither records tile costs nor advances the tile-order sort and is not
@@ -362,6 +363,35 @@ int kifs_render_accumulate_async(kifs_ctx* ctx, void* hip_stream, int count, int
                                  const KifsOptionsUniform* options,  /* count * samples images, or NULL: the context's options */
                                  uint8_t* const* dev_outs_rgba8,     /* count destinations */
                                  size_t pitch_bytes, int y0, int y1, int encode);
+
+/* ---- extension: jittered accumulated frames -- a sub-pixel cell per sub-frame, so that blur also anti-aliases -----
+ * NOT part of the reference.  kifs_render_accumulate_async sends every sub-frame's ray through the pixel centre: its
+ * frames are blurred where something moves and stair-stepped where nothing does.  Distributed ray tracing gives each
+ * sub-frame another point of the pixel instead, and the S rays of the blur anti-alias as well -- not S k^2 rays.
+ *   base      everything kifs_render_accumulate_async says holds: sub-frames and views, the resolve and its order, misses,
+ *             limits, what may vary between option images, bands, tables and the launch's debug hooks
+ *             (KIFS_KERNEL_ACCUMULATE; not timed by kifs_set_profiling).
+ *   cells     the one difference.  With g = grid, sub-frame v = i_frame * samples + s shades pixel
+ *             (g x + cells[v].i, g y + cells[v].j) of the VIRTUAL screen kifs_set_supersampling defines for k = g: width
+ *             g W, height g H, the same aspect_ratio float, the same fs_main at the same kind of fragment centre.  (x, y)
+ *             is the output pixel, global in a band.  Heatmap colours and soft shadows apply per sub-frame at the
+ *             sub-frame's own point.
+ *   NULL      cells == NULL is allowed only with samples == grid * grid: sub-frame s of every frame then takes cell
+ *             (s % grid, s / grid) -- the supersampling order.  With one camera and one scene for all of a frame's
+ *             sub-frames and grid <= KIFS_MAX_SUPERSAMPLING the frame holds exactly the bytes
+ *             kifs_set_supersampling(ctx, grid) + kifs_render_batch_async write.
+ *   grid 1    cells must be (0, 0) or NULL, and the call is kifs_render_accumulate_async exactly (the same kernel).
+ *   refusals  a refused call launches and writes nothing.  KIFS_ERR_BAD_ARG: everything kifs_render_accumulate_async
+ *             refuses with that status, the context's own supersampling factor above 1 included; grid outside
+ *             1 .. KIFS_MAX_JITTER_GRID; a cell with i >= grid or j >= grid; cells == NULL with samples != grid * grid.
+ *             KIFS_ERR_BAD_SIZE: a bad pitch; g W or g H above 65536, as for supersampling.  KIFS_ERR_UNCONFIGURED as the
+ *             unjittered call. */
+#define KIFS_MAX_JITTER_GRID 8
+typedef struct KifsSubpixel { uint8_t i, j; } KifsSubpixel;   /* cell of the g x g grid inside a pixel: column i, row j */
+int kifs_render_accumulate_jittered_async(kifs_ctx* ctx, void* hip_stream, int count, int samples,
+                                          const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
+                                          int grid, const KifsSubpixel* cells /* count * samples, or NULL */,
+                                          uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, int y0, int y1, int encode);
 
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */

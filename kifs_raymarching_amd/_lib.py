@@ -45,6 +45,13 @@ class AdaptiveAAC(C.Structure):  # KifsAdaptiveAA
     _fields_ = [("factor", C.c_int32), ("normal_cos", C.c_float), ("depth_rel", C.c_float)]
 
 
+class KifsSubpixel(C.Structure):  # a cell of the g x g grid inside a pixel (kifs_render_accumulate_jittered_async)
+    _fields_ = [("i", C.c_uint8), ("j", C.c_uint8)]
+
+
+MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
+
+
 class GuiDataC(C.Structure):  # KifsGuiData
     _fields_ = [("max_iterations", C.c_uint32), ("max_distance", C.c_float),
                 ("epsilon", C.c_float), ("fractal_color", C.c_uint8 * 3),
@@ -72,6 +79,7 @@ MULTI_FRAMES_UNTOUCHED = 1
 assert C.sizeof(ScreenUniform) == 12
 assert C.sizeof(CameraUniform) == 64
 assert C.sizeof(OptionsUniform) == 80
+assert C.sizeof(KifsSubpixel) == 2
 
 # every symbol include/kifs_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -103,6 +111,9 @@ SIGNATURES = {
                                               C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_render_accumulate_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
                                                _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_render_accumulate_jittered_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
+                                                        C.c_int, _P(KifsSubpixel), _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int,
+                                                        C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

@@ -184,3 +184,35 @@ def lens_cameras(camera_data: CameraData, aperture: float, focus_distance: float
         for c, col in enumerate((m0_s, m[1], m[2])):
             u.matrix[c][:] = [float(v) for v in col] + [0.0]
     return out
+
+
+def grid_cells(g: int) -> list:
+    """The g^2 cells (i, j) of the g x g grid inside a pixel in supersampling order, j outer and i inner: what
+    GraphicState.render_accumulate(jitter=(g, None)) takes for samples = g^2."""
+    if g < 1:
+        raise ValueError("grid_cells: a grid of at least one cell")
+    return [(n % g, n // g) for n in range(g * g)]
+
+
+def jitter_stride(g: int) -> int:
+    """The smallest integer >= 0.618 g^2 that is coprime to g^2: the step of jitter_cells through the numbered cells."""
+    n = g * g
+    a = math.ceil(0.618 * n)
+    while math.gcd(a, n) != 1:
+        a += 1
+    return a
+
+
+def jitter_cells(g: int, samples: int, frame: int = 0) -> list:
+    """`samples` <= g^2 distinct cells (i, j) of the g x g grid for the sub-frames of output frame `frame`
+    (GraphicState.render_accumulate's jitter): with the cells numbered n = j g + i, sub-frame s takes
+    n_s = ((s + frame) * a) mod g^2, a = jitter_stride(g).  a is coprime to g^2, so the cells are distinct and
+    samples == g^2 uses every cell exactly once; a step of about 0.618 of the grid keeps a sub-frame's cell unrelated to
+    its time within the shutter interval or its place on the lens."""
+    if g < 1:
+        raise ValueError("jitter_cells: a grid of at least one cell")
+    n = g * g
+    if not 0 <= samples <= n:
+        raise ValueError(f"jitter_cells: at most {n} distinct cells in a {g} x {g} grid, {samples} asked for")
+    a = jitter_stride(g)
+    return [((((s + frame) * a) % n) % g, (((s + frame) * a) % n) // g) for s in range(samples)]

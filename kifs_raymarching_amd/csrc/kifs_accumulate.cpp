@@ -4,6 +4,9 @@
 // kifs_render_animation_async uses (filled with the context's scene when the caller gives no options: the kernel has one
 // path), the view-table ring beyond MAX_BATCH_INLINE views, view 0's options standing in for the context's for the
 // length of a call, and the one launch (launch_accumulate_render, kifs_accumulate_kernels.hip).
+// kifs_render_accumulate_jittered_async is the same call with a cell of a g x g grid inside the pixel per sub-frame (a
+// Jitter: null for the unjittered call): the cell travels in pad[0] of the view's scene record, the grid as the launch's
+// FrameParams::ssaa, and the launcher takes the jitter kernel from g = 2.
 #include <cstring>
 #include <vector>
 
@@ -11,6 +14,26 @@
 
 namespace kifs {
 namespace accum {
+
+// The sub-pixel cells of a jittered call: sub-frame v goes through cell cells[v] of the grid x grid cells of its pixel;
+// cells == nullptr (samples == grid * grid): sub-frame s of every frame through cell (s % grid, s / grid).
+struct Jitter {
+    int grid;
+    const KifsSubpixel* cells;
+};
+
+// What the jittered call refuses beyond check(): after it, so that every refusal of the unjittered call keeps its status.
+static int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter& j) {
+    if (j.grid < 1 || j.grid > KIFS_MAX_JITTER_GRID) return KIFS_ERR_BAD_ARG;
+    if (!j.cells && samples != j.grid * j.grid) return KIFS_ERR_BAD_ARG;
+    if (j.cells)
+        for (int v = 0; v < count * samples; ++v)
+            if (j.cells[v].i >= j.grid || j.cells[v].j >= j.grid) return KIFS_ERR_BAD_ARG;
+    int w = 0, h = 0;
+    if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
+    // the virtual g W x g H screen stays within frame_dims' limit, as a supersampled launch's (render_dims)
+    return (int64_t(w) * j.grid > 65536 || int64_t(h) * j.grid > 65536) ? KIFS_ERR_BAD_SIZE : KIFS_OK;
+}
 
 static int check(const kifs_ctx* c, int count, int samples, const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
                  uint8_t* const* outs, size_t pitch, int y0, int y1, int encode) {
@@ -34,7 +57,8 @@ static int check(const kifs_ctx* c, int count, int samples, const KifsCameraUnif
 }
 
 static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, const KifsCameraUniform* cameras,
-                   const KifsOptionsUniform* options, uint8_t* const* outs, size_t pitch, int y0, int y1, int encode) {
+                   const KifsOptionsUniform* options, const Jitter* jitter, uint8_t* const* outs, size_t pitch, int y0, int y1,
+                   int encode) {
     host::hip_ok(hipGetLastError(), "stale error before enqueue");
     const int views = count * samples;
     Params A;
@@ -56,6 +80,10 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
     P.round_steps = 0;
     P.workgroups_per_cu = 0;
     P.orbit_x2 = 0;
+    // (the context's own factor is 1: check)  A grid of 1 is the unjittered call: its kernel, zero pad words.
+    const int grid = jitter ? jitter->grid : 1;
+    P.ssaa = grid;
+    P.ssaa_inv_height = 1.0f / (float(grid) * c->screen.height);  // as fill_params computes a supersampled launch's
     if (options) host::julia_culls_of_frames(c, P, options, views);  // (fill_params certified view 0's constant alone)
     if (y1 == y0) return KIFS_OK;
 
@@ -77,6 +105,11 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
         s.background_color = {o.background_color[0], o.background_color[1], o.background_color[2]};
         s.background_rgba = host::background_pixel(c, s.background_color, encode);  // (not read: a miss is averaged too)
         std::memset(s.pad, 0, sizeof s.pad);
+        if (grid > 1) {  // the view's cell: pad[0] = i | j << 8
+            const int n = v % samples;
+            const KifsSubpixel cell = jitter->cells ? jitter->cells[v] : KifsSubpixel{uint8_t(n % grid), uint8_t(n / grid)};
+            s.pad[0] = uint32_t(cell.i) | uint32_t(cell.j) << 8;
+        }
     }
     P.background_rgba = scenes[0].background_rgba;
 
@@ -127,5 +160,20 @@ extern "C" int kifs_render_accumulate_async(kifs_ctx* c, void* hip_stream, int c
     if (!g.ok) return KIFS_ERR_RUNTIME;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
-    return accum::enqueue(c, s, count, samples, cameras, options, dev_outs, pitch, y0, y1, encode);
+    return accum::enqueue(c, s, count, samples, cameras, options, nullptr, dev_outs, pitch, y0, y1, encode);
+}
+
+extern "C" int kifs_render_accumulate_jittered_async(kifs_ctx* c, void* hip_stream, int count, int samples,
+                                                     const KifsCameraUniform* cameras, const KifsOptionsUniform* options, int grid,
+                                                     const KifsSubpixel* cells, uint8_t* const* dev_outs, size_t pitch, int y0,
+                                                     int y1, int encode) {
+    using namespace kifs;
+    if (const int st = accum::check(c, count, samples, cameras, options, dev_outs, pitch, y0, y1, encode); st != KIFS_OK) return st;
+    const accum::Jitter jitter{grid, cells};
+    if (const int st = accum::check_jitter(c, count, samples, jitter); st != KIFS_OK) return st;
+    host::DeviceGuard g(c->device);
+    if (!g.ok) return KIFS_ERR_RUNTIME;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
+    return accum::enqueue(c, s, count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode);
 }

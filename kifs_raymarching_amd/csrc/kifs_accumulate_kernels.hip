@@ -9,6 +9,10 @@
 //                                      block's 64 pixels, under the wave-level cull of that sub-frame's camera, and leaves
 //                                      each lane's linear colour in LDS at [s][channel][lane].  After a barrier wave 0 adds
 //                                      a pixel's sub-frames in the contract's order, divides, encodes and stores.
+//   accum::jitter_render_kernel<GROUP, PRIM>  the same with a sub-pixel cell per sub-frame
+//                                      (kifs_render_accumulate_jittered_async): sub-frame v's ray goes through cell (i, j)
+//                                      of the g x g grid inside its pixel, pixel (g x + i, g y + j) of the virtual
+//                                      g W x g H screen kifs_set_supersampling defines.  Both kernels are one body.
 // Why not the supersampling kernel's shape (a lane marches all of its samples one after another): a launch is as long as
 // its longest rays, and that shape makes a lone frame's critical ray `samples` rays long.  Here the
 // sub-frames of a block run side by side on four waves, and the blocks of every output frame side by side on the device.
@@ -55,12 +59,21 @@ __device__ __forceinline__ const Params& reloaded(ConstParams& kp) {
     return *(const Params*)kp;
 }
 
-// (amdgpu_waves_per_eu: as ssaa::render_kernel, whose sample loop this one's sub-frame loop resembles)
-template <int GROUP, int PRIM>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void render_kernel(const Params A) {
-    __shared__ float s_srgb[256];
-    extern __shared__ float s_colour[];  // [samples][3][64]
+// A jittered view's cell of the g x g grid inside a pixel (kifs_render_accumulate_jittered_async): pad[0] = i | j << 8 of
+// its scene record, one more scalar load beside overlay_scene's.
+__device__ __forceinline__ uint32_t cell_of(const anim::SceneView* scenes, uint32_t view) {
+    typedef const anim::SceneView __attribute__((address_space(4))) * ConstScene;
+    return ((ConstScene)(scenes + view))->pad[0];
+}
 
+// The body of both kernels: the operation order exists once.  JITTER: sub-frame v's ray goes through cell (i, j) of its
+// pixel instead of the centre, i.e. through pixel (g x + i, g y + j) of the VIRTUAL g W x g H screen with the frame's
+// aspect float, as ssaa::render_kernel's samples do (g = frame.ssaa, the virtual screen's 1 / height from the host).
+// Only the wave-level cull is used, and its argument is per lane with the screen's own 1 / height: it holds on the
+// virtual screen as it stands (cull_n2 and quick_cull_n2 are radii in scene space: fill_params).  `valid` and the store
+// guards stay on OUTPUT coordinates.
+template <int GROUP, int PRIM, bool JITTER>
+__device__ __forceinline__ void render_body(const Params& A, float* s_srgb, float* s_colour) {
     ConstParams kp = (ConstParams)__builtin_amdgcn_kernarg_segment_ptr();  // = &A
     int tid = threadIdx.x;
     const uint32_t wave = uint32_t(__builtin_amdgcn_readfirstlane(tid >> 6));  // uniform, and known to be
@@ -84,10 +97,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
         FrameParams P = batch_frame(L.B, view);
         overlay_scene(P, L.scenes, view);
         const bool valid = (x < P.width) && (y < P.y1);
+        int px = x, py = y;  // the pixel the ray goes through: of the frame, or of the virtual screen
+        if constexpr (JITTER) {
+            const uint32_t cell = cell_of(L.scenes, view);  // wave-uniform
+            const int g = P.ssaa;                           // 2..KIFS_MAX_JITTER_GRID
+            px = g * x + int(cell & 0xffu);
+            py = g * y + int((cell >> 8) & 0xffu);
+            P.height = float(g) * P.height;  // exact: integers below 2^24
+            P.inv_height = P.ssaa_inv_height;
+        }
         V3 c = P.background_color;  // a ray the cull drops is a miss
-        if (!wave_is_culled(P, x, y, valid)) {  // wave-uniform
+        if (!wave_is_culled(P, px, py, valid)) {  // wave-uniform
             int steps = 0;
-            const V3 dir = ray_direction(P, x, y);
+            const V3 dir = ray_direction(P, px, py);
             c = raymarch<GROUP, PRIM>(P, dir, valid, steps);
         }
         float* const slot = s_colour + s * SLOT + lane;
@@ -118,29 +140,50 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     }
 }
 
+// (amdgpu_waves_per_eu: as ssaa::render_kernel, whose sample loop this one's sub-frame loop resembles)
+template <int GROUP, int PRIM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void render_kernel(const Params A) {
+    __shared__ float s_srgb[256];
+    extern __shared__ float s_colour[];  // [samples][3][64]
+    render_body<GROUP, PRIM, false>(A, s_srgb, s_colour);
+}
+
+// The same with a sub-pixel cell per sub-frame (A.B.frame.ssaa = g > 1).  A kernel of its own, not a template parameter
+// of the one above: the unjittered launch keeps its code and its name.
+template <int GROUP, int PRIM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void jitter_render_kernel(const Params A) {
+    __shared__ float s_srgb[256];
+    extern __shared__ float s_colour[];  // [samples][3][64]
+    render_body<GROUP, PRIM, true>(A, s_srgb, s_colour);
+}
+
 // From 63 sub-frames the dynamic LDS and the 1 KB sRGB table together pass the default limit of 48 KB: the kernel then opts
 // in, once per instantiation and device, as ensure_dynamic_lds does for the residency pad (kifs_render_common.hpp).
-template <int GROUP, int PRIM>
+template <int GROUP, int PRIM, bool JITTER>
 static hipError_t ensure_lds(unsigned dynamic_bytes) {
     if (dynamic_bytes + 256u * unsigned(sizeof(float)) <= 48u * 1024u) return hipSuccess;
     static std::atomic<bool> opted_in[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-        hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        const void* const kernel = JITTER ? reinterpret_cast<const void*>(&jitter_render_kernel<GROUP, PRIM>)
+                                          : reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>);
+        hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         if (attr != hipSuccess) return attr;
         if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
     }
     return hipSuccess;
 }
 
-template <int GROUP, int PRIM>
+template <int GROUP, int PRIM, bool JITTER>
 static hipError_t launch(const Params& A, hipStream_t stream) {
     const unsigned lds = unsigned(A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
-    if (hipError_t e = ensure_lds<GROUP, PRIM>(lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), dim3(A.B.frame.tile_count * BLOCKS * uint32_t(A.frames)), dim3(BLOCK), lds,
-                       stream, A);
+    if (hipError_t e = ensure_lds<GROUP, PRIM, JITTER>(lds); e != hipSuccess) return e;
+    const dim3 grid(A.B.frame.tile_count * BLOCKS * uint32_t(A.frames));
+    if (JITTER)
+        hipLaunchKernelGGL((jitter_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
+    else
+        hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
     return hipGetLastError();
 }
 
@@ -148,10 +191,13 @@ static hipError_t launch(const Params& A, hipStream_t stream) {
 
 hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream) {
     if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
+    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
+    const bool jitter = A.B.frame.ssaa > 1;  // a cell per sub-frame in its scene record: jitter_render_kernel
     // Julia: the short divide / square root by sdf_iters; the doubled orbit trip is the throughput kernels' only.
     // The bunny: per-lane bunny_sdf -- slow, correct.
     return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
-        return accum::launch<decltype(g)::value, decltype(prim)::value>(A, stream);
+        return jitter ? accum::launch<decltype(g)::value, decltype(prim)::value, true>(A, stream)
+                      : accum::launch<decltype(g)::value, decltype(prim)::value, false>(A, stream);
     });
 }
 

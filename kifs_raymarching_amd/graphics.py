@@ -24,7 +24,8 @@ SPARSE_RECORD_BYTES = 1040  # KIFS_SPARSE_RECORD_BYTES
 STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
-from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, OptionsUniform,
+MAX_JITTER_GRID = _lib.MAX_JITTER_GRID  # KIFS_MAX_JITTER_GRID
+from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -504,7 +505,7 @@ class GraphicState:
 
     # ---- accumulated frames (kifs_render_accumulate_async): every frame the linear-colour mean of its sub-frames
     def render_accumulate(self, cameras, samples, options=None, outs=None, y0: int = 0, y1: int = None,
-                          encode: int = ENCODE_SRGB, stream=None):
+                          encode: int = ENCODE_SRGB, stream=None, jitter=None):
         """One launch for len(cameras) / samples output frames, each the mean of `samples` sub-frames taken in linear
         colour before the encode: motion blur (configs.shutter_cameras), depth of field (configs.lens_cameras), a morph
         without temporal aliasing (per-sub-frame options).  Sub-frame s of frame i is cameras[i * samples + s] (CameraData
@@ -513,7 +514,11 @@ class GraphicState:
         1 <= samples <= MAX_ACCUMULATE and len(cameras) <= MAX_BATCH.  Returns the frames as one uint8
         (count, rows, W, 4) torch tensor on this context's device; `outs`: a contiguous destination tensor of that shape
         to reuse.  Enqueued on `stream` like render_async and ordered after torch's current stream; the caller
-        synchronises before reading, and keeps a tensor this method allocated alive until the launch has run."""
+        synchronises before reading, and keeps a tensor this method allocated alive until the launch has run.
+        `jitter` = (grid, cells) sends sub-frame v through cell cells[v] = (i, j) of the grid x grid cells of its pixel
+        instead of the centre (kifs_render_accumulate_jittered_async: the blur's rays anti-alias too); cells: a sequence
+        of len(cameras) pairs (configs.jitter_cells), a ready KifsSubpixel array, or None with samples == grid * grid for
+        the supersampling order (configs.grid_cells).  None: today's call and bytes."""
         import torch
         w, h = self.screen_data.width, self.screen_data.height
         y1 = h if y1 is None else y1
@@ -536,8 +541,17 @@ class GraphicState:
         base, frame_bytes = _device_pointer(outs), rows * w * 4
         ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
         self._order_after_producer(outs, stream)
-        check(lib.kifs_render_accumulate_async(self._ctx, stream, n, samples, cams, opts, ptrs, w * 4, y0, y1, encode),
-              "render_accumulate")
+        if jitter is None:
+            check(lib.kifs_render_accumulate_async(self._ctx, stream, n, samples, cams, opts, ptrs, w * 4, y0, y1, encode),
+                  "render_accumulate")
+            return outs
+        grid, cells = jitter
+        if cells is not None and not isinstance(cells, C.Array):
+            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
+        if cells is not None and len(cells) != views:
+            raise ValueError(f"render_accumulate: {len(cells)} cells for {views} cameras")
+        check(lib.kifs_render_accumulate_jittered_async(self._ctx, stream, n, samples, cams, opts, int(grid), cells, ptrs, w * 4,
+                                                        y0, y1, encode), "render_accumulate")
         return outs
 
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,

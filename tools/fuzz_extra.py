@@ -3,7 +3,9 @@
 render_wave_kernel and mid-size ones for render_group_kernel with the soft-shadow extension on (pooled secondary rays), and
 bunny batches through render_bunny_coop_kernel, random primitives / cameras / epsilon / extension parameters, two views per launch against the
 oracle.  Prints one line per launch and a summary; exit code 1 on any mismatch.
-    python tools/fuzz_extra.py [launches] [seed]"""
+    python tools/fuzz_extra.py [launches] [seed]
+    python tools/fuzz_extra.py jitter [launches] [seed]   # kifs_render_accumulate_jittered_async against tests/jitter_reference.py:
+                                                          # random pipeline, grid, samples, cells, band and encode"""
 import sys
 from pathlib import Path
 
@@ -18,6 +20,46 @@ import kifs_raymarching_amd as K  # noqa: E402
 import oracle as O  # noqa: E402
 from helpers import diff_report, oracle_uniforms  # noqa: E402
 
+
+
+def jitter_mode(argv):
+    """Random jittered accumulated launches on small frames, every byte against the model."""
+    import accumulate_cases as AC
+    import jitter_reference as JR
+    n = int(argv[0]) if argv else 40
+    rng = np.random.default_rng(int(argv[1]) if len(argv) > 1 else 20261019)
+    wrong = 0
+    with K.GraphicState(0) as g:
+        for it in range(n):
+            name = AC.PIPELINES[int(rng.integers(0, len(AC.PIPELINES)))]
+            w, h = int(rng.integers(9, 100)), int(rng.integers(3, 60))
+            screen, cam, gui, iters = AC.scene(K, name, w, h)
+            grid = int(rng.integers(1, K.MAX_JITTER_GRID + 1))
+            null_cells = bool(rng.integers(0, 3) == 0)
+            samples = grid * grid if null_cells else int(rng.integers(1, 17))
+            count = int(rng.integers(1, 5)) if samples <= 16 else 1
+            cells = None if null_cells else [(int(rng.integers(0, grid)), int(rng.integers(0, grid))) for _ in range(count * samples)]
+            y0 = int(rng.integers(0, h))
+            y1 = int(rng.integers(y0 + 1, h + 1))
+            encode = int(rng.integers(0, 2))
+            g.update_screen_data(screen)
+            g.set_camera(cam)
+            g.update_options(gui.u if isinstance(gui, AC.Raw) else gui)
+            g.set_iters(*iters)
+            cams = AC.blur_cameras(K, cam, count, samples)
+            got = g.render_accumulate(cams, samples, y0=y0, y1=y1, encode=encode, jitter=(grid, cells))
+            g.synchronize()
+            want = JR.jittered_frames(O, K, screen, cams, gui, iters, samples, grid, cells, encode, y0=y0, y1=y1)
+            miss = int((got.cpu().numpy() != want).any(-1).sum())
+            wrong += miss > 0
+            print(f"{it:3d} {name:12s} {w}x{h} rows [{y0}, {y1}) {count} x {samples} grid {grid} cells {'NULL' if null_cells else 'given'} "
+                  f"encode={encode} mismatched={miss}", flush=True)
+    print(f"{n} jittered launches, {wrong} with mismatches")
+    sys.exit(1 if wrong else 0)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "jitter":
+    jitter_mode(sys.argv[2:])
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 20261006)
 FG, PS = K.FractalGroup, K.PrimitiveShape

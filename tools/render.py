@@ -10,6 +10,8 @@
     python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --shutter 0.5   # motion blur
     python tools/render.py cfg2_julia_1080p out.png --dof 0.05,3.2 --samples 32                # depth of field
     python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --motion-blur 8   # a blurred morph
+    python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --jitter 4   # blur that anti-aliases
+    python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --aa 2           # an anti-aliased morph
 """
 import argparse
 import sys
@@ -17,7 +19,7 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
-from kifs_raymarching_amd.configs import WORKLOADS, lens_cameras, morph_options, orbit_camera, shutter_cameras  # noqa: E402
+from kifs_raymarching_amd.configs import WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, shutter_cameras  # noqa: E402
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -27,7 +29,8 @@ ap.add_argument("--frames", type=int, nargs="*", default=None,
                 help="orbit frame indices (out needs %%d); with --morph-to: one number, the frames of the morph")
 ap.add_argument("--morph-to", metavar="R,I,J,K", default=None,
                 help="a morph of the constant from the workload's to this quaternion, --frames N frames in launches of up to "
-                     "512 (kifs_render_animation_async), written to OUT_000.png ..; not with --aa, --aa-adaptive or --geometry")
+                     "512 (kifs_render_animation_async), written to OUT_000.png ..; with --aa K every frame is the K x K cells of "
+                     "kifs_render_accumulate_jittered_async; not with --aa-adaptive or --geometry")
 ap.add_argument("--scale", type=float, default=1.0, help="resolution scale")
 ap.add_argument("--heatmap", action="store_true")
 ap.add_argument("--aa", type=int, default=1, metavar="K", help="K x K supersampled anti-aliasing (1..4; 1 = off)")
@@ -55,6 +58,10 @@ ap.add_argument("--dof", metavar="APERTURE,FOCUS", default=None,
                      "share the plane at distance FOCUS; one frame, or the orbit frames of --frames; not with --motion-blur, "
                      "--morph-to, --aa, --aa-adaptive or --geometry")
 ap.add_argument("--samples", type=int, default=16, metavar="S", help="with --dof: sub-frames per frame (1..64)")
+ap.add_argument("--jitter", type=int, default=0, metavar="G",
+                help="with --motion-blur S or --dof .. --samples S (S <= G x G): sub-frame s goes through its own cell of a "
+                     f"G x G grid inside the pixel (1..{K.MAX_JITTER_GRID}; kifs_render_accumulate_jittered_async, cells from "
+                     "configs.jitter_cells), so the blur's rays anti-alias as well")
 args = ap.parse_args()
 dof = None
 if args.dof is not None:
@@ -71,6 +78,13 @@ if (args.motion_blur or dof) and not 1 <= accumulate <= K.MAX_ACCUMULATE:
     ap.error(f"1..{K.MAX_ACCUMULATE} sub-frames per frame")
 if accumulate and (args.aa != 1 or args.aa_adaptive or args.geometry):
     ap.error("--motion-blur and --dof render without --aa, --aa-adaptive or --geometry")
+if args.jitter:
+    if not accumulate:
+        ap.error("--jitter goes with --motion-blur or --dof")
+    if not 1 <= args.jitter <= K.MAX_JITTER_GRID or accumulate > args.jitter ** 2:
+        ap.error(f"--jitter G: 1..{K.MAX_JITTER_GRID}, with at most G x G sub-frames per frame")
+# --aa K for a morph or several orbit frames: one launch, every frame the K x K cells of a pixel in supersampling order
+aa_grid = args.aa > 1 and not accumulate and (args.morph_to is not None or (args.frames is not None and len(args.frames) > 1))
 if args.motion_blur and args.morph_to is None and not args.frames:
     ap.error("--motion-blur needs the orbit frames of --frames (or --morph-to)")
 if args.geometry and (args.aa != 1 or args.frames is not None):
@@ -87,8 +101,8 @@ if args.morph_to is not None:
         morph_to = ()
     if len(morph_to) != 4:
         ap.error("--morph-to takes four numbers R,I,J,K")
-    if args.aa != 1 or args.aa_adaptive or args.geometry:
-        ap.error("--morph-to renders plain frames, without --aa, --aa-adaptive or --geometry")
+    if args.aa_adaptive or args.geometry:
+        ap.error("--morph-to renders without --aa-adaptive or --geometry")
     if args.frames is None or len(args.frames) != 1 or args.frames[0] < 1:
         ap.error("--morph-to needs --frames N, the number of frames (at least 1)")
 w = WORKLOADS[args.workload]
@@ -100,7 +114,8 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
     gs.set_iters(*w.iters)
     if w.extensions:
         gs.set_extensions(**w.extensions)
-    gs.set_supersampling(args.aa)
+    gs.set_supersampling(1 if aa_grid else args.aa)
+    jitter_of = lambda frames, S: None if not args.jitter else (args.jitter, [c for k in frames for c in jitter_cells(args.jitter, S, k or 0)])
     if args.geometry:
         import numpy as np
         colour, geometry = gs.render_geometry()
@@ -130,7 +145,7 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
         per_call = max(1, K.MAX_BATCH // S)
         for first in range(0, n, per_call):
             sub = guis[first * S:(first + per_call) * S]
-            frames = gs.render_accumulate([w.camera] * len(sub), S, options=sub)
+            frames = gs.render_accumulate([w.camera] * len(sub), S, options=sub, jitter=jitter_of(range(first, first + len(sub) // S), S))
             gs.synchronize()
             for i, frame in enumerate(frames.cpu().numpy(), start=first):
                 write_png(str(out.with_name(f"{out.stem}_{i:03d}{out.suffix}")), frame)
@@ -149,13 +164,34 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                     cams.extend(lens_cameras(w.camera if k is None else orbit_camera(w, k), dof[0], dof[1], S))
                 else:
                     cams.extend(c.into_buffer_data() for c in shutter_cameras(w, k, S, args.shutter))
-            frames = gs.render_accumulate(cams, S)
+            frames = gs.render_accumulate(cams, S, jitter=jitter_of(part, S))
             gs.synchronize()
             for k, frame in zip(part, frames.cpu().numpy()):
                 path = args.out if k is None else args.out % k
                 write_png(path, frame)
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
-                      + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})"))
+                      + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})")
+                      + (f", jittered over a {args.jitter}x{args.jitter} grid" if args.jitter else ""))
+    elif aa_grid:
+        # the whole grid: K x K sub-frames per frame that differ in their cell alone -- the supersampled frame's bytes
+        S = args.aa * args.aa
+        out = Path(args.out)
+        if morph_to is not None:
+            n = args.frames[0]
+            guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n)
+            todo = [(str(out.with_name(f"{out.stem}_{i:03d}{out.suffix}")), w.camera, guis[i]) for i in range(n)]
+        else:
+            todo = [(args.out % k, orbit_camera(w, k), gui) for k in args.frames]
+        per_call = max(1, K.MAX_BATCH // S)
+        for first in range(0, len(todo), per_call):
+            part = todo[first:first + per_call]
+            frames = gs.render_accumulate([cam for _, cam, _ in part for _ in range(S)], S,
+                                          options=[g for _, _, g in part for _ in range(S)], jitter=(args.aa, None))
+            gs.synchronize()
+            for (path, _, _), frame in zip(part, frames.cpu().numpy()):
+                write_png(path, frame)
+        print(f"{todo[0][0]} .. : {len(todo)} frames of {screen.width}x{screen.height}, {args.aa}x{args.aa} supersampled, up to "
+              f"{per_call} frames per launch")
     elif morph_to is not None:
         n = args.frames[0]
         guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n)
