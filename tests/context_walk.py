@@ -11,6 +11,13 @@ between launches: "adaptive" (kifs_render_adaptive_async: the scratch block and 
 "batch66", its own stream rule on the tile table).  Frame j of an animated launch uses camera batch_cameras(camera, n)[j]
 and the option image morph_of(that camera) of the context's options, so that a launch's frames differ in scene as well
 as in view and still need no more than four references per context state.
+
+The accumulated launches (kifs_render_accumulate_async and kifs_render_accumulate_jittered_async) share both rings with
+them and write the tile table's last_stream as they do: "accumulate" is a blur launch of 2 frames x 3 sub-frames on the
+whole frame or a band, "jitter" one of 2 x 2 on a grid of 2, and "accumulate66" 33 frames of 2 identical sub-frames each
+-- 66 views, a third user of the view-table ring, whose frames are the oracle's plain frames.  The cameras are
+batch_cameras(camera, views) and every sub-frame carries the option image morph_of(its camera), so a context state needs
+at most four linear views for blur and eight for jitter (linear_view_keys counts them per plan).
 """
 import random
 
@@ -19,8 +26,10 @@ N_CAMERAS, N_OPTIONS, N_ITERS, N_BANDS, N_STREAMS = 4, 3, 2, 12, 3
 N_MORPHS = 3  # option images per option set: 0 the set itself, 1 and 2 with other constant, power and colours
 TABLE_SLOTS = 8  # MAX_TILE_TABLES of kifs_context.hpp
 VIEW_RING = 4    # kifs_ctx::VIEW_RING: the view tables of launches beyond 64 views
+SCENE_RING = 4   # kifs_ctx::SCENE_RING: the scene tables of animated and accumulated launches
+MODEL_UP_TO = (330, 149)  # the largest screen a launch is held to a per-pixel model of the oracle on
 STEPS = 72
-SEEDS = (16, 2039, 2360)
+SEEDS = (882, 2444, 3958)  # the three of 0..3999 that meet tests/test_context_walk_plan.py at 72 steps
 
 # kind -> (weight, arguments to draw from); the renders outweigh the state changes so that the set of distinct
 # (scene, camera, size) references stays small
@@ -41,12 +50,18 @@ OPS = {
     "adaptive": (3, (2, 3)),          # k; the thresholds are adaptive_reference.DEFAULT
     "animation3": (3, (-1, 2, 7)),    # -1: the whole frame, else the band band_rows(h, argument)
     "animation66": (2, (0,)),         # the whole frame, 66 frames: beyond MAX_BATCH_INLINE
+    "accumulate": (3, (-1, 2, 7)),    # blur, 2 frames x 3 sub-frames; the rows as "animation3"
+    "jitter": (3, (-1, 5)),           # 2 frames x 2 sub-frames through cells JITTER_CELLS of a grid of 2; the rows likewise
+    "accumulate66": (2, (0,)),        # pairs: 33 frames x 2 equal sub-frames = 66 views, the whole frame
 }
-RENDERS = ("band", "batch3", "batch66", "shard", "geometry", "adaptive", "animation3", "animation66")
-ONE_SAMPLE_ONLY = ("geometry", "adaptive", "animation3", "animation66")  # refused by the API while supersampling > 1
-STATEFUL = ("adaptive", "animation3", "animation66")                     # entry points with state of their own
+ACCUMULATED = {"accumulate": (2, 3), "jitter": (2, 2), "accumulate66": (33, 2)}  # kind -> (frames, sub-frames per frame)
+RENDERS = ("band", "batch3", "batch66", "shard", "geometry", "adaptive", "animation3", "animation66") + tuple(ACCUMULATED)
+# refused by the API while supersampling > 1
+ONE_SAMPLE_ONLY = ("geometry", "adaptive", "animation3", "animation66") + tuple(ACCUMULATED)
+STATEFUL = ("adaptive", "animation3", "animation66") + tuple(ACCUMULATED)  # entry points with state of their own
 ANIMATED = {"animation3": 3, "animation66": 66}                          # kind -> frames
-VIEW_RING_USERS = ("batch66", "animation66")
+VIEW_RING_USERS = ("batch66", "animation66", "accumulate66")
+JITTER_GRID, JITTER_CELLS = 2, ((1, 0), (0, 1))  # sub-frame s of every frame of a "jitter" launch goes through JITTER_CELLS[s]
 
 
 def morph_of(camera_index):
@@ -60,7 +75,7 @@ def band_rows(height, i):
 
 
 def animation_rows(height, arg):
-    """The rows of an "animation3" launch: the whole frame for -1, else band `arg`."""
+    """The rows of an "animation3", "accumulate" or "jitter" launch: the whole frame for -1, else band `arg`."""
     return (0, height) if arg < 0 else band_rows(height, arg)
 
 
@@ -104,8 +119,8 @@ def batch_cameras(camera, n):
 def replay(ops):
     """The tile-table geometries a plan visits: yields (op index, key, event) for every render, event one of "hit",
     "fill" (an empty slot), "evict" and "return" (a miss on a geometry this walk has evicted before: also an eviction).
-    An animated band takes the table of the plain band of its rows; an adaptive call's first pass and a whole-frame
-    animated launch take the full frame's."""
+    An animated or accumulated band takes the table of the plain band of its rows; an adaptive call's first pass and a
+    whole-frame animated or accumulated launch take the full frame's."""
     size = SIZES[0]
     slots, clock, evicted = {}, 0, set()
     for i, (kind, arg) in enumerate(ops):
@@ -114,7 +129,7 @@ def replay(ops):
         if kind not in RENDERS:
             continue
         w, h = size
-        if kind == "band" or (kind == "animation3" and arg >= 0):
+        if kind == "band" or (kind in ("animation3", "accumulate", "jitter") and arg >= 0):
             key = (w, h) + band_rows(h, arg) + (None,)
         elif kind == "shard":
             key = (w, h, 0, h, shard_stripes(h, arg))
@@ -134,16 +149,52 @@ def replay(ops):
         yield i, key, event
 
 
+def modelled(size):
+    return size[0] <= MODEL_UP_TO[0] and size[1] <= MODEL_UP_TO[1]
+
+
+def blur_views(camera):
+    """(camera, option image) of the six sub-frames of an "accumulate" launch, frame by frame."""
+    return [(cam, morph_of(cam)) for cam in batch_cameras(camera, 6)]
+
+
+def jitter_views(camera):
+    """(camera, option image, cell) of the four sub-frames of a "jitter" launch, frame by frame."""
+    return [(cam, morph_of(cam), JITTER_CELLS[v % 2]) for v, cam in enumerate(batch_cameras(camera, 4))]
+
+
+def linear_view_keys(ops):
+    """The distinct per-pixel linear views (size, camera, options, iters, extensions, option image, cell) the blur and
+    jitter launches of a plan are modelled from: the cost of their references, known before a GPU run.  cell is None for
+    blur; screens beyond MODEL_UP_TO need none (there the launch is compared with a fresh context's)."""
+    keys = set()
+    for _, kind, _, st in trace(ops):
+        size = SIZES[st["size"]]
+        if kind in ("accumulate", "jitter") and modelled(size):
+            views = [v + (None,) for v in blur_views(st["camera"])] if kind == "accumulate" else jitter_views(st["camera"])
+            keys |= {(size, cam, st["options"], st["iters"], st["extensions"], m, cell) for cam, m, cell in views}
+    return keys
+
+
+def _passages(users, ring):
+    """The unordered pairs of different users of which one takes a ring's slot from the other: user n and user n + ring."""
+    return {frozenset((users[i], users[i + ring])) for i in range(len(users) - ring) if users[i] != users[i + ring]}
+
+
 def coverage(ops):
     """What a plan exercises: launches per kind, evictions and returns of the table model, per entry point with state of
-    its own the launches made while the walk's stream is a caller's (1 or 2), and whether a slot of the view-table ring
-    passes from one entry point to the other: some user of the ring and the user VIEW_RING later, which takes the same
-    slot, are a "batch66" and an "animation66" in either order (so that window of VIEW_RING + 1 users holds both)."""
+    its own the launches made while the walk's stream is a caller's (1 or 2), and how the two rings are shared.  A user
+    of a ring and the user four later take the same slot.  view_ring_passages: the pairs of kinds of VIEW_RING_USERS
+    between which a view-table slot passes, in either order; view_ring_shared: "batch66" and "animation66" are one of
+    them.  scene_ring_shared: among the users of the scene ring -- every animated and every accumulated launch -- some
+    user and the user SCENE_RING later belong to different entry points, animation against accumulate."""
     events = [e for _, _, e in replay(ops)]
     kinds = {k: sum(1 for kind, _ in ops if kind == k) for k in OPS}
     renders = list(trace(ops))
     on_caller_stream = {k: sum(1 for _, kind, _, st in renders if kind == k and st["stream"] in (1, 2)) for k in STATEFUL}
-    users = [kind for _, kind, _, _ in renders if kind in VIEW_RING_USERS]
-    shared = any(users[i] != users[i + VIEW_RING] for i in range(len(users) - VIEW_RING))
+    passages = _passages([kind for _, kind, _, _ in renders if kind in VIEW_RING_USERS], VIEW_RING)
+    scene_users = ["animation" if kind in ANIMATED else "accumulate" for _, kind, _, _ in renders if kind in ANIMATED or kind in ACCUMULATED]
     return {"kinds": kinds, "evictions": events.count("evict") + events.count("return"), "returns": events.count("return"),
-            "on_caller_stream": on_caller_stream, "view_ring_shared": shared}
+            "on_caller_stream": on_caller_stream, "view_ring_passages": passages,
+            "view_ring_shared": frozenset(("batch66", "animation66")) in passages,
+            "scene_ring_shared": bool(_passages(scene_users, SCENE_RING))}

@@ -344,24 +344,28 @@ SSAA_FORMS = {
 }
 
 
-# geom::, adaptive:: and anim::render_kernel<G, P>, chosen by dispatch_pipeline<2>(group, primitive, sdf_iters <= 24): each
-# is claimed by the geometry_cases.PIPELINES name that reaches it in test_every_pipeline_bit_exact of
-# tests/test_gpu_geometry.py, test_gpu_adaptive.py and test_gpu_animation.py (and in the seeded scenes of
-# tests/extension_fuzz_cases.py, which take the same names).  adaptive::classify_kernel is no render form -- it reads a
+# geom::, adaptive::, anim:: and accum::render_kernel<G, P> and accum::jitter_render_kernel<G, P>, chosen by
+# dispatch_pipeline<2>(group, primitive, sdf_iters <= 24): each is claimed by the geometry_cases.PIPELINES name that reaches
+# it in test_every_pipeline_bit_exact of tests/test_gpu_geometry.py, test_gpu_adaptive.py, test_gpu_animation.py,
+# test_gpu_accumulate.py and test_gpu_accumulate_jitter.py (and in the seeded scenes of tests/extension_fuzz_cases.py, which
+# take the same names).  adaptive::classify_kernel is no render form -- it reads a
 # geometry plane and marches nothing -- and stays out of the table.
 _EXTENSION_PIPELINES = {(0, 0): "sphere", (0, 1): "cylinder", (0, 2): "box", (0, 3): "torus", (0, 4): "sierpinski",
                         (0, 5): "bunny", (0, 6): "unknown_id", (1, 0): "julia_25", (1, 1): "julia_24", (2, 0): "genjulia"}
 
 
-def _extension_forms(namespace, params):
-    return {f"void kifs::{namespace}::render_kernel<{g}, {p}>({params})": name for (g, p), name in _EXTENSION_PIPELINES.items()}
+def _extension_forms(namespace, params, kernel="render_kernel"):
+    return {f"void kifs::{namespace}::{kernel}<{g}, {p}>({params})": name for (g, p), name in _EXTENSION_PIPELINES.items()}
 
 
 GEOMETRY_FORMS = _extension_forms("geom", "kifs::BatchParams")
 ADAPTIVE_FORMS = _extension_forms("adaptive", "kifs::adaptive::Params")
 ANIMATION_FORMS = _extension_forms("anim", "kifs::anim::Params")
+ACCUMULATE_FORMS = _extension_forms("accum", "kifs::accum::Params")
+JITTER_FORMS = _extension_forms("accum", "kifs::accum::Params", "jitter_render_kernel")
 EXTENSION_FORMS = {"test_gpu_geometry.py": GEOMETRY_FORMS, "test_gpu_adaptive.py": ADAPTIVE_FORMS,
-                   "test_gpu_animation.py": ANIMATION_FORMS}
+                   "test_gpu_animation.py": ANIMATION_FORMS, "test_gpu_accumulate.py": ACCUMULATE_FORMS,
+                   "test_gpu_accumulate_jitter.py": JITTER_FORMS}
 
 
 def short(name):

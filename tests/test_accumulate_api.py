@@ -1,7 +1,7 @@
 """Accumulated frames (kifs_render_accumulate_async), the parts a machine without a GPU can check: the ABI surface, the
 Python and CLI surface, and that hipcc compiled accum::render_kernel for every pipeline -- ten instantiations, none with
-scratch or spills, none matching the existing form table's pattern (that table covers the existing kernel families; this
-family's coverage is stated here), and their (GROUP, PRIM) pairs the ones geometry_cases.PIPELINES dispatch to."""
+scratch or spills, each with its claim in the kernel-form table (kernel_forms.ACCUMULATE_FORMS), and their (GROUP, PRIM)
+pairs the ones geometry_cases.PIPELINES dispatch to."""
 import ctypes as C
 import re
 import subprocess
@@ -45,13 +45,14 @@ def test_render_tool_offers_motion_blur_and_depth_of_field(kifs):
         assert flag in p.stdout, flag
 
 
-def test_every_pipeline_is_compiled_without_scratch_and_outside_the_form_table(kifs):
+def test_every_pipeline_is_compiled_without_scratch_and_claimed_by_the_form_table(kifs):
     from geometry_cases import PIPELINES, cases
-    from test_kernel_form_coverage import RENDER  # the existing form table's pattern
+    from kernel_forms import ACCUMULATE_FORMS
+    from test_kernel_form_coverage import RENDER  # the form table's own pattern
     report = kernel_report()
     names = [n for n in report if "kifs::accum::render_kernel<" in n]
     assert len(names) == len(PIPELINES) == 10, names
-    assert not any(RENDER.search(n) for n in names), [n for n in names if RENDER.search(n)]
+    assert all(RENDER.search(n) for n in names) and sorted(names) == sorted(ACCUMULATE_FORMS)
     for n in names:
         r = report[n]
         assert int(r["ScratchSize [bytes/lane]"]) == 0 and int(r["VGPRs Spill"]) == 0 and r.get("Dynamic Stack") == "False", (n, r)

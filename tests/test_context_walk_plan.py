@@ -2,8 +2,12 @@
 least twice, at least three tile-table evictions, and at least one return to a geometry the walk has evicted; no
 geometry, adaptive or animated launch while supersampling is on (the API refuses them); an adaptive call and an animated
 launch on a caller's stream; and a batch beyond 64 views and an animated launch beyond 64 views exactly four view-ring
-users apart, so that a slot of the four-deep view-table ring passes from one entry point to the other.  A seed that falls
-short is replaced in context_walk.SEEDS; the condition stays."""
+users apart, so that a slot of the four-deep view-table ring passes from one entry point to the other.  Since the
+accumulated launches joined: none of them while supersampling is on either; a blur or pairs launch and a jittered launch
+on a caller's stream; a slot of the scene-table ring passing between an animated and an accumulated launch; and a
+view-table slot passing between "accumulate66" and one of the two older users, besides the passage between batch and
+animation.  A seed that falls short is replaced in context_walk.SEEDS; the condition stays."""
+import numpy as np
 import pytest
 
 import context_walk as W
@@ -18,10 +22,32 @@ def test_walk_covers_the_context_state(seed):
     assert cov["evictions"] >= 3 and cov["returns"] >= 1, cov
     assert not any(kind == "geometry" and ss > 1 for kind, ss in _supersampling_at(ops))
     assert not any(kind in ("adaptive", "animation3", "animation66") and ss > 1 for kind, ss in _supersampling_at(ops))
+    assert not any(kind in W.ACCUMULATED and ss > 1 for kind, ss in _supersampling_at(ops))
     caller = cov["on_caller_stream"]
     assert caller["adaptive"] >= 1, caller
     assert caller["animation3"] + caller["animation66"] >= 1, caller
-    assert cov["view_ring_shared"], [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.VIEW_RING_USERS]
+    assert caller["accumulate"] + caller["accumulate66"] >= 1 and caller["jitter"] >= 1, caller
+    view_users = [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.VIEW_RING_USERS]
+    assert cov["view_ring_shared"], view_users
+    assert cov["view_ring_passages"] & {frozenset(("accumulate66", "batch66")), frozenset(("accumulate66", "animation66"))}, view_users
+    assert cov["scene_ring_shared"], [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.ANIMATED or kind in W.ACCUMULATED]
+
+
+LINEAR_VIEWS = {882: 0, 2444: 0, 3958: 16}  # per seed: what the blur and jitter models of its walk cost, in per-pixel linear views
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_linear_views_of_a_walk(seed):
+    """The distinct linear views a walk's blur and jitter launches are modelled from, counted from the plan: at most four
+    per context state for blur and eight for jitter, none beyond MODEL_UP_TO, and the recorded count per seed -- the CPU
+    cost of the new references is visible before a GPU run (0.01 s to 0.19 s per view at these sizes)."""
+    keys = W.linear_view_keys(W.plan(seed))
+    assert len(keys) == LINEAR_VIEWS[seed], len(keys)
+    assert all(W.modelled(k[0]) for k in keys)
+    states = {}
+    for k in keys:
+        states.setdefault(k[:1] + k[2:5], set()).add(k)
+    assert all(sum(1 for k in v if k[6] is None) <= 4 and sum(1 for k in v if k[6] is not None) <= 8 for v in states.values())
 
 
 def _supersampling_at(ops):
@@ -44,6 +70,12 @@ def test_model_of_the_table_cache():
     # an animated band lands in the slot of the plain band of its rows; whole frames share the full frame's
     events = [e for _, _, e in W.replay([("band", 7), ("animation3", 7), ("animation3", -1), ("adaptive", 2), ("animation66", 0)])]
     assert events == ["fill", "hit", "fill", "hit", "hit"]
+    # and so do the accumulated launches: a banded one the plain band's key, a whole-frame one the full frame's
+    ops = [("band", 7), ("accumulate", 7), ("band", 5), ("jitter", 5), ("accumulate", 2), ("band", 2), ("accumulate", -1), ("jitter", -1),
+           ("accumulate66", 0), ("animation3", -1)]
+    assert [e for _, _, e in W.replay(ops)] == ["fill", "hit", "fill", "hit", "fill", "hit", "fill", "hit", "hit", "hit"]
+    assert [k for _, k, _ in W.replay([("screen", 2), ("jitter", 5), ("accumulate66", 0)])] == \
+        [(64, 40) + W.band_rows(40, 5) + (None,), (64, 40, 0, 40, None)]
 
 
 def test_coverage_counts_caller_streams_and_the_shared_view_ring():
@@ -51,7 +83,9 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
     ops = [("adaptive", 2), ("stream", 1), ("adaptive", 3), ("animation3", -1), ("stream", 0), ("animation66", 0), ("stream", 2),
            ("animation66", 0)]
     cov = W.coverage(ops)
-    assert cov["on_caller_stream"] == {"adaptive": 1, "animation3": 1, "animation66": 1}
+    assert cov["on_caller_stream"] == {"adaptive": 1, "animation3": 1, "animation66": 1, "accumulate": 0, "jitter": 0, "accumulate66": 0}
+    cov = W.coverage([("jitter", 5), ("stream", 2), ("jitter", -1), ("accumulate66", 0), ("stream", 0), ("accumulate", 2)])
+    assert cov["on_caller_stream"] == {"adaptive": 0, "animation3": 0, "animation66": 0, "accumulate": 0, "jitter": 1, "accumulate66": 1}
     assert not cov["view_ring_shared"]
     A, B = ("animation66", 0), ("batch66", 0)
     assert W.coverage([A, B, B, B, B])["view_ring_shared"]          # the fifth user takes the first one's slot
@@ -61,3 +95,42 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
     assert not W.coverage([A, B, B, A])["view_ring_shared"]
     assert not W.coverage([A, A, B, B, A, A, B, B, A])["view_ring_shared"]  # both in every window, every slot stays with its kind
     assert not W.coverage([A, B, A, B, A, B, A, B])["view_ring_shared"]
+    # the view ring by pair of kinds: "accumulate66" (P) is a third user
+    P = ("accumulate66", 0)
+    pair = lambda a, b: frozenset((a[0], b[0]))
+    cov = W.coverage([P, B, B, B, B])
+    assert cov["view_ring_passages"] == {pair(P, B)} and not cov["view_ring_shared"]  # (shared: batch against animation alone)
+    assert W.coverage([B, B, B, B, P])["view_ring_passages"] == {pair(P, B)}
+    assert W.coverage([A, P, B, B, P, A, A, B])["view_ring_passages"] == {pair(A, P), pair(A, B)}
+    assert W.coverage([A, P, B, B, B, A, P])["view_ring_passages"] == {pair(A, B), pair(A, P), pair(B, P)}
+    assert W.coverage([A, P, B, B, B, A, P])["view_ring_shared"]
+    assert W.coverage([P] * 6)["view_ring_passages"] == set() and W.coverage([P, A, B, P])["view_ring_passages"] == set()
+    assert W.coverage([P, A, B, B, P, A, B, B, P])["view_ring_passages"] == set()  # every slot stays with its kind
+    # the scene ring: every animated and accumulated launch uses it, whatever its size; animation against accumulate
+    a3, blur, jit = ("animation3", -1), ("accumulate", 2), ("jitter", 5)
+    assert W.coverage([a3, blur, jit, P, blur])["scene_ring_shared"]            # the fifth user takes the first one's slot
+    assert W.coverage([blur, ("band", 0), a3, a3, ("batch66", 0), jit, A])["scene_ring_shared"]  # (plain launches use no scene table)
+    assert not W.coverage([a3, blur, jit, P])["scene_ring_shared"]              # the ring never comes round
+    assert not W.coverage([blur, jit, P, blur, jit, P, blur, blur])["scene_ring_shared"]  # one entry point, three kinds
+    assert not W.coverage([a3, A, a3, A, A, a3])["scene_ring_shared"]
+    assert not W.coverage([a3, blur, jit, A, a3, P, blur, A, A])["scene_ring_shared"]  # both in every window, every slot stays with its own
+
+
+@pytest.mark.parametrize("ext", [0, 1])
+@pytest.mark.parametrize("options", range(W.N_OPTIONS))
+def test_pairs_are_the_plain_frames(options, ext, kifs, oracle):
+    """What the "accumulate66" launches and Ctx.pairs of tests/test_gpu_context_lifecycle.py rest on, from the references
+    alone: a frame of two equal sub-frames is (c + c) / 2 = c in f32, so accumulate_reference's frame is the oracle's
+    plain frame byte for byte -- the three option sets, their own image and a morphed one, extensions off and on."""
+    import accumulate_reference as ACC
+    import test_gpu_context_lifecycle as L
+    from helpers import oracle_uniforms
+    K, O = kifs, oracle
+    screen, cam, iters = K.ScreenData(64, 40), L._cameras(K)[1], L.ITERS[0]
+    e = O.Ext(1, L.SHADOWS["shadow_steps"], L.SHADOWS["shadow_k"], L.SHADOWS["shadow_t0"], L.SHADOWS["shadow_max_t"]) if ext else None
+    for m in (0, 1):
+        image = L._morph(K, L._options(K)[options], m)
+        frames = ACC.accumulate_frames(O, K, screen, [cam, cam], image, iters, 2, ext=e)
+        s, c, o = oracle_uniforms(O, K, (screen, cam, L.Raw(image)))
+        plain = O.render(s, c, o, O.iters(*iters), **(dict(ext=e) if ext else {}))
+        assert frames.shape == (1, 40, 64, 4) and np.array_equal(frames[0], plain), (options, ext, m)

@@ -39,14 +39,37 @@ are 88 (20.9 Mpixel) with them; the 57 of them that the older tests did not need
 14 adaptive-model frames (0.32 Mpixel; the three of 330 x 149 about 0.4 s each) 2.0 to 6.3 s, nearly all of it the
 per-sample calls into the oracle.  That is 3 to 10 s of new references for the module, of which the 330 x 149 models are
 1.2 s: they do not dominate, and the model's ceiling stays at 330 x 149.
+
+The accumulated launches (kifs_render_accumulate_async, kifs_render_accumulate_jittered_async) share the scene-table ring
+with the animated ones and the view-table ring with them and the batches, write last_stream as they do, and replace the
+context's options by view 0's for a call.  Three kinds of launch hold them to the oracle here (Ctx.pairs, blur, jitter).
+Pairs: n frames of two equal sub-frames, and (c + c) / 2 = c in f32, so every frame is the oracle's plain frame of its
+camera and option image at any size (tests/test_context_walk_plan.py::test_pairs_are_the_plain_frames, from the
+references alone) -- a stale or foreign record in either table changes a frame.  Blur: 2 frames x 3 sub-frames whose
+cameras and option images all differ, against accumulate_reference.  Jitter: 2 x 2 through cells (1, 0) and (0, 1) of a
+grid of 2, against jitter_reference.  The models are per-pixel Python loops, so blur and jitter are held to them up to
+MODEL_UP_TO (soft shadows included: the references take the extension) and to the same call on a fresh context beyond;
+each model frame differs from the plain frame of its first sub-frame in at least 1 % of its pixels (asserted where it is
+built).  Where they are covered: the seeded walks ("accumulate", "jitter", "accumulate66"); every phase of the lone
+period, a caller's stream included (test_transition_at_every_phase); the view-table ring among three kinds of user
+(test_view_ring_shared_between_entry_points); the scene-table ring among animated, blur and jittered launches
+(test_scene_ring_shared_with_blur_and_jitter); resizes (test_resize_sequence); the diagnostics buffer and the profiling
+ring (test_diagnostics_buffer).  Cost: the module's blur and jitter models are built from 56 distinct linear views (32 of
+64 x 40, 16 of 200 x 135, 8 of 330 x 149; the walks' share is 0, 0 and 16 of 64 x 40, counted from the plans in
+tests/test_context_walk_plan.py), 3.7 s of wall time on an 8-CPU host, 2.3 s of it the 200 x 135 views of the scene-ring
+test; the pairs need no reference the animated launches did not.  That is below the 3.9 to 11.8 s of the oracle and
+adaptive-model frames above.  On one MI355X machine the whole module, references included, ran 60 tests in 5.4 s of wall
+time before the accumulated launches joined and runs 78 tests in 10.1 s with them; no new case takes more than 2.2 s.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import accumulate_reference as ACC
 import adaptive_reference as AR
 import context_walk as W
+import jitter_reference as JR
 from geometry_cases import Raw
 from helpers import oracle_uniforms
 
@@ -55,7 +78,8 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 0xEE
 FULL = (1024, 512)   # 32 x 64 = 2048 tiles: the >= edge of FEEDBACK_MIN_TILES
 ITERS = ((12, 10, 10), (10, 6, 8))
-MODEL_UP_TO = (330, 149)  # the largest screen an adaptive call is also held to adaptive_reference.expected_frame on
+MODEL_UP_TO = W.MODEL_UP_TO  # (330, 149): the largest screen an adaptive call is also held to adaptive_reference.expected_frame
+                             # on, and a blur or jitter launch to accumulate_reference / jitter_reference
 EDGE_SENTINEL = 0x5A5A5A5A
 HOLD_PASSES = 384  # _hold_back: 9.4 ms of GPU time per 128 passes as measured on the MI355X, 0.7 ms of host time to enqueue them
 SHADOWS = dict(soft_shadow=True, shadow_steps=16, shadow_k=8.0, shadow_t0=0.02, shadow_max_t=10.0)
@@ -100,6 +124,7 @@ class Refs:
         self.K, self.O, self.cams, self.opts, self.frames = K, O, _cameras(K), _options(K), {}
         self.morphs = [[_morph(K, g, m) for m in range(W.N_MORPHS)] for g in self.opts]
         self.geoms, self.means, self.models = {}, {}, {}
+        self.linears, self.accums = {}, {}
 
     def frame(self, size, cam, options=0, iters=0, ext=0, morph=0):
         import torch
@@ -126,6 +151,53 @@ class Refs:
                                             means=self.means.setdefault(key[:4], {}))
             self.models[key] = (torch.from_numpy(frame).to("cuda:0"), int(mask.sum()))
         return self.models[key]
+
+
+    def linear(self, size, cam, options=0, iters=0, ext=0, morph=0, cell=None):
+        """(H, W, 3) float32 on the host: the linear view of accumulate_reference.linear_views (cell None) or of
+        jitter_reference.linear_views through `cell` of the grid of W.JITTER_GRID."""
+        key = (size, cam, options, iters, ext, morph, cell)
+        if key not in self.linears:
+            K, O = self.K, self.O
+            scene = (K.ScreenData(*size), [self.cams[cam]], self.morphs[options][morph], ITERS[iters])
+            e = O.Ext(1, SHADOWS["shadow_steps"], SHADOWS["shadow_k"], SHADOWS["shadow_t0"], SHADOWS["shadow_max_t"]) if ext else None
+            if cell is None:
+                self.linears[key] = ACC.linear_views(O, K, *scene, e)[0]
+            else:
+                self.linears[key] = JR.linear_views(O, K, *scene, W.JITTER_GRID, [cell], 1, e)[0]
+        return self.linears[key]
+
+    def accumulated(self, size, views, samples, options=0, iters=0, ext=0):
+        """(frames, H, W, 4) on the device: accumulate_reference.accumulate_frames, or jitter_reference.jittered_frames
+        when the views carry cells, of the sub-frames `views` = ((camera, option image, cell or None), ..), `samples` per
+        frame.  Not vacuous, from the references alone: every frame differs from the oracle's plain frame of its first
+        sub-frame in at least 1 % of its pixels."""
+        import torch
+        views = tuple(views)
+        key = (size, views, samples, options, iters, ext)
+        if key not in self.accums:
+            lin = np.stack([self.linear(size, cam, options, iters, ext, m, cell) for cam, m, cell in views])
+            if views[0][2] is None:
+                frames = ACC.accumulate_frames(self.O, self.K, None, None, None, None, samples, lin=lin)
+            else:
+                frames = JR.jittered_frames(self.O, self.K, None, None, None, None, samples, W.JITTER_GRID, lin=lin)
+            for f, frame in enumerate(frames):
+                cam, m, _ = views[f * samples]
+                differ = int((frame != self.frame(size, cam, options, iters, ext, m).cpu().numpy()).any(-1).sum())
+                assert 100 * differ >= size[0] * size[1], (differ, key, f)
+            self.accums[key] = torch.from_numpy(frames).to("cuda:0")
+        return self.accums[key]
+
+    def blur(self, size, cam0, options=0, iters=0, ext=0, own_options=True):
+        return self.accumulated(size, _blur_views(cam0, own_options), 3, options, iters, ext)
+
+    def jitter(self, size, cam0, options=0, iters=0, ext=0):
+        return self.accumulated(size, W.jitter_views(cam0), 2, options, iters, ext)
+
+
+def _blur_views(cam0, own_options=True):
+    """The sub-frames of a blur launch; without options of their own every one has the context's image (0)."""
+    return [(cam, m if own_options else 0, None) for cam, m in W.blur_views(cam0)]
 
 
 @pytest.fixture(scope="module")
@@ -209,6 +281,56 @@ class Ctx:
         self.log.append(what or ("animation", n, y0, y1, shift, "caller stream" if stream is not None else "context stream"))
         for j, (cam, m) in enumerate(zip(cams, morphs)):
             self.pending.append((outs[j], self.want(cam, y0, y1, m), len(self.log)))
+        return outs
+
+    def pairs(self, n, y0=0, y1=None, stream=None, shift=0, what=None):
+        """An accumulated launch of n frames of two equal sub-frames each: frame f has camera batch_cameras(camera, n)[f]
+        and the option image (morph_of(that camera) + shift) % N_MORPHS in both.  (c + c) / 2 is c in f32
+        (test_pairs_are_the_plain_frames), so every frame against the oracle's plain frame, as an animated launch's."""
+        y1 = self.state["size"][1] if y1 is None else y1
+        cams = W.batch_cameras(self.state["camera"], n)
+        morphs = [(W.morph_of(cam) + shift) % W.N_MORPHS for cam in cams]
+        images = self.refs.morphs[self.state["options"]]
+        outs = self.dest(y1 - y0, n)
+        self.gs.render_accumulate([self.refs.cams[cam] for cam in cams for _ in range(2)], 2,
+                                  options=[images[m] for m in morphs for _ in range(2)], outs=outs, y0=y0, y1=y1, stream=stream)
+        self.log.append(what or ("pairs", n, y0, y1, shift, "caller stream" if stream is not None else "context stream"))
+        for f, (cam, m) in enumerate(zip(cams, morphs)):
+            self.pending.append((outs[f], self.want(cam, y0, y1, m), len(self.log)))
+        return outs
+
+    def blur(self, y0=0, y1=None, stream=None, fresh=None, own_options=True, what=None):
+        """An accumulated launch of 2 frames x 3 sub-frames: the cameras batch_cameras(camera, 6), each sub-frame with the
+        option image of its camera (own_options False: options NULL, the context's for all).  Against
+        accumulate_reference up to MODEL_UP_TO, and against the same call on `fresh` when there is one."""
+        return self._accumulated(_blur_views(self.state["camera"], own_options), 3, y0, y1, stream, fresh, own_options, what or "blur")
+
+    def jitter(self, y0=0, y1=None, stream=None, fresh=None, what=None):
+        """A jittered accumulated launch of 2 frames x 2 sub-frames on a grid of 2, through cells (1, 0) and (0, 1): the
+        cameras batch_cameras(camera, 4), option images as for blur.  Against jitter_reference up to MODEL_UP_TO, and
+        against the same call on `fresh` when there is one."""
+        return self._accumulated(W.jitter_views(self.state["camera"]), 2, y0, y1, stream, fresh, True, what or "jitter")
+
+    def _accumulated(self, views, samples, y0, y1, stream, fresh, own_options, what):
+        st = self.state
+        y1 = st["size"][1] if y1 is None else y1
+        args = dict(options=[self.refs.morphs[st["options"]][m] for _, m, _ in views] if own_options else None, y0=y0, y1=y1,
+                    jitter=None if views[0][2] is None else (W.JITTER_GRID, [cell for _, _, cell in views]))
+        cams = [self.refs.cams[cam] for cam, _, _ in views]
+        outs = self.dest(y1 - y0, len(views) // samples)
+        self.gs.render_accumulate(cams, samples, outs=outs, stream=stream, **args)
+        if isinstance(what, str):
+            what = (what, st["camera"], y0, y1, "own options" if own_options else "the context's options",
+                    "caller stream" if stream is not None else "context stream")
+        self.log.append(what)
+        assert W.modelled(st["size"]) or fresh is not None
+        if W.modelled(st["size"]):
+            model = self.refs.accumulated(st["size"], views, samples, st["options"], st["iters"], st["ext"])
+            self.pending.append((outs, model[:, y0:y1], len(self.log)))
+        if fresh is not None:
+            want = self.dest(y1 - y0, len(views) // samples)
+            fresh.render_accumulate(cams, samples, outs=want, **args)
+            self.pending.append((outs, want, len(self.log)))
         return outs
 
     def adaptive(self, k, count=None, stream=None, fresh=None, what=None):
@@ -307,6 +429,17 @@ def _hold_back(torch, passes=HOLD_PASSES):
     return x
 
 
+def _warm_up(c, views):
+    """What would make the host wait on the first launches behind _hold_back, done before it: a tile table's first use
+    copies its order with a blocking hipMemcpy, which waits for torch's stream, and a ring's slots are allocated on first
+    use.  One lone launch, then four users of the scene ring (and with `views` of the view ring): the rings come round to
+    slot 0 again, every slot allocated and its last reader over."""
+    c.lone()
+    for _ in range(4):
+        c.animation(views)
+    c.verify()
+
+
 def _fresh_order(K, size):
     with K.GraphicState(0, screen_data=K.ScreenData(*size)) as g:
         return g.debug_get_tile_order()
@@ -345,22 +478,23 @@ def test_eviction_round_trip(k, ctx, kifs):
 
 
 TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504",
-               "adaptive", "animation3", "animation70", "animation_caller_stream")
+               "adaptive", "animation3", "animation70", "animation_caller_stream", "pairs3", "pairs70", "pairs_caller_stream", "jitter")
 
 
 @pytest.mark.parametrize("k", range(4))
 @pytest.mark.parametrize("transition", TRANSITIONS)
 def test_transition_at_every_phase(transition, k, ctx, kifs):
     """k lone launches bring the full-frame table to phase k of its period; then one transition the comments of
-    enqueue_batch call out -- or an adaptive call or animated launches, which keep state of their own and pass through the
-    full frame's tile table --, then six more lone launches.  Everything equals the oracle, the order table stays a
+    enqueue_batch call out -- or an adaptive call, animated or accumulated launches, which keep state of their own and pass
+    through the full frame's tile table --, then six more lone launches.  The accumulated pairs are held to the oracle's plain
+    frames, the jittered launch to a fresh context.  Everything equals the oracle, the order table stays a
     permutation, and the lone launches before and after run the same kernel."""
     import torch
     c = ctx()
     for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch: the lone launches', then the animated ones'
         c.refs.frame(FULL, cam)
-        if transition.startswith("animation"):
-            for shift in range(W.N_MORPHS if transition == "animation_caller_stream" else 1):
+        if transition.startswith(("animation", "pairs")):
+            for shift in range(W.N_MORPHS if transition.endswith("_caller_stream") else 1):
                 c.refs.frame(FULL, cam, morph=(W.morph_of(cam) + shift) % W.N_MORPHS)
     if transition == "sphere":
         c.refs.frame(FULL, 1, options=2)
@@ -428,6 +562,26 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
         assert np.array_equal(c.gs.debug_get_tile_order(), before)  # neither the sort nor the order has moved
         if transition == "animation_caller_stream":
             c.animation(3, stream=s, shift=2)  # and one that the lone launches below follow without a wait in between
+    elif transition in ("pairs3", "pairs70", "pairs_caller_stream"):
+        before = c.gs.debug_get_tile_order()
+        c.camera(1)
+        if transition == "pairs_caller_stream":
+            s = torch.cuda.Stream()
+            c.pairs(3, stream=s)
+            c.pairs(3, stream=s, shift=1)
+        else:
+            c.pairs(int(transition[5:]) // (2 if transition == "pairs70" else 1))  # 35 frames are 70 views
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)  # neither the sort nor the order has moved
+        if transition == "pairs_caller_stream":
+            c.pairs(3, stream=s, shift=2)  # and one that the lone launches below follow without a wait in between
+    elif transition == "jitter":
+        before = c.gs.debug_get_tile_order()
+        with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[1], gui_data=c.refs.opts[0]) as fresh:
+            fresh.set_iters(*ITERS[0])
+            c.camera(1)
+            c.jitter(fresh=fresh)
+            fresh.synchronize()
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)
     for i in range(6):
         c.lone(cam=(i + 1) % 4, record_kernel=True)
     c.verify()
@@ -438,22 +592,29 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
 def test_resize_sequence(ctx, kifs):
     """1024x512 -> 330x149 -> 64x40 -> 1056x516 -> 1024x512 on one context: every set_screen is issued while the previous
     size's launch is still enqueued, host and device destinations alternate, and one stripe list is rendered in place and
-    packed at two sizes."""
+    packed at two sizes.  The first launch after every set_screen is an accumulated one of three pairs, held to the oracle's
+    plain frames, and at the two sizes with a model a blur launch renders the band rows h // 3 .. h - 3."""
     import torch
     sizes = [(1024, 512), (330, 149), (64, 40), (1056, 516), (1024, 512)]
     stripes = [0, 2, 4]  # rows 0..7, 16..23, 32..39: inside every size
     c = ctx()
-    for size in sizes:  # every reference before the first launch: nothing but launches between two set_screen calls
+    for n, size in enumerate(sizes):  # every reference before the first launch: nothing but launches between two set_screen calls
         for cam in range(W.N_CAMERAS):
             c.refs.frame(size, cam)
+            c.refs.frame(size, cam, morph=W.morph_of(cam))
+        if W.modelled(size):
+            c.refs.blur(size, (n + 2) % 4)
     host = []
     for n, (w, h) in enumerate(sizes):
         c.screen((w, h))            # (the previous size's launches are still in flight)
+        c.pairs(3)                  # (the first launch at the new size: the scene ring's records, the new frame's table)
         c.lone(cam=n % 4)
         if n % 2:
             c.camera((n + 1) % 4)
             host.append((c.gs.render(), c.want((n + 1) % 4, 0, h).cpu().numpy(), (w, h)))   # synchronous, host destination
         c.lone((n + 2) % 4, h // 3, h - 3)
+        if W.modelled((w, h)):
+            c.blur(h // 3, h - 3)   # the band's table, just taken by the lone launch; camera (n + 2) % 4
         if (w, h) in ((330, 149), (1056, 516)):
             cams = [c.refs.cams[1], c.refs.cams[2]]
             packed = c.dest(24, 2)
@@ -489,8 +650,10 @@ def test_resize_sequence(ctx, kifs):
 @pytest.mark.parametrize("seed", W.SEEDS)
 def test_seeded_walk(seed, ctx, kifs):
     """72 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
-    checked, and a failure prints the plan up to it.  Adaptive calls and animated launches run on the walk's current
-    stream like every other render: every animated frame against the oracle, an adaptive call as Ctx.adaptive says."""
+    checked, and a failure prints the plan up to it.  Adaptive calls, animated and accumulated launches run on the walk's
+    current stream like every other render: every animated frame and every frame of an "accumulate66" against the oracle,
+    an adaptive call as Ctx.adaptive says, a blur or jitter launch against its model up to MODEL_UP_TO and against the same
+    call on the fresh context beyond."""
     import torch
     ops = W.plan(seed)
     c = ctx()
@@ -499,10 +662,15 @@ def test_seeded_walk(seed, ctx, kifs):
     try:
         for _, kind, arg, st in W.trace(ops):  # every oracle and model frame before the first launch
             if st["supersampling"] == 1:
-                n = {"batch3": 3, "batch66": 66, **W.ANIMATED}.get(kind, 1)
+                n = {"batch3": 3, "batch66": 66, **W.ANIMATED, "accumulate66": 33}.get(kind, 1)
                 scene = (W.SIZES[st["size"]], st["options"], st["iters"])
+                if kind in ("accumulate", "jitter"):
+                    if W.modelled(scene[0]):
+                        (c.refs.blur if kind == "accumulate" else c.refs.jitter)(scene[0], st["camera"], *scene[1:], st["extensions"])
+                    continue
+                morphed = kind in W.ANIMATED or kind == "accumulate66"
                 for cam in set(W.batch_cameras(st["camera"], n)):
-                    c.refs.frame(scene[0], cam, *scene[1:], st["extensions"], W.morph_of(cam) if kind in W.ANIMATED else 0)
+                    c.refs.frame(scene[0], cam, *scene[1:], st["extensions"], W.morph_of(cam) if morphed else 0)
                 if kind == "adaptive" and _modelled(scene[0], st["extensions"]):
                     c.refs.adaptive(scene[0], st["camera"], *scene[1:], arg)
         state = dict(size=0, camera=0, options=0, iters=0, extensions=0, supersampling=1, frames_in_flight=1, stream=0)
@@ -539,7 +707,8 @@ def test_seeded_walk(seed, ctx, kifs):
             cam0 = state["camera"]
             what = (i, kind, arg, dict(state))
             exact = state["supersampling"] == 1  # else: against the same call on the fresh context
-            if not exact or kind in ("geometry", "adaptive"):
+            beyond_the_model = kind in ("accumulate", "jitter") and not W.modelled((w, h))
+            if not exact or kind in ("geometry", "adaptive") or beyond_the_model:
                 mirror(fresh)
             if kind == "band" or kind in ("batch3", "batch66"):
                 n = {"band": 1, "batch3": 3, "batch66": 66}[kind]
@@ -573,6 +742,11 @@ def test_seeded_walk(seed, ctx, kifs):
                 c.expect(out[0], want, what)
             elif kind in W.ANIMATED:
                 c.animation(W.ANIMATED[kind], *W.animation_rows(h, arg if kind == "animation3" else -1), stream=stream, what=what)
+            elif kind == "accumulate66":
+                c.pairs(33, stream=stream, what=what)
+            elif kind in ("accumulate", "jitter"):
+                launch = c.blur if kind == "accumulate" else c.jitter
+                launch(*W.animation_rows(h, arg), stream=stream, fresh=fresh if beyond_the_model else None, what=what)
             elif kind == "adaptive":
                 fresh.set_camera(c.refs.cams[cam0])
                 c.adaptive(arg, stream=stream, fresh=fresh, what=what)
@@ -589,30 +763,105 @@ def test_seeded_walk(seed, ctx, kifs):
         fresh.close()
 
 
+# test_view_ring_shared_between_entry_points: per round a batch of 70 (B), pairs(35) (P: 70 views) and an animated launch
+# of 70 (A); rounds 1 and 4 hold a second animated launch
+VIEW_ROUNDS = ("BPA", "BPAA", "BPA", "BPA", "BPAA", "BPA", "BPA")
+
+
+def _takes_over(users, ring=4):
+    """(previous user, next user) of every hand-over of a slot of a ring of four: user n + 4 takes user n's."""
+    return {(users[i], users[i + ring]) for i in range(len(users) - ring)}
+
+
 @pytest.mark.parametrize("size", [(64, 40), (330, 149)])
 def test_view_ring_shared_between_entry_points(size, ctx):
-    """Batches of 70 views and animated launches of 70 frames in turn, six rounds without a wait; rounds 1 and 4 hold two
-    batches, so that the users of the four view tables (host::take_view_slot) run B A B B A B A B A B B A B A and a slot
-    passes from a batch to an animated launch and back (user n and user n + 4 share one): fourteen users of the view
-    tables, six of the four scene tables.  The context's camera moves between the launches, so that no two tables of one
-    kind in flight hold the same views or scenes, two of the animated launches run on a caller's stream, and the first four
-    users of each ring queue up behind work that holds the streams back (_hold_back).  Every frame of every launch against
-    the oracle: 4 cameras x 3 option images.  64 x 40 is the size this needs; at 330 x 149, added because it costs a tenth
-    of a second, a launch is long enough to be still reading its tables when a launch on the other stream is let go."""
+    """Batches of 70 views (B), accumulated launches of 35 pairs (P) and animated launches of 70 frames (A) in turn, seven
+    rounds without a wait; rounds 1 and 4 hold two animated launches, so that the users of the four view tables
+    (host::take_view_slot) run B P A  B P A A  B P A  B P A  B P A A  B P A  B P A and slot 0 passes B -> P -> P -> A -> A -> B
+    (user n and user n + 4 share one): from a batch to an accumulated launch, on to an animated one and back to a batch;
+    slots 1 and 2 make the same round trip from another start.  The users of the four scene tables
+    (anim::take_scene_slot) run P A  P A A  P A  P A  P A A  P A  P A: slot 0 passes P -> A -> A -> P, slot 1 A -> P -> P -> A.
+    Twenty-three users of the view tables, sixteen of the scene tables.  The context's camera moves between the launches,
+    so that no two tables of one kind in flight hold the same views or scenes; two of the animated launches (rounds 1 and
+    4) and two of the accumulated ones (rounds 2 and 5) run on a caller's stream, and the first four users of each ring
+    queue up behind work that holds the streams back (_hold_back; the tile table and the rings' slots exist by then:
+    _warm_up).  Every frame of every launch against the oracle: 4 cameras x 3 option images.  64 x 40 is the size this needs; at 330 x 149, added because it costs a tenth of a second,
+    a launch is long enough to be still reading its tables when a launch on the other stream is let go."""
     import torch
+    users = "".join(VIEW_ROUNDS)
+    assert {("B", "P"), ("P", "A"), ("A", "B")} <= _takes_over(users) and users[0::4] == "BPPAAB"
+    assert {("A", "P"), ("P", "A")} <= _takes_over(users.replace("B", ""))  # the scene ring: animation -> accumulate and back
     c = ctx(size=size)
     for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch
         for m in range(W.N_MORPHS):
             c.refs.frame(size, cam, morph=m)
     s = torch.cuda.Stream()
+    _warm_up(c, 70)
     held = _hold_back(torch)
-    for i in range(6):
-        c.camera((3 * i) % W.N_CAMERAS)
-        c.batch(70)
-        if i in (1, 4):
-            c.camera((3 * i + 1) % W.N_CAMERAS)
-            c.batch(70)
-        c.animation(70, stream=s if i in (1, 4) else None, shift=i)
+    for i, round_ in enumerate(VIEW_ROUNDS):
+        for j, user in enumerate(round_):
+            c.camera((3 * i + j) % W.N_CAMERAS)
+            if user == "B":
+                c.batch(70)
+            elif user == "P":
+                c.pairs(35, stream=s if i in (2, 5) else None, shift=i + 1)
+            else:
+                c.animation(70, stream=s if i in (1, 4) else None, shift=i + j)
+    c.verify()
+    del held
+
+
+SCENE_USERS = (("blur", 0, 1), ("jitter", 1, 0), ("animation", 2, 0), ("blur", 3, 1),      # kind, camera, on the caller's stream
+               ("animation", 1, 0), ("blur", 2, 1), ("jitter", 2, 0), ("animation", 3, 1),  # (options(1) before the seventh)
+               ("jitter", 0, 0), ("animation", 1, 1), ("blur", 3, 0), ("jitter", 2, 1))
+
+
+@pytest.mark.parametrize("size", [(64, 40), (200, 135)])
+def test_scene_ring_shared_with_blur_and_jitter(size, ctx):
+    """Twelve users of the four scene tables (anim::take_scene_slot) without a wait, behind _hold_back and after _warm_up,
+    which brings the ring round to slot 0 with every slot allocated: blur launches (U),
+    jittered launches (J) and animated launches of 3 (A) in turn, U J A U  A U J A  J A U J, so that slot 0 passes
+    U -> A -> J, slot 1 J -> U -> A, slot 2 A -> J -> U and slot 3 U -> A -> J: every slot changes entry point, and in slots 1
+    and 2 a jittered launch is followed directly by an unjittered one, which must find the pad word of its records zero
+    again (the cell travels there).  None of these launches goes through the view tables, so nothing but the scene
+    table's own event keeps a launch from rewriting records that a launch held back is still to read.  Two streams in
+    turn, the camera moves between the launches, and before the seventh the context's option set changes; the last blur
+    launch passes options NULL, so that its records are filled from the context's own options, and is held to the model
+    with those.  Every frame against accumulate_reference, jitter_reference or the oracle."""
+    import torch
+    kinds = [kind for kind, _, _ in SCENE_USERS]
+    assert len(kinds) >= 10 and all(a != b for a, b in zip(kinds, kinds[1:]))
+    entry = ["anim" if kind == "animation" else "accum" for kind in kinds]
+    assert all(len({entry[n] for n in range(slot, len(kinds), 4)}) == 2 for slot in range(4))
+    assert sum(kinds[n] == "jitter" and kinds[n + 4] == "blur" for n in range(len(kinds) - 4)) == 2
+    c = ctx(size=size)
+    last_blur = max(n for n, kind in enumerate(kinds) if kind == "blur")
+    for n, (kind, cam, _) in enumerate(SCENE_USERS):  # every reference before the first launch
+        options = int(n >= 6)
+        if kind == "blur":
+            c.refs.blur(size, cam, options, own_options=n != last_blur)
+        elif kind == "jitter":
+            c.refs.jitter(size, cam, options)
+        else:
+            for j in W.batch_cameras(cam, 3):
+                c.refs.frame(size, j, options, morph=W.morph_of(j))
+    for cam in range(W.N_CAMERAS):  # (the warm-up's)
+        c.refs.frame(size, cam)
+        c.refs.frame(size, cam, morph=W.morph_of(cam))
+    s = torch.cuda.Stream()
+    _warm_up(c, 3)
+    held = _hold_back(torch)
+    for n, (kind, cam, caller) in enumerate(SCENE_USERS):
+        if n == 6:
+            c.options(1)
+        c.camera(cam)
+        stream = s if caller else None
+        if kind == "blur":
+            c.blur(stream=stream, own_options=n != last_blur)
+        elif kind == "jitter":
+            c.jitter(stream=stream)
+        else:
+            c.animation(3, stream=stream)
     c.verify()
     del held
 
@@ -649,17 +898,20 @@ def test_adaptive_scratch_across_sizes_and_counts(ctx):
 
 def test_diagnostics_buffer(ctx, kifs):
     """kifs_debug_counters sizes the per-wave record buffer for the screen of the call; a launch with more waves than it
-    holds (a batch, a larger screen set since) runs as a normal launch without diagnostics, and so do an animated launch
-    and an adaptive call (what they leave in the records is not defined).  Then the profiling ring, which those two leave
-    consistent."""
+    holds (a batch, a larger screen set since) runs as a normal launch without diagnostics, and so do an animated launch,
+    an adaptive call and the accumulated launches, blur and jitter (what they leave in the records is not defined).  Then
+    the profiling ring, which the first two leave consistent and an accumulated launch does not enter."""
     from kifs_raymarching_amd._lib import lib
     small, tiles = (330, 149), 11 * 19
     c = ctx(size=small)
     gs = c.gs
     c.refs.adaptive(small, 1, 0, 0, 2)  # (the references of the first calls before the first launch)
+    c.refs.blur(small, 1)
+    c.refs.jitter(small, 1)
     plain = c.lone(cam=1)
     animated = c.animation(3)
     resolved, edges = c.adaptive(2)
+    blurred, jittered = c.blur(), c.jitter()
     c.verify()
     out8 = (C.c_uint64 * 8)()
     zero = lambda: lib.kifs_debug_counters(gs._ctx, 1, out8)
@@ -676,6 +928,11 @@ def test_diagnostics_buffer(ctx, kifs):
     resolved_on, edges_on = c.adaptive(2)
     c.verify()
     assert c.torch.equal(animated_on, animated) and c.torch.equal(resolved_on, resolved) and c.torch.equal(edges_on, edges)
+    assert gs.debug_wave_records().shape == (4 * tiles, 4)
+    assert zero() == 0
+    blurred_on, jittered_on = c.blur(), c.jitter()  # and the accumulated launches, each against its model both times
+    c.verify()
+    assert c.torch.equal(blurred_on, blurred) and c.torch.equal(jittered_on, jittered)
     assert gs.debug_wave_records().shape == (4 * tiles, 4)
     assert zero() == 0
     c.lone(2, 16, 56)                      # a band of five tile rows: 55 workgroups
@@ -719,5 +976,19 @@ def test_diagnostics_buffer(ctx, kifs):
     launches, mean, lo, hi = gs.profile_read()
     assert launches >= 0 and (launches == 0 or lo <= mean <= hi), (launches, mean, lo, hi)
     assert gs.profile_read()[0] == 0
-    gs.set_profiling(0)
+    # An accumulated launch, jittered or not, is not timed either (kifs_render_accumulate_async, "launch"): with every
+    # launch timed, the two alone leave the ring empty, and the lone launch after them is the one launch in it.
+    # (The screen is 1024 x 512 by now: both against the same call on a fresh context.)
+    with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[2], gui_data=c.refs.opts[0]) as fresh:
+        fresh.set_iters(*ITERS[0])
+        c.blur(fresh=fresh)
+        c.jitter(fresh=fresh)
+        assert gs.profile_read()[0] == 0
+        c.blur(fresh=fresh)
+        c.jitter(fresh=fresh)
+        c.lone(cam=2)
+        launches, mean, lo, hi = gs.profile_read()
+        assert launches == 1 and 0 < lo <= mean <= hi, (launches, mean, lo, hi)
+        gs.set_profiling(0)
+        fresh.synchronize()
     c.verify()

@@ -1,7 +1,7 @@
 """Jittered accumulated frames (kifs_render_accumulate_jittered_async), the parts a machine without a GPU can check: the ABI
 surface, the Python and CLI surface, and that hipcc compiled accum::jitter_render_kernel for every pipeline -- ten
-instantiations, none with scratch, spills or a dynamic stack, none matching the existing form table's pattern, their
-(GROUP, PRIM) pairs the ones geometry_cases.PIPELINES dispatch to -- beside accum::render_kernel's ten, which stay."""
+instantiations, none with scratch, spills or a dynamic stack, each with its claim in the kernel-form table
+(kernel_forms.JITTER_FORMS), their (GROUP, PRIM) pairs the ones geometry_cases.PIPELINES dispatch to -- beside accum::render_kernel's ten, which stay."""
 import ctypes as C
 import re
 import subprocess
@@ -50,13 +50,14 @@ def test_render_tool_offers_the_jitter(kifs):
     assert "--jitter" in p.stdout
 
 
-def test_every_pipeline_is_compiled_without_scratch_and_outside_the_form_table(kifs):
+def test_every_pipeline_is_compiled_without_scratch_and_claimed_by_the_form_table(kifs):
     from geometry_cases import PIPELINES, cases
-    from test_kernel_form_coverage import RENDER  # the existing form table's pattern
+    from kernel_forms import JITTER_FORMS
+    from test_kernel_form_coverage import RENDER  # the form table's own pattern
     report = kernel_report()
     names = [n for n in report if "kifs::accum::jitter_render_kernel<" in n]
     assert len(names) == len(PIPELINES) == 10, names
-    assert not any(RENDER.search(n) for n in names), [n for n in names if RENDER.search(n)]
+    assert all(RENDER.search(n) for n in names) and sorted(names) == sorted(JITTER_FORMS)
     assert len([n for n in report if "kifs::accum::render_kernel<" in n]) == 10  # the unjittered kernel keeps its ten
     for n in names:
         r = report[n]
