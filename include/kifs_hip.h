@@ -393,6 +393,48 @@ int kifs_render_accumulate_jittered_async(kifs_ctx* ctx, void* hip_stream, int c
                                           int grid, const KifsSubpixel* cells /* count * samples, or NULL */,
                                           uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, int y0, int y1, int encode);
 
+/* ---- extension: progressive accumulation -- a frame's linear sums carried across launches ----
+ * NOT part of the reference.  The two calls above average at most KIFS_MAX_ACCUMULATE sub-frames and start from nothing
+ * every time: the running f32 sum lives inside the launch, and no caller can continue it from encoded RGBA8 bytes.  This
+ * call makes the resolve's accumulator resumable: a PASS starts from a plane of f32 sums left by earlier passes, adds its
+ * own sub-frames in the contract's order, writes the sums back and, when asked, encodes sum / float(total).  A lens at
+ * hundreds of samples per pixel is a sequence of passes; so is a viewer that refines its picture while nothing moves.
+ *   base      everything kifs_render_accumulate_jittered_async says holds for the pass's own count * samples views: views
+ *             and cells (grid = 1: cells (0, 0) or NULL, the pixel centre), what may vary between option images, misses,
+ *             limits (samples <= KIFS_MAX_ACCUMULATE PER PASS), bands, the tables and the debug hooks
+ *             (KIFS_KERNEL_ACCUMULATE; not timed by kifs_set_profiling).
+ *   plane     one 16-byte texel per pixel, four f32: (sum.r, sum.g, sum.b, float(total)).  The layout is the geometry
+ *             output's: row y of frame i at (char*)dev_sums + i * sums_stride_bytes + (y - y0) * sums_pitch_bytes.  The base
+ *             is 16-byte aligned; the pitch is >= 16 W and a multiple of 16; the stride is a multiple of 16 and, with
+ *             count > 1, >= (y1 - y0) * sums_pitch_bytes.  Bytes of a row beyond 16 W are not touched.
+ *   fold      per channel in f32, without fma.  prior_samples == 0: the plane is NOT READ, whatever it holds (NaNs
+ *             included): acc = c_0(p); acc = acc + c_s(p) for s = 1 .. samples-1.  prior_samples > 0: acc = the texel's
+ *             sum; acc = acc + c_s(p) for s = 0 .. samples-1.  Either way total = prior_samples + samples and the texel
+ *             becomes (acc, float(total)).  The w word is written and never read: it makes the plane self-describing for
+ *             a caller that wants the linear HDR mean, sum / w.
+ *   picture   with dev_outs_rgba8 != NULL frame i receives encode(acc / float(total)): the divide correctly rounded, the
+ *             encoder the frame's, exactly as the resolve of the calls above.  With NULL the pass only advances the
+ *             plane, and pitch_bytes is ignored.
+ *   identities (a) prior_samples == 0 with a picture gives the bytes of kifs_render_accumulate_jittered_async for the
+ *             same arguments (at grid 1: of kifs_render_accumulate_async).  (b) Passes whose views concatenate to one
+ *             call's views give that call's bytes after the last pass, for any split: the fold is a left fold.  Beyond
+ *             KIFS_MAX_ACCUMULATE sub-frames the same formula defines the result.  (c) The library keeps NO STATE between
+ *             passes: the plane and prior_samples are the whole state.  Passes may come from different streams or from
+ *             different contexts of the device; passes on different streams must be ordered by the caller, e.g. with
+ *             kifs_order_after.
+ *   refusals  a refused call launches and writes nothing.  Everything kifs_render_accumulate_jittered_async refuses, with
+ *             its status, except that dev_outs_rgba8 itself may be NULL (a null or misaligned ENTRY of a non-NULL array
+ *             is still KIFS_ERR_BAD_ARG).  Then KIFS_ERR_BAD_ARG: a null or misaligned dev_sums; a bad plane pitch or
+ *             stride; prior_samples + samples > KIFS_MAX_PROGRESSIVE_SAMPLES.
+ *   no shards row shards, the geometry output, adaptive anti-aliasing and kifs_multi_* have no progressive form. */
+#define KIFS_MAX_PROGRESSIVE_SAMPLES 16777216u   /* 2^24: float(total) stays exact */
+int kifs_render_accumulate_resume_async(kifs_ctx* ctx, void* hip_stream, int count, int samples,
+                                        const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
+                                        int grid, const KifsSubpixel* cells,
+                                        float* dev_sums, size_t sums_pitch_bytes, size_t sums_stride_bytes, uint32_t prior_samples,
+                                        uint8_t* const* dev_outs_rgba8 /* NULL: no picture from this pass */,
+                                        size_t pitch_bytes, int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -50,6 +50,7 @@ class KifsSubpixel(C.Structure):  # a cell of the g x g grid inside a pixel (kif
 
 
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
+MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
 
 class GuiDataC(C.Structure):  # KifsGuiData
@@ -114,6 +115,9 @@ SIGNATURES = {
     "kifs_render_accumulate_jittered_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
                                                         C.c_int, _P(KifsSubpixel), _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int,
                                                         C.c_int]),
+    "kifs_render_accumulate_resume_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
+                                                      C.c_int, _P(KifsSubpixel), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                                      _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

@@ -186,6 +186,18 @@ def lens_cameras(camera_data: CameraData, aperture: float, focus_distance: float
     return out
 
 
+def pass_splits(total: int, per_pass: int = 64) -> list:
+    """The pass sizes of a progressive frame of `total` sub-frames (GraphicState.render_accumulate_resume, Accumulator):
+    total // per_pass passes of `per_pass` and, if anything is left, one of the remainder -- [64, 64, 22] for 150.  A
+    pass holds at most MAX_ACCUMULATE = 64 sub-frames.  (shutter_cameras and lens_cameras take any number of samples: the
+    cameras of a frame are made once for `total` and handed out pass by pass; jitter_cells gives at most g^2 distinct
+    cells, so the passes of a frame take jitter_cells(g, n, frame=first sub-frame of the pass), which walks on through
+    the grid and round again.)"""
+    if total < 1 or not 1 <= per_pass <= 64:
+        raise ValueError("pass_splits: at least one sub-frame, 1..64 per pass")
+    return [per_pass] * (total // per_pass) + ([total % per_pass] if total % per_pass else [])
+
+
 def grid_cells(g: int) -> list:
     """The g^2 cells (i, j) of the g x g grid inside a pixel in supersampling order, j outer and i inner: what
     GraphicState.render_accumulate(jitter=(g, None)) takes for samples = g^2."""

@@ -15,15 +15,8 @@
 namespace kifs {
 namespace accum {
 
-// The sub-pixel cells of a jittered call: sub-frame v goes through cell cells[v] of the grid x grid cells of its pixel;
-// cells == nullptr (samples == grid * grid): sub-frame s of every frame through cell (s % grid, s / grid).
-struct Jitter {
-    int grid;
-    const KifsSubpixel* cells;
-};
-
-// What the jittered call refuses beyond check(): after it, so that every refusal of the unjittered call keeps its status.
-static int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter& j) {
+// (Jitter, check, check_jitter and enqueue are declared in kifs_context.hpp: kifs_progressive.cpp shares them.)
+int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter& j) {
     if (j.grid < 1 || j.grid > KIFS_MAX_JITTER_GRID) return KIFS_ERR_BAD_ARG;
     if (!j.cells && samples != j.grid * j.grid) return KIFS_ERR_BAD_ARG;
     if (j.cells)
@@ -35,11 +28,11 @@ static int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter&
     return (int64_t(w) * j.grid > 65536 || int64_t(h) * j.grid > 65536) ? KIFS_ERR_BAD_SIZE : KIFS_OK;
 }
 
-static int check(const kifs_ctx* c, int count, int samples, const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
-                 uint8_t* const* outs, size_t pitch, int y0, int y1, int encode) {
-    if (!c || !cameras || !outs) return KIFS_ERR_BAD_ARG;
+int check(const kifs_ctx* c, int count, int samples, const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
+          uint8_t* const* outs, size_t pitch, int y0, int y1, int encode, bool outs_optional) {
+    if (!c || !cameras || (!outs && !outs_optional)) return KIFS_ERR_BAD_ARG;
     if (samples < 1 || samples > KIFS_MAX_ACCUMULATE || count < 1 || count > MAX_BATCH / samples) return KIFS_ERR_BAD_ARG;
-    for (int i = 0; i < count; ++i)
+    for (int i = 0; outs && i < count; ++i)
         if (!outs[i] || (reinterpret_cast<uintptr_t>(outs[i]) & 3u) != 0) return KIFS_ERR_BAD_ARG;
     if (encode != KIFS_ENCODE_UNORM && encode != KIFS_ENCODE_SRGB) return KIFS_ERR_BAD_ARG;
     if (c->supersampling > 1) return KIFS_ERR_BAD_ARG;  // out of scope, as for the geometry output
@@ -52,13 +45,13 @@ static int check(const kifs_ctx* c, int count, int samples, const KifsCameraUnif
     int w = 0, h = 0;
     if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
     if (y0 < 0 || y1 > h || y0 > y1) return KIFS_ERR_BAD_ARG;
-    if (pitch < size_t(w) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull) return KIFS_ERR_BAD_SIZE;
+    if (outs && (pitch < size_t(w) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull)) return KIFS_ERR_BAD_SIZE;
     return KIFS_OK;
 }
 
-static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, const KifsCameraUniform* cameras,
-                   const KifsOptionsUniform* options, const Jitter* jitter, uint8_t* const* outs, size_t pitch, int y0, int y1,
-                   int encode) {
+int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, const KifsCameraUniform* cameras,
+            const KifsOptionsUniform* options, const Jitter* jitter, uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
+            LaunchFn launch, void* user) {
     host::hip_ok(hipGetLastError(), "stale error before enqueue");
     const int views = count * samples;
     Params A;
@@ -72,8 +65,8 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
     P.y0 = y0;
     P.y1 = y1;
     P.encode = encode;
-    P.pitch_words = uint32_t(pitch >> 2);
-    P.out = reinterpret_cast<uint32_t*>(outs[0]);
+    P.pitch_words = outs ? uint32_t(pitch >> 2) : 0u;
+    P.out = outs ? reinterpret_cast<uint32_t*>(outs[0]) : nullptr;
     // whole rays, one kernel form for every scene: no costs, no diagnostics, no rounds, the plain orbit trip
     P.tile_cost = nullptr;
     P.counters = nullptr;
@@ -92,7 +85,7 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
     if (big)
         if (const int st = host::take_view_slot(c, &vs); st != KIFS_OK) return st;
     std::vector<uint8_t*> view_outs(size_t(views), nullptr);  // every sub-frame of a frame carries the frame's destination
-    for (int v = 0; v < views; ++v) view_outs[size_t(v)] = outs[v / samples];
+    for (int v = 0; outs && v < views; ++v) view_outs[size_t(v)] = outs[v / samples];
     host::fill_views(c, P, big ? c->h_views[vs] : A.B.view, views, cameras, view_outs.data());
     if (const int st = anim::take_scene_slot(c, &ss); st != KIFS_OK) return st;
     anim::SceneView* const scenes = static_cast<anim::SceneView*>(c->h_scenes[ss]);
@@ -136,7 +129,7 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
     c->last_bunny_form = -1;
     c->last_kernel = KIFS_KERNEL_ACCUMULATE;
     const KifsOptionsUniform& first = options ? options[0] : c->options;
-    const bool launched = host::hip_ok(launch_accumulate_render(A, first.fractal_group_id, first.primitive_id, stream),
+    const bool launched = host::hip_ok(launch(A, first.fractal_group_id, first.primitive_id, stream, user),
                                        "accumulate render_kernel launch");
     // (also after a failed launch: the copies above are enqueued and read the pinned images)
     bool marked = host::hip_ok(hipEventRecord(c->scenes_used[ss], stream), "record(scene table)");
@@ -146,6 +139,11 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, cons
         c->views_busy[vs] = true;
     }
     return launched && marked ? KIFS_OK : KIFS_ERR_RUNTIME;
+}
+
+// The launch step of the two calls below.
+static hipError_t launch_render(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void*) {
+    return launch_accumulate_render(A, group, primitive, stream);
 }
 
 }  // namespace accum
@@ -160,7 +158,8 @@ extern "C" int kifs_render_accumulate_async(kifs_ctx* c, void* hip_stream, int c
     if (!g.ok) return KIFS_ERR_RUNTIME;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
-    return accum::enqueue(c, s, count, samples, cameras, options, nullptr, dev_outs, pitch, y0, y1, encode);
+    return accum::enqueue(c, s, count, samples, cameras, options, nullptr, dev_outs, pitch, y0, y1, encode, accum::launch_render,
+                          nullptr);
 }
 
 extern "C" int kifs_render_accumulate_jittered_async(kifs_ctx* c, void* hip_stream, int count, int samples,
@@ -175,5 +174,6 @@ extern "C" int kifs_render_accumulate_jittered_async(kifs_ctx* c, void* hip_stre
     if (!g.ok) return KIFS_ERR_RUNTIME;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
-    return accum::enqueue(c, s, count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode);
+    return accum::enqueue(c, s, count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode, accum::launch_render,
+                          nullptr);
 }

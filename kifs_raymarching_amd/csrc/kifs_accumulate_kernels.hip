@@ -13,6 +13,15 @@
 //                                      (kifs_render_accumulate_jittered_async): sub-frame v's ray goes through cell (i, j)
 //                                      of the g x g grid inside its pixel, pixel (g x + i, g y + j) of the virtual
 //                                      g W x g H screen kifs_set_supersampling defines.  Both kernels are one body.
+//   accum::carry_render_kernel<GROUP, PRIM>  one PASS of a progressive frame (kifs_render_accumulate_resume_async): the
+//                                      jittered kernel's marches for every grid (g = 1: cell (0, 0), the pixel centre),
+//                                      and a resolve that starts from the pixel's texel of a plane of f32 sums earlier
+//                                      passes left -- (sum.r, sum.g, sum.b, float(total)), one 16-byte load per lane,
+//                                      issued by wave 0 after its own last march and before the barrier, so that its
+//                                      latency hides behind the other waves' marches -- adds the pass's sub-frames in the
+//                                      contract's order, stores the texel with one 16-byte store and, when the pass has
+//                                      destinations, encodes sum / float(total).  A texel is read and written by one
+//                                      lane of one workgroup.  The same body again.
 // Why not the supersampling kernel's shape (a lane marches all of its samples one after another): a launch is as long as
 // its longest rays, and that shape makes a lone frame's critical ray `samples` rays long.  Here the
 // sub-frames of a block run side by side on four waves, and the blocks of every output frame side by side on the device.
@@ -72,7 +81,11 @@ __device__ __forceinline__ uint32_t cell_of(const anim::SceneView* scenes, uint3
 // Only the wave-level cull is used, and its argument is per lane with the screen's own 1 / height: it holds on the
 // virtual screen as it stands (cull_n2 and quick_cull_n2 are radii in scene space: fill_params).  `valid` and the store
 // guards stay on OUTPUT coordinates.
-template <int GROUP, int PRIM, bool JITTER>
+// CARRY: the kernel argument is a CarryParams whose first member is A; the resolve starts from the plane's texel when
+// earlier passes left one (prior > 0), writes the texel back and encodes only for a pass with destinations.
+typedef float Texel __attribute__((ext_vector_type(4)));
+typedef const CarryParams __attribute__((address_space(4))) * ConstCarry;
+template <int GROUP, int PRIM, bool JITTER, bool CARRY = false>
 __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, float* s_colour) {
     ConstParams kp = (ConstParams)__builtin_amdgcn_kernarg_segment_ptr();  // = &A
     int tid = threadIdx.x;
@@ -117,7 +130,29 @@ __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, floa
         slot[64] = c.y;
         slot[128] = c.z;
     }
+    // A resumed pass: wave 0's lanes fetch their pixels' texels now, behind the marches the other waves are still in --
+    // eight lanes of a block row read 128 contiguous bytes -- under the guard of the store below.
+    [[maybe_unused]] Texel texel{0.0f, 0.0f, 0.0f, 0.0f};
+    [[maybe_unused]] Texel* cell = nullptr;
+    [[maybe_unused]] uint32_t prior = 0u;
+    if constexpr (CARRY) {
+        prior = ((ConstCarry)kp)->prior;  // launch-uniform: a scalar
+        if (wave == 0u) {
+            const ConstCarry K = (ConstCarry)kp;
+            const FrameParams& C = reloaded(kp).B.frame;
+            const uint32_t lane = uint32_t(tid) & 63u;
+            const int ly = int(lane >> 3);
+            const int x = block_x + int(lane & 7u), y = frame_y + ly;
+            if (x < C.width && y < C.y1) {
+                cell = reinterpret_cast<Texel*>(K->sums) + size_t(frame) * K->sums_stride_texels +
+                       size_t(tile_y + ly) * K->sums_pitch_texels + uint32_t(x);
+                if (prior != 0u) texel = *cell;
+            }
+        }
+    }
     __syncthreads();  // every sub-frame's colours and s_srgb visible
+    // (the texel is first looked at here: the wait for the load comes behind the barrier, not in front of it)
+    if constexpr (CARRY) asm volatile("" : "+v"(texel));
     if (wave != 0u) return;
 
     // The resolve of the contract, per channel in f32: acc = c_0, then acc + c_s in order (-ffp-contract=off: no fma),
@@ -125,11 +160,18 @@ __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, floa
     const uint32_t lane = uint32_t(tid) & 63u;
     const float* at = s_colour + lane;
     V3 acc{at[0], at[64], at[128]};
+    if constexpr (CARRY)  // acc = the texel's sum, then + c_0; a first pass starts from c_0 itself (no 0 + c_0: -0)
+        if (prior != 0u) acc = V3{texel.x + acc.x, texel.y + acc.y, texel.z + acc.z};
     for (uint32_t s = 1; s < samples; ++s) {
         at += SLOT;
         acc = V3{acc.x + at[0], acc.y + at[64], acc.z + at[128]};
     }
-    const float n = float(samples);
+    float n = float(samples);
+    if constexpr (CARRY) {
+        n = float(prior + samples);  // exact: at most 2^24 (KIFS_MAX_PROGRESSIVE_SAMPLES)
+        if (cell) *cell = Texel{acc.x, acc.y, acc.z, n};
+        if (((ConstCarry)kp)->picture == 0u) return;  // launch-uniform: the pass only advances the plane
+    }
     const FrameParams& C = reloaded(kp).B.frame;  // what every view shares
     const uint32_t rgba = encode_rgba(V3{acc.x / n, acc.y / n, acc.z / n}, C.encode == 1, s_srgb);
     const int ly = int(lane >> 3);
@@ -157,17 +199,28 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     render_body<GROUP, PRIM, true>(A, s_srgb, s_colour);
 }
 
+// One pass of a progressive frame: the plane of sums carried across launches (CarryParams, kifs_params.hpp).  The marches
+// are the jittered kernel's for every grid: at g = 1 the cell is (0, 0) and the virtual screen is the frame.
+template <int GROUP, int PRIM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void carry_render_kernel(const CarryParams K) {
+    __shared__ float s_srgb[256];
+    extern __shared__ float s_colour[];  // [samples][3][64]
+    render_body<GROUP, PRIM, true, true>(K.A, s_srgb, s_colour);
+}
+
 // From 63 sub-frames the dynamic LDS and the 1 KB sRGB table together pass the default limit of 48 KB: the kernel then opts
 // in, once per instantiation and device, as ensure_dynamic_lds does for the residency pad (kifs_render_common.hpp).
-template <int GROUP, int PRIM, bool JITTER>
+enum Family { PLAIN, JITTERED, CARRIED };
+template <int GROUP, int PRIM, Family FAMILY>
 static hipError_t ensure_lds(unsigned dynamic_bytes) {
     if (dynamic_bytes + 256u * unsigned(sizeof(float)) <= 48u * 1024u) return hipSuccess;
     static std::atomic<bool> opted_in[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-        const void* const kernel = JITTER ? reinterpret_cast<const void*>(&jitter_render_kernel<GROUP, PRIM>)
-                                          : reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>);
+        const void* const kernel = FAMILY == CARRIED    ? reinterpret_cast<const void*>(&carry_render_kernel<GROUP, PRIM>)
+                                   : FAMILY == JITTERED ? reinterpret_cast<const void*>(&jitter_render_kernel<GROUP, PRIM>)
+                                                        : reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>);
         hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         if (attr != hipSuccess) return attr;
         if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
@@ -178,12 +231,21 @@ static hipError_t ensure_lds(unsigned dynamic_bytes) {
 template <int GROUP, int PRIM, bool JITTER>
 static hipError_t launch(const Params& A, hipStream_t stream) {
     const unsigned lds = unsigned(A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
-    if (hipError_t e = ensure_lds<GROUP, PRIM, JITTER>(lds); e != hipSuccess) return e;
+    if (hipError_t e = ensure_lds<GROUP, PRIM, JITTER ? JITTERED : PLAIN>(lds); e != hipSuccess) return e;
     const dim3 grid(A.B.frame.tile_count * BLOCKS * uint32_t(A.frames));
     if (JITTER)
         hipLaunchKernelGGL((jitter_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
     else
         hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
+    return hipGetLastError();
+}
+
+template <int GROUP, int PRIM>
+static hipError_t launch_carry(const CarryParams& K, hipStream_t stream) {
+    const unsigned lds = unsigned(K.A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
+    if (hipError_t e = ensure_lds<GROUP, PRIM, CARRIED>(lds); e != hipSuccess) return e;
+    const dim3 grid(K.A.B.frame.tile_count * BLOCKS * uint32_t(K.A.frames));
+    hipLaunchKernelGGL((carry_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, K);
     return hipGetLastError();
 }
 
@@ -198,6 +260,18 @@ hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint
     return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
         return jitter ? accum::launch<decltype(g)::value, decltype(prim)::value, true>(A, stream)
                       : accum::launch<decltype(g)::value, decltype(prim)::value, false>(A, stream);
+    });
+}
+
+hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, uint32_t primitive, hipStream_t stream) {
+    const accum::Params& A = K.A;
+    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
+    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
+    if (!K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
+        uint64_t(K.prior) + uint64_t(A.samples) > (1ull << 24))
+        return hipErrorInvalidValue;  // (refused by the API before it gets here)
+    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
+        return accum::launch_carry<decltype(g)::value, decltype(prim)::value>(K, stream);
     });
 }
 

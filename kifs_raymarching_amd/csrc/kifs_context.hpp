@@ -199,4 +199,32 @@ struct OptionsOfFrame0 {
 };
 
 }  // namespace anim
+
+// What kifs_accumulate.cpp shares with kifs_progressive.cpp: a pass of a progressive frame is the jittered call's launch
+// with another kernel behind it.
+namespace accum {
+
+// The sub-pixel cells of a jittered call: sub-frame v goes through cell cells[v] of the grid x grid cells of its pixel;
+// cells == nullptr (samples == grid * grid): sub-frame s of every frame through cell (s % grid, s / grid).
+struct Jitter {
+    int grid;
+    const KifsSubpixel* cells;
+};
+// The launch step of enqueue(): receives the filled Params, the pipeline and the stream.
+typedef hipError_t (*LaunchFn)(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void* user);
+
+// What every accumulated call refuses.  `outs_optional`: a null `outs` array is accepted (a pass without a picture); a
+// null or misaligned entry of a given array is refused either way.
+int check(const kifs_ctx* c, int count, int samples, const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
+          uint8_t* const* outs, size_t pitch, int y0, int y1, int encode, bool outs_optional = false);
+// What the jittered call refuses beyond check(): after it, so that every refusal of the unjittered call keeps its status.
+int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter& j);
+// The one launch of an accumulated call; `outs` may be null when check() allowed it (every view then carries a null
+// destination and `pitch` is ignored).  `launch` is the last step: the two calls of kifs_accumulate.cpp pass
+// launch_accumulate_render, a pass of a progressive frame wraps the Params into its CarryParams (`user`).
+int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, const KifsCameraUniform* cameras,
+            const KifsOptionsUniform* options, const Jitter* jitter, uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
+            LaunchFn launch, void* user);
+
+}  // namespace accum
 }  // namespace kifs

@@ -24,6 +24,9 @@ hipError_t launch_animation_render(const anim::Params& A, uint32_t group, uint32
 // Accumulated frames (kifs_accumulate_kernels.hip; the host side is kifs_accumulate.cpp): every output frame the mean of
 // its sub-frames' linear colours, one workgroup per 8 x 8 output block and output frame.
 hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream);
+// One pass of a progressive frame (kifs_render_accumulate_resume_async; the host side is kifs_progressive.cpp): the same
+// launch with the resolve started from, and written back to, a plane of f32 sums (accum::carry_render_kernel).
+hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

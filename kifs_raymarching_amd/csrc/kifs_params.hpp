@@ -177,6 +177,19 @@ struct Params {
 };
 static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
 
+// The argument of accum::carry_render_kernel (kifs_render_accumulate_resume_async): one PASS of a progressive frame.  A is
+// the pass's own launch, exactly as the jittered call fills it (A first: the kernel argument's address is A's); the plane
+// of 16-byte texels (sum.r, sum.g, sum.b, float(total)) is laid out as the geometry output's -- row r of the band of
+// output frame f at sums + 4 * (f * sums_stride_texels + r * sums_pitch_texels) floats.
+struct CarryParams {
+    Params A;
+    float* sums;                                     // first row of frame 0's plane (device memory, 16-byte aligned)
+    uint32_t sums_pitch_texels, sums_stride_texels;  // row pitch and per-frame stride in texels
+    uint32_t prior;                                  // sub-frames already in the plane; 0: the plane is not read
+    uint32_t picture;                                // 0: no destinations, the pass only advances the plane
+};
+static_assert(sizeof(CarryParams) <= 4096, "the kernel argument is limited to 4 KB");
+
 }  // namespace accum
 
 }  // namespace kifs

@@ -554,6 +554,63 @@ class GraphicState:
                                                         y0, y1, encode), "render_accumulate")
         return outs
 
+    # ---- progressive accumulation (kifs_render_accumulate_resume_async): a frame's linear sums carried across launches
+    def render_accumulate_resume(self, sums, prior, cameras, samples, options=None, outs=None, picture: bool = True,
+                                 y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, stream=None, jitter=None):
+        """One PASS of a progressive frame: render_accumulate's launch for these cameras, options and jitter, whose
+        resolve starts from `sums` -- a contiguous float32 (count, rows, W, 4) tensor on this context's device holding
+        (sum.r, sum.g, sum.b, float(total)) per pixel after `prior` sub-frames; prior == 0: not read, whatever it holds --
+        adds the pass's sub-frames in the contract's order and writes the sums back with total = prior + samples.  With
+        `picture` the frames encode(sum / total) are returned as render_accumulate returns them (`outs` to reuse); without,
+        the pass only advances the plane and returns None.  Passes whose views concatenate to one render_accumulate
+        call's give that call's bytes, for any split; the library keeps no state, `sums` and `prior` are all of it
+        (Accumulator below keeps them together).  jitter None: the pixel centre.  Ordered after the producers of both
+        `sums` and `outs`."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        samples, prior = int(samples), int(prior)
+        cams = camera_array(cameras)
+        views = len(cams)
+        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
+            raise ValueError(f"render_accumulate_resume: 1..{MAX_ACCUMULATE} samples per frame and pass, count * samples "
+                             f"cameras, at most {MAX_BATCH} of them")
+        if not 0 <= prior <= _lib.MAX_PROGRESSIVE_SAMPLES - samples:
+            raise ValueError(f"render_accumulate_resume: prior + samples within 0..{_lib.MAX_PROGRESSIVE_SAMPLES}")
+        n = views // samples
+        opts = None if options is None else options_array(options)
+        if opts is not None and len(opts) != views:
+            raise ValueError(f"render_accumulate_resume: {len(opts)} option images for {views} cameras")
+        if (not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (n, rows, w, 4) or sums.dtype != torch.float32
+                or not sums.is_contiguous() or not sums.is_cuda):
+            raise ValueError(f"render_accumulate_resume: sums float32 ({n}, {rows}, {w}, 4), contiguous, on the device")
+        ptrs = None
+        if picture:
+            if outs is None:
+                outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
+                raise ValueError(f"render_accumulate_resume: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+            base, frame_bytes = _device_pointer(outs), rows * w * 4
+            ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+        grid, cells = (1, None) if jitter is None else jitter
+        if cells is not None and not isinstance(cells, C.Array):
+            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
+        if cells is not None and len(cells) != views:
+            raise ValueError(f"render_accumulate_resume: {len(cells)} cells for {views} cameras")
+        if cells is None and samples != int(grid) * int(grid):  # (the C call takes NULL only for the whole grid in order)
+            if int(grid) != 1:
+                raise ValueError("render_accumulate_resume: cells None needs samples == grid * grid")
+            cells = (KifsSubpixel * views)()  # the pixel centre: cell (0, 0) of the one-cell grid
+        stream = self._stream_handle(stream, "render_accumulate_resume")
+        self._order_after_producer(sums, stream)
+        if picture:
+            self._order_after_producer(outs, stream)
+        check(lib.kifs_render_accumulate_resume_async(self._ctx, stream, n, samples, cams, opts, int(grid), cells,
+                                                      _device_pointer(sums), w * 16, rows * w * 16, prior, ptrs, w * 4, y0, y1,
+                                                      encode), "render_accumulate_resume")
+        return outs if picture else None
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -804,6 +861,42 @@ class GraphicState:
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         check(lib.kifs_eval_math(self._ctx, fn, fp(xs), param, fp(out), xs.size), "eval_math")
         return out
+
+
+class Accumulator:
+    """The state of a progressive frame (GraphicState.render_accumulate_resume): the plane of linear sums and the number
+    of sub-frames in it, for `count` frames of rows [y0, y1) of `state`'s screen.  add() is one pass; passes of any sizes
+    give the bytes of one render_accumulate call over all their views."""
+
+    def __init__(self, state, count: int = 1, y0: int = 0, y1: int = None):
+        import torch
+        self.state, self.count, self.y0 = state, int(count), int(y0)
+        self.y1 = state.screen_data.height if y1 is None else int(y1)
+        rows = max(self.y1 - self.y0, 0)
+        self.sums = torch.zeros((self.count, rows, state.screen_data.width, 4), dtype=torch.float32,
+                                device=torch.device("cuda", state.device))
+        self.total = 0
+
+    def add(self, cameras, samples, options=None, outs=None, picture: bool = True, encode: int = ENCODE_SRGB, stream=None,
+            jitter=None):
+        """One pass of `samples` sub-frames per frame (len(cameras) == count * samples): the frames after it, or None
+        with picture=False."""
+        if len(camera_array(cameras)) != self.count * int(samples):
+            raise ValueError(f"Accumulator.add: {self.count} x {samples} cameras")
+        frames = self.state.render_accumulate_resume(self.sums, self.total, cameras, samples, options=options, outs=outs,
+                                                     picture=picture, y0=self.y0, y1=self.y1, encode=encode, stream=stream,
+                                                     jitter=jitter)
+        self.total += int(samples)
+        return frames
+
+    def reset(self):
+        """Start over: the next pass does not read the plane."""
+        self.total = 0
+
+    def linear_mean(self):
+        """The linear HDR mean of every pixel, float32 (count, rows, W, 3): sums / total, as the plane describes itself.
+        The caller synchronises first."""
+        return self.sums[..., :3] / self.sums[..., 3:]
 
 
 class MultiGraphicState:

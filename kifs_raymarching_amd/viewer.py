@@ -160,11 +160,27 @@ class HttpSink:
 class ViewerSession:
     """The reference's event handlers and redraw, around `renderer` (a GraphicState, or anything with
     enable_camera_rotation / disable_camera_rotation / mouse_motion(dx, dy) / zoom_camera(distance) /
-    render() -> (H, W, 4) uint8)."""
+    render() -> (H, W, 4) uint8).
 
-    def __init__(self, renderer, sinks=()):
+    `refine` = (grid, samples_per_pass, max_passes) turns on progressive refinement, as every path tracer and fractal
+    explorer does while nothing moves: after a redraw caused by input -- which is the plain render(), unchanged -- every
+    idle redraw() adds one jittered pass of `samples_per_pass` rays per pixel to the session's accumulator
+    (graphics.Accumulator over the renderer; pass p takes configs.jitter_cells(grid, samples, frame=p * samples) with the
+    renderer's camera) and presents the refined frame, until `max_passes` passes are in it; any input resets the
+    accumulator.  `accumulator`: an object with add(cameras, samples, jitter=) -> (1, H, W, 4) frames, reset() and
+    `total` to use instead.  refine=None: no accumulator, redraw() draws only when something changed."""
+
+    def __init__(self, renderer, sinks=(), refine=None, accumulator=None):
         self.renderer = renderer
         self.sinks = list(sinks)
+        if refine is not None:
+            grid, samples, passes = (int(v) for v in refine)
+            if grid < 1 or not 1 <= samples <= grid * grid or passes < 0:
+                raise ValueError("ViewerSession: refine = (grid, samples per pass <= grid^2, passes)")
+            refine = (grid, samples, passes)
+        self.refine = refine
+        self.accumulator = accumulator
+        self.passes_added = 0
         self.frames_presented = 0
         self.last_frame_ms = 0.0
         self._dirty = True  # the first redraw always draws
@@ -210,16 +226,42 @@ class ViewerSession:
         """Renders and presents if anything changed since the last redraw."""
         with self._lock:
             if not self._dirty:
-                return False
-            self._dirty = False
-            t0 = time.perf_counter()
-            frame = self.renderer.render()
+                if self.refine is None or self.passes_added >= self.refine[2]:
+                    return False
+                t0 = time.perf_counter()
+                frame = self._refine_pass()
+            else:
+                self._dirty = False
+                if self.refine is not None:
+                    self._reset_refinement()
+                t0 = time.perf_counter()
+                frame = self.renderer.render()
             self.last_frame_ms = (time.perf_counter() - t0) * 1e3
             index = self.frames_presented
             self.frames_presented += 1
         for s in self.sinks:
             s.present(frame, index)
         return True
+
+    def _reset_refinement(self):
+        self.passes_added = 0
+        if self.accumulator is not None:
+            self.accumulator.reset()
+
+    def _refine_pass(self):
+        """One more jittered pass into the accumulator: the refined frame, (H, W, 4) uint8 on the host."""
+        from .configs import jitter_cells
+        grid, samples, _ = self.refine
+        if self.accumulator is None:
+            from .graphics import Accumulator
+            self.accumulator = Accumulator(self.renderer)
+        cells = jitter_cells(grid, samples, frame=self.passes_added * samples)
+        frames = self.accumulator.add([self.renderer.camera_data] * samples, samples, jitter=(grid, cells))
+        self.passes_added += 1
+        if hasattr(self.renderer, "synchronize"):
+            self.renderer.synchronize()
+        frame = frames[0]
+        return frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)
 
     def run(self, seconds: float = None, idle_sleep: float = 0.005):
         """Redraw loop: until `seconds` have passed (None: until interrupted)."""

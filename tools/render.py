@@ -12,6 +12,8 @@
     python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --motion-blur 8   # a blurred morph
     python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --jitter 4   # blur that anti-aliases
     python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --aa 2           # an anti-aliased morph
+    python tools/render.py cfg2_julia_1080p out.png --dof 0.05,3.2 --spp 400 --jitter 8        # a lens at print quality: 7 passes
+    python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --spp 150   # 64 + 64 + 22 sub-frames
 """
 import argparse
 import sys
@@ -19,7 +21,8 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
-from kifs_raymarching_amd.configs import WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, shutter_cameras  # noqa: E402
+from kifs_raymarching_amd.configs import (WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, pass_splits,  # noqa: E402
+                                          shutter_cameras)
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -62,6 +65,11 @@ ap.add_argument("--jitter", type=int, default=0, metavar="G",
                 help="with --motion-blur S or --dof .. --samples S (S <= G x G): sub-frame s goes through its own cell of a "
                      f"G x G grid inside the pixel (1..{K.MAX_JITTER_GRID}; kifs_render_accumulate_jittered_async, cells from "
                      "configs.jitter_cells), so the blur's rays anti-alias as well")
+ap.add_argument("--spp", type=int, default=None, metavar="N",
+                help="with --dof, --motion-blur (also with --morph-to) and --jitter: N sub-frames per output frame in all, "
+                     "instead of --samples S / --motion-blur S -- progressive accumulation "
+                     "(kifs_render_accumulate_resume_async): passes of at most 64 (with --jitter G: at most G x G) carry the "
+                     "frame's linear sums, only the last one encodes; N may be far above 64")
 args = ap.parse_args()
 dof = None
 if args.dof is not None:
@@ -74,14 +82,20 @@ if args.dof is not None:
     if args.motion_blur or args.morph_to is not None:
         ap.error("--dof goes without --motion-blur and --morph-to")
 accumulate = args.motion_blur or (args.samples if dof else 0)
-if (args.motion_blur or dof) and not 1 <= accumulate <= K.MAX_ACCUMULATE:
-    ap.error(f"1..{K.MAX_ACCUMULATE} sub-frames per frame")
+if args.spp is not None:
+    if not accumulate:
+        ap.error("--spp goes with --dof or --motion-blur")
+    if not 1 <= args.spp <= 1 << 24:
+        ap.error("--spp N: 1..16777216 sub-frames per frame")
+    accumulate = args.spp
+elif (args.motion_blur or dof) and not 1 <= accumulate <= K.MAX_ACCUMULATE:
+    ap.error(f"1..{K.MAX_ACCUMULATE} sub-frames per frame (more with --spp)")
 if accumulate and (args.aa != 1 or args.aa_adaptive or args.geometry):
     ap.error("--motion-blur and --dof render without --aa, --aa-adaptive or --geometry")
 if args.jitter:
     if not accumulate:
         ap.error("--jitter goes with --motion-blur or --dof")
-    if not 1 <= args.jitter <= K.MAX_JITTER_GRID or accumulate > args.jitter ** 2:
+    if not 1 <= args.jitter <= K.MAX_JITTER_GRID or (accumulate > args.jitter ** 2 and args.spp is None):
         ap.error(f"--jitter G: 1..{K.MAX_JITTER_GRID}, with at most G x G sub-frames per frame")
 # --aa K for a morph or several orbit frames: one launch, every frame the K x K cells of a pixel in supersampling order
 aa_grid = args.aa > 1 and not accumulate and (args.morph_to is not None or (args.frames is not None and len(args.frames) > 1))
@@ -137,6 +151,45 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
         pixels = screen.width * screen.height
         print(f"{args.out}: {screen.width}x{screen.height}, {edges} of {pixels} pixels supersampled "
               f"{args.aa_adaptive}x{args.aa_adaptive} ({100.0 * edges / pixels:.2f} %)")
+    elif args.spp is not None:
+        # progressive accumulation: N sub-frames per frame as passes that carry the frames' linear sums (K.Accumulator);
+        # the views are those of the one-launch forms below for S = N, handed out pass by pass
+        N, G = args.spp, args.jitter
+        splits = pass_splits(N, min(K.MAX_ACCUMULATE, G * G) if G else K.MAX_ACCUMULATE)
+        morph = morph_to is not None
+        if morph:
+            n = args.frames[0]
+            guis = morph_options(gui, K.GuiData(**{**gui.__dict__, "constant": morph_to}), n * N)
+            indices, out = list(range(n)), Path(args.out)
+        else:
+            indices = args.frames if args.frames is not None else [None]
+        per_call = max(1, K.MAX_BATCH // max(splits))
+        for first in range(0, len(indices), per_call):
+            part = indices[first:first + per_call]
+            cams, opts = [], None
+            for k in part:
+                if morph:
+                    cams.append([w.camera.into_buffer_data()] * N)
+                elif dof:
+                    cams.append(lens_cameras(w.camera if k is None else orbit_camera(w, k), dof[0], dof[1], N))
+                else:
+                    cams.append([c.into_buffer_data() for c in shutter_cameras(w, k, N, args.shutter)])
+            if morph:
+                opts = [guis[k * N:(k + 1) * N] for k in part]
+            acc = K.Accumulator(gs, count=len(part))
+            done = 0
+            for p, S in enumerate(splits):
+                jitter = None if not G else (G, [c for k in part for c in jitter_cells(G, S, (k or 0) + done)])
+                frames = acc.add([cams[f][done + s] for f in range(len(part)) for s in range(S)], S,
+                                 options=None if opts is None else [opts[f][done + s] for f in range(len(part)) for s in range(S)],
+                                 picture=p == len(splits) - 1, jitter=jitter)
+                done += S
+            gs.synchronize()
+            for k, frame in zip(part, frames.cpu().numpy()):
+                path = str(out.with_name(f"{out.stem}_{k:03d}{out.suffix}")) if morph else args.out if k is None else args.out % k
+                write_png(path, frame)
+                print(f"{path}: {screen.width}x{screen.height}, the mean of {N} sub-frames in {len(splits)} passes"
+                      + (f", jittered over a {G}x{G} grid" if G else ""))
     elif morph_to is not None and args.motion_blur:
         # frame i of the morph is the mean of steps i S .. i S + S - 1 of a morph of n S steps
         n, S = args.frames[0], args.motion_blur
