@@ -318,6 +318,11 @@ class GraphicState:
             return
         check(lib.kifs_order_after(self._ctx, launch_stream, producer or None), "order_after")
 
+    def order_after(self, stream, producer):
+        """kifs_order_after on raw hipStream_t handles: the context's next work on `stream` (None: its own stream) runs
+        after everything `producer` (a caller's stream) holds now.  Nothing blocks the host."""
+        check(lib.kifs_order_after(self._ctx, stream or None, producer), "order_after")
+
     def render(self, out=None, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB,
                pitch_bytes: int = None):
         """Synchronous frame.  `out` None -> returns a (rows, W, 4) uint8 ndarray; an
@@ -565,7 +570,8 @@ class GraphicState:
         the pass only advances the plane and returns None.  Passes whose views concatenate to one render_accumulate
         call's give that call's bytes, for any split; the library keeps no state, `sums` and `prior` are all of it
         (Accumulator below keeps them together).  jitter None: the pixel centre.  Ordered after the producers of both
-        `sums` and `outs`."""
+        `sums` and `outs` -- torch's current stream -- and after nothing else: two passes of one plane on different
+        streams are the caller's to order (contract (c) of the header); Accumulator.add does it."""
         import torch
         w, h = self.screen_data.width, self.screen_data.height
         y1 = h if y1 is None else y1
@@ -863,10 +869,16 @@ class GraphicState:
         return out
 
 
+_NO_PASS = object()  # Accumulator._last_stream before the first pass (None is the context's own stream)
+
+
 class Accumulator:
     """The state of a progressive frame (GraphicState.render_accumulate_resume): the plane of linear sums and the number
     of sub-frames in it, for `count` frames of rows [y0, y1) of `state`'s screen.  add() is one pass; passes of any sizes
-    give the bytes of one render_accumulate call over all their views."""
+    give the bytes of one render_accumulate call over all their views.  Passes may run on different streams: add() orders
+    a pass after the previous one when its stream differs (render_accumulate_resume leaves that to its caller) -- with
+    kifs_order_after when the previous pass ran on a caller's stream, and with state.synchronize(), A HOST WAIT, when it
+    ran on the context's own stream, for which the header has no handle to name as a producer."""
 
     def __init__(self, state, count: int = 1, y0: int = 0, y1: int = None):
         import torch
@@ -875,23 +887,33 @@ class Accumulator:
         rows = max(self.y1 - self.y0, 0)
         self.sums = torch.zeros((self.count, rows, state.screen_data.width, 4), dtype=torch.float32,
                                 device=torch.device("cuda", state.device))
-        self.total = 0
+        self.reset()
 
     def add(self, cameras, samples, options=None, outs=None, picture: bool = True, encode: int = ENCODE_SRGB, stream=None,
             jitter=None):
         """One pass of `samples` sub-frames per frame (len(cameras) == count * samples): the frames after it, or None
-        with picture=False."""
+        with picture=False.  `stream` as render_async takes it; a pass on another stream than the previous pass's is
+        ordered after that pass first -- without blocking the host when it ran on a caller's stream, and by waiting on
+        the host for the context's own stream (state.synchronize()) when it ran there."""
         if len(camera_array(cameras)) != self.count * int(samples):
             raise ValueError(f"Accumulator.add: {self.count} x {samples} cameras")
+        handle = getattr(stream, "cuda_stream", stream) or None  # None: the context's own stream
+        if self._last_stream is not _NO_PASS and handle != self._last_stream:
+            if self._last_stream is None:
+                self.state.synchronize()
+            else:
+                self.state.order_after(handle, self._last_stream)
         frames = self.state.render_accumulate_resume(self.sums, self.total, cameras, samples, options=options, outs=outs,
                                                      picture=picture, y0=self.y0, y1=self.y1, encode=encode, stream=stream,
                                                      jitter=jitter)
         self.total += int(samples)
+        self._last_stream = handle
         return frames
 
     def reset(self):
-        """Start over: the next pass does not read the plane."""
+        """Start over: the next pass does not read the plane, and is ordered after no earlier pass."""
         self.total = 0
+        self._last_stream = _NO_PASS
 
     def linear_mean(self):
         """The linear HDR mean of every pixel, float32 (count, rows, W, 3): sums / total, as the plane describes itself.

@@ -6,7 +6,10 @@ users apart, so that a slot of the four-deep view-table ring passes from one ent
 accumulated launches joined: none of them while supersampling is on either; a blur or pairs launch and a jittered launch
 on a caller's stream; a slot of the scene-table ring passing between an animated and an accumulated launch; and a
 view-table slot passing between "accumulate66" and one of the two older users, besides the passage between batch and
-animation.  A seed that falls short is replaced in context_walk.SEEDS; the condition stays."""
+animation.  Since progressive accumulation joined ("progressive", "progressive_jitter": two passes each, every pass a
+user of the scene ring): neither while supersampling is on; at least one of them on a caller's stream; a scene-table slot
+passing between a pass and an animated launch, and one passing between a pass and an accumulated launch.  A seed that
+falls short is replaced in context_walk.SEEDS; the condition stays."""
 import numpy as np
 import pytest
 
@@ -31,9 +34,16 @@ def test_walk_covers_the_context_state(seed):
     assert cov["view_ring_shared"], view_users
     assert cov["view_ring_passages"] & {frozenset(("accumulate66", "batch66")), frozenset(("accumulate66", "animation66"))}, view_users
     assert cov["scene_ring_shared"], [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.ANIMATED or kind in W.ACCUMULATED]
+    assert not any(kind in W.PROGRESSIVE and ss > 1 for kind, ss in _supersampling_at(ops))
+    assert caller["progressive"] + caller["progressive_jitter"] >= 1, caller
+    scene_users = [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.ANIMATED or kind in W.ACCUMULATED or kind in W.PROGRESSIVE]
+    assert frozenset(("progressive", "animation")) in cov["scene_ring_passages"], scene_users
+    assert frozenset(("progressive", "accumulate")) in cov["scene_ring_passages"], scene_users
 
 
-LINEAR_VIEWS = {882: 0, 2444: 0, 3958: 16}  # per seed: what the blur and jitter models of its walk cost, in per-pixel linear views
+# per seed: what the blur and jitter models of its walk cost, in per-pixel linear views -- the progressive kinds' passes
+# are modelled from the views of their one-call twins, so they are counted here too
+LINEAR_VIEWS = {381: 0, 1626: 12, 2849: 12}
 
 
 @pytest.mark.parametrize("seed", W.SEEDS)
@@ -76,6 +86,12 @@ def test_model_of_the_table_cache():
     assert [e for _, _, e in W.replay(ops)] == ["fill", "hit", "fill", "hit", "fill", "hit", "fill", "hit", "hit", "hit"]
     assert [k for _, k, _ in W.replay([("screen", 2), ("jitter", 5), ("accumulate66", 0)])] == \
         [(64, 40) + W.band_rows(40, 5) + (None,), (64, 40, 0, 40, None)]
+    # and the progressive kinds: the key of the band or frame they render (the lone launch between the passes renders it too)
+    ops = [("band", 7), ("progressive", 7), ("progressive_jitter", 5), ("band", 5), ("jitter", 5), ("progressive", -1), ("animation3", -1),
+           ("progressive_jitter", -1), ("progressive", 2), ("accumulate", 2)]
+    assert [e for _, _, e in W.replay(ops)] == ["fill", "hit", "fill", "hit", "hit", "fill", "hit", "hit", "fill", "hit"]
+    assert [k for _, k, _ in W.replay([("screen", 2), ("progressive_jitter", 5), ("progressive", -1)])] == \
+        [(64, 40) + W.band_rows(40, 5) + (None,), (64, 40, 0, 40, None)]
 
 
 def test_coverage_counts_caller_streams_and_the_shared_view_ring():
@@ -83,9 +99,11 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
     ops = [("adaptive", 2), ("stream", 1), ("adaptive", 3), ("animation3", -1), ("stream", 0), ("animation66", 0), ("stream", 2),
            ("animation66", 0)]
     cov = W.coverage(ops)
-    assert cov["on_caller_stream"] == {"adaptive": 1, "animation3": 1, "animation66": 1, "accumulate": 0, "jitter": 0, "accumulate66": 0}
+    assert cov["on_caller_stream"] == {"adaptive": 1, "animation3": 1, "animation66": 1, "accumulate": 0, "jitter": 0, "accumulate66": 0,
+                                       "progressive": 0, "progressive_jitter": 0}
     cov = W.coverage([("jitter", 5), ("stream", 2), ("jitter", -1), ("accumulate66", 0), ("stream", 0), ("accumulate", 2)])
-    assert cov["on_caller_stream"] == {"adaptive": 0, "animation3": 0, "animation66": 0, "accumulate": 0, "jitter": 1, "accumulate66": 1}
+    assert cov["on_caller_stream"] == {"adaptive": 0, "animation3": 0, "animation66": 0, "accumulate": 0, "jitter": 1, "accumulate66": 1,
+                                       "progressive": 0, "progressive_jitter": 0}
     assert not cov["view_ring_shared"]
     A, B = ("animation66", 0), ("batch66", 0)
     assert W.coverage([A, B, B, B, B])["view_ring_shared"]          # the fifth user takes the first one's slot
@@ -114,6 +132,25 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
     assert not W.coverage([blur, jit, P, blur, jit, P, blur, blur])["scene_ring_shared"]  # one entry point, three kinds
     assert not W.coverage([a3, A, a3, A, A, a3])["scene_ring_shared"]
     assert not W.coverage([a3, blur, jit, A, a3, P, blur, A, A])["scene_ring_shared"]  # both in every window, every slot stays with its own
+    # every PASS of a progressive kind is a user of the scene ring (two per launch), an entry point of its own
+    prog, pj = ("progressive", 2), ("progressive_jitter", -1)
+    pair = lambda a, b: frozenset((a, b))
+    cov = W.coverage([("stream", 1), prog, ("stream", 0), pj, a3])   # users G G G G A: slot 0 passes from a pass to an animated launch
+    assert cov["scene_ring_passages"] == {pair("progressive", "animation")} and not cov["scene_ring_shared"]
+    assert cov["on_caller_stream"]["progressive"] == 1 and cov["on_caller_stream"]["progressive_jitter"] == 0
+    cov = W.coverage([a3, a3, a3, prog, blur])                       # A A A G G U: A -> G (the second pass), A -> U
+    assert cov["scene_ring_passages"] == {pair("animation", "progressive"), pair("animation", "accumulate")} and cov["scene_ring_shared"]
+    cov = W.coverage([blur, a3, a3, a3, prog])                       # U A A A G G: U -> G, A -> G
+    assert cov["scene_ring_passages"] == {pair("accumulate", "progressive"), pair("animation", "progressive")}
+    assert W.coverage([blur, jit, blur, P, prog])["scene_ring_passages"] == {pair("accumulate", "progressive")}  # U U U U G G
+    cov = W.coverage([a3, blur, a3, blur, a3, prog])                 # A U A U A G G: U -> G, A -> G, and never A against U
+    assert cov["scene_ring_passages"] == {pair("accumulate", "progressive"), pair("animation", "progressive")}
+    assert cov["scene_ring_shared"] is False
+    assert W.coverage([a3, a3, a3, blur, blur])["scene_ring_shared"] and W.coverage([prog, pj, prog])["scene_ring_passages"] == set()
+    assert W.scene_ring_users(W.trace([a3, ("band", 0), pj, P, prog])) == ["animation", "progressive", "progressive", "accumulate",
+                                                                          "progressive", "progressive"]
+    keys = W.linear_view_keys([("screen", 2), ("camera", 1), prog, pj])   # the views of the one-call twins
+    assert keys == W.linear_view_keys([("screen", 2), ("camera", 1), blur, jit]) and len(keys) == 4 + 4
 
 
 @pytest.mark.parametrize("ext", [0, 1])
@@ -134,3 +171,38 @@ def test_pairs_are_the_plain_frames(options, ext, kifs, oracle):
         s, c, o = oracle_uniforms(O, K, (screen, cam, L.Raw(image)))
         plain = O.render(s, c, o, O.iters(*iters), **(dict(ext=e) if ext else {}))
         assert frames.shape == (1, 40, 64, 4) and np.array_equal(frames[0], plain), (options, ext, m)
+        # and Ctx.carried: the same two sub-frames as two passes through progressive_reference.fold, pass 1 at prior 0 over a
+        # plane of NaNs, pass 2 at prior 1 -- the plain frame again, and the plane's w word is 2.0
+        lin = ACC.linear_views(O, K, screen, [cam], image, iters, e)
+        two, plane = L.carried_pair_model(O, lin)
+        assert two.shape == (1, 40, 64, 4) and np.array_equal(two[0], plain), (options, ext, m)
+        assert (plane[..., 3] == np.float32(2.0)).all() and not np.isnan(plane).any()
+        assert (plane[..., :3].view(np.uint32) == (lin + lin).astype(np.float32).view(np.uint32)).all()
+        _, mistaken = L.carried_pair_model(O, lin, prior_of_pass_2=0)  # (a pass 2 modelled at prior 0 would not pass the line above)
+        assert (mistaken[..., 3] == np.float32(1.0)).all()
+
+
+def test_the_progressive_split_shows_in_the_model(kifs, oracle):
+    """What Ctx.progressive's comparisons rest on, from the references alone, at 64 x 40: the final plane and picture of
+    the blur views are the same bits for the splits 1 + 2 and 2 + 1 (the fold is one sum in one order), so it is pass 1's
+    picture that holds the split -- for 1 + 2 the plain frame of every frame's first sub-frame, and another picture for
+    2 + 1.  A model with the two pass sizes swapped fails the comparison of pass 1's picture."""
+    import accumulate_reference as ACC
+    import test_gpu_context_lifecycle as L
+    from helpers import oracle_uniforms
+    K, O = kifs, oracle
+    screen, cams, gui, iters = K.ScreenData(64, 40), L._cameras(K), L._options(K)[0], L.ITERS[0]
+    views, samples, splits = L.progressive_views("blur", 1)
+    assert (samples, splits) == (3, (1, 2)) and len(views) == 6
+    lin = np.stack([ACC.linear_views(O, K, screen, [cams[cam]], L._morph(K, gui, m), iters, None)[0] for cam, m, _ in views])
+    frames, plane = L.progressive_model(O, lin, samples, splits)
+    swapped, swapped_plane = L.progressive_model(O, lin, samples, splits[::-1])
+    assert (plane.view(np.uint32) == swapped_plane.view(np.uint32)).all() and np.array_equal(frames[-1], swapped[-1])
+    assert (frames[0] != swapped[0]).any(-1).sum() * 100 >= 64 * 40
+    for f in range(2):
+        cam, m, _ = views[f * samples]
+        s, c, o = oracle_uniforms(O, K, (screen, cams[cam], L.Raw(L._morph(K, gui, m))))
+        assert np.array_equal(frames[0][f], O.render(s, c, o, O.iters(*iters)))
+    assert L.progressive_views("jitter", 1)[1:] == (2, (1, 1))
+    # the walks' kinds and Ctx.progressive's agree on the passes
+    assert {k: (sum(v), v) for k, v in W.PROGRESSIVE.items()} == {k: L.PROGRESSIVE_SPLITS[L.PROGRESSIVE_KINDS[k]] for k in W.PROGRESSIVE}

@@ -60,6 +60,36 @@ tests/test_context_walk_plan.py), 3.7 s of wall time on an 8-CPU host, 2.3 s of 
 test; the pairs need no reference the animated launches did not.  That is below the 3.9 to 11.8 s of the oracle and
 adaptive-model frames above.  On one MI355X machine the whole module, references included, ran 60 tests in 5.4 s of wall
 time before the accumulated launches joined and runs 78 tests in 10.1 s with them; no new case takes more than 2.2 s.
+
+Progressive accumulation (kifs_render_accumulate_resume_async) goes through the same rings, tile tables, last_stream and
+options scope, and a progressive frame is the one result that depends on SEVERAL launches with other launches between
+them: a stale scene record changes one frame of a blur launch, and here it ends up in a sum every later pass inherits.
+Two kinds of launch on planes of the test's own, every byte 0xFF before the first pass (NaNs: a first pass that read the
+plane would show).  Ctx.carried: n views as two passes of one sub-frame, the second with a picture at prior 1 --
+(c + c) / 2 = c, so the oracle's plain frames at any size, and the plane's w word is 2.0; c / 2 if pass 2 ignored the plane,
+the sentinel if it did not run.  Ctx.progressive: the views of Ctx.blur as passes of 1 + 2 sub-frames per frame, or of
+Ctx.jitter as 1 + 1, a picture from every pass; up to MODEL_UP_TO the final picture against the one-call model
+(identity (b)) and every pass's picture and every f32 bit pattern of the plane against progressive_reference.fold over the
+same linear views, beyond it against one render_accumulate call and the same passes on a fresh context.  Not vacuous from
+the references alone: the final frame differs from pass 1's picture in at least 1 % of the pixels, and it is pass 1's
+picture that tells 1 + 2 from 2 + 1 (tests/test_context_walk_plan.py).  All passes of one frame run on one stream.  Where:
+every phase of the lone period with a lone launch BETWEEN the passes, a caller's stream included
+(test_transition_at_every_phase: "carried3", "carried_caller_stream", "progressive"); four set_screen calls and every
+launch of three other sizes between the passes (test_resize_sequence); both rings among passes of five frames, two of
+them open at once, and the other entry points (test_rings_carry_progressive_frames); the diagnostics buffer and the
+profiling ring (test_diagnostics_buffer); the seeded walks ("progressive", "progressive_jitter", a lone launch between the
+passes).  Still not covered: passes handed from the context's own stream to a caller's without a host wait (the header has
+no call that names the context's stream as a producer), and prior near 2^24 on a long-lived context.
+Cost, counted from the plans before a GPU run: the transitions and the resize need no oracle frame the pairs did not and
+no linear view (1024 x 512 is beyond the model); test_rings_carry_progressive_frames needs 6 oracle frames and 12 linear
+views per size, all of them already those of test_scene_ring_shared_with_blur_and_jitter (0 new when the module runs in
+order), and builds 4 two-pass models per size from them (16 encoded frames); test_diagnostics_buffer one model from the 4
+views it had; the three walks 24 linear views of 64 x 40 (0, 12, 12; the old seeds' 16) and 24, 25 and 21 oracle frames
+(12.8, 9.1 and 6.4 Mpixel), none of them only for the lone launches between the passes.  On one MI355X machine the module,
+references included, ran 78 tests in 10.3 s of wall time before these launches joined and runs 92 tests in 10.5 s with
+them (one session, one run after the other; the recorded 10.1 s above was another session); no new case takes more than
+0.5 s in the module's order, and test_rings_carry_progressive_frames run on its own, its references not yet there, takes
+1.4 s at 200 x 135 and 1.8 s at 64 x 40 as the first test of its process.
 """
 import ctypes as C
 
@@ -70,6 +100,7 @@ import accumulate_reference as ACC
 import adaptive_reference as AR
 import context_walk as W
 import jitter_reference as JR
+import progressive_reference as PR
 from geometry_cases import Raw
 from helpers import oracle_uniforms
 
@@ -124,7 +155,7 @@ class Refs:
         self.K, self.O, self.cams, self.opts, self.frames = K, O, _cameras(K), _options(K), {}
         self.morphs = [[_morph(K, g, m) for m in range(W.N_MORPHS)] for g in self.opts]
         self.geoms, self.means, self.models = {}, {}, {}
-        self.linears, self.accums = {}, {}
+        self.linears, self.accums, self.passes = {}, {}, {}
 
     def frame(self, size, cam, options=0, iters=0, ext=0, morph=0):
         import torch
@@ -188,6 +219,26 @@ class Refs:
             self.accums[key] = torch.from_numpy(frames).to("cuda:0")
         return self.accums[key]
 
+    def progressive(self, size, kind, cam0, options=0, iters=0, ext=0):
+        """(the frames after every pass, (frames, H, W, 4) uint8 each; the final plane, (frames, H, W, 4) float32), on the
+        device: progressive_model over the linear views of a Ctx.progressive(kind) with the context's camera cam0.  The
+        final frame is the one-call model's (identity (b), here from the references alone), which `accumulated` has
+        shown to differ from the plain frame of its first sub-frame -- for the blur split, pass 1's own picture."""
+        import torch
+        views, samples, splits = progressive_views(kind, cam0)
+        key = (size, tuple(views), samples, splits, options, iters, ext)
+        if key not in self.passes:
+            lin = np.stack([self.linear(size, cam, options, iters, ext, m, cell) for cam, m, cell in views])
+            frames, plane = progressive_model(self.O, lin, samples, splits)
+            one_call = self.accumulated(size, views, samples, options, iters, ext)
+            assert np.array_equal(frames[-1], one_call.cpu().numpy()), key
+            if splits[0] == 1:  # a first pass of one sub-frame: its picture is that sub-frame's plain frame
+                for f in range(len(views) // samples):
+                    cam, m, cell = views[f * samples]
+                    assert cell is not None or np.array_equal(frames[0][f], self.frame(size, cam, options, iters, ext, m).cpu().numpy()), key
+            self.passes[key] = ([torch.from_numpy(f).to("cuda:0") for f in frames], torch.from_numpy(plane).to("cuda:0"))
+        return self.passes[key]
+
     def blur(self, size, cam0, options=0, iters=0, ext=0, own_options=True):
         return self.accumulated(size, _blur_views(cam0, own_options), 3, options, iters, ext)
 
@@ -198,6 +249,35 @@ class Refs:
 def _blur_views(cam0, own_options=True):
     """The sub-frames of a blur launch; without options of their own every one has the context's image (0)."""
     return [(cam, m if own_options else 0, None) for cam, m in W.blur_views(cam0)]
+
+
+PROGRESSIVE_KINDS = {"progressive": "blur", "progressive_jitter": "jitter"}  # context_walk's kinds -> Ctx.progressive's
+PROGRESSIVE_SPLITS = {"blur": (3, (1, 2)), "jitter": (2, (1, 1))}  # Ctx.progressive: kind -> sub-frames per frame, per pass
+
+
+def progressive_views(kind, cam0):
+    """(the sub-frames of a Ctx.progressive launch as Ctx.blur's or Ctx.jitter's one call takes them, sub-frames per
+    frame, sub-frames per frame and pass)."""
+    samples, splits = PROGRESSIVE_SPLITS[kind]
+    return (_blur_views(cam0) if kind == "blur" else W.jitter_views(cam0)), samples, splits
+
+
+def progressive_model(O, lin, samples, splits):
+    """progressive_reference.fold over the (frames * samples, H, W, 3) linear views `lin` of one call, pass by pass: (the
+    frames after every pass, the final plane).  Nothing but the oracle's views and np.float32 additions."""
+    passes = PR.split_views(lin, lin.shape[0] // samples, samples, splits)
+    frames, plane, total = PR.carried(O, passes)
+    assert total == samples and (plane[..., 3] == np.float32(samples)).all()
+    return frames, plane
+
+
+def carried_pair_model(O, lin, prior_of_pass_2=1):
+    """What Ctx.carried rests on, through progressive_reference.fold in two passes: pass 1 folds the (frames, H, W, 3)
+    linear views `lin` at prior 0 over a plane of NaNs, pass 2 the same views at prior 1.  (frames, plane)."""
+    lin = np.asarray(lin, dtype=np.float32)[:, None]
+    plane, total = PR.fold(np.full(lin.shape[:1] + lin.shape[2:4] + (4,), np.nan, dtype=np.float32), 0, lin)
+    plane, total = PR.fold(plane, prior_of_pass_2, lin)
+    return PR.picture(O, plane), plane
 
 
 @pytest.fixture(scope="module")
@@ -240,6 +320,11 @@ class Ctx:
     def want(self, cam, y0, y1, morph=0):
         st = self.state
         return self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"], morph)[y0:y1]
+
+    def plane(self, rows, n):
+        """A plane of n frames of the test's own, every byte 0xFF: NaNs, so that a first pass that reads it shows."""
+        w, torch = self.state["size"][0], self.torch
+        return torch.full((n, rows, w, 16), 0xFF, dtype=torch.uint8, device="cuda:0").view(torch.float32)
 
     def dest(self, rows, n=None):
         w = self.state["size"][0]
@@ -298,6 +383,109 @@ class Ctx:
         for f, (cam, m) in enumerate(zip(cams, morphs)):
             self.pending.append((outs[f], self.want(cam, y0, y1, m), len(self.log)))
         return outs
+
+    def carried_open(self, n, y0=0, y1=None, stream=None, shift=0, what=None):
+        """Pass 1 of Ctx.carried; returns the function that enqueues pass 2, whatever the context has done since."""
+        st = dict(self.state)
+        y1 = st["size"][1] if y1 is None else y1
+        cams = W.batch_cameras(st["camera"], n)
+        morphs = [(W.morph_of(cam) + shift) % W.N_MORPHS for cam in cams]
+        images = [self.refs.morphs[st["options"]][m] for m in morphs]
+        uniforms = [self.refs.cams[cam] for cam in cams]
+        wants = [self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"], m)[y0:y1] for cam, m in zip(cams, morphs)]
+        sums = self.plane(y1 - y0, n)
+        what = what or ("carried", n, y0, y1, shift, "caller stream" if stream is not None else "context stream")
+        assert self.gs.render_accumulate_resume(sums, 0, uniforms, 1, options=images, picture=False, y0=y0, y1=y1, stream=stream) is None
+        self.log.append(what + ("pass 1",))
+
+        def finish():
+            assert self.state["size"] == st["size"]
+            outs = self.torch.full((n, y1 - y0, st["size"][0], 4), SENTINEL, dtype=self.torch.uint8, device="cuda:0")
+            self.gs.render_accumulate_resume(sums, 1, uniforms, 1, options=images, outs=outs, y0=y0, y1=y1, stream=stream)
+            self.log.append(what + ("pass 2",))
+            for f in range(n):
+                self.pending.append((outs[f], wants[f], len(self.log)))
+            self.pending.append((sums[..., 3:], self.torch.full_like(sums[..., 3:], 2.0), len(self.log)))  # the w word: 2.0 everywhere
+            return outs, sums
+        return finish
+
+    def carried(self, n, y0=0, y1=None, stream=None, shift=0, between=None, what=None):
+        """Carried pairs, a progressive frame per view: pass 1 is n frames x 1 sub-frame without a picture at prior 0 over
+        a plane of NaNs, then `between` (any other launches of this Ctx), then pass 2 the same n views again with a
+        picture at prior 1.  Cameras and option images as Ctx.pairs; (c + c) / 2 is c in f32, so every frame against the
+        oracle's plain frame (test_pairs_are_the_plain_frames, through progressive_reference.fold too).  A pass 2 that
+        ignored the plane or took it for empty gives c / 2, one that did not run the sentinel; the plane's w word is 2.0."""
+        finish = self.carried_open(n, y0, y1, stream, shift, what)
+        if between is not None:
+            between()
+        return finish()
+
+    def progressive_open(self, kind, y0=0, y1=None, stream=None, fresh=None, what=None):
+        """Pass 1 of Ctx.progressive; returns the function that enqueues the last pass."""
+        st = dict(self.state)
+        torch = self.torch
+        y1 = st["size"][1] if y1 is None else y1
+        rows, width = y1 - y0, st["size"][0]
+        views, samples, splits = progressive_views(kind, st["camera"])
+        count = len(views) // samples
+        images = [self.refs.morphs[st["options"]][m] for _, m, _ in views]
+        uniforms = [self.refs.cams[cam] for cam, _, _ in views]
+        cells = None if views[0][2] is None else [cell for _, _, cell in views]
+        cam_p, opt_p = PR.pass_views(uniforms, count, samples, splits), PR.pass_views(images, count, samples, splits)
+        cell_p = [None] * len(splits) if cells is None else PR.pass_views(cells, count, samples, splits)
+        what = what or ("progressive " + kind, st["camera"], y0, y1, "caller stream" if stream is not None else "context stream")
+        assert W.modelled(st["size"]) or fresh is not None
+        sums = self.plane(rows, count)
+        pictures = [torch.full((count, rows, width, 4), SENTINEL, dtype=torch.uint8, device="cuda:0") for _ in splits]
+
+        def run(g, p, plane, outs, stream):
+            g.render_accumulate_resume(plane, sum(splits[:p]), cam_p[p], splits[p], options=opt_p[p], outs=outs, y0=y0, y1=y1,
+                                       stream=stream, jitter=None if cells is None else (W.JITTER_GRID, cell_p[p]))
+
+        def enqueue(p):
+            run(self.gs, p, sums, pictures[p], stream)
+            self.log.append(what + (f"pass {p + 1} of {len(splits)}",))
+
+        def finish():
+            assert self.state["size"] == st["size"]
+            enqueue(len(splits) - 1)
+            upto = len(self.log)
+            if W.modelled(st["size"]):
+                frames, plane = self.refs.progressive(st["size"], kind, st["camera"], st["options"], st["iters"], st["ext"])
+                one_call = self.refs.accumulated(st["size"], views, samples, st["options"], st["iters"], st["ext"])
+                self.pending.append((pictures[-1], one_call[:, y0:y1], upto))
+                for p in range(len(splits)):
+                    self.pending.append((pictures[p], frames[p][:, y0:y1], upto))
+                self.pending.append((sums.view(torch.int32), plane[:, y0:y1].contiguous().view(torch.int32), upto))  # every f32 bit pattern
+            if fresh is not None:  # the one call for the picture, the same passes for the plane and the earlier pictures
+                want = torch.full_like(pictures[-1], SENTINEL)
+                fresh.render_accumulate(uniforms, samples, options=images, outs=want, y0=y0, y1=y1,
+                                        jitter=None if cells is None else (W.JITTER_GRID, cells))
+                self.pending.append((pictures[-1], want, upto))
+                want_sums = self.plane(rows, count)
+                for p in range(len(splits)):
+                    want_p = torch.full_like(pictures[p], SENTINEL)
+                    run(fresh, p, want_sums, want_p, None)
+                    self.pending.append((pictures[p], want_p, upto))
+                self.pending.append((sums.view(torch.int32), want_sums.view(torch.int32), upto))
+            return pictures[-1], sums
+
+        for p in range(len(splits) - 1):
+            enqueue(p)
+        return finish
+
+    def progressive(self, kind, y0=0, y1=None, stream=None, fresh=None, between=None, what=None):
+        """The views of Ctx.blur (kind "blur": 2 frames x 3 sub-frames with their own option images, pixel centres, as
+        passes of 1 + 2) or of Ctx.jitter ("jitter": 2 x 2 on a grid of 2, as 1 + 1) through render_accumulate_resume on
+        a plane of NaNs of the test's own, a picture from every pass, `between` (other launches of this Ctx) between the
+        passes.  Up to MODEL_UP_TO the final picture against the one-call model of Ctx.blur / Ctx.jitter (identity (b)),
+        every pass's picture and every f32 bit pattern of the plane against progressive_reference.fold over the same
+        linear views; with `fresh` the final picture against its one render_accumulate call, the plane and the earlier
+        pictures against the same passes on it.  Returns (the final picture, the plane)."""
+        finish = self.progressive_open(kind, y0, y1, stream, fresh, what)
+        if between is not None:
+            between()
+        return finish()
 
     def blur(self, y0=0, y1=None, stream=None, fresh=None, own_options=True, what=None):
         """An accumulated launch of 2 frames x 3 sub-frames: the cameras batch_cameras(camera, 6), each sub-frame with the
@@ -478,7 +666,8 @@ def test_eviction_round_trip(k, ctx, kifs):
 
 
 TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504",
-               "adaptive", "animation3", "animation70", "animation_caller_stream", "pairs3", "pairs70", "pairs_caller_stream", "jitter")
+               "adaptive", "animation3", "animation70", "animation_caller_stream", "pairs3", "pairs70", "pairs_caller_stream", "jitter",
+               "carried3", "carried_caller_stream", "progressive")
 
 
 @pytest.mark.parametrize("k", range(4))
@@ -488,12 +677,14 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
     enqueue_batch call out -- or an adaptive call, animated or accumulated launches, which keep state of their own and pass
     through the full frame's tile table --, then six more lone launches.  The accumulated pairs are held to the oracle's plain
     frames, the jittered launch to a fresh context.  Everything equals the oracle, the order table stays a
-    permutation, and the lone launches before and after run the same kernel."""
+    permutation, and the lone launches before and after run the same kernel.  Carried pairs and a progressive blur frame
+    (against a fresh context: 1024 x 512 is beyond the model) are progressive frames whose two passes STRADDLE a lone launch
+    of the full frame, which advances the feedback period; neither pass moves the order."""
     import torch
     c = ctx()
     for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch: the lone launches', then the animated ones'
         c.refs.frame(FULL, cam)
-        if transition.startswith(("animation", "pairs")):
+        if transition.startswith(("animation", "pairs", "carried")):
             for shift in range(W.N_MORPHS if transition.endswith("_caller_stream") else 1):
                 c.refs.frame(FULL, cam, morph=(W.morph_of(cam) + shift) % W.N_MORPHS)
     if transition == "sphere":
@@ -582,6 +773,30 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
             c.jitter(fresh=fresh)
             fresh.synchronize()
         assert np.array_equal(c.gs.debug_get_tile_order(), before)
+    elif transition in ("carried3", "carried_caller_stream", "progressive"):
+        def straddled(open_, cam):
+            """Pass 1, a lone launch of the full frame, pass 2: the order moves across neither pass."""
+            before = c.gs.debug_get_tile_order()
+            finish = open_()
+            assert np.array_equal(c.gs.debug_get_tile_order(), before)
+            c.lone(cam=cam)  # (advances the period; what it does to the order is the lone launches' business)
+            before = c.gs.debug_get_tile_order()
+            finish()
+            assert np.array_equal(c.gs.debug_get_tile_order(), before)
+            c.camera(1)
+        c.camera(1)
+        if transition == "carried3":
+            straddled(lambda: c.carried_open(3), 2)
+        elif transition == "carried_caller_stream":
+            s = torch.cuda.Stream()
+            straddled(lambda: c.carried_open(3, stream=s), 2)
+            straddled(lambda: c.carried_open(3, stream=s, shift=1), 3)
+            straddled(lambda: c.carried_open(3, stream=s, shift=2), 0)  # pass 2: the lone launches below follow it without a wait
+        else:
+            with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[1], gui_data=c.refs.opts[0]) as fresh:
+                fresh.set_iters(*ITERS[0])
+                straddled(lambda: c.progressive_open("blur", fresh=fresh), 2)
+                fresh.synchronize()
     for i in range(6):
         c.lone(cam=(i + 1) % 4, record_kernel=True)
     c.verify()
@@ -593,7 +808,9 @@ def test_resize_sequence(ctx, kifs):
     """1024x512 -> 330x149 -> 64x40 -> 1056x516 -> 1024x512 on one context: every set_screen is issued while the previous
     size's launch is still enqueued, host and device destinations alternate, and one stripe list is rendered in place and
     packed at two sizes.  The first launch after every set_screen is an accumulated one of three pairs, held to the oracle's
-    plain frames, and at the two sizes with a model a blur launch renders the band rows h // 3 .. h - 3."""
+    plain frames, and at the two sizes with a model a blur launch renders the band rows h // 3 .. h - 3.  Pass 1 of three
+    carried pairs is enqueued at the first 1024 x 512 and pass 2 when the sequence is back there at its end: four set_screen
+    calls and every launch of the other sizes lie between the passes of frames that are the oracle's plain frames."""
     import torch
     sizes = [(1024, 512), (330, 149), (64, 40), (1056, 516), (1024, 512)]
     stripes = [0, 2, 4]  # rows 0..7, 16..23, 32..39: inside every size
@@ -608,6 +825,11 @@ def test_resize_sequence(ctx, kifs):
     for n, (w, h) in enumerate(sizes):
         c.screen((w, h))            # (the previous size's launches are still in flight)
         c.pairs(3)                  # (the first launch at the new size: the scene ring's records, the new frame's table)
+        if n == 0:
+            c.camera(1)
+            finish_carried = c.carried_open(3)
+        elif n == len(sizes) - 1:
+            finish_carried()
         c.lone(cam=n % 4)
         if n % 2:
             c.camera((n + 1) % 4)
@@ -649,11 +871,12 @@ def test_resize_sequence(ctx, kifs):
 
 @pytest.mark.parametrize("seed", W.SEEDS)
 def test_seeded_walk(seed, ctx, kifs):
-    """72 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
+    """88 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
     checked, and a failure prints the plan up to it.  Adaptive calls, animated and accumulated launches run on the walk's
     current stream like every other render: every animated frame and every frame of an "accumulate66" against the oracle,
     an adaptive call as Ctx.adaptive says, a blur or jitter launch against its model up to MODEL_UP_TO and against the same
-    call on the fresh context beyond."""
+    call on the fresh context beyond.  A "progressive" or "progressive_jitter" is Ctx.progressive with a lone launch of
+    the same rows and the context's camera between its passes, all three on the walk's current stream."""
     import torch
     ops = W.plan(seed)
     c = ctx()
@@ -664,6 +887,11 @@ def test_seeded_walk(seed, ctx, kifs):
             if st["supersampling"] == 1:
                 n = {"batch3": 3, "batch66": 66, **W.ANIMATED, "accumulate66": 33}.get(kind, 1)
                 scene = (W.SIZES[st["size"]], st["options"], st["iters"])
+                if kind in W.PROGRESSIVE:
+                    if W.modelled(scene[0]):
+                        c.refs.progressive(scene[0], PROGRESSIVE_KINDS[kind], st["camera"], *scene[1:], st["extensions"])
+                    c.refs.frame(scene[0], st["camera"], *scene[1:], st["extensions"])  # the lone launch between the passes
+                    continue
                 if kind in ("accumulate", "jitter"):
                     if W.modelled(scene[0]):
                         (c.refs.blur if kind == "accumulate" else c.refs.jitter)(scene[0], st["camera"], *scene[1:], st["extensions"])
@@ -707,7 +935,7 @@ def test_seeded_walk(seed, ctx, kifs):
             cam0 = state["camera"]
             what = (i, kind, arg, dict(state))
             exact = state["supersampling"] == 1  # else: against the same call on the fresh context
-            beyond_the_model = kind in ("accumulate", "jitter") and not W.modelled((w, h))
+            beyond_the_model = W.AS_ONE_CALL.get(kind, kind) in ("accumulate", "jitter") and not W.modelled((w, h))
             if not exact or kind in ("geometry", "adaptive") or beyond_the_model:
                 mirror(fresh)
             if kind == "band" or kind in ("batch3", "batch66"):
@@ -747,6 +975,10 @@ def test_seeded_walk(seed, ctx, kifs):
             elif kind in ("accumulate", "jitter"):
                 launch = c.blur if kind == "accumulate" else c.jitter
                 launch(*W.animation_rows(h, arg), stream=stream, fresh=fresh if beyond_the_model else None, what=what)
+            elif kind in W.PROGRESSIVE:
+                rows = W.animation_rows(h, arg)
+                c.progressive(PROGRESSIVE_KINDS[kind], *rows, stream=stream, fresh=fresh if beyond_the_model else None, what=what,
+                              between=lambda: c.lone(cam0, *rows, stream=stream))
             elif kind == "adaptive":
                 fresh.set_camera(c.refs.cams[cam0])
                 c.adaptive(arg, stream=stream, fresh=fresh, what=what)
@@ -866,6 +1098,92 @@ def test_scene_ring_shared_with_blur_and_jitter(size, ctx):
     del held
 
 
+# test_rings_carry_progressive_frames: the users of the scene ring in order.  A pass is (frame, pass number); the frames are
+# X, X2 (Ctx.progressive "blur": pixel centres), Y, Y2 ("jitter") and K (Ctx.carried of 3: pixel centres); "A" an animated
+# launch of 3, "U" a blur launch, "J" a jittered launch.
+RING_FRAMES = {"X": ("blur", 0, 0), "Y": ("jitter", 1, 1), "K": ("carried", 2, 1), "X2": ("blur", 3, 1), "Y2": ("jitter", 3, 0)}  # kind, camera, caller's stream
+RING_USERS = (("X", 1), ("Y", 1), "A", "U",
+              "J", ("K", 1), ("Y", 2), ("X", 2),
+              ("K", 2), "U", "A", "J",
+              "A", ("X2", 1), ("Y2", 1), ("X2", 2),
+              ("Y2", 2))
+
+
+@pytest.mark.parametrize("size", [(64, 40), (200, 135)])
+def test_rings_carry_progressive_frames(size, ctx):
+    """Seventeen users of the four scene tables without a wait, behind _warm_up and _hold_back, ten of them passes of five
+    progressive frames.  Two frames are open at once from the start: a blur split on the context's stream (X) and a
+    jitter split on a caller's (Y); their passes, those of three carried pairs (K) and of a second blur and jitter split
+    (on the other stream each) are interleaved with animated launches of 3, blur launches and jittered launches, so that
+    every slot passes from a pass to another entry point and back to a pass -- slot 0 X -> J -> K, slot 1 K -> U -> X2,
+    slot 2 Y -> A -> Y2, slot 3 X -> J -> X2 -- and in slot 1 the jittered pass Y 1 is followed, four users later, by the
+    pixel-centre pass K 1, which must find the pad word of its records zero again.  A stale or foreign scene record in a
+    pass ends up in a sum that the frame's later passes inherit: every pass's picture and the final plane are held to
+    progressive_reference.fold, the final picture to the one-call model, the carried pairs to the oracle's plain frames.
+    At 64 x 40 three carried pairs of 70 views follow, with three batches of 70, an animated launch of 70 and three more
+    batches between the passes: the users of the view ring run pass B B B  A B B B  pass, so slot 0 passes pass -> animation
+    -> pass there."""
+    import torch
+    is_pass = [not isinstance(u, str) for u in RING_USERS]
+    kind_of = [RING_FRAMES[u[0]][0] if p else u for u, p in zip(RING_USERS, is_pass)]
+    for slot in range(W.SCENE_RING):  # a pass, then another entry point, then a pass again
+        seen = "".join("p" if p else "o" for p in is_pass[slot::W.SCENE_RING])
+        assert "po" in seen and "p" in seen[seen.index("po") + 2:], (slot, seen)
+    assert any(kind_of[n] == "jitter" and is_pass[n] and is_pass[n + 4] and kind_of[n + 4] in ("blur", "carried")
+               for n in range(len(RING_USERS) - 4))  # a jittered pass, then a pixel-centre pass in its slot
+    assert {kind_of[n] for n in range(len(RING_USERS)) if not is_pass[n]} == {"A", "U", "J"}
+    for name in RING_FRAMES:  # every frame's passes in order, on one stream; X and Y open before either is finished
+        assert [u[1] for u in RING_USERS if not isinstance(u, str) and u[0] == name] == [1, 2]
+    assert RING_USERS.index(("Y", 1)) < RING_USERS.index(("X", 2)) and RING_USERS.index(("X", 1)) < RING_USERS.index(("Y", 2))
+    assert RING_FRAMES["X"][2] == 0 and RING_FRAMES["Y"][2] == 1
+    c = ctx(size=size)
+    lone_cam = lambda n: (2 * n + 1) % W.N_CAMERAS  # odd cameras: the jittered launches' views are those of frames Y and Y2
+    for cam in range(W.N_CAMERAS):  # every reference before the first launch
+        c.refs.frame(size, cam)
+        c.refs.frame(size, cam, morph=W.morph_of(cam))
+    for n, user in enumerate(RING_USERS):
+        if user == "U":
+            c.refs.blur(size, lone_cam(n))
+        elif user == "J":
+            c.refs.jitter(size, lone_cam(n))
+    for kind, cam, _ in RING_FRAMES.values():
+        if kind != "carried":
+            c.refs.progressive(size, kind, cam)
+    s = torch.cuda.Stream()
+    _warm_up(c, 70 if size == (64, 40) else 3)
+    held = _hold_back(torch)
+    open_ = {}
+    for n, user in enumerate(RING_USERS):
+        if isinstance(user, str):
+            c.camera(lone_cam(n))
+            stream = s if n % 2 else None
+            if user == "A":
+                c.animation(3, stream=stream)
+            elif user == "U":
+                c.blur(stream=stream)
+            else:
+                c.jitter(stream=stream)
+            continue
+        name, number = user
+        kind, cam, caller = RING_FRAMES[name]
+        if number == 2:
+            open_.pop(name)()
+            continue
+        c.camera(cam)
+        stream = s if caller else None
+        open_[name] = c.carried_open(3, stream=stream) if kind == "carried" else c.progressive_open(kind, stream=stream)
+    assert not open_
+    if size == (64, 40):
+        c.camera(2)
+        finish = c.carried_open(70, stream=s)
+        for n in range(7):
+            c.camera(n % W.N_CAMERAS)
+            c.animation(70, stream=s if n % 2 else None) if n == 3 else c.batch(70)
+        finish()
+    c.verify()
+    del held
+
+
 def test_adaptive_scratch_across_sizes_and_counts(ctx):
     """Adaptive calls of 1, 5, 1 and 3 frames at 200 x 135, 64 x 40, 330 x 149 and 200 x 135 on one context and two streams
     in turn, an animated launch and a batch of three between each pair, nothing waited for by the test: the offsets of the
@@ -899,8 +1217,9 @@ def test_adaptive_scratch_across_sizes_and_counts(ctx):
 def test_diagnostics_buffer(ctx, kifs):
     """kifs_debug_counters sizes the per-wave record buffer for the screen of the call; a launch with more waves than it
     holds (a batch, a larger screen set since) runs as a normal launch without diagnostics, and so do an animated launch,
-    an adaptive call and the accumulated launches, blur and jitter (what they leave in the records is not defined).  Then
-    the profiling ring, which the first two leave consistent and an accumulated launch does not enter."""
+    an adaptive call, the accumulated launches, blur and jitter, and the passes of a progressive frame (what they leave in
+    the records is not defined).  Then the profiling ring, which the first two leave consistent and neither an accumulated
+    launch nor a pass enters."""
     from kifs_raymarching_amd._lib import lib
     small, tiles = (330, 149), 11 * 19
     c = ctx(size=small)
@@ -912,6 +1231,7 @@ def test_diagnostics_buffer(ctx, kifs):
     animated = c.animation(3)
     resolved, edges = c.adaptive(2)
     blurred, jittered = c.blur(), c.jitter()
+    carried, carried_plane = c.progressive("blur")
     c.verify()
     out8 = (C.c_uint64 * 8)()
     zero = lambda: lib.kifs_debug_counters(gs._ctx, 1, out8)
@@ -933,6 +1253,12 @@ def test_diagnostics_buffer(ctx, kifs):
     blurred_on, jittered_on = c.blur(), c.jitter()  # and the accumulated launches, each against its model both times
     c.verify()
     assert c.torch.equal(blurred_on, blurred) and c.torch.equal(jittered_on, jittered)
+    assert gs.debug_wave_records().shape == (4 * tiles, 4)
+    assert zero() == 0
+    carried_on, carried_plane_on = c.progressive("blur")  # and a progressive frame: the same bytes, the same plane
+    c.verify()
+    assert c.torch.equal(carried_on, carried) and c.torch.equal(carried_plane_on.view(c.torch.int32), carried_plane.view(c.torch.int32))
+    assert c.torch.equal(carried, blurred)                # (identity (b): the one call's bytes)
     assert gs.debug_wave_records().shape == (4 * tiles, 4)
     assert zero() == 0
     c.lone(2, 16, 56)                      # a band of five tile rows: 55 workgroups
@@ -983,6 +1309,8 @@ def test_diagnostics_buffer(ctx, kifs):
         fresh.set_iters(*ITERS[0])
         c.blur(fresh=fresh)
         c.jitter(fresh=fresh)
+        assert gs.profile_read()[0] == 0
+        c.progressive("blur", fresh=fresh)  # passes are not timed either (kifs_render_accumulate_resume_async): alone, an empty ring
         assert gs.profile_read()[0] == 0
         c.blur(fresh=fresh)
         c.jitter(fresh=fresh)

@@ -60,11 +60,11 @@ def test_the_tools_offer_it(kifs):
 
 def test_every_pipeline_is_compiled_without_scratch(kifs):
     from geometry_cases import PIPELINES, cases
-    from test_kernel_form_coverage import RENDER  # the form table's own pattern: must not claim the new family
+    from test_kernel_form_coverage import RENDER  # the form table's own pattern: it claims the new family (kernel_forms.CARRY_FORMS)
     report = kernel_report()
     names = [n for n in report if "kifs::accum::carry_render_kernel<" in n]
     assert len(names) == len(PIPELINES) == 10, names
-    assert not any(RENDER.search(n) for n in names)
+    assert all(RENDER.search(n) for n in names)
     assert len([n for n in report if "kifs::accum::render_kernel<" in n]) == 10  # the twenty existing names stay
     assert len([n for n in report if "kifs::accum::jitter_render_kernel<" in n]) == 10
     for n in names:
@@ -78,3 +78,65 @@ def test_every_pipeline_is_compiled_without_scratch(kifs):
         pair = (1, int(iters[0] <= 24)) if group == 1 else (2, 0) if group == 2 else (0, min(prim, 6))
         want.append(tuple(str(v) for v in pair))
     assert sorted(want) == got and len(set(want)) == 10
+
+
+class _FakeState:
+    """What Accumulator.add asks of its state, recorded: which of order_after and synchronize were called."""
+
+    def __init__(self):
+        self.calls = []
+
+    def render_accumulate_resume(self, sums, prior, cameras, samples, stream=None, **kw):
+        self.calls.append(("pass", prior, getattr(stream, "cuda_stream", stream)))
+        return None
+
+    def order_after(self, stream, producer):
+        self.calls.append(("order_after", stream, producer))
+
+    def synchronize(self):
+        self.calls.append(("synchronize",))
+
+
+class _Stream:
+    def __init__(self, handle):
+        self.cuda_stream = handle
+
+
+def test_accumulator_orders_a_pass_after_the_previous_pass_on_another_stream(kifs):
+    """No GPU: an Accumulator around a fake state.  Same stream: neither call; caller -> caller and caller -> own:
+    kifs_order_after(new, last), no host wait; own -> caller: state.synchronize(), a host wait, because no handle names
+    the context's own stream as a producer; after reset(): nothing, the stream is forgotten.  A torch stream and its raw
+    handle are the same stream."""
+    def accumulator():
+        state = _FakeState()
+        acc = kifs.Accumulator.__new__(kifs.Accumulator)  # (__init__ allocates the plane on a device)
+        acc.state, acc.count, acc.y0, acc.y1, acc.sums = state, 1, 0, 8, None
+        acc.reset()
+        return acc, state
+
+    cam = [kifs.CameraData()]
+    A, B = 0x1000, 0x2000
+    acc, st = accumulator()
+    for stream in (_Stream(A), A, _Stream(A)):  # same stream, as an object and as a handle
+        acc.add(cam, 1, stream=stream)
+    assert st.calls == [("pass", 0, A), ("pass", 1, A), ("pass", 2, A)] and acc.total == 3
+    acc, st = accumulator()
+    acc.add(cam, 1, stream=None)
+    acc.add(cam, 1)                       # own -> own
+    assert st.calls == [("pass", 0, None), ("pass", 1, None)]
+    acc, st = accumulator()
+    acc.add(cam, 1, stream=_Stream(A))
+    acc.add(cam, 1, stream=_Stream(B))    # caller -> caller
+    acc.add(cam, 1, stream=None)          # caller -> own
+    acc.add(cam, 1, stream=A)             # own -> caller
+    acc.add(cam, 1, stream=A)
+    assert st.calls == [("pass", 0, A), ("order_after", B, A), ("pass", 1, B), ("order_after", None, B), ("pass", 2, None),
+                        ("synchronize",), ("pass", 3, A), ("pass", 4, A)]
+    acc, st = accumulator()
+    acc.add(cam, 1, stream=None)
+    acc.reset()
+    acc.add(cam, 1, stream=B)             # after reset(): the first pass again, ordered after nothing
+    acc.add(cam, 1, stream=A)
+    acc.reset()
+    acc.add(cam, 1, stream=None)
+    assert st.calls == [("pass", 0, None), ("pass", 0, B), ("order_after", A, B), ("pass", 1, A), ("pass", 0, None)]

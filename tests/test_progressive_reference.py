@@ -89,3 +89,25 @@ def test_pass_splits(kifs):
     for bad in ((0, 64), (5, 0), (5, 65), (-1, 4)):
         with pytest.raises(ValueError):
             pass_splits(*bad)
+
+
+def test_pass_by_pass_cells_concatenate_to_the_one_call_cells(kifs):
+    """What tools/render.py --spp and the viewer's refinement hand out: pass p of S sub-frames takes
+    jitter_cells(g, S, k + done).  Up to g^2 sub-frames in all the passes' cells concatenate to jitter_cells(g, N, k); beyond
+    g^2, to that formula -- n_s = ((s + k) a) mod g^2 -- continued round the grid."""
+    from kifs_raymarching_amd.configs import jitter_cells, jitter_stride, pass_splits
+    for g in (1, 2, 3, 4, 8):
+        n, a = g * g, jitter_stride(g)
+        for k in (0, 1, 5):
+            for per_pass in {1, min(2, n), min(4, n), n}:  # tools/render.py: at most g^2 per pass
+                for N in sorted({1, per_pass, n - 1, n, n + 1, 2 * n + 3, 3 * n} - {0}):
+                    got, done = [], 0
+                    for S in pass_splits(N, per_pass):
+                        got += jitter_cells(g, S, k + done)
+                        done += S
+                    want = [((((s + k) * a) % n) % g, (((s + k) * a) % n) // g) for s in range(N)]
+                    assert got == want, (g, k, per_pass, N)
+                    if N <= n:
+                        assert got == jitter_cells(g, N, k) and len(set(got)) == N
+                    else:
+                        assert got[:n] == jitter_cells(g, n, k) and got[n:] == (got[:n] * (N // n + 1))[:N - n]  # round the grid again
