@@ -435,6 +435,62 @@ int kifs_render_accumulate_resume_async(kifs_ctx* ctx, void* hip_stream, int cou
                                         uint8_t* const* dev_outs_rgba8 /* NULL: no picture from this pass */,
                                         size_t pitch_bytes, int y0, int y1, int encode);
 
+/* ---- extension: converging accumulation -- stop sampling the pixels whose mean has settled ----
+ * NOT part of the reference.  A progressive frame of the call above marches every pixel in every pass.  This pass carries
+ * a per-pixel count and a per-pixel second moment beside the sums, marches only the pixels whose mean has not settled,
+ * skips the 8 x 8 blocks in which none is left, and tells the caller how many pixels remain.
+ *   base      everything kifs_render_accumulate_resume_async says holds for the pass's own count * samples views: views,
+ *             cells and grid 1, what may vary between option images, misses, bands, samples <= KIFS_MAX_ACCUMULATE per
+ *             pass, the debug hooks (KIFS_KERNEL_ACCUMULATE; not timed by kifs_set_profiling); no shard, geometry,
+ *             adaptive or kifs_multi_* form.
+ *   state     two planes of the caller's and nothing in the library.  dev_sums is the resume call's plane, same layout and
+ *             rules: (sum.r, sum.g, sum.b, n) -- here n is THE PIXEL'S OWN count of sub-frames, and it is read.
+ *             dev_moments holds one f32 per pixel, q = the sum of the squared luminances of the pixel's sub-frames: row y
+ *             of frame i at (char*)dev_moments + i * moments_stride_bytes + (y - y0) * moments_pitch_bytes.  Its base is
+ *             4-byte aligned; the pitch is >= 4 W and a multiple of 4; the stride is a multiple of 4 and, with count > 1,
+ *             >= (y1 - y0) * moments_pitch_bytes.  Bytes of a row beyond 4 W are not touched.
+ *   rule      all in f32, without fma; tolerance * tolerance is one f32 multiply done on the host.
+ *                 Y(c)       = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b
+ *                 L = Y(sum);  d = n*q - L*L;  b = (tolerance*tolerance) * ((n*n) * (n - 1.0f))
+ *                 settled(p) = n >= float(min_samples)  &&  d <= b        (a NaN compares false: not settled)
+ *                 active(p)  = !settled(p)  &&  n + float(samples) <= 16777216.0f
+ *             i.e. "variance of the mean <= tolerance^2", multiplied out so that there is no divide.  With restart != 0
+ *             NEITHER PLANE IS READ, whatever they hold (NaNs included): every pixel is active with n = 0.  With
+ *             restart == 0 `active` is evaluated on the state the planes hold when the pass starts, with THIS call's rule:
+ *             a caller may tighten the tolerance between passes.  At tolerance 0 even identical samples need not settle:
+ *             n*q - L*L rounds.
+ *   pass      an active pixel folds all `samples` sub-frames in the contract's order, exactly as the resume call does: on
+ *             restart acc = c_0, then + c_s; otherwise acc = sum, then + c_0 ...; q folds the same way over Y(c_s)*Y(c_s);
+ *             its texel becomes (acc, n + float(samples)) and its moment the new q.  An inactive pixel's texel and moment
+ *             are NOT WRITTEN and none of its rays is marched.
+ *   picture   with dev_outs_rgba8 != NULL every pixel of the band receives encode(sum / n) of its state after the pass, an
+ *             inactive pixel from the texel as it stands.  NULL: the pass only advances the planes.
+ *   counts    dev_active_counts[i], when given, receives the number of pixels of rows [y0, y1) of frame i for which
+ *             `active` holds on the state AFTER the pass, with this call's rule and samples; the words are zeroed on the
+ *             stream first.  Zero: the frame is done.
+ *   identities (a) a restart pass with a picture writes the bytes of kifs_render_accumulate_jittered_async, and its sums
+ *             plane has the resume call's bits.  (b) With min_samples above every count reached, any sequence of passes
+ *             leaves the sums plane and the pictures of the same sequence of resume passes.  (c) With tolerance +inf every
+ *             pixel stops at the end of the first pass after which n >= min_samples.  (d) No state between passes: they
+ *             may come from other streams or contexts, ordered by the caller.
+ *   refusals  a refused call launches and writes nothing.  Everything kifs_render_accumulate_resume_async refuses, with
+ *             its status.  Then KIFS_ERR_BAD_ARG: a null or misaligned dev_moments, a bad moments pitch or stride; a null
+ *             rule; a NaN or negative tolerance (+inf is allowed); min_samples < 2 or > 2^24.  y1 == y0 returns KIFS_OK,
+ *             enqueues nothing and leaves the counts untouched. */
+typedef struct KifsConvergence {
+    float    tolerance;    /* standard error of the mean linear luminance at which a pixel stops; >= 0, not NaN, +inf allowed */
+    uint32_t min_samples;  /* a pixel holding fewer sub-frames than this never stops; >= 2 */
+} KifsConvergence;
+int kifs_render_accumulate_converge_async(kifs_ctx* ctx, void* hip_stream, int count, int samples,
+                                          const KifsCameraUniform* cameras, const KifsOptionsUniform* options,
+                                          int grid, const KifsSubpixel* cells,
+                                          float* dev_sums, size_t sums_pitch_bytes, size_t sums_stride_bytes,
+                                          float* dev_moments, size_t moments_pitch_bytes, size_t moments_stride_bytes,
+                                          int restart, const KifsConvergence* rule,
+                                          uint32_t* dev_active_counts /* may be NULL */,
+                                          uint8_t* const* dev_outs_rgba8 /* may be NULL */,
+                                          size_t pitch_bytes, int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -49,6 +49,10 @@ class KifsSubpixel(C.Structure):  # a cell of the g x g grid inside a pixel (kif
     _fields_ = [("i", C.c_uint8), ("j", C.c_uint8)]
 
 
+class KifsConvergence(C.Structure):  # the stopping rule of kifs_render_accumulate_converge_async
+    _fields_ = [("tolerance", C.c_float), ("min_samples", C.c_uint32)]
+
+
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -118,6 +122,10 @@ SIGNATURES = {
     "kifs_render_accumulate_resume_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
                                                       C.c_int, _P(KifsSubpixel), C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                                       _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_render_accumulate_converge_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, _P(CameraUniform), _P(OptionsUniform),
+                                                        C.c_int, _P(KifsSubpixel), C.c_void_p, C.c_size_t, C.c_size_t,
+                                                        C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _P(KifsConvergence),
+                                                        C.c_void_p, _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

@@ -22,6 +22,16 @@
 //                                      contract's order, stores the texel with one 16-byte store and, when the pass has
 //                                      destinations, encodes sum / float(total).  A texel is read and written by one
 //                                      lane of one workgroup.  The same body again.
+//   accum::converge_render_kernel<GROUP, PRIM>  one CONVERGING pass (kifs_render_accumulate_converge_async): the carried
+//                                      pass for the pixels whose mean has not settled.  The texel's w word is the pixel's
+//                                      own count n, a second plane holds q = the sum of its squared luminances, and a
+//                                      pixel is ACTIVE unless n q - L^2 <= tol^2 n^2 (n - 1) at n >= min_samples (L the
+//                                      luminance of the sum) or n could leave 2^24.  Every wave derives the block's
+//                                      64-bit active mask from the planes itself (the same memory; nobody writes before
+//                                      the resolve), a block without an active pixel leaves at once (wave 0 stays to
+//                                      encode when the pass has a picture), an inactive lane is marched as a lane
+//                                      beyond the frame's edge, and the resolve folds, stores and counts what is still
+//                                      active for the active lanes alone.  The same body once more.
 // Why not the supersampling kernel's shape (a lane marches all of its samples one after another): a launch is as long as
 // its longest rays, and that shape makes a lone frame's critical ray `samples` rays long.  Here the
 // sub-frames of a block run side by side on four waves, and the blocks of every output frame side by side on the device.
@@ -85,7 +95,104 @@ __device__ __forceinline__ uint32_t cell_of(const anim::SceneView* scenes, uint3
 // earlier passes left one (prior > 0), writes the texel back and encodes only for a pass with destinations.
 typedef float Texel __attribute__((ext_vector_type(4)));
 typedef const CarryParams __attribute__((address_space(4))) * ConstCarry;
-template <int GROUP, int PRIM, bool JITTER, bool CARRY = false>
+typedef const ConvergeParams __attribute__((address_space(4))) * ConstConverge;
+
+// The stopping rule of kifs_render_accumulate_converge_async, stated once for the device (include/kifs_hip.h; the NumPy
+// model is tests/converge_reference.py): all in f32, no fma (-ffp-contract=off), a NaN compares false.
+__device__ __forceinline__ float luminance(V3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+__device__ __forceinline__ bool is_active(float n, V3 sum, float q, float min_samples, float tol2, float samples) {
+    const float L = luminance(sum);
+    const float d = n * q - L * L;
+    const float b = tol2 * ((n * n) * (n - 1.0f));
+    const bool settled = (n >= min_samples) && (d <= b);
+    return !settled && (n + samples <= 16777216.0f);
+}
+
+// The resolve of a converging pass, wave 0 (the other waves leave behind the barrier).  The lane's texel and moment are
+// fetched as carry_render_kernel fetches its texel: after wave 0's last march, before the barrier, the wait behind it.
+// An active lane folds colours and squared luminances in the contract's order and stores both; every guarded lane
+// encodes its state as it stands after the pass; then the lanes still active under the same rule are counted, and one
+// lane adds the block's count to the frame's word -- only when it is not zero: the blocks that are all settled must not
+// queue up on one address.
+__device__ __forceinline__ void converge_resolve(ConstParams kp, float* s_srgb, const float* s_colour, int tid, uint32_t wave,
+                                                 uint32_t frame, uint32_t samples, int block_x, int tile_y, int frame_y,
+                                                 uint64_t mask) {
+    const ConstConverge K = (ConstConverge)kp;
+    const uint32_t restart = K->restart;  // launch-uniform
+    const uint32_t lane = uint32_t(tid) & 63u;
+    const int ly = int(lane >> 3);
+    const int x = block_x + int(lane & 7u), y = frame_y + ly;
+    Texel texel{0.0f, 0.0f, 0.0f, 0.0f};
+    float moment = 0.0f;
+    Texel* cell = nullptr;
+    float* word = nullptr;
+    if (wave == 0u) {
+        const FrameParams& C = reloaded(kp).B.frame;
+        if (x < C.width && y < C.y1) {
+            const size_t row = size_t(tile_y + ly);
+            cell = reinterpret_cast<Texel*>(K->sums) + size_t(frame) * K->sums_stride_texels + row * K->sums_pitch_texels + uint32_t(x);
+            word = K->moments + size_t(frame) * K->moments_stride_words + row * K->moments_pitch_words + uint32_t(x);
+            if (restart == 0u) {
+                texel = *cell;
+                moment = *word;
+            }
+        }
+    }
+    if (mask != 0u) {  // uniform over the workgroup: every wave derived the same mask
+        __syncthreads();  // every sub-frame's colours and s_srgb visible
+    } else {           // wave 0 alone, nothing marched: the rest of the encode table is its own to fill
+        const FrameParams& C = reloaded(kp).B.frame;
+        if (C.encode == 1)
+            for (uint32_t k = 64u; k < 256u; k += 64u) s_srgb[lane + k] = C.srgb_table[lane + k];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    // (the texel is first looked at here: the wait for the loads comes behind the barrier, not in front of it)
+    asm volatile("" : "+v"(texel), "+v"(moment));
+    if (wave != 0u) return;
+
+    V3 acc{texel.x, texel.y, texel.z};
+    float q = moment, n = texel.w;
+    if ((mask >> lane) & 1u) {
+        const float* at = s_colour + lane;
+        V3 c{at[0], at[64], at[128]};
+        float l = luminance(c);
+        if (restart != 0u) {  // acc = c_0 itself (no 0 + c_0: -0)
+            acc = c;
+            q = l * l;
+        } else {
+            acc = V3{acc.x + c.x, acc.y + c.y, acc.z + c.z};
+            q = q + l * l;
+        }
+        for (uint32_t s = 1; s < samples; ++s) {
+            at += SLOT;
+            c = V3{at[0], at[64], at[128]};
+            acc = V3{acc.x + c.x, acc.y + c.y, acc.z + c.z};
+            l = luminance(c);
+            q = q + l * l;
+        }
+        n = n + float(samples);  // exact: at most 2^24 (is_active)
+        *cell = Texel{acc.x, acc.y, acc.z, n};
+        *word = q;
+    }
+    if (K->counts) {  // launch-uniform
+        const bool still = cell && is_active(n, acc, q, float(K->min_samples), K->tol2, float(samples));
+        const uint64_t left = __ballot(still);
+        if (left != 0u && lane == 0u) atomicAdd(K->counts + frame, uint32_t(__popcll(left)));
+    }
+    if (K->picture == 0u) return;  // launch-uniform: the pass only advances the planes
+    const FrameParams& C = reloaded(kp).B.frame;
+    const uint32_t rgba = encode_rgba(V3{acc.x / n, acc.y / n, acc.z / n}, C.encode == 1, s_srgb);
+    if (cell) {
+        uint32_t* const out = batch_frame(reloaded(kp).B, frame * samples).out;
+        out[out_row(C, y, tile_y + ly) * C.pitch_words + uint32_t(x)] = rgba;
+    }
+}
+
+// CONVERGE: the kernel argument is a ConvergeParams whose first member is A.  `mask` holds the block's active lanes
+// across the marches (two SGPRs); the resolve is converge_resolve above.
+template <int GROUP, int PRIM, bool JITTER, bool CARRY = false, bool CONVERGE = false>
 __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, float* s_colour) {
     ConstParams kp = (ConstParams)__builtin_amdgcn_kernarg_segment_ptr();  // = &A
     int tid = threadIdx.x;
@@ -101,7 +208,31 @@ __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, floa
     const int tile_y = int(tile >> 16) * TILE_H;
     const int frame_y = tile_frame_row(A.B.frame, tile >> 16);
 
-    for (uint32_t s = wave; s < samples; s += WAVES) {  // scalar
+    // A converging pass: the block's active lanes, derived by every wave from the state the planes hold (nothing of this
+    // launch has written them: a texel belongs to one lane of one workgroup, whose stores come behind its barrier).
+    [[maybe_unused]] uint64_t mask = 0u;
+    if constexpr (CONVERGE) {
+        const ConstConverge K = (ConstConverge)kp;
+        const uint32_t lane = uint32_t(tid) & 63u;
+        const int ly = int(lane >> 3);
+        const int x = block_x + int(lane & 7u);
+        bool active = (x < A.B.frame.width) && (frame_y + ly < A.B.frame.y1);
+        if (K->restart == 0u) {  // launch-uniform: a scalar branch
+            bool unsettled = false;
+            if (active) {
+                const size_t row = size_t(tile_y + ly);
+                const Texel t = reinterpret_cast<const Texel*>(K->sums)[size_t(frame) * K->sums_stride_texels +
+                                                                        row * K->sums_pitch_texels + uint32_t(x)];
+                const float q = K->moments[size_t(frame) * K->moments_stride_words + row * K->moments_pitch_words + uint32_t(x)];
+                unsettled = is_active(t.w, V3{t.x, t.y, t.z}, q, float(K->min_samples), K->tol2, float(samples));
+            }
+            active = unsettled;
+        }
+        mask = __ballot(active);
+        if (mask == 0u && (K->picture == 0u || wave != 0u)) return;  // uniform, before any barrier: nothing to march
+    }
+
+    for (uint32_t s = wave; s < samples && (!CONVERGE || mask != 0u); s += WAVES) {  // scalar
         const Params& L = reloaded(kp);
         asm volatile("" : "+v"(tid));  // (and the lane's pixel from its number: one VGPR across the march, not four)
         const uint32_t lane = uint32_t(tid) & 63u;
@@ -109,7 +240,8 @@ __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, floa
         const uint32_t view = frame * samples + s;
         FrameParams P = batch_frame(L.B, view);
         overlay_scene(P, L.scenes, view);
-        const bool valid = (x < P.width) && (y < P.y1);
+        bool valid = (x < P.width) && (y < P.y1);
+        if constexpr (CONVERGE) valid = valid && ((mask >> lane) & 1u) != 0u;  // a settled pixel: a lane beyond the edge
         int px = x, py = y;  // the pixel the ray goes through: of the frame, or of the virtual screen
         if constexpr (JITTER) {
             const uint32_t cell = cell_of(L.scenes, view);  // wave-uniform
@@ -132,6 +264,10 @@ __device__ __forceinline__ void render_body(const Params& A, float* s_srgb, floa
     }
     // A resumed pass: wave 0's lanes fetch their pixels' texels now, behind the marches the other waves are still in --
     // eight lanes of a block row read 128 contiguous bytes -- under the guard of the store below.
+    if constexpr (CONVERGE) {
+        converge_resolve(kp, s_srgb, s_colour, tid, wave, frame, samples, block_x, tile_y, frame_y, mask);
+        return;
+    }
     [[maybe_unused]] Texel texel{0.0f, 0.0f, 0.0f, 0.0f};
     [[maybe_unused]] Texel* cell = nullptr;
     [[maybe_unused]] uint32_t prior = 0u;
@@ -208,9 +344,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     render_body<GROUP, PRIM, true, true>(K.A, s_srgb, s_colour);
 }
 
+// One converging pass: the planes and the rule in a ConvergeParams (kifs_params.hpp).
+template <int GROUP, int PRIM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void converge_render_kernel(const ConvergeParams K) {
+    __shared__ float s_srgb[256];
+    extern __shared__ float s_colour[];  // [samples][3][64]
+    render_body<GROUP, PRIM, true, false, true>(K.A, s_srgb, s_colour);
+}
+
 // From 63 sub-frames the dynamic LDS and the 1 KB sRGB table together pass the default limit of 48 KB: the kernel then opts
 // in, once per instantiation and device, as ensure_dynamic_lds does for the residency pad (kifs_render_common.hpp).
-enum Family { PLAIN, JITTERED, CARRIED };
+enum Family { PLAIN, JITTERED, CARRIED, CONVERGING };
 template <int GROUP, int PRIM, Family FAMILY>
 static hipError_t ensure_lds(unsigned dynamic_bytes) {
     if (dynamic_bytes + 256u * unsigned(sizeof(float)) <= 48u * 1024u) return hipSuccess;
@@ -218,7 +362,8 @@ static hipError_t ensure_lds(unsigned dynamic_bytes) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-        const void* const kernel = FAMILY == CARRIED    ? reinterpret_cast<const void*>(&carry_render_kernel<GROUP, PRIM>)
+        const void* const kernel = FAMILY == CONVERGING ? reinterpret_cast<const void*>(&converge_render_kernel<GROUP, PRIM>)
+                                   : FAMILY == CARRIED  ? reinterpret_cast<const void*>(&carry_render_kernel<GROUP, PRIM>)
                                    : FAMILY == JITTERED ? reinterpret_cast<const void*>(&jitter_render_kernel<GROUP, PRIM>)
                                                         : reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>);
         hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
@@ -249,6 +394,15 @@ static hipError_t launch_carry(const CarryParams& K, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <int GROUP, int PRIM>
+static hipError_t launch_converge(const ConvergeParams& K, hipStream_t stream) {
+    const unsigned lds = unsigned(K.A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
+    if (hipError_t e = ensure_lds<GROUP, PRIM, CONVERGING>(lds); e != hipSuccess) return e;
+    const dim3 grid(K.A.B.frame.tile_count * BLOCKS * uint32_t(K.A.frames));
+    hipLaunchKernelGGL((converge_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, K);
+    return hipGetLastError();
+}
+
 }  // namespace accum
 
 hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream) {
@@ -272,6 +426,19 @@ hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, 
         return hipErrorInvalidValue;  // (refused by the API before it gets here)
     return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
         return accum::launch_carry<decltype(g)::value, decltype(prim)::value>(K, stream);
+    });
+}
+
+hipError_t launch_accumulate_converge(const accum::ConvergeParams& K, uint32_t group, uint32_t primitive, hipStream_t stream) {
+    const accum::Params& A = K.A;
+    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
+    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
+    if (!K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
+        !K.moments || (reinterpret_cast<uintptr_t>(K.moments) & 3u) != 0 || K.moments_pitch_words < uint32_t(A.B.frame.width) ||
+        K.min_samples < 2u || K.min_samples > (1u << 24) || !(K.tol2 >= 0.0f))
+        return hipErrorInvalidValue;  // (refused by the API before it gets here)
+    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
+        return accum::launch_converge<decltype(g)::value, decltype(prim)::value>(K, stream);
     });
 }
 

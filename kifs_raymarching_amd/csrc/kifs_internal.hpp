@@ -27,6 +27,9 @@ hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint
 // One pass of a progressive frame (kifs_render_accumulate_resume_async; the host side is kifs_progressive.cpp): the same
 // launch with the resolve started from, and written back to, a plane of f32 sums (accum::carry_render_kernel).
 hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, uint32_t primitive, hipStream_t stream);
+// One converging pass (kifs_render_accumulate_converge_async; the host side is kifs_converge.cpp): the same launch again,
+// marching only the pixels whose mean has not settled (accum::converge_render_kernel).
+hipError_t launch_accumulate_converge(const accum::ConvergeParams& K, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

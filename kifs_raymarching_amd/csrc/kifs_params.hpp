@@ -190,6 +190,25 @@ struct CarryParams {
 };
 static_assert(sizeof(CarryParams) <= 4096, "the kernel argument is limited to 4 KB");
 
+// The argument of accum::converge_render_kernel (kifs_render_accumulate_converge_async): one pass that marches only the
+// pixels whose mean has not settled.  A first, as in CarryParams; the sums plane is the resume call's, with the texel's w
+// word the PIXEL'S OWN count, read here; the moments plane holds one f32 per pixel, the sum of the squared luminances of
+// the pixel's sub-frames -- row r of the band of output frame f at moments + f * moments_stride_words +
+// r * moments_pitch_words floats.
+struct ConvergeParams {
+    Params A;
+    float* sums;                                       // as CarryParams::sums
+    uint32_t sums_pitch_texels, sums_stride_texels;
+    float* moments;                                    // first row of frame 0's plane (device memory, 4-byte aligned)
+    uint32_t moments_pitch_words, moments_stride_words;
+    uint32_t restart;                                  // != 0: neither plane is read, every pixel is active with n = 0
+    uint32_t picture;                                  // 0: no destinations, the pass only advances the planes
+    uint32_t min_samples;                              // KifsConvergence::min_samples, 2..2^24
+    float tol2;                                        // tolerance * tolerance, one f32 multiply on the host
+    uint32_t* counts;                                  // null, or per output frame the pixels still active after the pass
+};
+static_assert(sizeof(ConvergeParams) <= 4096, "the kernel argument is limited to 4 KB");
+
 }  // namespace accum
 
 }  // namespace kifs

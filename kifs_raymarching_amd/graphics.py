@@ -617,6 +617,69 @@ class GraphicState:
                                                       encode), "render_accumulate_resume")
         return outs if picture else None
 
+    def render_accumulate_converge(self, sums, moments, cameras, samples, rule, restart: bool = False, counts=None,
+                                   options=None, outs=None, picture: bool = True, y0: int = 0, y1: int = None,
+                                   encode: int = ENCODE_SRGB, stream=None, jitter=None):
+        """One CONVERGING pass of a progressive frame (kifs_render_accumulate_converge_async): render_accumulate_resume's
+        pass for the pixels whose mean has not settled under rule = (tolerance, min_samples).  `sums` is that call's plane
+        with w the PIXEL'S OWN count; `moments` a contiguous float32 (count, rows, W) tensor, the sum of the squared
+        luminances of every pixel's sub-frames; restart=True reads neither (the first pass).  A settled pixel is neither
+        marched nor written; with `picture` every pixel is encoded from its state after the pass.  `counts`, an int32 or
+        uint32 (count,) tensor on the device, receives per frame the pixels still active after the pass (0: done).  The
+        library keeps no state.  Ordered after the producers of all four tensors -- torch's current stream -- and after
+        nothing else, as render_accumulate_resume."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        samples = int(samples)
+        cams = camera_array(cameras)
+        views = len(cams)
+        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
+            raise ValueError(f"render_accumulate_converge: 1..{MAX_ACCUMULATE} samples per frame and pass, count * samples "
+                             f"cameras, at most {MAX_BATCH} of them")
+        n = views // samples
+        tolerance, min_samples = float(rule[0]), int(rule[1])
+        if not tolerance >= 0.0 or not 2 <= min_samples <= _lib.MAX_PROGRESSIVE_SAMPLES:
+            raise ValueError(f"render_accumulate_converge: tolerance >= 0, min_samples within 2..{_lib.MAX_PROGRESSIVE_SAMPLES}")
+        opts = None if options is None else options_array(options)
+        if opts is not None and len(opts) != views:
+            raise ValueError(f"render_accumulate_converge: {len(opts)} option images for {views} cameras")
+        for name, plane, shape in (("sums", sums, (n, rows, w, 4)), ("moments", moments, (n, rows, w))):
+            if (not isinstance(plane, torch.Tensor) or tuple(plane.shape) != shape or plane.dtype != torch.float32
+                    or not plane.is_contiguous() or not plane.is_cuda):
+                raise ValueError(f"render_accumulate_converge: {name} float32 {shape}, contiguous, on the device")
+        if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (n,) or not counts.is_cuda
+                                   or counts.dtype not in (torch.int32, torch.uint32) or not counts.is_contiguous()):
+            raise ValueError(f"render_accumulate_converge: counts int32 ({n},), contiguous, on the device")
+        ptrs = None
+        if picture:
+            if outs is None:
+                outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
+                raise ValueError(f"render_accumulate_converge: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+            base, frame_bytes = _device_pointer(outs), rows * w * 4
+            ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+        grid, cells = (1, None) if jitter is None else jitter
+        if cells is not None and not isinstance(cells, C.Array):
+            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
+        if cells is not None and len(cells) != views:
+            raise ValueError(f"render_accumulate_converge: {len(cells)} cells for {views} cameras")
+        if cells is None and samples != int(grid) * int(grid):  # (the C call takes NULL only for the whole grid in order)
+            if int(grid) != 1:
+                raise ValueError("render_accumulate_converge: cells None needs samples == grid * grid")
+            cells = (KifsSubpixel * views)()  # the pixel centre: cell (0, 0) of the one-cell grid
+        stream = self._stream_handle(stream, "render_accumulate_converge")
+        for tensor in (sums, moments, counts, outs if picture else None):
+            if tensor is not None:
+                self._order_after_producer(tensor, stream)
+        c_rule = _lib.KifsConvergence(tolerance, min_samples)
+        check(lib.kifs_render_accumulate_converge_async(
+            self._ctx, stream, n, samples, cams, opts, int(grid), cells, _device_pointer(sums), w * 16, rows * w * 16,
+            _device_pointer(moments), w * 4, rows * w * 4, int(bool(restart)), C.byref(c_rule),
+            None if counts is None else _device_pointer(counts), ptrs, w * 4, y0, y1, encode), "render_accumulate_converge")
+        return outs if picture else None
+
     def render_shard_async(self, outs, cameras, stripes, in_place: bool = False, stream=None,
                            encode: int = ENCODE_SRGB, pitch_bytes: int = None):
         """render_batch_async for a row shard (kifs_render_shard_async): `stripes` is the list of
@@ -919,6 +982,52 @@ class Accumulator:
         """The linear HDR mean of every pixel, float32 (count, rows, W, 3): sums / total, as the plane describes itself.
         The caller synchronises first."""
         return self.sums[..., :3] / self.sums[..., 3:]
+
+
+class ConvergingAccumulator(Accumulator):
+    """An Accumulator with a stopping rule (GraphicState.render_accumulate_converge): beside the plane of sums it owns a
+    plane of second moments and a tensor of counts, add() marches only the pixels whose mean luminance has not settled to
+    a standard error of `tolerance` (never before `min_samples` sub-frames), and active() tells how many are left.  The
+    first pass after reset() restarts the planes.  `total` stays the number of sub-frames OFFERED to every pixel; what a
+    pixel took is samples_per_pixel().  (A class of its own: Accumulator's constructor and passes stay as they are.)"""
+
+    def __init__(self, state, count: int = 1, y0: int = 0, y1: int = None, tolerance: float = 1.0 / 256.0, min_samples: int = 16):
+        import torch
+        super().__init__(state, count, y0, y1)
+        self.tolerance, self.min_samples = float(tolerance), int(min_samples)
+        self.moments = torch.zeros(tuple(self.sums.shape[:3]), dtype=torch.float32, device=self.sums.device)
+        self.counts = torch.zeros((self.count,), dtype=torch.int32, device=self.sums.device)
+
+    def add(self, cameras, samples, options=None, outs=None, picture: bool = True, encode: int = ENCODE_SRGB, stream=None,
+            jitter=None):
+        """Accumulator.add with the rule: one converging pass, ordered after the previous one as there."""
+        if len(camera_array(cameras)) != self.count * int(samples):
+            raise ValueError(f"ConvergingAccumulator.add: {self.count} x {samples} cameras")
+        handle = getattr(stream, "cuda_stream", stream) or None  # None: the context's own stream
+        if self._last_stream is not _NO_PASS and handle != self._last_stream:
+            if self._last_stream is None:
+                self.state.synchronize()
+            else:
+                self.state.order_after(handle, self._last_stream)
+        frames = self.state.render_accumulate_converge(self.sums, self.moments, cameras, samples, (self.tolerance, self.min_samples),
+                                                       restart=self.total == 0, counts=self.counts, options=options, outs=outs,
+                                                       picture=picture, y0=self.y0, y1=self.y1, encode=encode, stream=stream,
+                                                       jitter=jitter)
+        self.total += int(samples)
+        self._last_stream = handle
+        return frames
+
+    def active(self):
+        """Per frame the pixels still active after the last pass, as a list of ints (0: the frame is done).  Waits for
+        the context's launches and the device first."""
+        import torch
+        self.state.synchronize()
+        torch.cuda.synchronize(self.sums.device)
+        return [int(v) for v in self.counts.cpu().tolist()]
+
+    def samples_per_pixel(self):
+        """float32 (count, rows, W): the sub-frames every pixel holds, the plane's w.  The caller synchronises first."""
+        return self.sums[..., 3]
 
 
 class MultiGraphicState:

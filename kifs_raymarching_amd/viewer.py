@@ -168,9 +168,14 @@ class ViewerSession:
     (graphics.Accumulator over the renderer; pass p takes configs.jitter_cells(grid, samples, frame=p * samples) with the
     renderer's camera) and presents the refined frame, until `max_passes` passes are in it; any input resets the
     accumulator.  `accumulator`: an object with add(cameras, samples, jitter=) -> (1, H, W, 4) frames, reset() and
-    `total` to use instead.  refine=None: no accumulator, redraw() draws only when something changed."""
+    `total` to use instead.  refine=None: no accumulator, redraw() draws only when something changed.
 
-    def __init__(self, renderer, sinks=(), refine=None, accumulator=None):
+    `tolerance` (with refine) adds a stopping rule: the accumulator is a graphics.ConvergingAccumulator (min_samples =
+    `min_samples`, default two passes' worth), a pass marches only the pixels whose mean luminance has not settled to that
+    standard error, and the idle redraws stop as soon as no pixel is left -- accumulator.active() all zero -- or at
+    `max_passes`, whichever comes first.  tolerance=None: the session above, unchanged."""
+
+    def __init__(self, renderer, sinks=(), refine=None, accumulator=None, tolerance=None, min_samples=None):
         self.renderer = renderer
         self.sinks = list(sinks)
         if refine is not None:
@@ -179,6 +184,11 @@ class ViewerSession:
                 raise ValueError("ViewerSession: refine = (grid, samples per pass <= grid^2, passes)")
             refine = (grid, samples, passes)
         self.refine = refine
+        if tolerance is not None and refine is None:
+            raise ValueError("ViewerSession: tolerance goes with refine")
+        self.tolerance = None if tolerance is None else float(tolerance)
+        self.min_samples = None if tolerance is None else int(min_samples) if min_samples is not None else max(2, 2 * refine[1])
+        self.converged = False
         self.accumulator = accumulator
         self.passes_added = 0
         self.frames_presented = 0
@@ -226,7 +236,7 @@ class ViewerSession:
         """Renders and presents if anything changed since the last redraw."""
         with self._lock:
             if not self._dirty:
-                if self.refine is None or self.passes_added >= self.refine[2]:
+                if self.refine is None or self.passes_added >= self.refine[2] or self.converged:
                     return False
                 t0 = time.perf_counter()
                 frame = self._refine_pass()
@@ -245,6 +255,7 @@ class ViewerSession:
 
     def _reset_refinement(self):
         self.passes_added = 0
+        self.converged = False
         if self.accumulator is not None:
             self.accumulator.reset()
 
@@ -253,13 +264,16 @@ class ViewerSession:
         from .configs import jitter_cells
         grid, samples, _ = self.refine
         if self.accumulator is None:
-            from .graphics import Accumulator
-            self.accumulator = Accumulator(self.renderer)
+            from .graphics import Accumulator, ConvergingAccumulator
+            self.accumulator = (Accumulator(self.renderer) if self.tolerance is None else
+                                ConvergingAccumulator(self.renderer, tolerance=self.tolerance, min_samples=self.min_samples))
         cells = jitter_cells(grid, samples, frame=self.passes_added * samples)
         frames = self.accumulator.add([self.renderer.camera_data] * samples, samples, jitter=(grid, cells))
         self.passes_added += 1
         if hasattr(self.renderer, "synchronize"):
             self.renderer.synchronize()
+        if self.tolerance is not None:
+            self.converged = not any(self.accumulator.active())
         frame = frames[0]
         return frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)
 

@@ -70,7 +70,14 @@ ap.add_argument("--spp", type=int, default=None, metavar="N",
                      "instead of --samples S / --motion-blur S -- progressive accumulation "
                      "(kifs_render_accumulate_resume_async): passes of at most 64 (with --jitter G: at most G x G) carry the "
                      "frame's linear sums, only the last one encodes; N may be far above 64")
+ap.add_argument("--tolerance", type=float, default=None, metavar="T",
+                help="with --spp N: stop sampling the pixels whose mean luminance has settled to a standard error of T "
+                     "(kifs_render_accumulate_converge_async) and stop the passes once none is left; N stays the cap")
+ap.add_argument("--min-samples", type=int, default=16, metavar="M",
+                help="with --tolerance: a pixel holding fewer than M sub-frames never stops (at least 2)")
 args = ap.parse_args()
+if args.tolerance is not None and (args.spp is None or not args.tolerance >= 0.0 or not 2 <= args.min_samples <= 1 << 24):
+    ap.error("--tolerance T >= 0 goes with --spp, --min-samples M within 2..16777216")
 dof = None
 if args.dof is not None:
     try:
@@ -176,18 +183,31 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                     cams.append([c.into_buffer_data() for c in shutter_cameras(w, k, N, args.shutter)])
             if morph:
                 opts = [guis[k * N:(k + 1) * N] for k in part]
-            acc = K.Accumulator(gs, count=len(part))
-            done = 0
+            converging = args.tolerance is not None
+            acc = (K.ConvergingAccumulator(gs, count=len(part), tolerance=args.tolerance, min_samples=args.min_samples) if converging
+                   else K.Accumulator(gs, count=len(part)))
+            done, frames, passes_run = 0, None, 0
             for p, S in enumerate(splits):
                 jitter = None if not G else (G, [c for k in part for c in jitter_cells(G, S, (k or 0) + done)])
+                # (a converging run does not know its last pass beforehand: every pass encodes, into the same frames)
                 frames = acc.add([cams[f][done + s] for f in range(len(part)) for s in range(S)], S,
                                  options=None if opts is None else [opts[f][done + s] for f in range(len(part)) for s in range(S)],
-                                 picture=p == len(splits) - 1, jitter=jitter)
+                                 picture=converging or p == len(splits) - 1, jitter=jitter, outs=frames)
                 done += S
+                passes_run += 1
+                if converging and not any(acc.active()):
+                    break
             gs.synchronize()
+            if converging:
+                rays = acc.samples_per_pixel().mean(dim=(1, 2)).cpu().tolist()
             for k, frame in zip(part, frames.cpu().numpy()):
                 path = str(out.with_name(f"{out.stem}_{k:03d}{out.suffix}")) if morph else args.out if k is None else args.out % k
                 write_png(path, frame)
+                if converging:
+                    print(f"{path}: {screen.width}x{screen.height}, tolerance {args.tolerance:g}: {passes_run} of {len(splits)} passes run"
+                          f"{' (stopped early)' if passes_run < len(splits) else ''}, {rays[part.index(k)]:.2f} rays per pixel on average "
+                          f"of at most {N}" + (f", jittered over a {G}x{G} grid" if G else ""))
+                    continue
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {N} sub-frames in {len(splits)} passes"
                       + (f", jittered over a {G}x{G} grid" if G else ""))
     elif morph_to is not None and args.motion_blur:

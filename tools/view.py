@@ -3,6 +3,7 @@
 drives the camera as the reference's window does (drag = rotate, wheel = zoom).
 
     python tools/view.py [workload] [--port 8080] [--host 127.0.0.1] [--seconds S] [--png-dir DIR] [--refine G,S,P]
+                         [--tolerance T]
 
 --refine G,S,P: while nothing moves, every idle redraw adds a pass of S jittered rays per pixel (cells of a G x G grid) to
 the frame's linear sums and presents the refined picture, up to P passes; any input starts over.
@@ -23,7 +24,12 @@ def main():
     ap.add_argument("--png-dir", default=None, help="also keep every presented frame as a PNG here")
     ap.add_argument("--refine", default=None, metavar="G,S,P",
                     help="refine the still picture: grid, jittered samples per pass (<= G*G, <= 64), passes")
+    ap.add_argument("--tolerance", type=float, default=None, metavar="T",
+                    help="with --refine: a pass marches only the pixels whose mean luminance has not settled to a standard "
+                         "error of T, and the refinement stops once none is left (or at P passes)")
     args = ap.parse_args()
+    if args.tolerance is not None and (not args.refine or not args.tolerance >= 0.0):
+        ap.error("--tolerance T >= 0 goes with --refine")
     refine = None
     if args.refine:
         try:
@@ -37,7 +43,7 @@ def main():
     w = WORKLOADS[args.workload]
     with K.GraphicState(0, screen_data=w.screen, camera_data=w.camera, gui_data=w.gui) as gs:
         gs.set_iters(*w.iters)
-        session = ViewerSession(gs, refine=refine)
+        session = ViewerSession(gs, refine=refine, tolerance=args.tolerance)
         http = HttpSink(args.host, args.port, on_input=session.handle)
         session.sinks.append(http)
         if args.png_dir:
