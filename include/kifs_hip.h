@@ -491,6 +491,46 @@ int kifs_render_accumulate_converge_async(kifs_ctx* ctx, void* hip_stream, int c
                                           uint8_t* const* dev_outs_rgba8 /* may be NULL */,
                                           size_t pitch_bytes, int y0, int y1, int encode);
 
+/* ---- extension: ray queries -- trace caller-supplied rays to hit, normal and colour ---------------
+ * NOT part of the reference, whose every ray is a pixel of its pinhole camera (entry.wgsl:49-59).  Every other entry
+ * point shades the rays of that camera model; this one takes the RAYS: picking and autofocus (what does this pixel hit,
+ * and how far away), collision probes along a path, secondary rays from a hit point, and cameras the library does not
+ * model (an equirectangular panorama, a fisheye, an orthographic view) are each just another set of rays.
+ *   rays      n records of 32 bytes in device memory, 16-byte aligned; the two reserved words are not read.
+ *   march     ray k is marched exactly as entry.wgsl:11-25 marches a pixel's ray, in the contract's arithmetic, with the
+ *             record's origin and direction in the camera's place: t = 0, p = origin; while i < max_iterations and
+ *             t < max_distance: d = scene_SDF(p); d < epsilon: the ray hits and the loop breaks with i un-incremented;
+ *             otherwise t = t + d and p = fma(t, direction, origin) per component.
+ *   direction used as given, NOT normalised: t is in units of its length.  A zero direction is a ray that stands still.
+ *   state     the scene is the context's options, iteration counts and extensions at the call.  The screen, the camera
+ *             and the supersampling factor are not read: the call works on a context that never had kifs_set_screen or
+ *             kifs_set_camera called, and at any supersampling factor.
+ *   texel     dev_geometry[4 k ..]: (n.x, n.y, n.z, t) on a hit -- n the vector get_normal returned at the tested
+ *             position, t the parameter at the break -- and (0, 0, 0, +inf), bit pattern 0, 0, 0, 0x7f800000, on a miss:
+ *             the words of kifs_render_geometry_async's texel.
+ *   colour    dev_rgba8[4 k ..]: the pixel the same ray would have produced in a frame -- the shading of
+ *             entry.wgsl:16-19 encoded with `encode`, alpha 255; the heatmap colour from i; the soft-shadow secondary
+ *             march from the hit when the extension is on; the background on a miss.
+ *   outputs   either may be NULL, not both.  The bytes of the one that is given do not depend on whether the other is.
+ *             Exactly 16 n and 4 n bytes are written.  dev_geometry is 16-byte aligned, dev_rgba8 4-byte aligned.
+ *   non-finite  a ray with a NaN or an infinity among its six components gets unspecified words in its own two slots; it
+ *             cannot affect another ray and cannot run longer than max_iterations steps.
+ *   refusals  a refused call launches nothing and writes nothing.  KIFS_ERR_BAD_ARG: n < 0 or n > KIFS_MAX_RAYS; a NULL or
+ *             misaligned dev_rays; a misaligned output; both outputs NULL; a bad encode.  KIFS_ERR_UNCONFIGURED: options
+ *             never set.  n == 0 (with otherwise good arguments) returns KIFS_OK and enqueues nothing.
+ *   ordering  enqueued on hip_stream (NULL: the context's own) as the other async calls: kifs_order_after applies.
+ *   launch    not a render launch: it neither records tile costs nor advances the tile order, leaves
+ *             kifs_debug_last_kernel and kifs_debug_last_round_steps as they were and touches no profiling record.
+ * Every word equals the CPU restatement of the contract bit for bit (tests/ray_reference.c). */
+typedef struct KifsRay {          /* 32 bytes, 16-byte aligned */
+    float origin[3];    float reserved0;   /* reserved words are not read */
+    float direction[3]; float reserved1;
+} KifsRay;
+#define KIFS_MAX_RAYS (1 << 28)
+int kifs_trace_rays_async(kifs_ctx* ctx, void* hip_stream, const KifsRay* dev_rays, int n,
+                          float* dev_geometry /* n texels of 16 B, or NULL */,
+                          uint8_t* dev_rgba8  /* n pixels of 4 B, or NULL */, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -53,6 +53,11 @@ class KifsConvergence(C.Structure):  # the stopping rule of kifs_render_accumula
     _fields_ = [("tolerance", C.c_float), ("min_samples", C.c_uint32)]
 
 
+class KifsRay(C.Structure):  # a caller-supplied ray of kifs_trace_rays_async: two 16-byte rows
+    _fields_ = [("origin", C.c_float * 3), ("reserved0", C.c_float), ("direction", C.c_float * 3), ("reserved1", C.c_float)]
+
+
+MAX_RAYS = 1 << 28  # KIFS_MAX_RAYS
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -126,6 +131,7 @@ SIGNATURES = {
                                                         C.c_int, _P(KifsSubpixel), C.c_void_p, C.c_size_t, C.c_size_t,
                                                         C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _P(KifsConvergence),
                                                         C.c_void_p, _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_trace_rays_async": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

@@ -228,3 +228,66 @@ def jitter_cells(g: int, samples: int, frame: int = 0) -> list:
         raise ValueError(f"jitter_cells: at most {n} distinct cells in a {g} x {g} grid, {samples} asked for")
     a = jitter_stride(g)
     return [((((s + frame) * a) % n) % g, (((s + frame) * a) % n) // g) for s in range(samples)]
+
+
+# ---- rays for GraphicState.trace_rays (kifs_trace_rays_async) ------------------------------------------------------
+def _fma32(a, b, c):
+    """fma(a, b, c) of float32 arrays, correctly rounded, for ordinary magnitudes: the product is exact in f64, the sum is
+    rounded to odd there (its rounding error from the two-sum), and 53 bits rounded to odd round to 24 as the exact value."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = np.asarray(c, dtype=np.float64)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)                      # exact: p + c = s + err
+    bits = s.view(np.int64).copy()
+    inexact = err != 0.0
+    towards_zero = inexact & ((err < 0.0) == (s > 0.0))  # the exact value lies between s and zero: truncate
+    bits -= towards_zero.astype(np.int64)                # (sign-magnitude: one less is one step towards zero)
+    bits |= inexact.astype(np.int64)
+    return bits.view(np.float64).astype(np.float32)
+
+
+def pixel_rays(screen, camera) -> np.ndarray:
+    """The (H * W, 8) float32 rays of a frame in KifsRay layout, row by row: the origin is the camera's and the direction
+    of pixel (x, y) is, bit for bit, ray_direction of kifs_scene.hpp (entry.wgsl:49-59) -- the same f32 operations in
+    the same order: px = x + 0.5, uv.x = (2 px) / height - aspect, uv.y = (2 py) / height - 1 (divisions by the height,
+    no reciprocal), d = (uv.x m1 - uv.y m2) - m0 per component, l = sqrt(fma(d.z, d.z, fma(d.y, d.y, d.x d.x))), d / l.
+    `screen`: ScreenData or a ScreenUniform image; `camera`: CameraData or a CameraUniform image (a raw one may be
+    sheared, as lens_cameras' are)."""
+    f32 = np.float32
+    s = screen.into_buffer_data() if hasattr(screen, "into_buffer_data") else screen
+    c = camera.into_buffer_data() if hasattr(camera, "into_buffer_data") else camera
+    w, h = int(s.width), int(s.height)
+    height, aspect = f32(s.height), f32(s.aspect_ratio)
+    o = np.array(c.origin[:], dtype=f32)
+    m0, m1, m2 = (np.array(c.matrix[k][:3], dtype=f32) for k in range(3))
+    px = np.arange(w, dtype=f32) + f32(0.5)
+    py = np.arange(h, dtype=f32) + f32(0.5)
+    uvx = np.broadcast_to(((f32(2.0) * px) / height - aspect)[None, :], (h, w))
+    uvy = np.broadcast_to(((f32(2.0) * py) / height - f32(1.0))[:, None], (h, w))
+    d = [(uvx * m1[k] - uvy * m2[k]) - m0[k] for k in range(3)]
+    length = np.sqrt(_fma32(d[2], d[2], _fma32(d[1], d[1], d[0] * d[0])))
+    rays = np.zeros((h * w, 8), dtype=f32)
+    rays[:, 0:3] = o
+    for k in range(3):
+        rays[:, 4 + k] = (d[k] / length).reshape(-1)
+    return rays
+
+
+def panorama_rays(origin, width: int, height: int) -> np.ndarray:
+    """The (height * width, 8) float32 rays of an equirectangular picture seen from `origin`, row by row: longitude runs
+    over the columns and latitude over the rows, z is up (the axis the orbit camera turns about).  Pixel (i, j) looks along
+        lon = 2 pi (i + 0.5) / width - pi,   lat = pi / 2 - pi (j + 0.5) / height,
+        d = (cos lat cos lon, cos lat sin lon, sin lat),
+    computed in f64 and rounded to f32 (unit to rounding).  Data, not contract: any set of rays is as good."""
+    if width < 1 or height < 1:
+        raise ValueError("panorama_rays: at least one column and one row")
+    lon = 2.0 * math.pi * (np.arange(width, dtype=np.float64) + 0.5) / width - math.pi
+    lat = math.pi / 2.0 - math.pi * (np.arange(height, dtype=np.float64) + 0.5) / height
+    cl = np.cos(lat)[:, None]
+    rays = np.zeros((height * width, 8), dtype=np.float32)
+    rays[:, 0:3] = np.asarray(origin, dtype=np.float32)
+    rays[:, 4] = (cl * np.cos(lon)[None, :]).reshape(-1)
+    rays[:, 5] = (cl * np.sin(lon)[None, :]).reshape(-1)
+    rays[:, 6] = np.broadcast_to(np.sin(lat)[:, None], (height, width)).reshape(-1)
+    return rays

@@ -30,6 +30,9 @@ hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, 
 // One converging pass (kifs_render_accumulate_converge_async; the host side is kifs_converge.cpp): the same launch again,
 // marching only the pixels whose mean has not settled (accum::converge_render_kernel).
 hipError_t launch_accumulate_converge(const accum::ConvergeParams& K, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Ray queries (kifs_trace_rays_async; kifs_rays_kernels.hip, the host side is kifs_rays.cpp): one caller-supplied ray per
+// lane, ceil(n / 256) workgroups (rays::trace_render_kernel).
+hipError_t launch_trace_rays(const rays::Params& R, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

@@ -211,4 +211,23 @@ static_assert(sizeof(ConvergeParams) <= 4096, "the kernel argument is limited to
 
 }  // namespace accum
 
+namespace rays {
+
+// The argument of rays::trace_render_kernel (kifs_trace_rays_async, kifs_rays_kernels.hip): the scene's frame constants
+// -- nothing of a screen or a camera is read: the origin is the lane's -- and the caller's arrays.  Ray k is the two
+// 16-byte rows (origin, -), (direction, -) at rays + 8 k floats.
+struct Params {
+    FrameParams frame;
+    const float* rays;   // n records of 32 bytes (device memory, 16-byte aligned)
+    int n;               // 1..KIFS_MAX_RAYS
+    float* geom;         // null, or n texels of 16 bytes (16-byte aligned)
+    uint32_t* rgba;      // null, or n pixels
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+// The launch's grid: one ray per lane, 256 lanes per workgroup (n up to KIFS_MAX_RAYS = 2^28: 2^20 workgroups).
+constexpr uint32_t RAYS_PER_WORKGROUP = 256;
+constexpr uint32_t workgroups(int n) { return n > 0 ? (uint32_t(n) + RAYS_PER_WORKGROUP - 1u) / RAYS_PER_WORKGROUP : 0u; }
+
+}  // namespace rays
+
 }  // namespace kifs

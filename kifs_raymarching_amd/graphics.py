@@ -426,6 +426,48 @@ class GraphicState:
             torch.cuda.synchronize(colour.device)
         return colour[0], geometry[0]
 
+    # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
+    def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):
+        """Trace n rays of the caller's own through the context's scene (options, iteration counts, extensions; the
+        screen, the camera and the supersampling factor are not read).  `rays`: an (n, 8) float32 torch tensor on this
+        context's device in KifsRay layout -- (origin.xyz, -, direction.xyz, -), the two reserved words are not read -- or
+        a pair (origins, directions) of (n, 3) arrays or tensors, which is packed here.  A direction is used as given,
+        not normalised: t is in units of its length.  Returns (geometry, rgba): an (n, 4) float32 tensor of texels
+        (n.x, n.y, n.z, t), (0, 0, 0, +inf) on a miss, and an (n, 4) uint8 tensor of the pixels the rays would have
+        produced in a frame; None for the one not asked for.  Enqueued on `stream` like render_async (the launch is
+        ordered after torch's current stream, where the rays were produced); the caller synchronises before reading."""
+        import torch
+        if not colours and not geometry:
+            raise ValueError("trace_rays: colours, geometry or both")
+        dev = torch.device("cuda", self.device)
+        if isinstance(rays, (tuple, list)):
+            if len(rays) != 2:
+                raise ValueError("trace_rays: a packed (n, 8) tensor or an (origins, directions) pair")
+            o, d = (torch.as_tensor(np.asarray(v, dtype=np.float32) if not torch.is_tensor(v) else v).to(dev, torch.float32)
+                    for v in rays)
+            if o.dim() != 2 or o.shape[1] != 3 or tuple(d.shape) != tuple(o.shape):
+                raise ValueError("trace_rays: origins and directions are both (n, 3)")
+            packed = torch.zeros((o.shape[0], 8), dtype=torch.float32, device=dev)
+            packed[:, 0:3] = o
+            packed[:, 4:7] = d
+            rays = packed
+        if (not getattr(rays, "is_cuda", False) or rays.device != dev or rays.dtype != torch.float32 or rays.dim() != 2
+                or rays.shape[1] != 8 or not rays.is_contiguous()):
+            raise ValueError(f"trace_rays: rays is a contiguous (n, 8) float32 tensor on {dev}")
+        n = int(rays.shape[0])
+        if n > _lib.MAX_RAYS:
+            raise ValueError(f"trace_rays: at most {_lib.MAX_RAYS} rays per call")
+        geom = torch.empty((n, 4), dtype=torch.float32, device=dev) if geometry else None
+        rgba = torch.empty((n, 4), dtype=torch.uint8, device=dev) if colours else None
+        if n == 0:
+            return geom, rgba
+        stream = self._stream_handle(stream, "trace_rays")
+        self._order_after_producer(rays, stream)
+        check(lib.kifs_trace_rays_async(self._ctx, stream, _device_pointer(rays), n,
+                                        _device_pointer(geom) if geometry else None,
+                                        _device_pointer(rgba) if colours else None, encode), "trace_rays")
+        return geom, rgba
+
     # ---- adaptive anti-aliasing (kifs_render_adaptive_async): the k x k resolve for the edge pixels only
     def render_adaptive_batch(self, cameras=None, k: int = 2, normal_cos: float = 0.9, depth_rel: float = 0.05, stream=None,
                               encode: int = ENCODE_SRGB, colour=None, edge_counts=None):

@@ -14,6 +14,8 @@
     python tools/render.py cfg2_julia_1080p out.png --morph-to 0.3,0.5,-0.2,0.1 --frames 48 --aa 2           # an anti-aliased morph
     python tools/render.py cfg2_julia_1080p out.png --dof 0.05,3.2 --spp 400 --jitter 8        # a lens at print quality: 7 passes
     python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --spp 150   # 64 + 64 + 22 sub-frames
+    python tools/render.py cfg2_julia_1080p pano.png --panorama 0,0,2.5                        # 360 degrees from a point
+    python tools/render.py cfg2_julia_1080p out.png --dof 0.05 --focus-at 960,540 --samples 32 # focus on what that pixel hits
 """
 import argparse
 import sys
@@ -21,8 +23,8 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
-from kifs_raymarching_amd.configs import (WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, pass_splits,  # noqa: E402
-                                          shutter_cameras)
+from kifs_raymarching_amd.configs import (WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, panorama_rays,  # noqa: E402
+                                          pass_splits, pixel_rays, shutter_cameras)
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -75,7 +77,32 @@ ap.add_argument("--tolerance", type=float, default=None, metavar="T",
                      "(kifs_render_accumulate_converge_async) and stop the passes once none is left; N stays the cap")
 ap.add_argument("--min-samples", type=int, default=16, metavar="M",
                 help="with --tolerance: a pixel holding fewer than M sub-frames never stops (at least 2)")
+ap.add_argument("--panorama", metavar="X,Y,Z", default=None,
+                help="the equirectangular picture of the scene from the point X,Y,Z (kifs_trace_rays_async over "
+                     "configs.panorama_rays): as wide as the workload's frame and half as high; on its own")
+ap.add_argument("--focus-at", metavar="X,Y", default=None,
+                help="with --dof APERTURE (no FOCUS): focus on what pixel X,Y of the frame shows -- its ray is traced "
+                     "(kifs_trace_rays_async) and the focus distance is t * dot(dir, -m0), which is printed; a pixel that "
+                     "shows the background ends the run with status 1; one frame, not with --frames")
 args = ap.parse_args()
+def _numbers(text, count):
+    try:
+        v = tuple(float(x) for x in text.split(","))
+    except ValueError:
+        v = ()
+    return v if len(v) == count else None
+panorama = None
+if args.panorama is not None:
+    panorama = _numbers(args.panorama, 3)
+    others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at)
+    if panorama is None or args.aa != 1 or args.aa_adaptive or args.motion_blur or args.jitter or any(o is not None for o in others):
+        ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply)")
+focus_at = None
+if args.focus_at is not None:
+    focus_at = _numbers(args.focus_at, 2)
+    if focus_at is None or args.dof is None or args.frames is not None or any(v < 0 or v != int(v) for v in focus_at):
+        ap.error("--focus-at takes a pixel X,Y and goes with --dof APERTURE, without --frames")
+    args.dof = args.dof + ",1"  # (the focus distance is traced below)
 if args.tolerance is not None and (args.spp is None or not args.tolerance >= 0.0 or not 2 <= args.min_samples <= 1 << 24):
     ap.error("--tolerance T >= 0 goes with --spp, --min-samples M within 2..16777216")
 dof = None
@@ -136,8 +163,36 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
     if w.extensions:
         gs.set_extensions(**w.extensions)
     gs.set_supersampling(1 if aa_grid else args.aa)
+    if focus_at is not None:
+        import numpy as np
+        x, y = int(focus_at[0]), int(focus_at[1])
+        if x >= screen.width or y >= screen.height:
+            sys.exit(f"--focus-at {x},{y}: outside the {screen.width}x{screen.height} frame")
+        ray = pixel_rays(screen, w.camera)[y * screen.width + x]
+        geometry, _ = gs.trace_rays((ray[None, 0:3], ray[None, 4:7]), colours=False)
+        gs.synchronize()
+        t = geometry.cpu().numpy()[0, 3]
+        if not np.isfinite(t):
+            print(f"--focus-at {x},{y}: the pixel's ray misses the scene, nothing to focus on")
+            sys.exit(1)
+        m0 = np.array(w.camera.into_buffer_data().matrix[0][:3], dtype=np.float32)
+        d = ray[4:7]
+        focus = t * ((d[0] * -m0[0] + d[1] * -m0[1]) + d[2] * -m0[2])  # f32: the hit's distance along the view axis
+        print(f"--focus-at {x},{y}: hit at t = {float(t):.6g}, focus distance {float(focus):.6g}")
+        if not focus > 0.0:
+            sys.exit(1)
+        dof = (dof[0], float(focus))
     jitter_of = lambda frames, S: None if not args.jitter else (args.jitter, [c for k in frames for c in jitter_cells(args.jitter, S, k or 0)])
-    if args.geometry:
+    if panorama is not None:
+        pw, ph = screen.width, max(1, screen.width // 2)
+        import torch
+        rays = torch.from_numpy(panorama_rays(panorama, pw, ph)).to(f"cuda:{gs.device}")
+        geometry, rgba = gs.trace_rays(rays)
+        gs.synchronize()
+        write_png(args.out, rgba.cpu().numpy().reshape(ph, pw, 4))
+        hit = torch.isfinite(geometry[:, 3])
+        print(f"{args.out}: {pw}x{ph} equirectangular from {panorama}, {int(hit.sum())} rays hit")
+    elif args.geometry:
         import numpy as np
         colour, geometry = gs.render_geometry()
         rgba, geometry = colour.cpu().numpy(), geometry.cpu().numpy()
