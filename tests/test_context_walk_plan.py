@@ -8,8 +8,13 @@ on a caller's stream; a slot of the scene-table ring passing between an animated
 view-table slot passing between "accumulate66" and one of the two older users, besides the passage between batch and
 animation.  Since progressive accumulation joined ("progressive", "progressive_jitter": two passes each, every pass a
 user of the scene ring): neither while supersampling is on; at least one of them on a caller's stream; a scene-table slot
-passing between a pass and an animated launch, and one passing between a pass and an accumulated launch.  A seed that
-falls short is replaced in context_walk.SEEDS; the condition stays."""
+passing between a pass and an animated launch, and one passing between a pass and an accumulated launch.  Since
+converging accumulation and ray queries joined ("converge": two passes, "settle": three, every pass a user of the scene
+ring under the entry point "converge"; "trace": no table and no ring): neither converging kind while supersampling is on
+and at least one trace while it is 2; at least one of the converging kinds and at least one trace on a caller's stream; a
+scene-table slot passing between a converging pass and an animated launch, and one passing between a converging pass and
+an accumulated launch or a progressive pass.  A seed that falls short is replaced in context_walk.SEEDS; the condition
+stays."""
 import numpy as np
 import pytest
 
@@ -39,11 +44,19 @@ def test_walk_covers_the_context_state(seed):
     scene_users = [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.ANIMATED or kind in W.ACCUMULATED or kind in W.PROGRESSIVE]
     assert frozenset(("progressive", "animation")) in cov["scene_ring_passages"], scene_users
     assert frozenset(("progressive", "accumulate")) in cov["scene_ring_passages"], scene_users
+    assert not any(kind in W.CONVERGING and ss > 1 for kind, ss in _supersampling_at(ops))
+    assert any(kind == "trace" and ss == 2 for kind, ss in _supersampling_at(ops))
+    assert caller["converge"] + caller["settle"] >= 1 and caller["trace"] >= 1, caller
+    scene_users = [(i, kind) for i, (kind, _) in enumerate(ops) if kind in W.ANIMATED or kind in W.ACCUMULATED or kind in W.PROGRESSIVE
+                   or kind in W.CONVERGING]
+    assert frozenset(("converge", "animation")) in cov["scene_ring_passages"], scene_users
+    assert cov["scene_ring_passages"] & {frozenset(("converge", "accumulate")), frozenset(("converge", "progressive"))}, scene_users
 
 
 # per seed: what the blur and jitter models of its walk cost, in per-pixel linear views -- the progressive kinds' passes
-# are modelled from the views of their one-call twins, so they are counted here too
-LINEAR_VIEWS = {381: 0, 1626: 12, 2849: 12}
+# are modelled from the views of their one-call twins, so they are counted here too, and so are the eight views of a
+# modelled "converge"
+LINEAR_VIEWS = {3757: 4, 9353: 4, 19124: 20}
 
 
 @pytest.mark.parametrize("seed", W.SEEDS)
@@ -92,6 +105,15 @@ def test_model_of_the_table_cache():
     assert [e for _, _, e in W.replay(ops)] == ["fill", "hit", "fill", "hit", "hit", "fill", "hit", "hit", "fill", "hit"]
     assert [k for _, k, _ in W.replay([("screen", 2), ("progressive_jitter", 5), ("progressive", -1)])] == \
         [(64, 40) + W.band_rows(40, 5) + (None,), (64, 40, 0, 40, None)]
+    # and the converging kinds: "converge" the band's or the frame's key, "settle" the frame's; a trace takes no table at all
+    ops = [("band", 7), ("converge", 7), ("trace", 3), ("settle", 0), ("trace", 7), ("converge", -1), ("animation3", -1), ("converge", 2),
+           ("band", 2), ("trace", 2)]
+    assert [(i, e) for i, _, e in W.replay(ops)] == [(0, "fill"), (1, "hit"), (3, "fill"), (5, "hit"), (6, "hit"), (7, "fill"), (8, "hit")]
+    assert [k for _, k, _ in W.replay([("screen", 2), ("converge", 7), ("trace", 1), ("settle", 0)])] == \
+        [(64, 40) + W.band_rows(40, 7) + (None,), (64, 40, 0, 40, None)]
+    # eight traces between them do not age a slot: nine geometries are needed for the first eviction, as before
+    ops = [("band", i) for i in range(8)] + [("trace", i) for i in range(8)] + [("band", 0), ("band", 8)]
+    assert [e for _, _, e in W.replay(ops)] == ["fill"] * 8 + ["hit", "evict"]
 
 
 def test_coverage_counts_caller_streams_and_the_shared_view_ring():
@@ -100,10 +122,10 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
            ("animation66", 0)]
     cov = W.coverage(ops)
     assert cov["on_caller_stream"] == {"adaptive": 1, "animation3": 1, "animation66": 1, "accumulate": 0, "jitter": 0, "accumulate66": 0,
-                                       "progressive": 0, "progressive_jitter": 0}
+                                       "progressive": 0, "progressive_jitter": 0, "converge": 0, "settle": 0, "trace": 0}
     cov = W.coverage([("jitter", 5), ("stream", 2), ("jitter", -1), ("accumulate66", 0), ("stream", 0), ("accumulate", 2)])
     assert cov["on_caller_stream"] == {"adaptive": 0, "animation3": 0, "animation66": 0, "accumulate": 0, "jitter": 1, "accumulate66": 1,
-                                       "progressive": 0, "progressive_jitter": 0}
+                                       "progressive": 0, "progressive_jitter": 0, "converge": 0, "settle": 0, "trace": 0}
     assert not cov["view_ring_shared"]
     A, B = ("animation66", 0), ("batch66", 0)
     assert W.coverage([A, B, B, B, B])["view_ring_shared"]          # the fifth user takes the first one's slot
@@ -151,6 +173,28 @@ def test_coverage_counts_caller_streams_and_the_shared_view_ring():
                                                                           "progressive", "progressive"]
     keys = W.linear_view_keys([("screen", 2), ("camera", 1), prog, pj])   # the views of the one-call twins
     assert keys == W.linear_view_keys([("screen", 2), ("camera", 1), blur, jit]) and len(keys) == 4 + 4
+    # every PASS of a converging kind is a user too, under an entry point of its own: two of "converge" (C C), three of
+    # "settle" (C C C); a trace is none
+    conv, settle, tr = ("converge", 7), ("settle", 0), ("trace", 4)
+    assert W.scene_ring_users(W.trace([a3, tr, conv, ("band", 0), settle, tr, prog, blur])) == \
+        ["animation", "converge", "converge", "converge", "converge", "converge", "progressive", "progressive", "accumulate"]
+    cov = W.coverage([("stream", 2), conv, tr, ("stream", 0), conv, a3, settle])   # users C C C C A C C C: C -> A, A -> C (one pair)
+    assert cov["scene_ring_passages"] == {pair("converge", "animation")}
+    assert cov["on_caller_stream"]["converge"] == 1 and cov["on_caller_stream"]["trace"] == 1 and cov["on_caller_stream"]["settle"] == 0
+    cov = W.coverage([blur, a3, prog, tr, tr, settle])            # U A G G C C C: U -> C, A -> C, G -> C
+    assert cov["scene_ring_passages"] == {pair("accumulate", "converge"), pair("animation", "converge"), pair("progressive", "converge")}
+    assert W.coverage([settle, tr, conv, tr, settle])["scene_ring_passages"] == set()   # one entry point: no passage
+    assert W.coverage([a3, tr, tr, tr, tr, blur, jit, P, settle])["scene_ring_passages"] == \
+        {pair("animation", "converge"), pair("accumulate", "converge")}                  # (traces do not move the ring)
+    assert W.coverage([("stream", 1), settle])["on_caller_stream"]["settle"] == 1
+    # "converge": the four cameras through both cells, eight views per state; "settle" and "trace" need no linear view
+    keys = W.linear_view_keys([("screen", 2), ("camera", 1), conv, ("converge", -1), settle, tr])
+    assert len(keys) == 8 and {(k[1], k[6]) for k in keys} == {(cam, cell) for cam in range(W.N_CAMERAS) for cell in W.JITTER_CELLS}
+    assert all(k[5] == W.morph_of(k[1]) for k in keys) and not W.linear_view_keys([("converge", 7)])  # (1024 x 512: beyond the model)
+    views = W.converge_views(3)
+    assert [v[0] for v in views] == [3, 0, 1, 2, 0, 1, 2, 3] and [v[2] for v in views] == list(W.JITTER_CELLS) * 4
+    assert W.settle_views(2) == ([(2, 2), (3, 0), (0, 0)], [(3, 0), (0, 1), (1, 1)]) and W.trace_camera(3) == 0
+    assert all(a != b for a, b in zip(*W.settle_views(1, 70)))  # every foreign view differs from its own
 
 
 @pytest.mark.parametrize("ext", [0, 1])
@@ -180,6 +224,69 @@ def test_pairs_are_the_plain_frames(options, ext, kifs, oracle):
         assert (plane[..., :3].view(np.uint32) == (lin + lin).astype(np.float32).view(np.uint32)).all()
         _, mistaken = L.carried_pair_model(O, lin, prior_of_pass_2=0)  # (a pass 2 modelled at prior 0 would not pass the line above)
         assert (mistaken[..., 3] == np.float32(1.0)).all()
+
+
+@pytest.mark.parametrize("ext", [0, 1])
+@pytest.mark.parametrize("options", range(W.N_OPTIONS))
+def test_settled_frames_are_the_plain_frames(options, ext, kifs, oracle):
+    """What the "settle" launches and Ctx.settle of tests/test_gpu_context_lifecycle.py rest on, from the references
+    alone (converge_reference.converged over the oracle's linear views): under the rule (0.0, 2) pass 1 leaves every
+    pixel active (n = 1 < 2); pass 2 over the same views gives sums c + c, moment 2 Y(c)^2 and d = n q - L^2 = 0 <= 0
+    exactly, so every pixel settles, the picture is the oracle's plain frame, the w word is 2.0 and the counts are 0;
+    pass 3, handed a foreign view, marches nothing: the plain frame again, every bit of both planes kept.  The three
+    option sets, their own image and a morphed one, extensions off and on."""
+    import accumulate_reference as ACC
+    import test_gpu_context_lifecycle as L
+    from helpers import oracle_uniforms
+    K, O = kifs, oracle
+    screen, cams, iters = K.ScreenData(64, 40), L._cameras(K), L.ITERS[0]
+    e = O.Ext(1, L.SHADOWS["shadow_steps"], L.SHADOWS["shadow_k"], L.SHADOWS["shadow_t0"], L.SHADOWS["shadow_max_t"]) if ext else None
+    for m in (0, 1):
+        image, other = L._morph(K, L._options(K)[options], m), L._morph(K, L._options(K)[options], (m + 1) % W.N_MORPHS)
+        lin = ACC.linear_views(O, K, screen, [cams[1]], image, iters, e)
+        foreign = ACC.linear_views(O, K, screen, [cams[2]], other, iters, e)
+        assert (lin != foreign).any()
+        s, c, o = oracle_uniforms(O, K, (screen, cams[1], L.Raw(image)))
+        plain = O.render(s, c, o, O.iters(*iters), **(dict(ext=e) if ext else {}))
+        one, two, three = L.settle_model(O, lin, foreign)
+        assert one["counts"].tolist() == [64 * 40] and one["mask"].all()
+        assert two["counts"].tolist() == [0] and two["mask"].all() and np.array_equal(two["frames"][0], plain), (options, ext, m)
+        assert (two["sums"][..., 3] == np.float32(2.0)).all() and not np.isnan(two["sums"]).any() and not np.isnan(two["moments"]).any()
+        assert (two["sums"][..., :3].view(np.uint32) == (lin + lin).astype(np.float32).view(np.uint32)).all()
+        assert three["counts"].tolist() == [0] and not three["mask"].any() and np.array_equal(three["frames"][0], plain)
+        assert (three["sums"].view(np.uint32) == two["sums"].view(np.uint32)).all()
+        assert (three["moments"].view(np.uint32) == two["moments"].view(np.uint32)).all()
+        # (a pass 3 modelled as marching would fold the foreign view in: other planes, another picture)
+        mistaken = L.settle_model(O, lin, foreign, pass_3_marches=True)[2]
+        assert mistaken["mask"].all() and (mistaken["sums"].view(np.uint32) != two["sums"].view(np.uint32)).any()
+        assert not np.array_equal(mistaken["frames"][0], plain)
+
+
+def test_the_converge_split_shows_in_the_model(kifs, oracle):
+    """What Ctx.converge's comparisons rest on, from the references alone, at 64 x 40: under the rule of the walks the
+    passes of 2 + 2 mask pixels (checked where Refs.converged builds a model), and a model with the pass sizes swapped
+    -- 1 + 3 here, since 2 + 2 is its own mirror -- gives another pass 1 picture and other counts: the split is held."""
+    import test_gpu_context_lifecycle as L
+    K, O = kifs, oracle
+    refs = L.Refs(K, O)
+    want = refs.converged_on_host((64, 40), 1)
+    assert len(want) == 2 and want[0]["sums"].shape == (W.CONVERGE_FRAMES, 40, 64, 4)
+    lin = refs.converge_linear((64, 40), 1)
+    other = L.converge_model(O, lin, splits=(1, 3), rule=W.CONVERGE_RULE)
+    assert (other[0]["frames"] != want[0]["frames"]).any() and other[0]["counts"].tolist() != want[0]["counts"].tolist()
+    assert {k: v for k, v in W.CONVERGING.items()} == {"converge": L.CONVERGE_SPLITS, "settle": (1,) * 3}
+    assert L.CONVERGE_RULE == W.CONVERGE_RULE and L.SETTLE_RULE == W.SETTLE_RULE
+    # a band's model is the rows of the frame's, the counts its own
+    band = refs.converged_on_host((64, 40), 1, y0=7, y1=29)
+    assert (band[1]["sums"].view(np.uint32) == want[1]["sums"][:, 7:29].view(np.uint32)).all()
+    assert band[1]["counts"].tolist() == [int(m.sum()) for m in CR_active_rows(want[1], 7, 29)]
+
+
+def CR_active_rows(state, y0, y1):
+    """Per frame the pixels of rows [y0, y1) still active in a pass's state, under the walks' rule and pass size."""
+    import converge_reference as CR
+    left = CR.active(state["sums"][:, y0:y1], state["moments"][:, y0:y1], W.CONVERGE_RULE, W.CONVERGING["converge"][1])
+    return [left[f] for f in range(left.shape[0])]
 
 
 def test_the_progressive_split_shows_in_the_model(kifs, oracle):

@@ -90,6 +90,41 @@ references included, ran 78 tests in 10.3 s of wall time before these launches j
 them (one session, one run after the other; the recorded 10.1 s above was another session); no new case takes more than
 0.5 s in the module's order, and test_rings_carry_progressive_frames run on its own, its references not yet there, takes
 1.4 s at 200 x 135 and 1.8 s at 64 x 40 as the first test of its process.
+
+Converging accumulation (kifs_render_accumulate_converge_async) goes through the same rings, tile tables, last_stream and
+options scope and adds a memset of the caller's counts on the launch stream; a converging frame is the result most
+exposed to stale state, because a wrong record in one pass lands in sums AND moments, from which the next pass derives
+which pixels it marches at all.  Ray queries (kifs_trace_rays_async) keep nothing but overwrite the context's screen,
+camera and supersampling factor for the length of a fill.  Three kinds of launch.  Ctx.converge: the eight views of
+context_walk.converge_views, 2 frames x 4 sub-frames on a grid of 2 as passes of 2 + 2 under the rule (3/32, 2) over planes
+of NaNs; up to MODEL_UP_TO every pass's picture and counts, the guard words around the counts and every f32 bit of both
+planes against converge_reference, beyond it against the same passes on a fresh context.  The model is shown not to be
+vacuous where it is built (Refs.converged_on_host, for every frame: some pixels active after pass 1 and some not, the
+mask of pass 2 neither empty nor full, an 8 x 8 block without an active pixel and one partly active); the tolerance is
+3/32 because at 1/16 half of the module's states fail that (context_walk.CONVERGE_RULE).  Ctx.settle: n frames x 1
+sub-frame, three passes under (0.0, 2) -- after two equal sub-frames d = 0 <= 0 exactly, so the frames are the oracle's
+plain frames at any size, the w word is 2.0, the counts fall from W * H to 0, and pass 3, handed FOREIGN views, must march
+nothing and keep every bit of both planes (against a copy made on the passes' stream when it is a caller's, else against
+passes 1 and 2 on a fresh context).  Ctx.trace: the pixel rays of a band for another camera than the context's, the
+colours against the oracle's one-sample rows, both outputs against a fresh context, the launch-state hooks and (outside
+the walks, where reading it would drain the device) the tile order unchanged.  Where: the seeded walks ("converge",
+"settle", "trace" -- also while supersampling is 2 --, a lone launch and a trace between the passes); every phase of the
+lone period, the passes straddling a lone launch of the full frame and a trace of it, on the context's and a caller's
+stream, with 70 views per pass, and a trace followed by a supersampled launch (test_transition_at_every_phase: "trace",
+"trace_caller_stream", "settle3", "settle_caller_stream", "settle70", "converge"); four set_screen calls between the
+passes of settled frames and a trace right after every set_screen (test_resize_sequence); the scene ring among the
+passes of three converging frame pairs, two open at once, and four other kinds of user, and the view ring among the
+passes of a settle(70), batches and an animated launch (test_rings_carry_converging_frames); the diagnostics buffer and
+the profiling ring, which neither a converging pass nor a trace enters (test_diagnostics_buffer).  Still not covered:
+a trace or a converging pass from a second host thread (julia_cull_radius keeps its last answer per thread), converging
+passes whose counts are read back between the passes to decide the next one, and prior counts near 2^24 on a long-lived
+context.  Cost, counted from the plans before a GPU run: the three walks need 4, 4 and 20 linear views (64 x 40: 16,
+200 x 135: 4, 330 x 149: 8), the ring test 8 linear views per size of which 4 are new, the transitions and the resize
+none; a trace needs the oracle frame of one more camera per state, which the batches of the same state mostly had.  On one
+MI355X machine the module, references included, ran 92 tests in 10.7 s of wall time before these launches joined (two
+runs: 10.74, 10.69) and runs 118 tests in 14.4 s with them (14.34, 14.55; one session, one run after the other); the
+slowest new case is the walk of seed 19124 at 2.2 to 2.5 s, nearly all of it its 20 linear views and their models, then
+test_rings_carry_converging_frames at 0.5 s (200 x 135); no new transition takes more than 0.15 s.
 """
 import ctypes as C
 
@@ -99,6 +134,7 @@ import pytest
 import accumulate_reference as ACC
 import adaptive_reference as AR
 import context_walk as W
+import converge_reference as CR
 import jitter_reference as JR
 import progressive_reference as PR
 from geometry_cases import Raw
@@ -114,6 +150,10 @@ MODEL_UP_TO = W.MODEL_UP_TO  # (330, 149): the largest screen an adaptive call i
 EDGE_SENTINEL = 0x5A5A5A5A
 HOLD_PASSES = 384  # _hold_back: 9.4 ms of GPU time per 128 passes as measured on the MI355X, 0.7 ms of host time to enqueue them
 SHADOWS = dict(soft_shadow=True, shadow_steps=16, shadow_k=8.0, shadow_t0=0.02, shadow_max_t=10.0)
+COUNT_GUARD = -0x5A5A5A5B  # 0xA5A5A5A5: the words on either side of a converging pass's counts
+CONVERGE_SPLITS = (2, 2)   # Ctx.converge: sub-frames per frame of each pass, of 4 (context_walk.CONVERGING["converge"])
+CONVERGE_RULE = (3.0 / 32.0, 2)  # (tolerance, min_samples) of every pass of Ctx.converge: context_walk.CONVERGE_RULE says why 3/32
+SETTLE_RULE = (0.0, 2)           # and of Ctx.settle: exactly d <= 0 after two equal sub-frames
 
 
 def _cameras(K):
@@ -156,6 +196,7 @@ class Refs:
         self.morphs = [[_morph(K, g, m) for m in range(W.N_MORPHS)] for g in self.opts]
         self.geoms, self.means, self.models = {}, {}, {}
         self.linears, self.accums, self.passes = {}, {}, {}
+        self.ray_sets, self.converging = {}, {}
 
     def frame(self, size, cam, options=0, iters=0, ext=0, morph=0):
         import torch
@@ -239,6 +280,51 @@ class Refs:
             self.passes[key] = ([torch.from_numpy(f).to("cuda:0") for f in frames], torch.from_numpy(plane).to("cuda:0"))
         return self.passes[key]
 
+    def rays(self, size, cam):
+        """(H * W, 8) float32 on the device: configs.pixel_rays of camera `cam` at `size`, built on the host."""
+        import torch
+        from kifs_raymarching_amd.configs import pixel_rays
+        if (size, cam) not in self.ray_sets:
+            self.ray_sets[(size, cam)] = torch.from_numpy(pixel_rays(self.K.ScreenData(*size), self.cams[cam])).to("cuda:0")
+        return self.ray_sets[(size, cam)]
+
+    def converge_linear(self, size, cam0, options=0, iters=0, ext=0):
+        """(8, H, W, 3): the linear views of context_walk.converge_views(cam0), frame by frame."""
+        return np.stack([self.linear(size, cam, options, iters, ext, m, cell) for cam, m, cell in W.converge_views(cam0)])
+
+    def converged_on_host(self, size, cam0, options=0, iters=0, ext=0, y0=0, y1=None):
+        """converge_reference.converged over the linear views of a Ctx.converge with the context's camera cam0, rows
+        [y0, y1): per pass a dict of the picture, both planes, the mask marched and the counts.  Not vacuous, from the model alone, for every frame: after pass
+        1 some pixels are still active and some are not, the mask marched in pass 2 is neither empty nor full, and among
+        its 8 x 8 blocks (the kernel's, from the band's first row) one has no active pixel and one is partly active."""
+        y1 = size[1] if y1 is None else y1
+        key = (size, cam0, options, iters, ext, y0, y1)
+        if key not in self.converging:
+            want = converge_model(self.O, self.converge_linear(size, cam0, options, iters, ext), y0=y0, y1=y1)
+            rows, w = y1 - y0, size[0]
+            for f in range(W.CONVERGE_FRAMES):
+                assert 0 < want[0]["counts"][f] < rows * w, (key, f, want[0]["counts"])
+                mask = want[1]["mask"][f]
+                assert mask.any() and not mask.all(), (key, f)
+                assert int(mask.sum()) == want[0]["counts"][f], (key, f)  # what pass 1 left active is what pass 2 marches
+                none, part, _ = CR.blocks(mask)
+                assert none >= 1 and part >= 1, (key, f, none, part)
+            self.converging[key] = want
+        return self.converging[key]
+
+    def converged(self, size, cam0, options=0, iters=0, ext=0, y0=0, y1=None):
+        """converged_on_host, every pass with "dev": its picture, both planes as int32 and the counts between their two
+        guard words, on the device."""
+        import torch
+        want = self.converged_on_host(size, cam0, options, iters, ext, y0, y1)
+        for p in want:
+            if "dev" not in p:
+                guarded = np.concatenate([[COUNT_GUARD], p["counts"], [COUNT_GUARD]]).astype(np.int32)
+                p["dev"] = dict(frames=torch.from_numpy(p["frames"]).to("cuda:0"), counts=torch.from_numpy(guarded).to("cuda:0"),
+                                sums=torch.from_numpy(np.ascontiguousarray(p["sums"]).view(np.int32)).to("cuda:0"),
+                                moments=torch.from_numpy(np.ascontiguousarray(p["moments"]).view(np.int32)).to("cuda:0"))
+        return want
+
     def blur(self, size, cam0, options=0, iters=0, ext=0, own_options=True):
         return self.accumulated(size, _blur_views(cam0, own_options), 3, options, iters, ext)
 
@@ -271,6 +357,23 @@ def progressive_model(O, lin, samples, splits):
     return frames, plane
 
 
+def converge_model(O, lin, splits=CONVERGE_SPLITS, rule=CONVERGE_RULE, y0=0, y1=None):
+    """converge_reference.converged over the (frames * samples, H, W, 3) linear views `lin` of a Ctx.converge, as passes
+    of `splits` sub-frames per frame under one rule, the first restarting: a list of dicts per pass."""
+    samples = sum(splits)
+    passes = PR.split_views(lin, lin.shape[0] // samples, samples, splits)
+    return CR.converged(O, passes, [rule] * len(splits), y0=y0, y1=y1)
+
+
+def settle_model(O, lin, foreign, pass_3_marches=False):
+    """What Ctx.settle rests on, through converge_reference.converged: the (frames, H, W, 3) linear views `lin` as one
+    sub-frame per frame in pass 1 (restart) and again in pass 2, then `foreign` in pass 3, all under SETTLE_RULE.
+    (pass_3_marches: a mistaken model whose third pass finds nothing settled -- min_samples 4.)"""
+    lin, foreign = np.asarray(lin, dtype=np.float32)[:, None], np.asarray(foreign, dtype=np.float32)[:, None]
+    rules = [SETTLE_RULE, SETTLE_RULE, (SETTLE_RULE[0], 4) if pass_3_marches else SETTLE_RULE]
+    return CR.converged(O, [lin, lin, foreign], rules)
+
+
 def carried_pair_model(O, lin, prior_of_pass_2=1):
     """What Ctx.carried rests on, through progressive_reference.fold in two passes: pass 1 folds the (frames, H, W, 3)
     linear views `lin` at prior 0 over a plane of NaNs, pass 2 the same views at prior 1.  (frames, plane)."""
@@ -298,6 +401,7 @@ class Ctx:
         self.gs.set_iters(*ITERS[iters])
         self.gs.set_camera(refs.cams[0])
         self.pending, self.log, self.kernels, self.checks = [], [], [], []
+        self.keep = []  # tensors a launch still in flight writes and no comparison holds: alive until verify() has waited
 
     def close(self):
         self.gs.close()
@@ -487,6 +591,176 @@ class Ctx:
             between()
         return finish()
 
+    def converging_state(self, rows, n, passes):
+        """Everything the converging passes of one frame set may write, the test's own: both planes, every byte 0xFF
+        (NaNs: a first pass that read them would show), per pass the n counts between two guard words and a
+        sentinel-filled picture."""
+        w, torch = self.state["size"][0], self.torch
+        return dict(sums=self.plane(rows, n),
+                    moments=torch.full((n, rows, w * 4), 0xFF, dtype=torch.uint8, device="cuda:0").view(torch.float32),
+                    counts=torch.full((passes, n + 2), COUNT_GUARD, dtype=torch.int32, device="cuda:0"),
+                    pictures=[torch.full((n, rows, w, 4), SENTINEL, dtype=torch.uint8, device="cuda:0") for _ in range(passes)])
+
+    def converge_open(self, y0=0, y1=None, stream=None, fresh=None, what=None):
+        """Pass 1 of Ctx.converge; returns the function that enqueues pass 2."""
+        st = dict(self.state)
+        y1 = st["size"][1] if y1 is None else y1
+        views, samples, splits = W.converge_views(st["camera"]), sum(CONVERGE_SPLITS), CONVERGE_SPLITS
+        count = len(views) // samples
+        uniforms = PR.pass_views([self.refs.cams[cam] for cam, _, _ in views], count, samples, splits)
+        images = PR.pass_views([self.refs.morphs[st["options"]][m] for _, m, _ in views], count, samples, splits)
+        cells = PR.pass_views([cell for _, _, cell in views], count, samples, splits)
+        what = what or ("converge", st["camera"], y0, y1, "caller stream" if stream is not None else "context stream")
+        assert W.modelled(st["size"]) or fresh is not None
+        want = self.refs.converged(st["size"], st["camera"], st["options"], st["iters"], st["ext"], y0, y1) if W.modelled(st["size"]) else None
+        mine = self.converging_state(y1 - y0, count, len(splits))
+
+        def run(g, p, state, stream):
+            g.render_accumulate_converge(state["sums"], state["moments"], uniforms[p], splits[p], CONVERGE_RULE, restart=p == 0,
+                                         counts=state["counts"][p, 1:-1], options=images[p], outs=state["pictures"][p], y0=y0, y1=y1,
+                                         stream=stream, jitter=(W.JITTER_GRID, cells[p]))
+
+        def enqueue(p):
+            run(self.gs, p, mine, stream)
+            self.log.append(what + (f"pass {p + 1} of {len(splits)}",))
+
+        def finish():
+            assert self.state["size"] == st["size"]
+            enqueue(len(splits) - 1)
+            upto, int32 = len(self.log), self.torch.int32
+            if want is not None:
+                for p in range(len(splits)):
+                    self.pending.append((mine["pictures"][p], want[p]["dev"]["frames"], upto, f"the picture of pass {p + 1}, against the model"))
+                    self.pending.append((mine["counts"][p], want[p]["dev"]["counts"], upto, f"the counts of pass {p + 1}, against the model"))
+                self.pending.append((mine["sums"].view(int32), want[-1]["dev"]["sums"], upto, "the sums plane, against the model"))  # every f32 bit pattern
+                self.pending.append((mine["moments"].view(int32), want[-1]["dev"]["moments"], upto, "the moments plane, against the model"))
+            if fresh is not None:  # the same passes without history
+                other = self.converging_state(y1 - y0, count, len(splits))
+                for p in range(len(splits)):
+                    run(fresh, p, other, None)
+                    self.pending.append((mine["pictures"][p], other["pictures"][p], upto, f"the picture of pass {p + 1}, against a fresh context"))
+                self.pending.append((mine["counts"], other["counts"], upto, "the counts, against a fresh context"))
+                self.pending.append((mine["sums"].view(int32), other["sums"].view(int32), upto, "the sums plane, against a fresh context"))
+                self.pending.append((mine["moments"].view(int32), other["moments"].view(int32), upto, "the moments plane, against a fresh context"))
+            return mine["pictures"][-1], mine["sums"], mine["moments"]
+
+        for p in range(len(splits) - 1):
+            enqueue(p)
+        return finish
+
+    def converge(self, y0=0, y1=None, stream=None, fresh=None, between=None, what=None):
+        """A converging frame pair (kifs_render_accumulate_converge_async): the views context_walk.converge_views of the
+        context's camera, 2 frames x 4 sub-frames on a grid of 2, as passes of 2 + 2 under CONVERGE_RULE over planes of
+        NaNs of the test's own, a picture and the counts from every pass, `between` (other launches of this Ctx)
+        between the passes.  Up to MODEL_UP_TO every pass's picture and counts, the guard words around them and every
+        f32 bit pattern of both planes against converge_reference (Refs.converged, which shows the mask is neither
+        empty nor full); with `fresh` all of it against the same passes on it.  Returns (the last picture, the planes)."""
+        finish = self.converge_open(y0, y1, stream, fresh, what)
+        if between is not None:
+            between()
+        return finish()
+
+    def settle_open(self, n=W.SETTLE_FRAMES, stream=None, fresh=None, shift=0, what=None):
+        """Pass 1 of Ctx.settle; returns the function that enqueues pass 2, which returns the one that enqueues pass 3."""
+        st, torch = dict(self.state), self.torch
+        (w, h), int32 = st["size"], torch.int32
+        own, foreign = W.settle_views(st["camera"], n)
+        own = [(cam, (m + shift) % W.N_MORPHS) for cam, m in own]
+        foreign = [(cam, (m + shift) % W.N_MORPHS) for cam, m in foreign]
+        assert all(a != b for a, b in zip(own, foreign))
+        wants = [self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"], m) for cam, m in own]
+        what = what or ("settle", n, shift, "caller stream" if stream is not None else "context stream")
+        assert stream is not None or fresh is not None  # (what pass 2 left: copied on the caller's stream, or fresh's)
+        mine = self.converging_state(h, n, 3)
+        kept = {}
+
+        def run(g, p, state, stream):
+            views = foreign if p == 2 else own
+            out = g.render_accumulate_converge(state["sums"], state["moments"], [self.refs.cams[cam] for cam, _ in views], 1, SETTLE_RULE,
+                                               restart=p == 0, counts=state["counts"][p, 1:-1],
+                                               options=[self.refs.morphs[st["options"]][m] for _, m in views],
+                                               outs=state["pictures"][p] if p else None, picture=p > 0, stream=stream)
+            assert p > 0 or out is None
+
+        def third():
+            assert self.state["size"] == st["size"]
+            run(self.gs, 2, mine, stream)
+            self.log.append(what + ("pass 3 of 3",))
+            upto = len(self.log)
+            guard = [COUNT_GUARD]
+            counts = torch.tensor([guard + [w * h] * n + guard, guard + [0] * n + guard, guard + [0] * n + guard], dtype=int32, device="cuda:0")
+            for f in range(n):
+                self.pending.append((mine["pictures"][1][f], wants[f], upto, f"frame {f} after pass 2"))
+                self.pending.append((mine["pictures"][2][f], wants[f], upto, f"frame {f} after pass 3"))  # it marched nothing: the plain frame again
+            self.pending.append((mine["pictures"][0], torch.full_like(mine["pictures"][0], SENTINEL), upto, "pass 1's picture: none asked for"))
+            self.pending.append((mine["counts"], counts, upto, "the counts of the three passes"))
+            self.pending.append((mine["sums"][..., 3:], torch.full_like(mine["sums"][..., 3:], 2.0), upto, "the w word: 2.0 everywhere"))
+            self.pending.append((mine["sums"].view(int32), kept["sums"].view(int32), upto, "the sums plane: pass 3 keeps every bit"))
+            self.pending.append((mine["moments"].view(int32), kept["moments"].view(int32), upto, "the moments plane: pass 3 keeps every bit"))
+            return mine["pictures"][2], mine["sums"], mine["moments"]
+
+        def second():
+            assert self.state["size"] == st["size"]
+            run(self.gs, 1, mine, stream)
+            self.log.append(what + ("pass 2 of 3",))
+            if stream is not None:  # the planes as pass 2 left them, copied on the passes' own stream before pass 3 is enqueued
+                with torch.cuda.stream(stream):
+                    kept.update(sums=mine["sums"].clone(), moments=mine["moments"].clone())
+            else:                   # the context's stream cannot be named as a producer: passes 1 and 2 without history instead
+                other = self.converging_state(h, n, 3)
+                run(fresh, 0, other, None)
+                run(fresh, 1, other, None)
+                kept.update(sums=other["sums"], moments=other["moments"])
+                self.keep.append(other)  # (its counts and pass 2's picture are written too: not to be handed out again meanwhile)
+            return third
+
+        run(self.gs, 0, mine, stream)
+        self.log.append(what + ("pass 1 of 3",))
+        return second
+
+    def settle(self, n=W.SETTLE_FRAMES, stream=None, fresh=None, shift=0, between=None, what=None):
+        """Converging passes that are exact at any size: the whole frame, n frames x 1 sub-frame, three passes under
+        SETTLE_RULE = (0.0, 2) over planes of NaNs.  Frame f has camera batch_cameras(camera, n)[f] and its option image
+        (+ shift).  Pass 1 restarts without a picture; pass 2 takes the same views: c + c, d = 0 <= 0 exactly, so every
+        pixel settles, every frame is the oracle's plain frame, the w word is 2.0 and the counts fall from W * H to 0;
+        pass 3 is handed foreign views (camera + 1, the next option image) and must march nothing: the plain frames
+        again, the counts 0, every bit of both planes as pass 2 left it -- held against a copy made on the passes' own
+        stream when that is a caller's, else against passes 1 and 2 on `fresh`
+        (tests/test_context_walk_plan.py::test_settled_frames_are_the_plain_frames, from the references alone).
+        `between` (other launches of this Ctx) runs between the passes."""
+        step = self.settle_open(n, stream, fresh, shift, what)
+        while callable(step):
+            if between is not None:
+                between()
+            step = step()
+        return step
+
+    def trace(self, cam, y0=0, y1=None, stream=None, fresh=None, order=True, what=None):
+        """A ray query (kifs_trace_rays_async): the pixel rays of rows [y0, y1) for camera `cam` -- the context's own is
+        not set to it, the call must not read it -- both outputs, on `stream`.  The colours against the oracle's
+        one-sample frame rows of that camera under the context's options, iteration counts and extensions, whatever its
+        supersampling factor; both outputs against the same call on `fresh` when there is one.  The launch-state hooks
+        report what they reported before the call, and with `order` the tile order is what it was (reading it drains
+        the device and takes the full frame's tile table: not in a walk)."""
+        st, gs = self.state, self.gs
+        w, h = st["size"]
+        y1 = h if y1 is None else y1
+        rays = self.refs.rays(st["size"], cam)[y0 * w:y1 * w]
+        want = self.refs.frame(st["size"], cam, st["options"], st["iters"], st["ext"])[y0:y1].reshape(-1, 4)
+        hooks = lambda: (gs.debug_last_kernel(), gs.debug_last_round_steps(), gs.debug_last_group_tiles())
+        before = hooks(), gs.debug_get_tile_order() if order else None
+        geom, rgba = gs.trace_rays(rays, stream=stream)
+        assert hooks() == before[0], (hooks(), before[0])
+        assert not order or np.array_equal(gs.debug_get_tile_order(), before[1])
+        self.log.append(what or ("trace", cam, y0, y1, "caller stream" if stream is not None else "context stream"))
+        upto = len(self.log)
+        self.pending.append((rgba, want, upto, "the colours, against the oracle's rows"))
+        if fresh is not None:
+            want_geom, want_rgba = fresh.trace_rays(rays)
+            self.pending.append((rgba, want_rgba, upto, "the colours, against a fresh context"))
+            self.pending.append((geom.view(self.torch.int32), want_geom.view(self.torch.int32), upto, "the texels, against a fresh context"))
+        return geom, rgba
+
     def blur(self, y0=0, y1=None, stream=None, fresh=None, own_options=True, what=None):
         """An accumulated launch of 2 frames x 3 sub-frames: the cameras batch_cameras(camera, 6), each sub-frame with the
         option image of its camera (own_options False: options NULL, the context's for all).  Against
@@ -565,14 +839,15 @@ class Ctx:
     def verify(self):
         """Wait once, then every destination against its reference; a failure prints the history up to its launch."""
         self.torch.cuda.synchronize()
-        for out, want, upto in self.pending:
+        for out, want, upto, *which in self.pending:  # (which: what of the launch is compared, where it has several results)
             out = out() if callable(out) else out  # (a gather of a destination's rows: only once the launch is over)
             if not self.torch.equal(out, want):
                 bad = int((out != want).any(-1).sum())
-                raise AssertionError(f"{bad} pixels differ after {self.log[:upto]}")
+                words = f" (got {out.tolist()}, want {want.tolist()})" if out.numel() <= 64 else ""  # (counts: few enough to print)
+                raise AssertionError(f"{bad} pixels differ{' in ' + which[0] if which else ''}{words} after {self.log[:upto]}")
         for check in self.checks:  # (what needs a value read back: the adaptive calls' anchors)
             check()
-        self.pending, self.checks = [], []
+        self.pending, self.checks, self.keep = [], [], []
 
     def other_band(self, n):
         """The n-th of a supply of distinct bands, none the full frame: 8 rows from row 8 (n % 60), then longer ones."""
@@ -667,7 +942,8 @@ def test_eviction_round_trip(k, ctx, kifs):
 
 TRANSITIONS = ("batch3", "batch70", "frames_in_flight", "caller_stream", "supersampled", "geometry", "sphere", "band504",
                "adaptive", "animation3", "animation70", "animation_caller_stream", "pairs3", "pairs70", "pairs_caller_stream", "jitter",
-               "carried3", "carried_caller_stream", "progressive")
+               "carried3", "carried_caller_stream", "progressive",
+               "trace", "trace_caller_stream", "settle3", "settle_caller_stream", "settle70", "converge")
 
 
 @pytest.mark.parametrize("k", range(4))
@@ -679,16 +955,41 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
     frames, the jittered launch to a fresh context.  Everything equals the oracle, the order table stays a
     permutation, and the lone launches before and after run the same kernel.  Carried pairs and a progressive blur frame
     (against a fresh context: 1024 x 512 is beyond the model) are progressive frames whose two passes STRADDLE a lone launch
-    of the full frame, which advances the feedback period; neither pass moves the order."""
+    of the full frame, which advances the feedback period; neither pass moves the order.  So are the converging ones:
+    three settled frames on the context's and on a caller's stream, seventy of them (70 views per pass: a user of the
+    view-table ring) and a converging frame pair against a fresh context, whose passes straddle a lone launch of the full
+    frame AND a ray query of it; the order moves across neither pass nor the trace.  A trace alone, on the context's and
+    on a caller's stream, is a transition too: it overwrites the context's screen, camera and supersampling for the
+    length of a fill and must hand them back."""
     import torch
     c = ctx()
     for cam in range(W.N_CAMERAS):  # every oracle frame before the first launch: the lone launches', then the animated ones'
         c.refs.frame(FULL, cam)
-        if transition.startswith(("animation", "pairs", "carried")):
+        if transition.startswith(("animation", "pairs", "carried", "settle")):
             for shift in range(W.N_MORPHS if transition.endswith("_caller_stream") else 1):
                 c.refs.frame(FULL, cam, morph=(W.morph_of(cam) + shift) % W.N_MORPHS)
     if transition == "sphere":
         c.refs.frame(FULL, 1, options=2)
+    if transition.startswith(("trace", "settle", "converge")):
+        for cam in range(W.N_CAMERAS):
+            c.refs.rays(FULL, cam)
+
+    def straddled(open_, cam, traced=None):
+        """Pass 1, a lone launch of the full frame, pass 2 (and so on while a pass returns the next): the order moves
+        across no pass.  With `traced` = (stream, fresh) a ray query of the full frame follows every lone launch; Ctx.trace
+        asserts that the order does not move across it."""
+        before = c.gs.debug_get_tile_order()
+        step = open_()
+        assert np.array_equal(c.gs.debug_get_tile_order(), before)
+        while callable(step):
+            c.lone(cam=cam)  # (advances the period; what it does to the order is the lone launches' business)
+            if traced is not None:
+                c.trace(W.trace_camera(cam), stream=traced[0], fresh=traced[1])
+            before = c.gs.debug_get_tile_order()
+            step = step()
+            assert np.array_equal(c.gs.debug_get_tile_order(), before)
+        c.camera(1)
+
     for i in range(k):
         c.lone(cam=i % 4, record_kernel=True)
     if transition == "batch3":
@@ -774,16 +1075,6 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
             fresh.synchronize()
         assert np.array_equal(c.gs.debug_get_tile_order(), before)
     elif transition in ("carried3", "carried_caller_stream", "progressive"):
-        def straddled(open_, cam):
-            """Pass 1, a lone launch of the full frame, pass 2: the order moves across neither pass."""
-            before = c.gs.debug_get_tile_order()
-            finish = open_()
-            assert np.array_equal(c.gs.debug_get_tile_order(), before)
-            c.lone(cam=cam)  # (advances the period; what it does to the order is the lone launches' business)
-            before = c.gs.debug_get_tile_order()
-            finish()
-            assert np.array_equal(c.gs.debug_get_tile_order(), before)
-            c.camera(1)
         c.camera(1)
         if transition == "carried3":
             straddled(lambda: c.carried_open(3), 2)
@@ -797,6 +1088,41 @@ def test_transition_at_every_phase(transition, k, ctx, kifs):
                 fresh.set_iters(*ITERS[0])
                 straddled(lambda: c.progressive_open("blur", fresh=fresh), 2)
                 fresh.synchronize()
+    else:  # a ray query, settled frames, a converging frame pair
+        c.camera(1)
+        s = torch.cuda.Stream() if transition.endswith("_caller_stream") or transition == "settle70" else None
+        with kifs.GraphicState(0, screen_data=kifs.ScreenData(*FULL), camera_data=c.refs.cams[3], gui_data=c.refs.opts[0]) as fresh:
+            fresh.set_iters(*ITERS[0])
+            if transition in ("trace", "trace_caller_stream"):
+                c.trace(2, stream=s, fresh=fresh)             # the full frame of another camera than the context's
+                c.trace(0, 100, 229, stream=s, fresh=fresh)   # and a band, neither end on a tile row
+                for g in (c.gs, fresh):                       # the one call the API takes while supersampling is above 1:
+                    g.set_supersampling(2)                    # it sets the factor to 1 for its fill and must hand the 2 back
+                c.trace(3, stream=s, order=False)             # (against the oracle alone: `fresh` has not traced when it renders)
+                out, want = c.dest(FULL[1]), c.dest(FULL[1])
+                c.gs.render_async(out, stream=s)
+                fresh.set_camera(c.refs.cams[1])
+                fresh.render_async(want)
+                c.expect(out, want, ("supersampled x2 after a trace",))
+                one_sample = c.want(1, 0, FULL[1])
+
+                def resolved(out=out, one_sample=one_sample):
+                    assert not torch.equal(out, one_sample)   # (the resolve is not the one-sample frame)
+                c.checks.append(resolved)
+                for g in (c.gs, fresh):
+                    g.set_supersampling(1)
+            elif transition == "settle3":
+                straddled(lambda: c.settle_open(3, fresh=fresh), 2, traced=(None, fresh))
+            elif transition == "settle_caller_stream":
+                straddled(lambda: c.settle_open(3, stream=s), 2, traced=(s, fresh))
+                straddled(lambda: c.settle_open(3, stream=s, shift=1), 3, traced=(s, None))
+                straddled(lambda: c.settle_open(3, stream=s, shift=2), 0, traced=(s, None))  # pass 3: the lone launches below follow it
+            elif transition == "settle70":
+                straddled(lambda: c.settle_open(70, stream=s), 2, traced=(None, fresh))
+            else:
+                assert transition == "converge"
+                straddled(lambda: c.converge_open(fresh=fresh), 2, traced=(None, fresh))
+            fresh.synchronize()
     for i in range(6):
         c.lone(cam=(i + 1) % 4, record_kernel=True)
     c.verify()
@@ -810,7 +1136,10 @@ def test_resize_sequence(ctx, kifs):
     packed at two sizes.  The first launch after every set_screen is an accumulated one of three pairs, held to the oracle's
     plain frames, and at the two sizes with a model a blur launch renders the band rows h // 3 .. h - 3.  Pass 1 of three
     carried pairs is enqueued at the first 1024 x 512 and pass 2 when the sequence is back there at its end: four set_screen
-    calls and every launch of the other sizes lie between the passes of frames that are the oracle's plain frames."""
+    calls and every launch of the other sizes lie between the passes of frames that are the oracle's plain frames.  So it is
+    with three settled frames on a caller's stream: pass 1 at the first 1024 x 512, passes 2 and 3 back there.  And right
+    after every set_screen, before any launch has a tile table of the new size, a ray query of the new frame's pixel
+    rays for another camera than the context's: it reads neither the new screen nor the camera."""
     import torch
     sizes = [(1024, 512), (330, 149), (64, 40), (1056, 516), (1024, 512)]
     stripes = [0, 2, 4]  # rows 0..7, 16..23, 32..39: inside every size
@@ -819,17 +1148,22 @@ def test_resize_sequence(ctx, kifs):
         for cam in range(W.N_CAMERAS):
             c.refs.frame(size, cam)
             c.refs.frame(size, cam, morph=W.morph_of(cam))
+        c.refs.rays(size, (n + 1) % 4)
         if W.modelled(size):
             c.refs.blur(size, (n + 2) % 4)
     host = []
+    s = torch.cuda.Stream()
     for n, (w, h) in enumerate(sizes):
         c.screen((w, h))            # (the previous size's launches are still in flight)
+        c.trace((n + 1) % 4, order=False)  # (not a launch: no table; reading the order would drain the device)
         c.pairs(3)                  # (the first launch at the new size: the scene ring's records, the new frame's table)
         if n == 0:
             c.camera(1)
             finish_carried = c.carried_open(3)
+            settle_on = c.settle_open(3, stream=s)
         elif n == len(sizes) - 1:
             finish_carried()
+            settle_on()()
         c.lone(cam=n % 4)
         if n % 2:
             c.camera((n + 1) % 4)
@@ -871,22 +1205,41 @@ def test_resize_sequence(ctx, kifs):
 
 @pytest.mark.parametrize("seed", W.SEEDS)
 def test_seeded_walk(seed, ctx, kifs):
-    """88 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
+    """104 operations drawn by context_walk.plan(seed) on one context, nothing waited for until the end; every render is
     checked, and a failure prints the plan up to it.  Adaptive calls, animated and accumulated launches run on the walk's
     current stream like every other render: every animated frame and every frame of an "accumulate66" against the oracle,
     an adaptive call as Ctx.adaptive says, a blur or jitter launch against its model up to MODEL_UP_TO and against the same
     call on the fresh context beyond.  A "progressive" or "progressive_jitter" is Ctx.progressive with a lone launch of
-    the same rows and the context's camera between its passes, all three on the walk's current stream."""
+    the same rows and the context's camera between its passes, all three on the walk's current stream.  A "converge" is
+    Ctx.converge and a "settle" Ctx.settle, with such a lone launch and a trace of the same rows between their passes; a
+    "trace" is Ctx.trace of a band's rows for the camera after the context's, also while supersampling is 2 -- none of
+    them reads the tile order, which would drain the device and take a tile table the plan's model does not know of."""
     import torch
     ops = W.plan(seed)
     c = ctx()
     streams = [None, torch.cuda.Stream(), torch.cuda.Stream()]
     fresh = kifs.GraphicState(0)   # the reference for supersampled and geometry launches: configured alike, no history
     try:
-        for _, kind, arg, st in W.trace(ops):  # every oracle and model frame before the first launch
-            if st["supersampling"] == 1:
+        def for_a_trace(st):  # its rays and the one-sample frame of its camera, whatever the supersampling factor
+            size, cam = W.SIZES[st["size"]], W.trace_camera(st["camera"])
+            c.refs.rays(size, cam)
+            c.refs.frame(size, cam, st["options"], st["iters"], st["extensions"])
+
+        for _, kind, arg, st in W.trace(ops):  # every oracle and model frame and every ray before the first launch
+            if kind == "trace":
+                for_a_trace(st)
+            elif st["supersampling"] == 1:
                 n = {"batch3": 3, "batch66": 66, **W.ANIMATED, "accumulate66": 33}.get(kind, 1)
                 scene = (W.SIZES[st["size"]], st["options"], st["iters"])
+                if kind in W.CONVERGING:
+                    if kind == "settle":
+                        for cam, m in W.settle_views(st["camera"])[0]:
+                            c.refs.frame(scene[0], cam, *scene[1:], st["extensions"], m)
+                    elif W.modelled(scene[0]):
+                        c.refs.converged(scene[0], st["camera"], *scene[1:], st["extensions"], *W.animation_rows(scene[0][1], arg))
+                    c.refs.frame(scene[0], st["camera"], *scene[1:], st["extensions"])  # the lone launch between the passes,
+                    for_a_trace(st)                                                     # and the trace after it
+                    continue
                 if kind in W.PROGRESSIVE:
                     if W.modelled(scene[0]):
                         c.refs.progressive(scene[0], PROGRESSIVE_KINDS[kind], st["camera"], *scene[1:], st["extensions"])
@@ -935,8 +1288,8 @@ def test_seeded_walk(seed, ctx, kifs):
             cam0 = state["camera"]
             what = (i, kind, arg, dict(state))
             exact = state["supersampling"] == 1  # else: against the same call on the fresh context
-            beyond_the_model = W.AS_ONE_CALL.get(kind, kind) in ("accumulate", "jitter") and not W.modelled((w, h))
-            if not exact or kind in ("geometry", "adaptive") or beyond_the_model:
+            beyond_the_model = W.AS_ONE_CALL.get(kind, kind) in ("accumulate", "jitter", "converge") and not W.modelled((w, h))
+            if not exact or kind in ("geometry", "adaptive", "trace") or kind in W.CONVERGING or beyond_the_model:
                 mirror(fresh)
             if kind == "band" or kind in ("batch3", "batch66"):
                 n = {"band": 1, "batch3": 3, "batch66": 66}[kind]
@@ -979,6 +1332,18 @@ def test_seeded_walk(seed, ctx, kifs):
                 rows = W.animation_rows(h, arg)
                 c.progressive(PROGRESSIVE_KINDS[kind], *rows, stream=stream, fresh=fresh if beyond_the_model else None, what=what,
                               between=lambda: c.lone(cam0, *rows, stream=stream))
+            elif kind in W.CONVERGING:
+                rows = W.animation_rows(h, arg) if kind == "converge" else (0, h)
+
+                def between():
+                    c.lone(cam0, *rows, stream=stream)
+                    c.trace(W.trace_camera(cam0), *rows, stream=stream, fresh=fresh, order=False)
+                if kind == "converge":
+                    c.converge(*rows, stream=stream, fresh=fresh if beyond_the_model else None, between=between, what=what)
+                else:
+                    c.settle(stream=stream, fresh=fresh, between=between, what=what)
+            elif kind == "trace":
+                c.trace(W.trace_camera(cam0), *W.band_rows(h, arg), stream=stream, fresh=fresh, order=False, what=what)
             elif kind == "adaptive":
                 fresh.set_camera(c.refs.cams[cam0])
                 c.adaptive(arg, stream=stream, fresh=fresh, what=what)
@@ -1184,6 +1549,91 @@ def test_rings_carry_progressive_frames(size, ctx):
     del held
 
 
+# test_rings_carry_converging_frames: the users of the scene ring in order.  (frame, pass) is a pass of a converging frame
+# pair -- X on the context's stream, Y and Z on a caller's --, ("G", pass) one of a progressive blur frame; "A" an animated
+# launch of 3, "U" a blur launch, "J" a jittered launch.
+CONVERGING_FRAMES = {"X": (0, 0), "Y": (1, 1), "Z": (3, 1)}  # camera, on the caller's stream
+CONVERGING_USERS = (("X", 1), ("Y", 1), "A", "U",
+                    "J", ("G", 1), "A", ("G", 2),
+                    ("X", 2), ("Y", 2), "U", "A",
+                    "A", "U", ("Z", 1), "J",
+                    ("Z", 2))
+SETTLE_VIEW_USERS = "SBBBASBBBBS"  # the view ring at 64 x 40: the three passes of a settle(70), batches of 70, an animated launch of 70
+
+
+@pytest.mark.parametrize("size", [(64, 40), (200, 135)])
+def test_rings_carry_converging_frames(size, ctx):
+    """Seventeen users of the four scene tables without a wait, behind _warm_up and _hold_back, six of them passes of
+    three converging frame pairs.  Two are open at once from the start, X on the context's stream and Y on a caller's,
+    and seven other users of the ring -- animated, blur and jittered launches and both passes of a progressive frame --
+    lie between the passes of each, so that the slot of every first pass has been handed on (to a jittered launch, to a
+    progressive pass) before the second pass takes one from another entry point: a stale or foreign scene record in
+    either pass lands in sums and moments the mask of the next pass is derived from.  Every pass's picture and counts and
+    every bit of both planes against converge_reference.  At 64 x 40 a settle(70) follows, 70 views per pass, with
+    batches of 70 and an animated launch of 70 between its passes: S B B B A S B B B B S, so a view-table slot passes from
+    a settling pass to an animated launch, from a batch to a settling pass and from a settling pass to a batch."""
+    import torch
+    label = lambda u: u if isinstance(u, str) else ("G" if u[0] == "G" else "C")
+    users = [label(u) for u in CONVERGING_USERS]
+    assert {("C", "J"), ("C", "G"), ("J", "C"), ("G", "C"), ("C", "A"), ("C", "U"), ("U", "C"), ("A", "C")} <= _takes_over(users, W.SCENE_RING)
+    for name in CONVERGING_FRAMES:  # both passes in order; for the two open at once, SCENE_RING and more users of other entry points between them
+        first, second = CONVERGING_USERS.index((name, 1)), CONVERGING_USERS.index((name, 2))
+        assert first < second and (name == "Z" or sum(u != "C" for u in users[first + 1:second]) >= W.SCENE_RING), name
+    assert CONVERGING_USERS.index(("Y", 1)) < CONVERGING_USERS.index(("X", 2)) and CONVERGING_USERS.index(("X", 1)) < CONVERGING_USERS.index(("Y", 2))
+    assert {("S", "A"), ("B", "S"), ("S", "B")} <= _takes_over(SETTLE_VIEW_USERS, W.VIEW_RING)
+    c = ctx(size=size)
+    lone_cam = lambda n: (2 * n + 1) % W.N_CAMERAS
+    for cam in range(W.N_CAMERAS):  # every reference before the first launch
+        c.refs.frame(size, cam)
+        c.refs.frame(size, cam, morph=W.morph_of(cam))
+    for n, user in enumerate(CONVERGING_USERS):
+        if user == "U":
+            c.refs.blur(size, lone_cam(n))
+        elif user == "J":
+            c.refs.jitter(size, lone_cam(n))
+    c.refs.progressive(size, "blur", 3)
+    for cam, _ in CONVERGING_FRAMES.values():
+        c.refs.converged(size, cam)
+    s = torch.cuda.Stream()
+    _warm_up(c, 70 if size == (64, 40) else 3)
+    held = _hold_back(torch)
+    open_ = {}
+    for n, user in enumerate(CONVERGING_USERS):
+        if isinstance(user, str):
+            c.camera(lone_cam(n))
+            stream = s if n % 2 else None
+            if user == "A":
+                c.animation(3, stream=stream)
+            elif user == "U":
+                c.blur(stream=stream)
+            else:
+                c.jitter(stream=stream)
+            continue
+        name, number = user
+        if number == 2:
+            open_.pop(name)()
+        elif name == "G":
+            c.camera(3)
+            open_[name] = c.progressive_open("blur")
+        else:
+            cam, caller = CONVERGING_FRAMES[name]
+            c.camera(cam)
+            open_[name] = c.converge_open(stream=s if caller else None)
+    assert not open_
+    if size == (64, 40):
+        c.camera(2)
+        step = None
+        for n, user in enumerate(SETTLE_VIEW_USERS):
+            if user == "S":
+                step = c.settle_open(70, stream=s) if step is None else step()
+            else:
+                c.camera(n % W.N_CAMERAS)
+                c.animation(70, stream=s if n % 2 else None) if user == "A" else c.batch(70)
+        assert not callable(step)  # all three passes are enqueued
+    c.verify()
+    del held
+
+
 def test_adaptive_scratch_across_sizes_and_counts(ctx):
     """Adaptive calls of 1, 5, 1 and 3 frames at 200 x 135, 64 x 40, 330 x 149 and 200 x 135 on one context and two streams
     in turn, an animated launch and a batch of three between each pair, nothing waited for by the test: the offsets of the
@@ -1218,8 +1668,9 @@ def test_diagnostics_buffer(ctx, kifs):
     """kifs_debug_counters sizes the per-wave record buffer for the screen of the call; a launch with more waves than it
     holds (a batch, a larger screen set since) runs as a normal launch without diagnostics, and so do an animated launch,
     an adaptive call, the accumulated launches, blur and jitter, and the passes of a progressive frame (what they leave in
-    the records is not defined).  Then the profiling ring, which the first two leave consistent and neither an accumulated
-    launch nor a pass enters."""
+    the records is not defined).  A converging frame pair and a ray query with the counters on give the bytes and the plane
+    bits they gave with them off; the trace leaves no record at all.  Then the profiling ring, which the first two leave
+    consistent and neither an accumulated launch nor a pass, converging or not, nor a ray query enters."""
     from kifs_raymarching_amd._lib import lib
     small, tiles = (330, 149), 11 * 19
     c = ctx(size=small)
@@ -1227,11 +1678,15 @@ def test_diagnostics_buffer(ctx, kifs):
     c.refs.adaptive(small, 1, 0, 0, 2)  # (the references of the first calls before the first launch)
     c.refs.blur(small, 1)
     c.refs.jitter(small, 1)
+    c.refs.converged(small, 1)
+    c.refs.rays(small, 2)
     plain = c.lone(cam=1)
     animated = c.animation(3)
     resolved, edges = c.adaptive(2)
     blurred, jittered = c.blur(), c.jitter()
     carried, carried_plane = c.progressive("blur")
+    converged, converged_sums, converged_moments = c.converge()
+    traced_geom, traced_rgba = c.trace(2)
     c.verify()
     out8 = (C.c_uint64 * 8)()
     zero = lambda: lib.kifs_debug_counters(gs._ctx, 1, out8)
@@ -1260,6 +1715,18 @@ def test_diagnostics_buffer(ctx, kifs):
     assert c.torch.equal(carried_on, carried) and c.torch.equal(carried_plane_on.view(c.torch.int32), carried_plane.view(c.torch.int32))
     assert c.torch.equal(carried, blurred)                # (identity (b): the one call's bytes)
     assert gs.debug_wave_records().shape == (4 * tiles, 4)
+    assert zero() == 0
+    int32 = c.torch.int32
+    converged_on, sums_on, moments_on = c.converge()      # a converging frame pair: the same bytes, the same bits in both planes
+    c.verify()
+    assert c.torch.equal(converged_on, converged) and c.torch.equal(sums_on.view(int32), converged_sums.view(int32))
+    assert c.torch.equal(moments_on.view(int32), converged_moments.view(int32))
+    assert gs.debug_wave_records().shape == (4 * tiles, 4)
+    assert zero() == 0
+    geom_on, rgba_on = c.trace(2)                         # and a ray query, whose copy of the frame constants has no counters
+    c.verify()
+    assert c.torch.equal(rgba_on, traced_rgba) and c.torch.equal(geom_on.view(int32), traced_geom.view(int32))
+    assert gs.debug_wave_records().shape == (4 * tiles, 4) and not gs.debug_wave_records().any()  # it left no record
     assert zero() == 0
     c.lone(2, 16, 56)                      # a band of five tile rows: 55 workgroups
     c.verify()
@@ -1311,6 +1778,11 @@ def test_diagnostics_buffer(ctx, kifs):
         c.jitter(fresh=fresh)
         assert gs.profile_read()[0] == 0
         c.progressive("blur", fresh=fresh)  # passes are not timed either (kifs_render_accumulate_resume_async): alone, an empty ring
+        assert gs.profile_read()[0] == 0
+        c.converge(fresh=fresh)             # nor is a converging pass ("not timed by kifs_set_profiling", kifs_hip.h)
+        assert gs.profile_read()[0] == 0
+        c.refs.rays(FULL, 0)
+        c.trace(0, fresh=fresh)             # and a ray query "touches no profiling record"
         assert gs.profile_read()[0] == 0
         c.blur(fresh=fresh)
         c.jitter(fresh=fresh)

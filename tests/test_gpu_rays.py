@@ -116,6 +116,32 @@ def test_every_pipeline_bit_exact(name, encode, rgs, kifs, oracle):
         assert hit.sum() >= 200 and (~hit).sum() >= 200
 
 
+@pytest.mark.parametrize("name", PIPELINES)
+@pytest.mark.parametrize("encode", [1, 0])
+def test_far_and_grazing_rays_bit_exact(name, encode, rgs, kifs, oracle):
+    """ray_cases.grazing: 1600 rays (genjulia: 8000, ray_cases.N_GRAZING_OF) whose lines are tangent to spheres of 0.3 to
+    1.15 bounding radii, from distances 2.5, 8, 31.9 and 32.1 -- the far side of rays::never_inside, both sides of its
+    |o|^2 <= 1024 switch --, direction lengths 0.5 and 1.  The reference has no cull: a ray culled wrongly is a hit turned
+    into the miss texel."""
+    _, _, gui, iters = cases(kifs, W, H)[name]
+    _scene(rgs, gui, iters)
+    key = ("grazing", name, encode)
+    if key not in _REF:
+        rays, dist, _ = ray_cases.grazing(3, ray_cases.BOUND[name], ray_cases.N_GRAZING_OF.get(name, ray_cases.N_GRAZING))
+        geom, rgba, _ = RR.trace_scene(oracle, kifs, gui, iters, rays, encode)
+        geom.setflags(write=False)
+        rgba.setflags(write=False)
+        _REF[key] = (rays, geom, rgba, dist)
+    rays, want_geom, want_rgba, dist = _REF[key]
+    st, geom, rgba = _trace(rgs._ctx, rays, encode)
+    assert st == OK
+    _assert_same(geom, want_geom, name)
+    _assert_bytes(rgba, want_rgba, name)
+    if name != "unknown_id":
+        hit = RR.hits(want_geom)
+        assert all(hit[dist == d].sum() >= 30 and (~hit)[dist == d].sum() >= 30 for d in ray_cases.DISTANCES)
+
+
 def _oracle_frame(oracle, kifs, screen, cam, options, iters, encode, shadow):
     s = oracle.from_bytes(oracle.Screen, kifs.uniform_bytes(screen.into_buffer_data()))
     c = oracle.from_bytes(oracle.Camera, kifs.uniform_bytes(cam.into_buffer_data()))

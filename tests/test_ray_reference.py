@@ -84,6 +84,46 @@ def test_the_generator_is_seeded_and_keeps_its_classes():
     assert (a[:, 3] == 0).all() and (a[:, 7] == 0).all()
 
 
+@pytest.mark.parametrize("name", [p for p in PIPELINES if p != "unknown_id"])
+def test_the_grazing_rays_hit_and_miss_at_every_distance(name, kifs, oracle):
+    """ray_cases.grazing, from the reference alone (it has no cull): at every origin distance, on either side of the ray
+    kernel's |o|^2 <= 1024 switch, at least 30 rays hit and 30 miss -- a cull that took a hitting ray, or a march that
+    lost one from far away, would change bits the GPU comparison looks at."""
+    _, _, gui, iters = cases(kifs, W, H)[name]
+    rays, dist, length = ray_cases.grazing(3, ray_cases.BOUND[name], ray_cases.N_GRAZING_OF.get(name, ray_cases.N_GRAZING))
+    assert rays.shape == (ray_cases.N_GRAZING_OF.get(name, ray_cases.N_GRAZING), 8) and rays.dtype == np.float32
+    geom, _, _ = RR.trace_scene(oracle, kifs, gui, iters, rays)
+    hit = RR.hits(geom)
+    per = {d: (int(hit[dist == d].sum()), int((~hit)[dist == d].sum())) for d in ray_cases.DISTANCES}
+    print(f"{name}: hits, misses per distance {per}; hits per length "
+          f"{ {l: int(hit[length == l].sum()) for l in ray_cases.LENGTHS} }")
+    assert all(h >= 30 and m >= 30 for h, m in per.values()), per
+    assert not np.isnan(geom).any()
+
+
+def test_the_grazing_generator_is_seeded_and_tangent():
+    a, da, la = ray_cases.grazing(3, 2.0)
+    b, db, lb = ray_cases.grazing(3, 2.0)
+    c, _, _ = ray_cases.grazing(4, 2.0)
+    assert (a.view(np.uint32) == b.view(np.uint32)).all() and (da == db).all() and (la == lb).all() and (a != c).any()
+    o, d = a[:, 0:3].astype(np.float64), a[:, 4:7].astype(np.float64)
+    assert np.allclose(np.linalg.norm(o, axis=1), da, rtol=1e-6) and np.allclose(np.linalg.norm(d, axis=1), la, rtol=1e-6)
+    for dist in ray_cases.DISTANCES:
+        assert {l: int(((da == dist) & (la == l)).sum()) for l in ray_cases.LENGTHS} == {0.5: 200, 1.0: 200}
+    oo = (o * o).sum(1)
+    assert (oo[da <= 31.9] <= 1024.0).all() and (oo[da == 32.1] > 1024.0).all()  # either side of the cull's switch
+    od = (o * d).sum(1)
+    assert (od < 0).all()  # every ray approaches
+    closest = np.sqrt(oo - od * od / (d * d).sum(1))  # of the ray's line: u * bound
+    assert (closest >= 0.3 * 2.0 - 1e-3).all() and (closest <= 1.15 * 2.0 + 1e-3).all()
+    assert (closest > 2.2).sum() >= 50 and (closest < 1.0).sum() >= 100  # beyond the radius the cull stands on, and well inside
+    tall, dt, _ = ray_cases.grazing(3, ray_cases.BOUND["cylinder"])  # the tangent sphere stays short of an origin at 2.5
+    o, d = tall[:, 0:3].astype(np.float64), tall[:, 4:7].astype(np.float64)
+    closest = np.sqrt((o * o).sum(1) - (o * d).sum(1) ** 2 / (d * d).sum(1))
+    assert (closest[dt == 2.5] <= 0.95 * 2.5 + 1e-3).all() and closest[dt == 8.0].max() > 1.1 * ray_cases.BOUND["cylinder"]
+    assert (a[:, 3] == 0).all() and (a[:, 7] == 0).all()
+
+
 def _lens_camera(kifs):
     from kifs_raymarching_amd.configs import lens_cameras
     return lens_cameras(kifs.CameraData(origin_distance=3.0, phi=0.4, theta=0.2), 0.15, 2.5, 4)[3]
