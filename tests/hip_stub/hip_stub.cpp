@@ -124,6 +124,7 @@ struct StubRenderLaunch {
     int ssaa, encode, y0, y1;
     int cull, quick_cull, tile_cull;  // on or off
     int order;                        // the allocation the tile order was read from (order_allocation_of)
+    int orbit_x2;                     // FrameParams::orbit_x2: the doubled orbit trip is allowed
 };
 static StubRenderLaunch g_last_render{};
 
@@ -372,7 +373,7 @@ hipError_t launch_render(const BatchParams& B, uint32_t, uint32_t, hipStream_t s
     const StubRenderLaunch L = {B.count, P.tile_count, P.round_steps, P.group_tiles, P.bunny_coop, P.workgroups_per_cu,
                                 P.tile_cost != nullptr, P.counters != nullptr, P.geom != nullptr, P.stripe_rows != nullptr, B.table != nullptr,
                                 P.ssaa, P.encode, P.y0, P.y1, P.cull_n2 != 0.0f, P.quick_cull_n2 != 0.0f, P.tile_cull_beta != 0.0f,
-                                order_allocation_of(P.tile_order)};
+                                order_allocation_of(P.tile_order), P.orbit_x2 != 0};
     g_last_render = L;
     if (g_trace)
         std::fprintf(g_trace, "launch_render dev=%d stream=%d count=%d tiles=%u rounds=%d group_tiles=%d bunny=%d per_cu=%d cost=%d counters=%d "

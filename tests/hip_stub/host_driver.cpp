@@ -30,6 +30,7 @@ struct StubRenderLaunch {  // hip_stub.cpp: what the latest render launch was to
     int ssaa, encode, y0, y1;
     int cull, quick_cull, tile_cull;
     int order;
+    int orbit_x2;
 };
 
 extern "C" {
@@ -993,6 +994,150 @@ void launch_shapes() {
     kifs_destroy(c);
 }
 
+// ---- the option gates (fill_params' `sane` and rounds, orbit_x2_eligible, set_culls, fill_views), from both sides --------
+// kifs_set_options refuses nothing but a group id above 2, so these values reach the gates.  A case is an options image
+// written field by field, a frame of w x h pixels, a number of views and, for fill_views, the |origin| of one view (on the
+// x axis); after its launch the culls' three digits, FrameParams::orbit_x2 and round_steps must equal the literals beside
+// it.  THE LITERALS WERE WRITTEN FROM THE GATES' DEFINITIONS (the comments name the comparison each pair brackets), not
+// from a run.  Neighbours are nextafterf of the constant.  512 x 256 pixels x 8 views = 4096 workgroups: a batch with
+// rounds; a lone frame of that size has none.  tests/option_gates.py holds the same cases for the GPU.
+const float F_NAN = std::nanf(""), F_INF = INFINITY;
+const float E15 = 1.0e15f, E15_BELOW = std::nextafterf(1.0e15f, 0.0f), E15_ABOVE = std::nextafterf(1.0e15f, F_INF);
+const float X_LO = 0x1p-14f, X_LO_BELOW = std::nextafterf(0x1p-14f, 0.0f), X_HI = 0x1p10f, X_HI_ABOVE = std::nextafterf(0x1p10f, F_INF);
+const float X_FAR = 0x1p60f, X_FAR_ABOVE = std::nextafterf(0x1p60f, F_INF);
+struct GateCase {
+    const char* what;
+    int group, prim;
+    float epsilon, max_distance;
+    float c[4];
+    int max_iterations, heatmap;
+    int w, h, views;
+    float origin;    // 0: every view from inside the bounding sphere; else |origin| of view `far_view` (of every view: -1)
+    int far_view;
+    int culls, orbit_x2, rounds;  // expected
+};
+#define C_IN {-0.2f, 0.6f, 0.2f, 0.2f}  /* every |c_i| far inside the doubled trip's window */
+const GateCase GATE_CASES[] = {
+    // E: `epsilon >= 0` for the culls, `epsilon > 0` for the rounds; bound_n2 = +inf for a NaN epsilon closes the doubled trip
+    {"E: epsilon 1e-6", JULIA, 0, 1.0e-6f, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"E: epsilon +0", JULIA, 0, 0.0f, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 0},
+    {"E: epsilon -0", JULIA, 0, -0.0f, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 0},
+    {"E: epsilon -1e-3", JULIA, 0, -1.0e-3f, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 0},
+    {"E: epsilon NaN", JULIA, 0, F_NAN, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 0, 0},
+    {"E: sphere, epsilon +0", KIFS, SPHERE, 0.0f, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 0},
+    {"E: sphere, epsilon NaN", KIFS, SPHERE, F_NAN, 1000.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 0, 0},
+    // R: `B + epsilon < 1e6` in f32 -- B = 1: 999999 and 1000001; B = 2: 999999 and 1000000
+    {"R: sphere, epsilon 999998", KIFS, SPHERE, 999998.0f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 8},
+    {"R: sphere, epsilon 1e6", KIFS, SPHERE, 1.0e6f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 8},
+    {"R: Julia, epsilon 999997", JULIA, 0, 999997.0f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"R: Julia, epsilon 999998", JULIA, 0, 999998.0f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 16},
+    {"R: Sierpinski, epsilon 999997", KIFS, SIERPINSKI, 999997.0f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 8},
+    {"R: Sierpinski, epsilon 999998", KIFS, SIERPINSKI, 999998.0f, 1.0e8f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 8},
+    // D: `max_distance < 1e15f`, a batch and a lone frame; the doubled trip wants 0 < max_distance <= 2^60
+    {"D: below 1e15", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"D: 1e15", JULIA, 0, 1.0e-4f, E15, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 16},
+    {"D: below 1e15, lone", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 1, 0, 0, /**/ 111, 1, 0},
+    {"D: 1e15, lone", JULIA, 0, 1.0e-4f, E15, C_IN, 256, 0, 512, 256, 1, 0, 0, /**/ 0, 1, 0},
+    {"D: sphere, below 1e15", KIFS, SPHERE, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 8},
+    {"D: sphere, 1e15", KIFS, SPHERE, 1.0e-4f, E15, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 8},
+    {"D: infinity", JULIA, 0, 1.0e-4f, F_INF, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 0, 16},
+    {"D: NaN", JULIA, 0, 1.0e-4f, F_NAN, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 0, 16},
+    {"D: 0", JULIA, 0, 1.0e-4f, 0.0f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"D: the GUI's 1e4", JULIA, 0, 1.0e-4f, 1.0e4f, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    // X: every |c_i| in [2^-14, 2^10], max_distance in (0, 2^60] -- where the culls are already off
+    {"X: c.x = 2^-14", JULIA, 0, 1.0e-4f, 1000.0f, {X_LO, 0.6f, 0.2f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"X: c.x below 2^-14", JULIA, 0, 1.0e-4f, 1000.0f, {X_LO_BELOW, 0.6f, 0.2f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"X: c.w = -2^-14", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, 0.6f, 0.2f, -X_LO}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"X: c.w above -2^-14", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, 0.6f, 0.2f, -X_LO_BELOW}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"X: c.y = 2^10", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, X_HI, 0.2f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 16},
+    {"X: c.y above 2^10", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, X_HI_ABOVE, 0.2f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"X: c.z = +0", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, 0.6f, 0.0f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"X: c.z = -0", JULIA, 0, 1.0e-4f, 1000.0f, {-0.2f, 0.6f, -0.0f, 0.2f}, 256, 0, 512, 256, 8, 0, 0, /**/ 111, 0, 16},
+    {"X: max_distance 2^60", JULIA, 0, 1.0e-4f, X_FAR, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 1, 16},
+    {"X: max_distance above 2^60", JULIA, 0, 1.0e-4f, X_FAR_ABOVE, C_IN, 256, 0, 512, 256, 8, 0, 0, /**/ 0, 0, 16},
+    // M: the quick cull (and with it the tile cull) wants max_iterations > 0; the round thresholds are in SHAPE_CASES
+    {"M: 1 step", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, 1, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 0},
+    {"M: 0 steps", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, 0, 0, 512, 256, 8, 0, 0, /**/ 100, 1, 0},
+    {"M: -5 steps", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, -5, 0, 512, 256, 8, 0, 0, /**/ 100, 1, 0},
+    {"M: 0 steps, heatmap", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, 0, 1, 512, 256, 8, 0, 0, /**/ 100, 1, 0},
+    {"M: sphere, 1 step", KIFS, SPHERE, 1.0e-4f, 1000.0f, C_IN, 1, 0, 512, 256, 8, 0, 0, /**/ 111, 1, 0},
+    {"M: sphere, 0 steps", KIFS, SPHERE, 1.0e-4f, 1000.0f, C_IN, 0, 0, 512, 256, 8, 0, 0, /**/ 100, 1, 0},
+    {"M: sphere, -5 steps", KIFS, SPHERE, 1.0e-4f, 1000.0f, C_IN, -5, 0, 512, 256, 8, 0, 0, /**/ 100, 1, 0},
+    // O: `|origin|^2 < 1e30` in double -- f32(1e15)^2 = 9.9999997e29, its neighbour's 1.0000001e30; lone, and one view of a batch
+    {"O: origin 1e15, lone", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 1, E15, -1, /**/ 111, 1, 0},
+    {"O: origin above 1e15, lone", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 1, E15_ABOVE, -1, /**/ 0, 1, 0},
+    {"O: one view at 1e15", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, E15, 5, /**/ 111, 1, 16},
+    {"O: one view above 1e15", JULIA, 0, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, E15_ABOVE, 5, /**/ 0, 1, 16},
+    {"O: sphere, one view at 1e15", KIFS, SPHERE, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, E15, 5, /**/ 111, 1, 8},
+    {"O: sphere, one view above 1e15", KIFS, SPHERE, 1.0e-4f, E15_BELOW, C_IN, 256, 0, 512, 256, 8, E15_ABOVE, 5, /**/ 0, 1, 8},
+    // H: the tile cull from 64 rows (512 x 64 x 64 views = 8192 workgroups)
+    {"H: 63 rows", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, 256, 0, 512, 63, 64, 0, 0, /**/ 110, 1, 16},
+    {"H: 64 rows", JULIA, 0, 1.0e-4f, 1000.0f, C_IN, 256, 0, 512, 64, 64, 0, 0, /**/ 111, 1, 16},
+};
+#undef C_IN
+
+void option_gates() {
+    stub_trace_mark("option_gates");
+    int st = 0;
+    kifs_ctx* c = kifs_create(0, &st);
+    CHECK(c && st == KIFS_OK);
+    uint8_t* frame = dev_alloc(size_t(512) * 256 * 4);  // every view of a batch writes this one frame
+    for (const GateCase& k : GATE_CASES) {
+        CHECK(k.w <= 512 && k.h <= 256 && k.views <= 64 && std::abs(k.max_iterations) <= 256);
+        KifsScreenUniform screen;
+        KifsOptionsUniform options;
+        KifsGuiData gui;
+        kifs_host_gui_default(&gui);
+        gui.fractal_group = uint32_t(k.group);
+        gui.primitive_shape = uint32_t(k.prim);
+        CHECK(kifs_host_screen(uint32_t(k.w), uint32_t(k.h), &screen) == KIFS_OK && kifs_host_options(&gui, &options) == KIFS_OK);
+        options.max_iterations = k.max_iterations;  // (written into the image: the GUI type holds none of these)
+        options.max_distance = k.max_distance;
+        options.epsilon = k.epsilon;
+        options.is_heatmap = uint32_t(k.heatmap);
+        for (int i = 0; i < 4; ++i) options.constant[i] = k.c[i];
+        KifsCameraData cd;
+        kifs_host_camera_default(&cd);
+        cd.origin_distance = IN;
+        KifsCameraUniform cam;
+        CHECK(kifs_host_camera(&cd, &cam) == KIFS_OK);
+        std::vector<KifsCameraUniform> cams(size_t(k.views), cam);
+        if (k.origin != 0.0f)
+            for (int v = 0; v < k.views; ++v)
+                if (k.far_view < 0 || v == k.far_view) {
+                    cams[size_t(v)].origin[0] = k.origin;
+                    cams[size_t(v)].origin[1] = cams[size_t(v)].origin[2] = 0.0f;
+                }
+        CHECK(kifs_set_screen(c, &screen) == KIFS_OK && kifs_set_options(c, &options) == KIFS_OK && kifs_set_camera(c, &cams[0]) == KIFS_OK);
+        const std::vector<uint8_t*> outs(size_t(k.views), frame);
+        if (k.views == 1)
+            CHECK(kifs_render_async(c, nullptr, frame, size_t(k.w) * 4, 0, k.h, 1) == KIFS_OK);
+        else
+            CHECK(kifs_render_batch_async(c, nullptr, k.views, cams.data(), outs.data(), size_t(k.w) * 4, 0, k.h, 1) == KIFS_OK);
+        StubRenderLaunch got;
+        stub_last_render(&got);
+        const int culls = 100 * got.cull + 10 * got.quick_cull + got.tile_cull;
+        const bool same = culls == k.culls && got.orbit_x2 == k.orbit_x2 && got.round_steps == k.rounds;
+        if (!same)
+            std::fprintf(stderr, "option_gates: %s: culls %03d, orbit_x2 %d, rounds %d\n", k.what, culls, got.orbit_x2, got.round_steps);
+        CHECK(same);
+        CHECK(got.count == k.views && kifs_debug_last_round_steps(c) == got.round_steps);
+    }
+    // julia_cull_radius repeats `sane` for the certified radius.  Its own range checks (16 epsilon of room below the bound,
+    // trips x log2(4 max_distance) <= 100, the escape radius inside the shell) already refuse both neighbours of every
+    // constant, so the repeat can only agree: a radius inside the GUI's ranges, none next to any gate.
+    const float c_in[4] = {-0.2f, 0.6f, 0.2f, 0.2f}, c_hi[4] = {-0.2f, X_HI, 0.2f, 0.2f}, c_hi_above[4] = {-0.2f, X_HI_ABOVE, 0.2f, 0.2f};
+    const double rho = kifs_host_julia_cull_radius(c_in, 1.0e-4f, 1000.0f, 24, nullptr);
+    CHECK(rho > 1.0 && rho < 2.0);
+    CHECK(kifs_host_julia_cull_radius(c_in, 1.0e-4f, 1.0e4f, 24, nullptr) > 1.0);
+    for (float eps : {999997.0f, 999998.0f, -1.0e-3f, -0.0f - 1.0e-30f, F_NAN}) CHECK(kifs_host_julia_cull_radius(c_in, eps, 1000.0f, 24, nullptr) == 0.0);
+    for (float md : {E15_BELOW, E15, F_INF, F_NAN}) CHECK(kifs_host_julia_cull_radius(c_in, 1.0e-4f, md, 24, nullptr) == 0.0);
+    CHECK(kifs_host_julia_cull_radius(c_hi, 1.0e-4f, 1000.0f, 24, nullptr) == 0.0);
+    CHECK(kifs_host_julia_cull_radius(c_hi_above, 1.0e-4f, 1000.0f, 24, nullptr) == 0.0);
+    CHECK(hipFree(frame) == hipSuccess);
+    kifs_destroy(c);
+}
+
 
 // ---- the adaptive and the animated entry points ----------------------------------------------------------------------
 // What the stand-in's launchers write, restated from its documentation (hip_stub.cpp: stub_key, stub_hit, stub_depth,
@@ -1695,6 +1840,7 @@ int main() {
     injected_failures(100, 50);
     context_lifecycle();
     launch_shapes();
+    option_gates();
     adaptive_batches(333, 211);  // neither dimension a multiple of the 32 x 8 tile
     adaptive_batches(96, 20);  // (every camera sees a tile that holds something)
     adaptive_scratch();

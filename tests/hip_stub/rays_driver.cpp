@@ -27,6 +27,7 @@ struct StubRenderLaunch {  // as tests/hip_stub/hip_stub.cpp declares it
     int ssaa, encode, y0, y1;
     int cull, quick_cull, tile_cull;
     int order;
+    int orbit_x2;
 };
 
 extern "C" {

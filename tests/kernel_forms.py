@@ -258,12 +258,13 @@ def shuffled_order(w, h):
 
 
 # ---- the debug tuple a launch must report --------------------------------------------------------------------------
-def expected_tuple(config, launch):
+def expected_tuple(config, launch, scenes=None):
     """The rules of kifs_schedule.cpp (fill_params, enqueue_batch) that remain once the configuration's knobs have forced
     the form: the round length per pipeline (16 Julia / gen-Julia, 8 KIFS and gen-Julia under 32 steps, 32 for a lone
     Julia frame of 64+ steps, 4 for KIFS on one wave per tile), no rounds below 2 x round_steps steps, below
-    REQUEUE_MIN_WORKGROUPS workgroups or for a lone bunny frame.  A forced KIFS_ROUND_STEPS replaces every round rule."""
-    s, knobs = SCENES[launch.scene], CONFIGS[config].knobs
+    REQUEUE_MIN_WORKGROUPS workgroups or for a lone bunny frame.  A forced KIFS_ROUND_STEPS replaces every round rule.
+    `scenes`: the table `launch.scene` names, when it is not this module's (tests/option_gates.py)."""
+    s, knobs = (SCENES if scenes is None else scenes)[launch.scene], CONFIGS[config].knobs
     views = len(launch.cams)
     forced = knobs.get("KIFS_ROUND_STEPS")
     bunny = s.group == KIFS and s.prim == BUNNY

@@ -3,9 +3,13 @@
 digest of every view to an .npz.  The KIFS_TUNING knobs that force the form come with the environment; they are read once
 per process, hence one process per configuration.
 
-    python tests/kernel_forms_child.py CONFIG OUT.npz
+    python tests/kernel_forms_child.py CONFIG OUT.npz [MODULE]
+
+MODULE (default kernel_forms) supplies plan, SCENES, options, camera and extensions: tests/test_gpu_option_gates.py passes
+option_gates.
 """
 import hashlib
+import importlib
 import sys
 from pathlib import Path
 
@@ -15,11 +19,11 @@ sys.path[:0] = [str(HERE.parent), str(HERE)]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-import kernel_forms as F  # noqa: E402
 import kifs_raymarching_amd as K  # noqa: E402
 
 
-def main(config, out_path):
+def main(config, out_path, module="kernel_forms"):
+    F = importlib.import_module(module)
     result = {}
     with K.GraphicState(0) as gs:
         for i, L in enumerate(F.plan(config)):
@@ -64,4 +68,4 @@ def main(config, out_path):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(*sys.argv[1:4])
