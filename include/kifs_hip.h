@@ -800,9 +800,14 @@ int kifs_debug_last_bunny_form(kifs_ctx* ctx);
  * frame (a permutation of (tile_x | tile_y << 16)); the order only affects speed. */
 int kifs_debug_get_tile_order(kifs_ctx* ctx, uint32_t* order, size_t max_count, size_t* count);
 int kifs_debug_set_tile_order(kifs_ctx* ctx, const uint32_t* order, size_t count);
+/* The full frame's tile costs as the launches and sorts so far left them, for tests (after a synchronisation of the
+ * device): `cost` -- what the latest recording launch wrote (row-major tile index; a sort clears it) -- and `seen` -- the
+ * memory of a batch's sorts, (largest cost of the last few sorts) << 8 | sorts since it was recorded.  Either may be NULL;
+ * `shift`, when given, receives the sort's shift for `cost`. */
+int kifs_debug_get_tile_costs(kifs_ctx* ctx, uint32_t* cost, uint32_t* seen, size_t max_count, size_t* count, uint32_t* shift);
 /* The tile-order sort on chosen costs, for tests: sorts the n host values `cost` (tile i = column i % tiles_x, row
  * i / tiles_x) exactly as a render's cost feedback would -- bin = 1023 - min(cost >> shift, 1023), lowest bin
- * (heaviest tiles) first, any order inside a bin -- on scratch device buffers and the context's stream, and returns
+ * (heaviest tiles) first, tile-index order inside a bin -- on scratch device buffers and the context's stream, and returns
  * the order (n words, tile_x | tile_y << 16) and the cost table as the kernel left it (n words, all zero).  None of
  * the context's own tile tables is read or written; no screen is needed.  n == 0, tiles_x == 0, tiles_x > 65536 or
  * more than 65536 tile rows give KIFS_ERR_BAD_SIZE; shift > 31 or a null pointer KIFS_ERR_BAD_ARG. */

@@ -180,6 +180,7 @@ SIGNATURES = {
     "kifs_eval_points": (C.c_int, [_ctx, _f32p, C.c_int, _f32p, _f32p]),
     "kifs_debug_counters": (C.c_int, [_ctx, C.c_int, _P(C.c_uint64)]),
     "kifs_debug_get_tile_order": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t, _P(C.c_size_t)]),
+    "kifs_debug_get_tile_costs": (C.c_int, [_ctx, _P(C.c_uint32), _P(C.c_uint32), C.c_size_t, _P(C.c_size_t), _P(C.c_uint32)]),
     "kifs_debug_set_tile_order": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t]),
     "kifs_debug_sort_tiles": (C.c_int, [_ctx, _P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, _P(C.c_uint32),
                                         _P(C.c_uint32)]),

@@ -394,6 +394,23 @@ int kifs_debug_get_tile_order(kifs_ctx* c, uint32_t* order, size_t max_count, si
                ? KIFS_OK : KIFS_ERR_RUNTIME;
 }
 
+int kifs_debug_get_tile_costs(kifs_ctx* c, uint32_t* cost, uint32_t* seen, size_t max_count, size_t* count, uint32_t* shift) {
+    if (!c || !count) return KIFS_ERR_BAD_ARG;
+    int w, h;
+    if (!c->have_screen || frame_dims(c, &w, &h) != KIFS_OK) return KIFS_ERR_UNCONFIGURED;
+    DeviceGuard g(c->device);
+    const TileTable* tt = tile_table(c, w, h, 0, h);
+    if (!tt) return KIFS_ERR_RUNTIME;
+    if (tt->count > max_count) return KIFS_ERR_BAD_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return KIFS_ERR_RUNTIME;
+    *count = tt->count;
+    if (shift) *shift = tt->cost_shift;
+    const size_t bytes = tt->count * sizeof(uint32_t);
+    if (cost && hipMemcpy(cost, tt->d_cost, bytes, hipMemcpyDeviceToHost) != hipSuccess) return KIFS_ERR_RUNTIME;
+    if (seen && hipMemcpy(seen, tt->d_seen, bytes, hipMemcpyDeviceToHost) != hipSuccess) return KIFS_ERR_RUNTIME;
+    return KIFS_OK;
+}
+
 int kifs_debug_sort_tiles(kifs_ctx* c, const uint32_t* cost, size_t n, uint32_t tiles_x, uint32_t shift, uint32_t* order_out,
                           uint32_t* cost_after_out) {
     if (!c || !cost || !order_out || !cost_after_out || shift > 31) return KIFS_ERR_BAD_ARG;

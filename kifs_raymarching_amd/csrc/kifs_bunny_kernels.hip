@@ -188,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void render_bunny_coop_kernel(const BatchPar
     __syncthreads();
 
     // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's run time
-    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, t_start);
+    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, feedback ? cost_from_cycles(__builtin_amdgcn_s_memtime() - t_start) : 0u);
 }
 
 hipError_t launch_bunny_coop(const BatchParams& B, hipStream_t stream) {

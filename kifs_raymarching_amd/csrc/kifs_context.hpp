@@ -36,6 +36,10 @@ struct TileTable {
     uint32_t* d_order = nullptr;      // order used by the next launch
     uint32_t* d_order_alt = nullptr;  // the other half of the double buffer (the sort's target)
     uint32_t* d_cost = nullptr;       // per-tile cost, written by the first launch of a feedback period, read by the sort
+    uint32_t* d_seen = nullptr;       // a batch's sorts: every tile's largest cost of the last few of them (tile_order_kernel)
+    uint32_t cost_shift = 0;          // the sort's shift for what d_cost holds: set by the launch that records (work_cost_shift)
+    uint64_t seen_scene = 0;          // what d_seen's costs were recorded with: options, iteration counts and shift (scene_key)
+    bool seen_stale = false;          // d_cost comes from another scene or scale than d_seen: the next sort starts the memory afresh
     hipEvent_t costs_written = nullptr;  // recorded after the launch that wrote d_cost
     hipEvent_t stream_left = nullptr;    // recorded on the stream the caller moved away from
     hipEvent_t sorted = nullptr;      // recorded after the sort that fills d_order_alt

@@ -37,6 +37,10 @@ hipError_t launch_trace_rays(const rays::Params& R, uint32_t group, uint32_t pri
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,
                              uint32_t tiles_x, uint32_t shift, hipStream_t stream);
+// The same for a batch's costs, with a memory: seen[] (tile_count words, zero at first) keeps every tile's largest cost
+// of the last `window` (1..255) calls, and the order is made from that.  window 1: the order of cost[] alone.
+hipError_t launch_tile_order_remembering(uint32_t* cost, uint32_t* seen, uint32_t* order, uint32_t tile_count,
+                                         uint32_t tiles_x, uint32_t shift, uint32_t window, hipStream_t stream);
 // Packed row shards -> frame rows: stripe s of shard f (8 rows at src + f * src_shard_stride + 8 s *
 // src_pitch) goes to frame rows stripe_rows[s].. of dst + f * dst_frame_stride.
 hipError_t launch_unpack_stripes(uint8_t* dst, size_t dst_pitch, size_t dst_frame_stride, const uint8_t* src,

@@ -343,6 +343,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     // (wave w: chunks w, w + 4, ..) the waves with the cheap ones waited at the round's barrier -- SQ_WAIT_ANY was 54 %
     // of the gen-Julia kernel's wave-cycles, 48 % of the bunny's (profiles/r04/stalls.json).  Same rotation as q_count.
     __shared__ uint32_t q_ticket[3];
+    __shared__ uint32_t s_work;  // march steps of every chunk-round so far (see the rounds): the group's cost
     static_assert(!W2LDS || (GROUP == GROUP_KIFS && PRIM == PRIM_BUNNY), "W2LDS is a form of the bunny's network");
     __shared__ float s_w2[W2LDS ? 256 : 1];  // (bunny, W2LDS: layer 2 of the network for the four column groups, see kifs_bunny.hpp)
 
@@ -356,8 +357,8 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     const int lx = (wave << 3) | (lane & 7);  // wave w -> 8x8 block w of a tile
     const int ly = lane >> 3;
     const bool feedback = P.tile_cost != nullptr;
-    const unsigned long long t_start = feedback ? __builtin_amdgcn_s_memtime() : 0ull;
     if (tid == 0) {
+        s_work = 0;
         q_count[0] = 0;
         q_count[1] = 0;
         q_count[2] = 0;
@@ -395,6 +396,11 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
         // (one chunk left: nothing more to merge, it is marched to the end -- see render_wave_kernel; not the
         // generalised Julia set, whose compiled march loses 5-10 % that way: 48 frames per launch 20.6 -> 19.6 Gpixel/s)
         const int limit = (GROUP != GROUP_GENJULIA && n <= RAYS) ? P.max_iterations : min(trips + P.round_steps, P.max_iterations);
+        // The group's cost (cost_from_work).  Which rays share a chunk depends on the order the waves filed them in, so a
+        // round of several chunks counts every chunk for the round's whole length -- a bound that depends on the number
+        // of live rays alone, the same whenever the same views are rendered; a single chunk counts the steps it ran.
+        const bool one_chunk = n <= RAYS;
+        if (tid == 0 && feedback && !one_chunk) s_work += ((n + RAYS - 1u) / RAYS) * uint32_t(limit - trips);
         const uint32_t cnt_next = (cnt + 1u) % 3u;
         for (;;) {
             uint32_t chunk = 0;
@@ -433,6 +439,7 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
             const unsigned long long mq = __builtin_amdgcn_ballot_w64(marching && leader);
             uint32_t bh = 0, bq = 0;
             if (lane == 0) {
+                if (feedback && one_chunk) s_work += uint32_t(wave_trips - trips);  // (the only chunk of the round)
                 if (mh) bh = atomicAdd(&h_count, uint32_t(__builtin_popcountll(mh)));
                 if (mq) bq = atomicAdd(&q_count[cnt_next], uint32_t(__builtin_popcountll(mq)));
             }
@@ -485,8 +492,8 @@ __global__ __launch_bounds__(BLOCK) void render_group_kernel(const BatchParams B
     }
     __syncthreads();
 
-    // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's run time
-    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, t_start);
+    // ---- store: linear rows of 128 bytes; cost of the group's tiles: the workgroup's work
+    store_group<T>(P, s_tiles, s_rows, s_tile, tid, S.batch, feedback, cost_from_work(s_work, hits));
 }
 
 // render_wave_kernel<GROUP, PRIM>: the throughput path with ONE WAVE per workgroup and tile.
@@ -528,7 +535,6 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     const uint32_t lane = threadIdx.x;
     const bool srgb = (P.encode == 1);
     const bool feedback = P.tile_cost != nullptr;
-    const unsigned long long t_start = feedback ? __builtin_amdgcn_s_memtime() : 0ull;
     const uint32_t tile = P.tile_order[slot];  // scalar load
     const int tile_x = int(tile & 0xffffu) * TILE_W;
     const int tile_y = int(tile >> 16) * TILE_H;         // row offset within the launch's rows
@@ -580,7 +586,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     __syncthreads();  // one wave: orders the LDS traffic, costs nothing
 
     // ---- rounds
-    uint32_t hits = 0;
+    uint32_t hits = 0, work = 0;  // work: march steps of every chunk-round so far, the tile's cost (cost_from_work)
     int trips = 0;
     for (uint32_t cur = 0; n != 0u; cur ^= 1u) {
         // Re-queuing pays when it turns several partly empty chunks into fewer full ones.  Once the tile's rays fit ONE
@@ -606,6 +612,7 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
             int wave_trips = trips;
             march_round<GROUP, PRIM, true>(P, dir, t, p, hit, marching, wave_trips, limit);  // the orbit in its scalar form
             __builtin_amdgcn_s_setprio(0);
+            work += uint32_t(wave_trips - trips);
             const unsigned long long mh = __builtin_amdgcn_ballot_w64(hit);
             const unsigned long long mq = __builtin_amdgcn_ballot_w64(marching);
             if (hit) {
@@ -655,18 +662,9 @@ __global__ __launch_bounds__(64) void render_wave_kernel(const BatchParams B) {
     }
     __syncthreads();
 
-    // ---- store: two full 128-byte rows per instruction; cost of the tile: the wave's run time
+    // ---- store: two full 128-byte rows per instruction; cost of the tile: the wave's work
     store_tile_wave(P, tile_x, tile_y, frame_y, lane, s_tile);
-    if (feedback) {
-        const unsigned long long cycles = __builtin_amdgcn_s_memtime() - t_start;
-        const uint32_t cost = uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
-        if (lane == 0) {
-            const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
-            uint32_t* cs = &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)];
-            if (batch > 1) atomicMax(cs, cost);  // the batch's views share the table (the sort clears it)
-            else *cs = cost;
-        }
-    }
+    if (feedback && lane == 0) record_tile_cost(tile_cost_slot(P, tile), cost_from_work(work, hits), batch);
 }
 
 // Dynamic LDS requested only to cap how many workgroups share a CU (the kernel never touches

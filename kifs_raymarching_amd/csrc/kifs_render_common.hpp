@@ -3,7 +3,7 @@
 // (launch_slot, batch_frame), the tile <-> frame row mapping of bands and row shards, the tile and lane prologue of the
 // whole-ray kernels (tile_origin, tile_frame), the wave- and tile-level forms of the bounding-sphere cull, a ray's
 // position (ray_at), the guarded store of a staged tile (store_tile, store_tile_wave, store_group) and the cost
-// write-back (tile_cost_slot, cost_from_cycles, record_tile_cost).  Host side: the pipeline dispatch
+// write-back (tile_cost_slot, cost_from_cycles, cost_from_work, record_tile_cost).  Host side: the pipeline dispatch
 // (dispatch_pipeline) and the opt-in to large dynamic LDS (ensure_dynamic_lds).
 // render_wave_kernel and the Julia builds are at the edge of their register budgets (the hand-written loop pins v30-v63
 // and s74-s97): where a helper cost one of them a register or a spill, that kernel keeps the text in place -- the
@@ -230,9 +230,16 @@ __device__ __forceinline__ void store_tile_wave(const FrameParams& P, int tile_x
     }
 }
 
-// Cost of a tile for the next frame's tile order (tile_order_kernel): the run time of the wave or workgroup that
-// rendered it in units of 1024 cycles, minus a floor that maps culled / instant ones to 0 (march steps alone are too
-// coarse: hundreds of tiles tie at max_iterations).
+// Cost of a tile for the next frame's tile order (tile_order_kernel).  render_kernel and the bunny's kernels: the run time
+// of the wave or workgroup that rendered it in units of 1024 cycles, minus a floor that maps culled / instant ones to 0
+// (march steps alone are too coarse there: hundreds of tiles tie at max_iterations).  The throughput kernels
+// (render_wave_kernel, render_group_kernel): the WORK of the tile's wave or workgroup, a count it holds anyway -- the march
+// steps of every chunk-round it ran (render_group_kernel, whose chunks are drawn by ticket: a round of several chunks
+// counts in full), plus WORK_PER_SHADED_CHUNK for every chunk of hits it shaded.  A run time depends on
+// who shared the SIMD and on when in the launch the wave ran, and it saturated the sort's 1024 bins from 1.05 M cycles,
+// which one tile in ten of a 48-frame launch exceeds; the count is the same whenever the same views are rendered, and
+// work_cost_shift() (kifs_schedule.cpp) fits its range -- 4 chunks per tile x max_iterations -- to the bins.
+constexpr uint32_t WORK_PER_SHADED_CHUNK = 8u;  // (a hit's normal and shading: about eight march steps' instructions)
 __device__ __forceinline__ uint32_t* tile_cost_slot(const FrameParams& P, uint32_t tile) {
     const uint32_t tiles_x = uint32_t(P.width + TILE_W - 1) / TILE_W;
     return &P.tile_cost[(tile >> 16) * tiles_x + (tile & 0xffffu)];
@@ -240,18 +247,20 @@ __device__ __forceinline__ uint32_t* tile_cost_slot(const FrameParams& P, uint32
 __device__ __forceinline__ uint32_t cost_from_cycles(unsigned long long cycles) {
     return uint32_t(min(cycles > 4096ull ? (cycles - 4096ull) >> 10 : 0ull, 1ull << 20));
 }
+__device__ __forceinline__ uint32_t cost_from_work(uint32_t march_steps, uint32_t hits) {
+    return min(march_steps + WORK_PER_SHADED_CHUNK * ((hits + 63u) >> 6), 1u << 20);  // (saturates)
+}
 __device__ __forceinline__ void record_tile_cost(uint32_t* slot, uint32_t cost, uint32_t batch) {
     if (batch > 1) atomicMax(slot, cost);  // the batch's views share the table (the sort clears it)
     else *slot = cost;
 }
 
 // The end of the two queue kernels, 256 threads: the T staged tiles of the group to the destination; cost of each of
-// them: the workgroup's run time since `t_start`.
+// them: the workgroup's, `cost`.
 template <int T>
 __device__ __forceinline__ void store_group(const FrameParams& P, const uint32_t* s_tiles, const int* s_rows,
                                             const uint32_t (*s_tile)[TILE_H][TILE_W], int tid, uint32_t batch, bool feedback,
-                                            unsigned long long t_start) {
-    const uint32_t cost = feedback ? cost_from_cycles(__builtin_amdgcn_s_memtime() - t_start) : 0u;
+                                            uint32_t cost) {
     for (int j = 0; j < T; ++j) {
         const uint32_t tile = s_tiles[j];
         if (tile == 0xffffffffu) break;

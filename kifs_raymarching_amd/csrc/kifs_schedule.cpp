@@ -34,6 +34,10 @@ constexpr uint32_t FEEDBACK_MIN_TILES = 2048u;        // Julia pipelines: 720p a
 constexpr uint32_t FEEDBACK_MIN_TILES_KIFS = 16384u;  // KIFS: 8K 2.58 -> 2.23 ms, 1080p nothing (round 1, same way)
 constexpr int FEEDBACK_PERIOD_LONE = 4;               // refresh every n-th lone launch           (tools/sweep_period.sh, r02)
 constexpr int FEEDBACK_PERIOD_BATCH = 3;              // every n-th batched launch                (tools/sweep_period.sh, r02)
+// a batch's order is made from every tile's largest cost of its last n sorts (n x the period launches), not of the last one:
+// 1080p Julia x48 on the orbit, five sets of poses in turn, n = 1/3/5/8/16/32/64: 0.788/0.781/0.721/0.719/0.722/0.718/0.723 ms
+// (KIFS_ORDER_WINDOW; profiles/r16/README.md) -- flat once the window holds every set; 16 sorts are 48 launches
+constexpr uint32_t ORDER_WINDOW_BATCH = 16u;
 // ray re-queuing: march steps per round
 constexpr int ROUND_STEPS_JULIA = 16;     // Julia and generalised Julia (4/8/12/16/24/32 -> 62.8/72.2/75.0/76.8/76.8/77.6
                                           // Gpixel/s at 32 frames per launch)                    (tools/sweep_rounds.sh)
@@ -63,7 +67,7 @@ constexpr double BUNNY_COOP_FROM = 5000.0;    // four waves per 64 rays (same fi
 }  // namespace rules
 
 // Tuning overrides (KIFS_ROUND_STEPS, KIFS_GROUP_TILES, KIFS_BUNNY_COOP, KIFS_TILE_FEEDBACK, KIFS_JULIA_CERT_CULL,
-// KIFS_FEEDBACK_PERIOD, KIFS_BATCH_PERIOD; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as well: they exist
+// KIFS_FEEDBACK_PERIOD, KIFS_BATCH_PERIOD, KIFS_ORDER_WINDOW; KIFS_LDS_PAD in kifs_kernels.hip) are honoured only when KIFS_TUNING=1 is set as well: they exist
 // for tools/sweep_kernels.sh and friends, not for production hosts.  Read once per process, clamped here.
 struct Knobs {
     int round_steps, group_tiles;        // -1: not set
@@ -71,6 +75,7 @@ struct Knobs {
     int tile_feedback;                   // 0 = never, 1 (default) = per pipeline thresholds, 2 = every frame of 2048+ tiles
     int julia_cert_cull;                 // 0: the Julia culls stay on the patch sphere (julia_culls); -1 / other: certified radius
     uint64_t period_lone, period_batch;  // launches between two refreshes of the tile order
+    uint32_t order_window;               // sorts a batch's order remembers (1: the latest costs alone)
 };
 static const Knobs& knobs() {
     static const Knobs k = [] {
@@ -80,10 +85,11 @@ static const Knobs& knobs() {
             return e ? int(std::strtol(e, nullptr, 10)) : -1;
         };
         const int coop = knob("KIFS_BUNNY_COOP"), mode = knob("KIFS_TILE_FEEDBACK");
-        const int lone = knob("KIFS_FEEDBACK_PERIOD"), batch = knob("KIFS_BATCH_PERIOD");
+        const int lone = knob("KIFS_FEEDBACK_PERIOD"), batch = knob("KIFS_BATCH_PERIOD"), window = knob("KIFS_ORDER_WINDOW");
         return Knobs{knob("KIFS_ROUND_STEPS"), knob("KIFS_GROUP_TILES"), std::min(coop, 2), mode >= 0 ? mode : 1, knob("KIFS_JULIA_CERT_CULL"),
                      uint64_t(lone < 0 ? rules::FEEDBACK_PERIOD_LONE : lone < 3 ? 3 : lone),
-                     uint64_t(batch < 0 ? rules::FEEDBACK_PERIOD_BATCH : batch < 2 ? 2 : batch)};
+                     uint64_t(batch < 0 ? rules::FEEDBACK_PERIOD_BATCH : batch < 2 ? 2 : batch),
+                     window < 1 ? rules::ORDER_WINDOW_BATCH : uint32_t(std::min(window, 255))};
     }();
     return k;
 }
@@ -410,6 +416,7 @@ void free_table(TileTable& t) {
     if (t.d_order) (void)hipFree(t.d_order);
     if (t.d_order_alt) (void)hipFree(t.d_order_alt);
     if (t.d_cost) (void)hipFree(t.d_cost);
+    if (t.d_seen) (void)hipFree(t.d_seen);
     if (t.costs_written) (void)hipEventDestroy(t.costs_written);
     if (t.stream_left) (void)hipEventDestroy(t.stream_left);
     if (t.sorted) (void)hipEventDestroy(t.sorted);
@@ -484,11 +491,13 @@ TileTable* tile_table(kifs_ctx* c, int width, int height, int y0, int y1, const 
     if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_order), bytes), "hipMalloc(tile order)") ||
         !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_order_alt), bytes), "hipMalloc(tile order 2)") ||
         !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_cost), bytes), "hipMalloc(tile cost)") ||
+        !hip_ok(hipMalloc(reinterpret_cast<void**>(&slot->d_seen), bytes), "hipMalloc(tile cost memory)") ||
         !hip_ok(hipEventCreateWithFlags(&slot->costs_written, hipEventDisableTiming), "hipEventCreate") ||
         !hip_ok(hipEventCreateWithFlags(&slot->stream_left, hipEventDisableTiming), "hipEventCreate") ||
         !hip_ok(hipEventCreateWithFlags(&slot->sorted, hipEventDisableTiming), "hipEventCreate") ||
         !hip_ok(hipMemcpy(slot->d_order, order.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(tile order)") ||
-        !hip_ok(hipMemset(slot->d_cost, 0, bytes), "hipMemset(tile cost)")) {
+        !hip_ok(hipMemset(slot->d_cost, 0, bytes), "hipMemset(tile cost)") ||
+        !hip_ok(hipMemset(slot->d_seen, 0, bytes), "hipMemset(tile cost memory)")) {
         free_table(*slot);
         return nullptr;
     }
@@ -650,12 +659,16 @@ static int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, u
     return KIFS_OK;
 }
 
-// Temporal feedback on the tile order.  A launch can leave a cost per tile (the run time of the tile's slowest wave); a
-// one-workgroup counting sort on the context's side stream turns those costs into a new order while the following launch
-// is running, so the sort is off the critical path.  The longest rays sit at the fractal's silhouette, which no static
+// Temporal feedback on the tile order.  A launch can leave a cost per tile (render_kernel: the run time of the tile's
+// slowest wave; the throughput kernels: the work of its wave or workgroup, cost_from_work); a one-workgroup counting sort
+// on the context's side stream turns those costs into a new order while the following launch is running, so the sort is
+// off the critical path.  The longest rays sit at the fractal's silhouette, which no static
 // order knows; with them first the frame ends when they do.  Tables:
 //   d_order      read by the launches      d_order_alt   written by the sort, then swapped in
 //   d_cost       written by the first launch of a period, read by the sort
+//   d_seen       a batch's sorts only: every tile's largest cost of the last ORDER_WINDOW_BATCH sorts, which the order is
+//                made from -- a batch's views move on between launches (an orbit), and the order of the latest views alone
+//                served the next ones worse than no feedback at all (profiles/r16/launch_spread.md)
 // Events order everything whichever streams the caller uses.  Off for small frames, where it does not pay for itself;
 // KIFS frames gain from it only when they are large (8K: 2.58 -> 2.23 ms; 1080p: nothing).
 // The order is refreshed every `period` launches (views change slowly; the events the refresh needs cost a few
@@ -704,8 +717,17 @@ static int feedback_before(kifs_ctx* c, TileTable* tt, hipStream_t stream, int c
     // cost[] twice and must not see it change.
     if (tt->sort_pending && adopt_sorted_order(tt, stream) != KIFS_OK) return KIFS_ERR_RUNTIME;
     if (f->inline_sort && f->k == 1) {
-        if (!hip_ok(kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, 0, stream), "tile_order_kernel launch"))
-            return KIFS_ERR_RUNTIME;
+        // A batch's sort remembers (tile_order_kernel): its views move, and where the long tiles were for the last few sets
+        // of views says more about the next set than the latest set alone.  d_seen belongs to these sorts, which are in
+        // stream order; a lone launch's sort (rules fitted to the latest costs) neither reads nor writes it.
+        // Costs of another scene or on another scale (options, iteration counts or the launch's shape changed since the
+        // memory's were recorded: record_scene) say nothing about this one: a window of one sort replaces every entry.
+        const uint32_t window = tt->seen_stale ? 1u : knobs().order_window;
+        if (count > 1) tt->seen_stale = false;  // (only the remembering sort takes the memory's fresh start)
+        const hipError_t e = count > 1 ? kifs::launch_tile_order_remembering(tt->d_cost, tt->d_seen, tt->d_order_alt, tt->count, tiles_x,
+                                                                             tt->cost_shift, window, stream)
+                                       : kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, tt->cost_shift, stream);
+        if (!hip_ok(e, "tile_order_kernel launch")) return KIFS_ERR_RUNTIME;
         std::swap(tt->d_order, tt->d_order_alt);  // stream order: the sort precedes this launch
     }
     return KIFS_OK;
@@ -737,12 +759,39 @@ static int feedback_after(kifs_ctx* c, TileTable* tt, hipStream_t stream, uint32
         // all of which precede launch 0 of this period
         if (!c->side_stream && !hip_ok(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking), "side stream")) return KIFS_ERR_RUNTIME;
         if (!hip_ok(hipStreamWaitEvent(c->side_stream, tt->costs_written, 0), "wait(render 0)") ||
-            !hip_ok(kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, 0, c->side_stream), "tile_order_kernel launch") ||
+            !hip_ok(kifs::launch_tile_order(tt->d_cost, tt->d_order_alt, tt->count, tiles_x, tt->cost_shift, c->side_stream), "tile_order_kernel launch") ||
             !hip_ok(hipEventRecord(tt->sorted, c->side_stream), "record(sorted)"))
             return KIFS_ERR_RUNTIME;
         tt->sort_pending = true;
     }
     return KIFS_OK;
+}
+
+// The sort's shift for the costs the launch P describes records.  The throughput kernels record work (cost_from_work: at
+// most 4 chunks per tile x (max_iterations march steps + one shaded chunk)), which the sort's 1024 bins must resolve up
+// to the top; render_kernel records run times in units of 1024 cycles, sorted as they are.
+static uint32_t work_cost_shift(const kifs::FrameParams& P) {
+    if (P.round_steps <= 0) return 0u;
+    const uint64_t top = 4ull * uint64_t(std::max(P.group_tiles, 1)) * (uint64_t(std::max(P.max_iterations, 0)) + 8ull);
+    uint32_t shift = 0;
+    while (shift < 31u && (top >> shift) > 1023ull) ++shift;
+    return shift;
+}
+
+// What a batch's recorded costs depend on besides the views: the scene (options, iteration counts, extensions) and the
+// scale they are counted on (the shape's shift).  A recording launch whose key differs from the memory's marks it stale.
+static void record_scene(const kifs_ctx* c, TileTable* tt) {
+    uint64_t h = 1469598103934665603ull;  // FNV-1a
+    const auto mix = [&h](const void* p, size_t n) {
+        for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+    };
+    const int iters[3] = {c->sdf_iters, c->normal_iters, c->fold_iters};
+    mix(&c->options, sizeof c->options);
+    mix(iters, sizeof iters);
+    mix(&c->ext, sizeof c->ext);
+    mix(&tt->cost_shift, sizeof tt->cost_shift);
+    if (h != tt->seen_scene) tt->seen_stale = true;
+    tt->seen_scene = h;
 }
 
 // A residency-capped lone Julia frame keeps the patch sphere's culls.  With one workgroup per CU the certified radius made
@@ -912,6 +961,15 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
     if (plain) {
         P.tile_cost = feedback.record_costs ? tt->d_cost : nullptr;
         choose_shape(c, P, count, h);
+        if (feedback.record_costs) {
+            tt->cost_shift = work_cost_shift(P);
+            if (count > 1) {
+                record_scene(c, tt);
+            } else {  // a lone launch's costs, should a batch's sort meet them: not the memory's scene either
+                tt->seen_scene = 0;
+                tt->seen_stale = true;
+            }
+        }
     } else {
         fixed_shape(c, P, count, h);
     }

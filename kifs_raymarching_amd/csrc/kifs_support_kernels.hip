@@ -7,24 +7,41 @@ namespace kifs {
 
 // ---- tile order from the previous frame's costs -----------------------------------------
 // One 1024-thread workgroup: histogram of clamped costs (bin 0 = heaviest), exclusive scan,
-// scatter.  Whatever the cost values are, the result is a permutation of the tile ids, so a
+// stable scatter.  Whatever the cost values are, the result is a permutation of the tile ids, so a
 // stale or garbage cost table can only cost speed, never pixels.
+// `seen` (batched launches; nullptr: none): the order's memory.  A batch's views move -- an orbit's next launch shows
+// other poses than the one that was measured -- and the tiles that were long for the last poses say little about the
+// next ones, while the tiles that were long for ANY recent pose say a lot (profiles/r16/README.md).  seen[i] keeps the
+// largest cost tile i had in the last `window` sorts (cost << 8 | sorts since it was recorded) and the order is made
+// from that; a value that was not reached again within the window gives way to the newest cost.
 __global__ __launch_bounds__(1024) void tile_order_kernel(uint32_t* __restrict__ cost,
                                                           uint32_t* __restrict__ order, uint32_t n,
-                                                          uint32_t tiles_x, uint32_t shift) {
+                                                          uint32_t tiles_x, uint32_t shift,
+                                                          uint32_t* __restrict__ seen, uint32_t window) {
     constexpr uint32_t BINS = 1024, LAST = BINS - 1;  // bin 0 = heaviest, LAST = cost 0
+    constexpr uint32_t SEEN_COST_MAX = (1u << 24) - 1u;  // (the kernels' costs end at 2^20)
     __shared__ uint32_t bins[BINS];
     __shared__ uint32_t wave_total[16];
+    __shared__ uint8_t wave_bin[16][BINS];  // the scatter: tiles of a round per (wave, bin), at most 64
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     bins[tid] = 0;
+    for (uint32_t v = 0; v < 16u; ++v) wave_bin[v][tid] = 0;
     __syncthreads();
     const uint32_t rounds = (n + 1023u) / 1024u;  // wave-uniform trip count (ballots inside)
+    if (seen) {  // each thread its own tiles, here and below: no barrier needed in between
+        for (uint32_t i = tid; i < n; i += 1024u) {
+            const uint32_t now = min(cost[i], SEEN_COST_MAX), old = seen[i];
+            const uint32_t age = (old & 0xffu) + 1u;
+            seen[i] = (now >= (old >> 8) || age >= window) ? now << 8 : (old & ~0xffu) | age;
+        }
+    }
+    const auto key = [&](uint32_t i) { return seen ? seen[i] >> 8 : cost[i]; };
     // After the culls almost every tile has cost 0: that class is counted with one atomic per
     // wave (ballot + popcount) instead of 64 atomics on the same LDS word.
     for (uint32_t k = 0; k < rounds; ++k) {
         const uint32_t i = k * 1024u + tid;
         const bool live = i < n;
-        const uint32_t bin = live ? LAST - min(cost[i] >> shift, LAST) : 0u;
+        const uint32_t bin = live ? LAST - min(key(i) >> shift, LAST) : 0u;
         const bool zero = live && bin == LAST;
         const unsigned long long zmask = __builtin_amdgcn_ballot_w64(zero);
         if (lane == 0 && zmask) atomicAdd(&bins[LAST], uint32_t(__builtin_popcountll(zmask)));
@@ -44,29 +61,56 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(uint32_t* __restrict__
     for (uint32_t k = 0; k < w; ++k) base += wave_total[k];
     bins[tid] = base + incl - mine;  // exclusive prefix = first slot of this bin
     __syncthreads();
+    // The scatter is STABLE -- equal bins in tile-index order, so equal cost tables give equal orders.  A round's 1024 tiles
+    // are consecutive; inside a wave a tile's rank among the lanes of its bin is a ballot and a prefix count, one distinct
+    // bin at a time; across the waves the counts per (wave, bin) sit in LDS, a tile adds those of the waves below its
+    // own, and the thread that owns a bin moves its slot on by the round's total.  No atomics.
     for (uint32_t k = 0; k < rounds; ++k) {
         const uint32_t i = k * 1024u + tid;
         const bool live = i < n;
-        const uint32_t bin = live ? LAST - min(cost[i] >> shift, LAST) : 0u;
-        const bool zero = live && bin == LAST;
-        const unsigned long long zmask = __builtin_amdgcn_ballot_w64(zero);
-        uint32_t zbase = 0;
-        if (lane == 0 && zmask) zbase = atomicAdd(&bins[LAST], uint32_t(__builtin_popcountll(zmask)));
-        zbase = __shfl(zbase, 0);
-        uint32_t pos;
-        if (zero) pos = zbase + uint32_t(__builtin_popcountll(zmask & ((1ull << lane) - 1ull)));
-        else if (live) pos = atomicAdd(&bins[bin], 1u);
+        const uint32_t bin = live ? LAST - min(key(i) >> shift, LAST) : 0u;
+        uint32_t rank = 0;
+        for (unsigned long long todo = __builtin_amdgcn_ballot_w64(live); todo != 0ull;) {  // wave-uniform
+            const int first = __builtin_ctzll(todo);
+            const uint32_t b = __shfl(bin, first);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(live && bin == b);
+            if (live && bin == b) {
+                rank = uint32_t(__builtin_popcountll(m & ((1ull << lane) - 1ull)));
+                if (int(lane) == first) wave_bin[w][b] = uint8_t(__builtin_popcountll(m));
+            }
+            todo &= ~m;
+        }
+        __syncthreads();
         if (live) {
+            uint32_t pos = bins[bin] + rank;
+            for (uint32_t v = 0; v < w; ++v) pos += wave_bin[v][bin];
             order[pos] = (i % tiles_x) | ((i / tiles_x) << 16);
             cost[i] = 0;  // ready for the next recording launch (batches accumulate with atomicMax)
         }
+        __syncthreads();
+        uint32_t total = 0;
+        for (uint32_t v = 0; v < 16u; ++v) {  // this thread's bin
+            total += wave_bin[v][tid];
+            wave_bin[v][tid] = 0;
+        }
+        bins[tid] += total;
+        __syncthreads();
     }
 }
 
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,
                              uint32_t tiles_x, uint32_t shift, hipStream_t stream) {
     if (tile_count == 0) return hipSuccess;
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, cost, order, tile_count, tiles_x, shift);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, cost, order, tile_count, tiles_x, shift,
+                       static_cast<uint32_t*>(nullptr), 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_order_remembering(uint32_t* cost, uint32_t* seen, uint32_t* order, uint32_t tile_count,
+                                         uint32_t tiles_x, uint32_t shift, uint32_t window, hipStream_t stream) {
+    if (tile_count == 0) return hipSuccess;
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, cost, order, tile_count, tiles_x, shift, seen,
+                       window < 1u ? 1u : window > 255u ? 255u : window);
     return hipGetLastError();
 }
 

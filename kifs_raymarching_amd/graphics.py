@@ -944,6 +944,16 @@ class GraphicState:
                                             buf.size, C.byref(n)), "get_tile_order")
         return buf[:n.value].copy()
 
+    def debug_get_tile_costs(self):
+        """(cost, seen, shift) of the full frame's tile table (kifs_debug_get_tile_costs): what the latest recording launch
+        wrote, the memory of a batch's sorts (cost << 8 | age) and the sort's shift for the costs."""
+        tiles = ((self.screen_data.width + 31) // 32) * ((self.screen_data.height + 7) // 8)
+        cost, seen = np.zeros(tiles, dtype=np.uint32), np.zeros(tiles, dtype=np.uint32)
+        n, shift = C.c_size_t(0), C.c_uint32(0)
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        check(lib.kifs_debug_get_tile_costs(self._ctx, up(cost), up(seen), cost.size, C.byref(n), C.byref(shift)), "get_tile_costs")
+        return cost[:n.value].copy(), seen[:n.value].copy(), int(shift.value)
+
     def debug_set_tile_order(self, order):
         o = np.ascontiguousarray(order, dtype=np.uint32)
         check(lib.kifs_debug_set_tile_order(self._ctx, o.ctypes.data_as(C.POINTER(C.c_uint32)),

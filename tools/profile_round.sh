@@ -3,11 +3,24 @@
 # Run on the GPU box from the repo root; results land in gpurun_out/prof/ (tools/profile_summary.py
 # turns them into the files kept under profiles/rNN/).  Counters are collected in passes of their own
 # (--pmc only; never combined with a trace), as MI355X_MICROARCH.md prescribes.
+# KIFS_PROFILE_HEADLINE_ONLY=1: the three counter passes of the headline launch alone (what profiles/pmc_traffic.json and
+# bench.py's roofline.valu_issue need after a change of the kernels), each under a time limit.
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd $R
+if [ -n "$KIFS_PROFILE_HEADLINE_ONLY" ]; then
+  cp $R/kifs_raymarching_amd/libkifs_hip.so.srchash $O/srchash.txt
+  cd /tmp && export TMPDIR=/tmp
+  B="$R/bench.py --cpu-seconds 0 --no-secondary"
+  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o cfg2 --output-format csv -- python3 $B --steps 12 --warmup 4 > $O/pmc_write.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o cfg2 --output-format csv -- python3 $B --steps 12 --warmup 4 > $O/pmc_fetch.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -d $O/pmc_sq -o cfg2 --output-format csv -- python3 $B --steps 12 --warmup 4 > $O/pmc_sq.log 2>&1
+  echo "pmc headline done"
+  find $O -name "*counter_collection.csv" | head
+  exit 0
+fi
 python bench.py --full > $O/cfg2_bench.json
 echo "bench default done"
 : > $O/other_workloads_bench.jsonl
