@@ -354,91 +354,72 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
 
 // From 63 sub-frames the dynamic LDS and the 1 KB sRGB table together pass the default limit of 48 KB: the kernel then opts
 // in, once per instantiation and device, as ensure_dynamic_lds does for the residency pad (kifs_render_common.hpp).
-enum Family { PLAIN, JITTERED, CARRIED, CONVERGING };
-template <int GROUP, int PRIM, Family FAMILY>
+template <auto KERNEL>
 static hipError_t ensure_lds(unsigned dynamic_bytes) {
     if (dynamic_bytes + 256u * unsigned(sizeof(float)) <= 48u * 1024u) return hipSuccess;
     static std::atomic<bool> opted_in[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev < 0 || dev >= 64 || !opted_in[dev].load(std::memory_order_acquire)) {
-        const void* const kernel = FAMILY == CONVERGING ? reinterpret_cast<const void*>(&converge_render_kernel<GROUP, PRIM>)
-                                   : FAMILY == CARRIED  ? reinterpret_cast<const void*>(&carry_render_kernel<GROUP, PRIM>)
-                                   : FAMILY == JITTERED ? reinterpret_cast<const void*>(&jitter_render_kernel<GROUP, PRIM>)
-                                                        : reinterpret_cast<const void*>(&render_kernel<GROUP, PRIM>);
-        hipError_t attr = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         if (attr != hipSuccess) return attr;
         if (dev >= 0 && dev < 64) opted_in[dev].store(true, std::memory_order_release);
     }
     return hipSuccess;
 }
 
-template <int GROUP, int PRIM, bool JITTER>
-static hipError_t launch(const Params& A, hipStream_t stream) {
+// One launch of the family: KERNEL is the instantiation, K its argument, A the Params at K's head.
+template <auto KERNEL, typename ARG>
+static hipError_t launch(const ARG& K, const Params& A, hipStream_t stream) {
     const unsigned lds = unsigned(A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
-    if (hipError_t e = ensure_lds<GROUP, PRIM, JITTER ? JITTERED : PLAIN>(lds); e != hipSuccess) return e;
+    if (hipError_t e = ensure_lds<KERNEL>(lds); e != hipSuccess) return e;
     const dim3 grid(A.B.frame.tile_count * BLOCKS * uint32_t(A.frames));
-    if (JITTER)
-        hipLaunchKernelGGL((jitter_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
-    else
-        hipLaunchKernelGGL((render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, A);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(BLOCK), lds, stream, K);
     return hipGetLastError();
 }
 
-template <int GROUP, int PRIM>
-static hipError_t launch_carry(const CarryParams& K, hipStream_t stream) {
-    const unsigned lds = unsigned(K.A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
-    if (hipError_t e = ensure_lds<GROUP, PRIM, CARRIED>(lds); e != hipSuccess) return e;
-    const dim3 grid(K.A.B.frame.tile_count * BLOCKS * uint32_t(K.A.frames));
-    hipLaunchKernelGGL((carry_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, K);
-    return hipGetLastError();
+// What every launcher refuses of the Params: the views are frames x samples, the grid is 1..KIFS_MAX_JITTER_GRID.
+static bool valid(const Params& A) {
+    return A.frames >= 1 && A.samples >= 1 && A.samples <= 64 && A.B.count == A.frames * A.samples && A.B.frame.ssaa >= 1 &&
+           A.B.frame.ssaa <= 8;
 }
 
-template <int GROUP, int PRIM>
-static hipError_t launch_converge(const ConvergeParams& K, hipStream_t stream) {
-    const unsigned lds = unsigned(K.A.samples) * SLOT * unsigned(sizeof(float));  // at most 48 KB
-    if (hipError_t e = ensure_lds<GROUP, PRIM, CONVERGING>(lds); e != hipSuccess) return e;
-    const dim3 grid(K.A.B.frame.tile_count * BLOCKS * uint32_t(K.A.frames));
-    hipLaunchKernelGGL((converge_render_kernel<GROUP, PRIM>), grid, dim3(BLOCK), lds, stream, K);
-    return hipGetLastError();
+// The pipeline's instantiation of a launcher's kernel.  Julia: the short divide / square root by sdf_iters; the doubled
+// orbit trip is the throughput kernels' only.  The bunny: per-lane bunny_sdf -- slow, correct.
+template <typename F>
+static hipError_t dispatch(const Params& A, uint32_t group, uint32_t primitive, F&& f) {
+    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), f);
 }
 
 }  // namespace accum
 
 hipError_t launch_accumulate_render(const accum::Params& A, uint32_t group, uint32_t primitive, hipStream_t stream) {
-    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
-    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
+    if (!accum::valid(A)) return hipErrorInvalidValue;
     const bool jitter = A.B.frame.ssaa > 1;  // a cell per sub-frame in its scene record: jitter_render_kernel
-    // Julia: the short divide / square root by sdf_iters; the doubled orbit trip is the throughput kernels' only.
-    // The bunny: per-lane bunny_sdf -- slow, correct.
-    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
-        return jitter ? accum::launch<decltype(g)::value, decltype(prim)::value, true>(A, stream)
-                      : accum::launch<decltype(g)::value, decltype(prim)::value, false>(A, stream);
+    return accum::dispatch(A, group, primitive, [&](auto g, auto prim) {
+        constexpr int G = decltype(g)::value, P = decltype(prim)::value;
+        return jitter ? accum::launch<accum::jitter_render_kernel<G, P>>(A, A, stream) : accum::launch<accum::render_kernel<G, P>>(A, A, stream);
     });
 }
 
 hipError_t launch_accumulate_carry(const accum::CarryParams& K, uint32_t group, uint32_t primitive, hipStream_t stream) {
     const accum::Params& A = K.A;
-    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
-    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
-    if (!K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
+    if (!accum::valid(A) || !K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
         uint64_t(K.prior) + uint64_t(A.samples) > (1ull << 24))
         return hipErrorInvalidValue;  // (refused by the API before it gets here)
-    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
-        return accum::launch_carry<decltype(g)::value, decltype(prim)::value>(K, stream);
+    return accum::dispatch(A, group, primitive, [&](auto g, auto prim) {
+        return accum::launch<accum::carry_render_kernel<decltype(g)::value, decltype(prim)::value>>(K, A, stream);
     });
 }
 
 hipError_t launch_accumulate_converge(const accum::ConvergeParams& K, uint32_t group, uint32_t primitive, hipStream_t stream) {
     const accum::Params& A = K.A;
-    if (A.frames < 1 || A.samples < 1 || A.samples > 64 || A.B.count != A.frames * A.samples) return hipErrorInvalidValue;
-    if (A.B.frame.ssaa < 1 || A.B.frame.ssaa > 8) return hipErrorInvalidValue;  // 1..KIFS_MAX_JITTER_GRID
-    if (!K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
+    if (!accum::valid(A) || !K.sums || (reinterpret_cast<uintptr_t>(K.sums) & 15u) != 0 || K.sums_pitch_texels < uint32_t(A.B.frame.width) ||
         !K.moments || (reinterpret_cast<uintptr_t>(K.moments) & 3u) != 0 || K.moments_pitch_words < uint32_t(A.B.frame.width) ||
         K.min_samples < 2u || K.min_samples > (1u << 24) || !(K.tol2 >= 0.0f))
         return hipErrorInvalidValue;  // (refused by the API before it gets here)
-    return dispatch_pipeline<2>(group, primitive, uint32_t(A.B.frame.sdf_iters <= 24), [&](auto g, auto prim) {
-        return accum::launch_converge<decltype(g)::value, decltype(prim)::value>(K, stream);
+    return accum::dispatch(A, group, primitive, [&](auto g, auto prim) {
+        return accum::launch<accum::converge_render_kernel<decltype(g)::value, decltype(prim)::value>>(K, A, stream);
     });
 }
 

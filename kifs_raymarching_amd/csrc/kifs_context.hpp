@@ -5,8 +5,12 @@
 //   kifs_shards.cpp    row shards and sparse shards (the multi-GPU partition's per-device entry points)
 //   kifs_multi.cpp     one process driving several devices (kifs_multi_*)
 //   kifs_adaptive.cpp  adaptive anti-aliasing (kifs_render_adaptive_async): scratch block, rounds, the three passes
-//   kifs_animation.cpp animated batches (kifs_render_animation_async): the scene-table ring, one launch
-//   kifs_accumulate.cpp accumulated frames (kifs_render_accumulate_async): sub-frames as views of one launch
+//   kifs_animation.cpp animated batches (kifs_render_animation_async), and the launch path of every call that carries
+//                      a scene table (launch_scenes): the scene-table ring, one launch
+//   kifs_accumulate.cpp accumulated frames (kifs_render_accumulate_async, _jittered_async): sub-frames as views
+//   kifs_progressive.cpp progressive accumulation (kifs_render_accumulate_resume_async): a plane of sums across launches
+//   kifs_converge.cpp  converging accumulation (kifs_render_accumulate_converge_async): sums, moments and a rule
+//   kifs_rays.cpp      ray queries (kifs_trace_rays_async): caller-supplied rays, one launch
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -174,15 +178,25 @@ bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what);
 
 }  // namespace host
 
-// What kifs_animation.cpp shares with kifs_accumulate.cpp: both launches carry a scene per view through the scene-table ring.
+// What every launch that carries a scene table shares (kifs_animation.cpp): the animated call and the four accumulated
+// ones differ in their checks and in the last step, the launch itself.
+namespace accum {
+
+// The sub-pixel cells of a jittered call: sub-frame v goes through cell cells[v] of the grid x grid cells of its pixel;
+// cells == nullptr (samples == grid * grid): sub-frame s of every frame through cell (s % grid, s / grid).
+struct Jitter {
+    int grid;
+    const KifsSubpixel* cells;
+};
+// The launch step of a SceneLaunch: receives the filled Params, the pipeline and the stream.
+typedef hipError_t (*LaunchFn)(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void* user);
+
+}  // namespace accum
+
 namespace anim {
 
 // The fields every view of a launch shares (one pipeline, one march budget), compared as bit patterns.
 bool same_pipeline(const KifsOptionsUniform& a, const KifsOptionsUniform& b);
-// The next slot of the scene-table ring, free to be rewritten when the call returns.
-int take_scene_slot(kifs_ctx* c, int* slot);
-// A launch on another stream than the tile table's feedback launches follows them.
-int follow_stream_change(TileTable* tt, hipStream_t stream);
 
 // The launch's frame constants come from fill_params, which reads the context's options: for the length of a call the
 // context holds frame 0's image in their place and gets its own back at the end, set or not.
@@ -202,20 +216,33 @@ struct OptionsOfFrame0 {
     OptionsOfFrame0& operator=(const OptionsOfFrame0&) = delete;
 };
 
+// One call that its entry point has checked: `frames` output frames of `samples` sub-frames each, the views of one launch
+// (view f * samples + s is sub-frame s of frame f and carries that frame's destination; an animated batch has samples 1).
+struct SceneLaunch {
+    int frames, samples;
+    const KifsCameraUniform* cameras;   // a camera per view; null: the context's
+    const KifsOptionsUniform* options;  // a scene per view; null: the context's for every view
+    const accum::Jitter* jitter;        // null: no cell, a grid of 1
+    uint8_t* const* outs;               // null: a pass without a picture (every view a null destination, no pitch)
+    size_t pitch;
+    int y0, y1, encode;
+    int last_kernel;                    // what kifs_debug_last_kernel reports afterwards
+    // The last step: `launch` receives the filled accum::Params (an animated batch's step makes its anim::Params of
+    // them) and `user`.  `workgroups_per_entry` != 0: the launcher's grid is that many workgroups per entry of the
+    // tile order and frame, and a call whose grid would pass 2^31 - 1 is refused (KIFS_ERR_BAD_SIZE).
+    accum::LaunchFn launch;
+    void* user;
+    uint32_t workgroups_per_entry;
+};
+// The call itself: the context's device and stream (`hip_stream` null), view 0's options for the context's, and the one
+// launch -- views, scene table, rings, tile table, copies, launch step, events.
+int launch_scenes(kifs_ctx* c, void* hip_stream, const SceneLaunch& L);
+
 }  // namespace anim
 
-// What kifs_accumulate.cpp shares with kifs_progressive.cpp: a pass of a progressive frame is the jittered call's launch
-// with another kernel behind it.
+// What kifs_accumulate.cpp shares with kifs_progressive.cpp and kifs_converge.cpp: a pass of a progressive frame is the
+// jittered call with more to refuse and another launch step.
 namespace accum {
-
-// The sub-pixel cells of a jittered call: sub-frame v goes through cell cells[v] of the grid x grid cells of its pixel;
-// cells == nullptr (samples == grid * grid): sub-frame s of every frame through cell (s % grid, s / grid).
-struct Jitter {
-    int grid;
-    const KifsSubpixel* cells;
-};
-// The launch step of enqueue(): receives the filled Params, the pipeline and the stream.
-typedef hipError_t (*LaunchFn)(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void* user);
 
 // What every accumulated call refuses.  `outs_optional`: a null `outs` array is accepted (a pass without a picture); a
 // null or misaligned entry of a given array is refused either way.
@@ -223,12 +250,12 @@ int check(const kifs_ctx* c, int count, int samples, const KifsCameraUniform* ca
           uint8_t* const* outs, size_t pitch, int y0, int y1, int encode, bool outs_optional = false);
 // What the jittered call refuses beyond check(): after it, so that every refusal of the unjittered call keeps its status.
 int check_jitter(const kifs_ctx* c, int count, int samples, const Jitter& j);
-// The one launch of an accumulated call; `outs` may be null when check() allowed it (every view then carries a null
-// destination and `pitch` is ignored).  `launch` is the last step: the two calls of kifs_accumulate.cpp pass
-// launch_accumulate_render, a pass of a progressive frame wraps the Params into its CarryParams (`user`).
-int enqueue(kifs_ctx* c, hipStream_t stream, int count, int samples, const KifsCameraUniform* cameras,
-            const KifsOptionsUniform* options, const Jitter* jitter, uint8_t* const* outs, size_t pitch, int y0, int y1, int encode,
-            LaunchFn launch, void* user);
+// What a pass refuses of a plane it carries across launches -- the sums (16-byte texels) or the moments (4-byte ones):
+// `count` bands of `rows` rows of `width` texels, `pitch` and `stride` in bytes.  The layout rules are the geometry
+// output's (set_destination, kifs_schedule.cpp).
+int check_plane(const void* plane, size_t pitch, size_t stride, size_t texel_bytes, int width, size_t rows, int count);
+// The three accumulate launchers' grid: four workgroups per entry of the order and output frame (SceneLaunch).
+constexpr uint32_t WORKGROUPS_PER_ENTRY = 4;
 
 }  // namespace accum
 }  // namespace kifs

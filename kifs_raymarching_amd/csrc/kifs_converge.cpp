@@ -1,7 +1,7 @@
 // kifs_converge.cpp -- the host side of converging accumulation (kifs_render_accumulate_converge_async,
 // include/kifs_hip.h): one pass of a progressive frame that marches only the pixels whose mean has not settled.  A pass
-// is the jittered accumulated call's launch (accum::check, check_jitter and enqueue of kifs_accumulate.cpp) with a launch
-// step of its own, as kifs_progressive.cpp has: it zeroes the caller's counts on the stream and wraps the filled Params
+// is the jittered accumulated call (accum::check and check_jitter of kifs_accumulate.cpp, then the SceneLaunch of
+// kifs_animation.cpp) with a launch step of its own, as kifs_progressive.cpp has: it zeroes the caller's counts on the stream and wraps the filled Params
 // into a ConvergeParams -- the two planes, the rule, whether the pass restarts and whether it has destinations -- for
 // launch_accumulate_converge (kifs_accumulate_kernels.hip).  The library keeps nothing between passes.
 #include <cmath>
@@ -21,26 +21,6 @@ struct Converging {
     KifsConvergence rule;
     uint32_t* counts;  // may be null
 };
-
-// What the pass refuses beyond check() and check_jitter(): after them, so that every refusal of the resume call keeps
-// its status.  The sums plane's rules are that call's; the moments plane's are the same with 4 bytes per pixel.
-static int check_state(const kifs_ctx* c, int count, const Converging& p, const KifsConvergence* rule, int y0, int y1) {
-    int w = 0, h = 0;
-    if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
-    const size_t rows = size_t(y1 - y0);
-    if (!p.sums || (reinterpret_cast<uintptr_t>(p.sums) & 15u) != 0) return KIFS_ERR_BAD_ARG;
-    if (p.sums_pitch < size_t(w) * 16 || (p.sums_pitch & 15u) != 0 || (p.sums_pitch >> 4) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if ((p.sums_stride & 15u) != 0 || (p.sums_stride >> 4) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if (count > 1 && p.sums_stride < rows * p.sums_pitch) return KIFS_ERR_BAD_ARG;
-    if (!p.moments || (reinterpret_cast<uintptr_t>(p.moments) & 3u) != 0) return KIFS_ERR_BAD_ARG;
-    if (p.moments_pitch < size_t(w) * 4 || (p.moments_pitch & 3u) != 0 || (p.moments_pitch >> 2) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if ((p.moments_stride & 3u) != 0 || (p.moments_stride >> 2) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if (count > 1 && p.moments_stride < rows * p.moments_pitch) return KIFS_ERR_BAD_ARG;
-    if (!rule) return KIFS_ERR_BAD_ARG;
-    if (std::isnan(rule->tolerance) || rule->tolerance < 0.0f) return KIFS_ERR_BAD_ARG;
-    if (rule->min_samples < 2u || rule->min_samples > KIFS_MAX_PROGRESSIVE_SAMPLES) return KIFS_ERR_BAD_ARG;
-    return KIFS_OK;
-}
 
 static hipError_t launch_converge(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void* user) {
     const Converging& p = *static_cast<const Converging*>(user);
@@ -76,13 +56,20 @@ extern "C" int kifs_render_accumulate_converge_async(kifs_ctx* c, void* hip_stre
     if (const int st = accum::check(c, count, samples, cameras, options, dev_outs, pitch, y0, y1, encode, true); st != KIFS_OK) return st;
     const accum::Jitter jitter{grid, cells};
     if (const int st = accum::check_jitter(c, count, samples, jitter); st != KIFS_OK) return st;
+    // What the pass refuses beyond check() and check_jitter(): after them, so that every refusal of the resume call
+    // keeps its status.  The sums plane's rules are that call's; the moments plane's are the same with 4 bytes per pixel.
+    int w = 0, h = 0;
+    if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
+    const size_t rows = size_t(y1 - y0);
+    if (const int st = accum::check_plane(dev_sums, sums_pitch, sums_stride, 16, w, rows, count); st != KIFS_OK) return st;
+    if (const int st = accum::check_plane(dev_moments, moments_pitch, moments_stride, 4, w, rows, count); st != KIFS_OK) return st;
+    if (!rule) return KIFS_ERR_BAD_ARG;
+    if (std::isnan(rule->tolerance) || rule->tolerance < 0.0f) return KIFS_ERR_BAD_ARG;
+    if (rule->min_samples < 2u || rule->min_samples > KIFS_MAX_PROGRESSIVE_SAMPLES) return KIFS_ERR_BAD_ARG;
     accum::Converging state{dev_sums, sums_pitch, sums_stride, dev_moments, moments_pitch, moments_stride, restart != 0,
-                            dev_outs != nullptr, rule ? *rule : KifsConvergence{0.0f, 0u}, dev_active_counts};
-    if (const int st = accum::check_state(c, count, state, rule, y0, y1); st != KIFS_OK) return st;
-    host::DeviceGuard g(c->device);
-    if (!g.ok) return KIFS_ERR_RUNTIME;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
-    // (an empty band returns from enqueue before the launch step: nothing enqueued, the counts untouched)
-    return accum::enqueue(c, s, count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode, accum::launch_converge, &state);
+                            dev_outs != nullptr, *rule, dev_active_counts};
+    // (an empty band returns before the launch step: nothing enqueued, the counts untouched)
+    return anim::launch_scenes(c, hip_stream, anim::SceneLaunch{count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode,
+                                                                KIFS_KERNEL_ACCUMULATE, accum::launch_converge, &state,
+                                                                accum::WORKGROUPS_PER_ENTRY});
 }

@@ -1,5 +1,6 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
-// kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip).
+// kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip,
+// kifs_rays_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

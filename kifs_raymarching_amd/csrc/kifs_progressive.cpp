@@ -1,7 +1,7 @@
 // kifs_progressive.cpp -- the host side of progressive accumulation (kifs_render_accumulate_resume_async,
 // include/kifs_hip.h): one PASS of a frame whose linear sums are carried across launches in a plane of the caller's.  A
-// pass is the jittered accumulated call's launch (accum::check, check_jitter and enqueue of kifs_accumulate.cpp: the same
-// views, scene table, rings and debug hooks) with another kernel behind it: the launch step wraps the filled Params into
+// pass is the jittered accumulated call (accum::check and check_jitter of kifs_accumulate.cpp, then the SceneLaunch of
+// kifs_animation.cpp: the same views, scene table, rings and debug hooks) with another kernel behind it: the launch step wraps the filled Params into
 // a CarryParams -- the plane, the sub-frames it already holds, whether the pass has destinations -- for
 // launch_accumulate_carry (kifs_accumulate_kernels.hip).  The library keeps nothing between passes.
 #include "kifs_context.hpp"
@@ -16,19 +16,6 @@ struct Plane {
     uint32_t prior;
     bool picture;
 };
-
-// What the pass refuses beyond check() and check_jitter(): after them, so that every refusal of the jittered call keeps
-// its status.  The layout rules are the geometry output's (set_destination, kifs_schedule.cpp).
-static int check_plane(const kifs_ctx* c, int count, int samples, const Plane& p, int y0, int y1) {
-    int w = 0, h = 0;
-    if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
-    if (!p.sums || (reinterpret_cast<uintptr_t>(p.sums) & 15u) != 0) return KIFS_ERR_BAD_ARG;
-    if (p.pitch < size_t(w) * 16 || (p.pitch & 15u) != 0 || (p.pitch >> 4) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if ((p.stride & 15u) != 0 || (p.stride >> 4) > 0xffffffffull) return KIFS_ERR_BAD_ARG;
-    if (count > 1 && p.stride < size_t(y1 - y0) * p.pitch) return KIFS_ERR_BAD_ARG;
-    if (uint64_t(p.prior) + uint64_t(samples) > uint64_t(KIFS_MAX_PROGRESSIVE_SAMPLES)) return KIFS_ERR_BAD_ARG;
-    return KIFS_OK;
-}
 
 static hipError_t launch_carry(const Params& A, uint32_t group, uint32_t primitive, hipStream_t stream, void* user) {
     const Plane& p = *static_cast<const Plane*>(user);
@@ -54,11 +41,14 @@ extern "C" int kifs_render_accumulate_resume_async(kifs_ctx* c, void* hip_stream
     if (const int st = accum::check(c, count, samples, cameras, options, dev_outs, pitch, y0, y1, encode, true); st != KIFS_OK) return st;
     const accum::Jitter jitter{grid, cells};
     if (const int st = accum::check_jitter(c, count, samples, jitter); st != KIFS_OK) return st;
+    // What the pass refuses beyond check() and check_jitter(): after them, so that every refusal of the jittered call
+    // keeps its status.
+    int w = 0, h = 0;
+    if (const int st = host::frame_dims(c, &w, &h); st != KIFS_OK) return st;
+    if (const int st = accum::check_plane(dev_sums, sums_pitch, sums_stride, 16, w, size_t(y1 - y0), count); st != KIFS_OK) return st;
+    if (uint64_t(prior_samples) + uint64_t(samples) > uint64_t(KIFS_MAX_PROGRESSIVE_SAMPLES)) return KIFS_ERR_BAD_ARG;
     accum::Plane plane{dev_sums, sums_pitch, sums_stride, prior_samples, dev_outs != nullptr};
-    if (const int st = accum::check_plane(c, count, samples, plane, y0, y1); st != KIFS_OK) return st;
-    host::DeviceGuard g(c->device);
-    if (!g.ok) return KIFS_ERR_RUNTIME;
-    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    anim::OptionsOfFrame0 scope(c, options ? options[0] : c->options);
-    return accum::enqueue(c, s, count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode, accum::launch_carry, &plane);
+    return anim::launch_scenes(c, hip_stream, anim::SceneLaunch{count, samples, cameras, options, &jitter, dev_outs, pitch, y0, y1, encode,
+                                                                KIFS_KERNEL_ACCUMULATE, accum::launch_carry, &plane,
+                                                                accum::WORKGROUPS_PER_ENTRY});
 }

@@ -186,6 +186,48 @@ def _producer_stream(dest):
     return int(torch.cuda.current_stream(dest.device).cuda_stream)
 
 
+# ---- what the wrappers of the calls that carry a scene per view share (render_animation, render_accumulate*); `name`
+# is the calling method's, for the message
+def _accumulated_views(name, cameras, samples, per="per frame"):
+    """The camera array of an accumulated call, its views and its output frames."""
+    cams = camera_array(cameras)
+    views = len(cams)
+    if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
+        raise ValueError(f"{name}: 1..{MAX_ACCUMULATE} samples {per}, count * samples cameras, at most {MAX_BATCH} of them")
+    return cams, views, views // samples
+
+
+def _one_per_view(name, what, items, views):
+    if items is not None and len(items) != views:
+        raise ValueError(f"{name}: {len(items)} {what} for {views} cameras")
+    return items
+
+
+def _frame_outs(name, outs, n, rows, w, device):
+    """`outs` (None: a new tensor) as the uint8 (n, rows, w, 4) destination, and the array of its frames' pointers."""
+    import torch
+    if outs is None:
+        outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", device))
+    if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
+        raise ValueError(f"{name}: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+    base, frame_bytes = _device_pointer(outs), rows * w * 4
+    return outs, (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
+
+
+def _jitter_cells(name, jitter, views, samples, centre=True):
+    """(grid, cells) as the C calls take them.  `centre`: the rule of the resume and converge calls for cells None,
+    which C takes only for the whole grid in order -- a grid of 1 then gets the pixel centre for every view."""
+    grid, cells = (1, None) if jitter is None else jitter
+    if cells is not None and not isinstance(cells, C.Array):
+        cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
+    _one_per_view(name, "cells", cells, views)
+    if centre and cells is None and samples != int(grid) * int(grid):
+        if int(grid) != 1:
+            raise ValueError(f"{name}: cells None needs samples == grid * grid")
+        cells = (KifsSubpixel * views)()  # cell (0, 0) of the one-cell grid
+    return int(grid), cells
+
+
 class GraphicState:
     """render/graphics.rs:25-37.  Owns one library context bound to one HIP device."""
 
@@ -527,7 +569,6 @@ class GraphicState:
         device; `outs`: a contiguous destination tensor of that shape to reuse.  Enqueued on `stream` like render_async
         and ordered after torch's current stream; the caller synchronises before reading, and keeps a tensor this
         method allocated alive until the launch has run (as with render_geometry_batch's planes)."""
-        import torch
         w, h = self.screen_data.width, self.screen_data.height
         y1 = h if y1 is None else y1
         rows = max(y1 - y0, 0)
@@ -535,16 +576,11 @@ class GraphicState:
         n = len(opts)
         if not 1 <= n <= MAX_BATCH:
             raise ValueError(f"render_animation: 1..{MAX_BATCH} frames")
-        if cameras is not None and len(cameras) != n:
-            raise ValueError(f"render_animation: {n} option images for {len(cameras)} cameras")
-        if outs is None:
-            outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
-            raise ValueError(f"render_animation: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+        if cameras is not None:
+            _one_per_view("render_animation", "option images", opts, len(cameras))
+        outs, ptrs = _frame_outs("render_animation", outs, n, rows, w, self.device)
         stream = self._stream_handle(stream, "render_animation")
         cams = None if cameras is None else camera_array(cameras)
-        base, frame_bytes = _device_pointer(outs), rows * w * 4
-        ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
         self._order_after_producer(outs, stream)
         check(lib.kifs_render_animation_async(self._ctx, stream, n, cams, opts, ptrs, w * 4, y0, y1, encode),
               "render_animation")
@@ -566,38 +602,21 @@ class GraphicState:
         instead of the centre (kifs_render_accumulate_jittered_async: the blur's rays anti-alias too); cells: a sequence
         of len(cameras) pairs (configs.jitter_cells), a ready KifsSubpixel array, or None with samples == grid * grid for
         the supersampling order (configs.grid_cells).  None: today's call and bytes."""
-        import torch
         w, h = self.screen_data.width, self.screen_data.height
         y1 = h if y1 is None else y1
         rows = max(y1 - y0, 0)
         samples = int(samples)
-        cams = camera_array(cameras)
-        views = len(cams)
-        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
-            raise ValueError(f"render_accumulate: 1..{MAX_ACCUMULATE} samples per frame, count * samples cameras, at most "
-                             f"{MAX_BATCH} of them")
-        n = views // samples
-        opts = None if options is None else options_array(options)
-        if opts is not None and len(opts) != views:
-            raise ValueError(f"render_accumulate: {len(opts)} option images for {views} cameras")
-        if outs is None:
-            outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
-            raise ValueError(f"render_accumulate: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
+        cams, views, n = _accumulated_views("render_accumulate", cameras, samples)
+        opts = _one_per_view("render_accumulate", "option images", None if options is None else options_array(options), views)
+        outs, ptrs = _frame_outs("render_accumulate", outs, n, rows, w, self.device)
         stream = self._stream_handle(stream, "render_accumulate")
-        base, frame_bytes = _device_pointer(outs), rows * w * 4
-        ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
         self._order_after_producer(outs, stream)
         if jitter is None:
             check(lib.kifs_render_accumulate_async(self._ctx, stream, n, samples, cams, opts, ptrs, w * 4, y0, y1, encode),
                   "render_accumulate")
             return outs
-        grid, cells = jitter
-        if cells is not None and not isinstance(cells, C.Array):
-            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
-        if cells is not None and len(cells) != views:
-            raise ValueError(f"render_accumulate: {len(cells)} cells for {views} cameras")
-        check(lib.kifs_render_accumulate_jittered_async(self._ctx, stream, n, samples, cams, opts, int(grid), cells, ptrs, w * 4,
+        grid, cells = _jitter_cells("render_accumulate", jitter, views, samples, centre=False)
+        check(lib.kifs_render_accumulate_jittered_async(self._ctx, stream, n, samples, cams, opts, grid, cells, ptrs, w * 4,
                                                         y0, y1, encode), "render_accumulate")
         return outs
 
@@ -619,42 +638,22 @@ class GraphicState:
         y1 = h if y1 is None else y1
         rows = max(y1 - y0, 0)
         samples, prior = int(samples), int(prior)
-        cams = camera_array(cameras)
-        views = len(cams)
-        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
-            raise ValueError(f"render_accumulate_resume: 1..{MAX_ACCUMULATE} samples per frame and pass, count * samples "
-                             f"cameras, at most {MAX_BATCH} of them")
+        cams, views, n = _accumulated_views("render_accumulate_resume", cameras, samples, "per frame and pass")
         if not 0 <= prior <= _lib.MAX_PROGRESSIVE_SAMPLES - samples:
             raise ValueError(f"render_accumulate_resume: prior + samples within 0..{_lib.MAX_PROGRESSIVE_SAMPLES}")
-        n = views // samples
-        opts = None if options is None else options_array(options)
-        if opts is not None and len(opts) != views:
-            raise ValueError(f"render_accumulate_resume: {len(opts)} option images for {views} cameras")
+        opts = _one_per_view("render_accumulate_resume", "option images", None if options is None else options_array(options), views)
         if (not isinstance(sums, torch.Tensor) or tuple(sums.shape) != (n, rows, w, 4) or sums.dtype != torch.float32
                 or not sums.is_contiguous() or not sums.is_cuda):
             raise ValueError(f"render_accumulate_resume: sums float32 ({n}, {rows}, {w}, 4), contiguous, on the device")
         ptrs = None
         if picture:
-            if outs is None:
-                outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
-            if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
-                raise ValueError(f"render_accumulate_resume: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
-            base, frame_bytes = _device_pointer(outs), rows * w * 4
-            ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
-        grid, cells = (1, None) if jitter is None else jitter
-        if cells is not None and not isinstance(cells, C.Array):
-            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
-        if cells is not None and len(cells) != views:
-            raise ValueError(f"render_accumulate_resume: {len(cells)} cells for {views} cameras")
-        if cells is None and samples != int(grid) * int(grid):  # (the C call takes NULL only for the whole grid in order)
-            if int(grid) != 1:
-                raise ValueError("render_accumulate_resume: cells None needs samples == grid * grid")
-            cells = (KifsSubpixel * views)()  # the pixel centre: cell (0, 0) of the one-cell grid
+            outs, ptrs = _frame_outs("render_accumulate_resume", outs, n, rows, w, self.device)
+        grid, cells = _jitter_cells("render_accumulate_resume", jitter, views, samples)
         stream = self._stream_handle(stream, "render_accumulate_resume")
         self._order_after_producer(sums, stream)
         if picture:
             self._order_after_producer(outs, stream)
-        check(lib.kifs_render_accumulate_resume_async(self._ctx, stream, n, samples, cams, opts, int(grid), cells,
+        check(lib.kifs_render_accumulate_resume_async(self._ctx, stream, n, samples, cams, opts, grid, cells,
                                                       _device_pointer(sums), w * 16, rows * w * 16, prior, ptrs, w * 4, y0, y1,
                                                       encode), "render_accumulate_resume")
         return outs if picture else None
@@ -675,18 +674,11 @@ class GraphicState:
         y1 = h if y1 is None else y1
         rows = max(y1 - y0, 0)
         samples = int(samples)
-        cams = camera_array(cameras)
-        views = len(cams)
-        if not 1 <= samples <= MAX_ACCUMULATE or not 1 <= views <= MAX_BATCH or views % samples:
-            raise ValueError(f"render_accumulate_converge: 1..{MAX_ACCUMULATE} samples per frame and pass, count * samples "
-                             f"cameras, at most {MAX_BATCH} of them")
-        n = views // samples
+        cams, views, n = _accumulated_views("render_accumulate_converge", cameras, samples, "per frame and pass")
         tolerance, min_samples = float(rule[0]), int(rule[1])
         if not tolerance >= 0.0 or not 2 <= min_samples <= _lib.MAX_PROGRESSIVE_SAMPLES:
             raise ValueError(f"render_accumulate_converge: tolerance >= 0, min_samples within 2..{_lib.MAX_PROGRESSIVE_SAMPLES}")
-        opts = None if options is None else options_array(options)
-        if opts is not None and len(opts) != views:
-            raise ValueError(f"render_accumulate_converge: {len(opts)} option images for {views} cameras")
+        opts = _one_per_view("render_accumulate_converge", "option images", None if options is None else options_array(options), views)
         for name, plane, shape in (("sums", sums, (n, rows, w, 4)), ("moments", moments, (n, rows, w))):
             if (not isinstance(plane, torch.Tensor) or tuple(plane.shape) != shape or plane.dtype != torch.float32
                     or not plane.is_contiguous() or not plane.is_cuda):
@@ -696,28 +688,15 @@ class GraphicState:
             raise ValueError(f"render_accumulate_converge: counts int32 ({n},), contiguous, on the device")
         ptrs = None
         if picture:
-            if outs is None:
-                outs = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
-            if tuple(outs.shape) != (n, rows, w, 4) or outs.dtype != torch.uint8 or not outs.is_contiguous():
-                raise ValueError(f"render_accumulate_converge: outs uint8 ({n}, {rows}, {w}, 4), contiguous")
-            base, frame_bytes = _device_pointer(outs), rows * w * 4
-            ptrs = (C.c_void_p * n)(*[base + i * frame_bytes for i in range(n)])
-        grid, cells = (1, None) if jitter is None else jitter
-        if cells is not None and not isinstance(cells, C.Array):
-            cells = (KifsSubpixel * len(cells))(*[KifsSubpixel(int(i), int(j)) for i, j in cells])
-        if cells is not None and len(cells) != views:
-            raise ValueError(f"render_accumulate_converge: {len(cells)} cells for {views} cameras")
-        if cells is None and samples != int(grid) * int(grid):  # (the C call takes NULL only for the whole grid in order)
-            if int(grid) != 1:
-                raise ValueError("render_accumulate_converge: cells None needs samples == grid * grid")
-            cells = (KifsSubpixel * views)()  # the pixel centre: cell (0, 0) of the one-cell grid
+            outs, ptrs = _frame_outs("render_accumulate_converge", outs, n, rows, w, self.device)
+        grid, cells = _jitter_cells("render_accumulate_converge", jitter, views, samples)
         stream = self._stream_handle(stream, "render_accumulate_converge")
         for tensor in (sums, moments, counts, outs if picture else None):
             if tensor is not None:
                 self._order_after_producer(tensor, stream)
         c_rule = _lib.KifsConvergence(tolerance, min_samples)
         check(lib.kifs_render_accumulate_converge_async(
-            self._ctx, stream, n, samples, cams, opts, int(grid), cells, _device_pointer(sums), w * 16, rows * w * 16,
+            self._ctx, stream, n, samples, cams, opts, grid, cells, _device_pointer(sums), w * 16, rows * w * 16,
             _device_pointer(moments), w * 4, rows * w * 4, int(bool(restart)), C.byref(c_rule),
             None if counts is None else _device_pointer(counts), ptrs, w * 4, y0, y1, encode), "render_accumulate_converge")
         return outs if picture else None

@@ -1,5 +1,5 @@
 // accumulate_driver.cpp -- TEST INFRASTRUCTURE: drives the host side of kifs_render_accumulate_async
-// (kifs_accumulate.cpp, with the seven other host units) against tests/hip_stub/hip_stub.cpp and accumulate_stub.cpp under
+// (kifs_accumulate.cpp, with the seven other host units) against tests/hip_stub/hip_stub.cpp and accumulate_family_stub.cpp under
 // AddressSanitizer + UndefinedBehaviorSanitizer (`make asan-accumulate`; tests/test_accumulate_host_sanitizers.py).
 // A stand-alone CPU program: 1 x 1, 6 x 8, 8 x 64 (the view-table path) and 13 x 5 views, options NULL and given, bands
 // with a padded pitch, two streams, the rings, every refusal, a failure injected into every HIP call and into the launch
@@ -17,20 +17,6 @@
 #include "../../include/kifs_hip.h"
 #include "accumulate_model.hpp"
 
-extern "C" {
-void stub_fail_in(long n);
-long stub_calls();
-long stub_launches();
-long stub_stream_waits();
-long stub_event_synchronizes();
-size_t stub_live_device_allocations();
-size_t stub_live_streams_and_events();
-void accumulate_stub_fail_next();
-long accumulate_stub_launches();
-int accumulate_stub_last_views();
-int accumulate_stub_last_table();
-}
-
 static long g_checks = 0;
 #define CHECK(cond)                                                                              \
     do {                                                                                         \
@@ -41,86 +27,9 @@ static long g_checks = 0;
         }                                                                                        \
     } while (0)
 
+#include "accumulate_driver_common.hpp"
+
 namespace {
-
-struct Scene {
-    KifsScreenUniform screen;
-    KifsOptionsUniform options;
-    int w, h;
-};
-
-Scene scene(int w, int h, uint8_t bg) {
-    Scene s{};
-    s.w = w;
-    s.h = h;
-    CHECK(kifs_host_screen(uint32_t(w), uint32_t(h), &s.screen) == KIFS_OK);
-    KifsGuiData gui;
-    kifs_host_gui_default(&gui);
-    gui.fractal_group = 1;  // Julia
-    gui.background_color[0] = bg;
-    CHECK(kifs_host_options(&gui, &s.options) == KIFS_OK);
-    return s;
-}
-
-std::vector<KifsCameraUniform> cameras(int n, int first) {
-    std::vector<KifsCameraUniform> out(static_cast<size_t>(n), KifsCameraUniform{});
-    for (int i = 0; i < n; ++i) {
-        KifsCameraData c;
-        kifs_host_camera_default(&c);
-        c.origin_distance = 3.0f + 0.25f * float((first + i) % 7);
-        c.phi = 0.37f * float(first + i);
-        c.theta = 0.2f * float((first + i) % 5) - 0.4f;
-        CHECK(kifs_host_camera(&c, &out[size_t(i)]) == KIFS_OK);
-    }
-    return out;
-}
-
-// Option images that differ where they may: constant, power and both colours.
-std::vector<KifsOptionsUniform> morph(const KifsOptionsUniform& base, int n) {
-    std::vector<KifsOptionsUniform> out(static_cast<size_t>(n), base);
-    for (int i = 0; i < n; ++i) {
-        KifsOptionsUniform& o = out[size_t(i)];
-        o.constant[0] += 0.01f * float(i);
-        o.constant[3] -= 0.02f * float(i % 9);
-        o.power = 2.0f + 0.125f * float(i % 16);
-        o.fractal_color[1] = 0.25f + 0.001f * float(i);
-        o.background_color[2] = 0.002f * float(i);
-    }
-    return out;
-}
-
-uint8_t* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    CHECK(hipMalloc(&p, bytes) == hipSuccess);
-    return static_cast<uint8_t*>(p);
-}
-
-kifs_ctx* context_for(const Scene& s, bool with_options) {
-    int st = 0;
-    kifs_ctx* c = kifs_create(0, &st);
-    CHECK(c && st == KIFS_OK);
-    CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
-    if (with_options) CHECK(kifs_set_options(c, &s.options) == KIFS_OK);
-    return c;
-}
-
-kifs::BatchView view_of(const KifsCameraUniform& cam) {
-    kifs::BatchView v{};
-    v.origin = {cam.origin[0], cam.origin[1], cam.origin[2]};
-    v.m0 = {cam.matrix[0][0], cam.matrix[0][1], cam.matrix[0][2]};
-    v.m1 = {cam.matrix[1][0], cam.matrix[1][1], cam.matrix[1][2]};
-    v.m2 = {cam.matrix[2][0], cam.matrix[2][1], cam.matrix[2][2]};
-    return v;
-}
-
-kifs::anim::SceneView scene_of(const KifsOptionsUniform& o) {
-    kifs::anim::SceneView s{};
-    s.c = {o.constant[0], o.constant[1], o.constant[2], o.constant[3]};
-    s.power = o.power;
-    s.fractal_color = {o.fractal_color[0], o.fractal_color[1], o.fractal_color[2]};
-    s.background_color = {o.background_color[0], o.background_color[1], o.background_color[2]};
-    return s;
-}
 
 // One call's destinations, expectation and checks.  `opts` empty: options NULL, the context's options for every view.
 struct Call {
@@ -149,15 +58,15 @@ struct Call {
         const size_t band = pitch() * size_t(y1 - y0);
         for (int f = 0; f < count; ++f) outs[size_t(f)] = dev + band * size_t(f);
         std::memset(dev, 0xEE, bytes());
-        const long launches = accumulate_stub_launches();
+        const long launches = family_stub_launches();
         const int st = kifs_render_accumulate_async(c, stream, count, samples, cams.data(), opts.empty() ? nullptr : opts.data(), outs.data(),
                                                     pitch(), y0, y1, encode);
         if (st != KIFS_OK || !compare) return st;
         if (y1 == y0) {
-            CHECK(accumulate_stub_launches() == launches);
+            CHECK(family_stub_launches() == launches);
         } else {
-            CHECK(accumulate_stub_launches() == launches + 1);
-            CHECK(accumulate_stub_last_views() == count * samples && accumulate_stub_last_table() == (count * samples > 64 ? 1 : 0));
+            CHECK(family_stub_launches() == launches + 1);
+            CHECK(family_stub_last_params().B.count == count * samples && (family_stub_last_params().B.table ? 1 : 0) == (count * samples > 64 ? 1 : 0));
             CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ACCUMULATE && kifs_debug_last_round_steps(c) == 0);
             CHECK(kifs_debug_last_group_tiles(c) == -1 && kifs_debug_last_bunny_form(c) == -1);
         }
@@ -187,7 +96,7 @@ void shapes(int w, int h) {
     for (const auto& shape : SHAPES) {
         const int count = shape[0], samples = shape[1], views = count * samples;
         const auto cams = cameras(views, 3);
-        const auto opts = morph(s.options, views);
+        const auto opts = morph(s.options, views, true);
         for (int given = 0; given < 2; ++given) {
             // options given: a context that never had kifs_set_options, and has none afterwards either
             kifs_ctx* c = context_for(s, !given);
@@ -219,7 +128,7 @@ void shapes(int w, int h) {
 void streams_and_rings() {
     const Scene s = scene(100, 50, 40);
     const auto cams = cameras(512, 1);
-    const auto opts = morph(s.options, 512);
+    const auto opts = morph(s.options, 512, true);
     kifs_ctx* c = context_for(s, true);
     Call A{s, 3, 4, cams, opts}, T{s, 8, 64, cams, opts};
     A.alloc();
@@ -269,7 +178,7 @@ void streams_and_rings() {
 void refusals() {
     const Scene s = scene(100, 50, 40);
     const auto cams = cameras(513, 1);
-    auto opts = morph(s.options, 513);
+    auto opts = morph(s.options, 513, true);
     const size_t pitch = size_t(s.w) * 4, fb = pitch * s.h;
     uint8_t* dev = dev_alloc(fb * 3);
     std::memset(dev, 0xEE, fb * 3);
@@ -279,9 +188,9 @@ void refusals() {
     kifs_ctx* c = context_for(s, true);
     auto call = [&](kifs_ctx* ctx, int count, int samples, const KifsCameraUniform* cm, const KifsOptionsUniform* o, uint8_t* const* out, size_t p,
                     int y0, int y1, int encode) {
-        const long calls = stub_calls(), launches = stub_launches() + accumulate_stub_launches();  // a refused call makes no HIP call
+        const long calls = stub_calls(), launches = stub_launches() + family_stub_launches();  // a refused call makes no HIP call
         const int st = kifs_render_accumulate_async(ctx, nullptr, count, samples, cm, o, out, p, y0, y1, encode);
-        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + accumulate_stub_launches() == launches);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + family_stub_launches() == launches);
         return st;
     };
     const KifsCameraUniform* cm = cams.data();
@@ -360,7 +269,7 @@ void refusals() {
 void injected_failures() {
     const Scene s = scene(40, 13, 10);
     const auto cams = cameras(512, 13);
-    const auto opts = morph(s.options, 512);
+    const auto opts = morph(s.options, 512, true);
     Call T{s, 8, 64, cams, opts};
     T.alloc();
     const size_t own_allocations = stub_live_device_allocations(), own_handles = stub_live_streams_and_events();
@@ -371,7 +280,7 @@ void injected_failures() {
             if (warm)
                 for (int k = 0; k < KIFS_ANIMATION_RING; ++k) CHECK(T.run(c, nullptr, 0, s.h) == KIFS_OK);
             const long before = stub_calls();
-            if (n == 0) accumulate_stub_fail_next();
+            if (n == 0) family_stub_fail_next();
             else stub_fail_in(n);
             const int st = T.run(c, nullptr, 0, s.h);  // (KIFS_OK: the frames have been compared)
             const bool reached = n == 0 || stub_calls() - before >= n;
@@ -398,6 +307,7 @@ void injected_failures() {
 }  // namespace
 
 int main() {
+    family_stub_expect_grid(1);  // the unjittered call: a launch with any other grid aborts in the stand-in
     shapes(74, 45);  // neither dimension a multiple of the 32 x 8 tile
     shapes(64, 8);
     streams_and_rings();

@@ -1,15 +1,31 @@
-// converge_stub.cpp -- TEST INFRASTRUCTURE, never shipped: stand-ins for ALL THREE accumulate launchers
-// (kifs_accumulate_kernels.hip) for converge_driver.cpp (`make asan-converge`): launch_accumulate_render and
-// launch_accumulate_carry as progressive_stub.cpp has them, and launch_accumulate_converge, which RECORDS the
-// ConvergeParams a pass carries -- both planes with their pitches and strides, restart, picture, min_samples, tol2, the
-// counts -- and models the pass on the two planes with converge_model.hpp: a pixel is active on restart, or when the
-// model's rule says so of the texel and the moment it READS; an active pixel's word 0 is accumulate_model.hpp's fold
-// (started from the texel unless the pass restarts), its w grows by the pass's sub-frames and its moment folds the same
-// samples; an inactive pixel's two texels are not written; every pixel of a pass with destinations gets the model's pixel
-// of its state; the pixels active afterwards are ADDED to the frame's count, which must have been zeroed before the
-// launch (the stand-in refuses a word that is not).  Every launcher goes through the launch's tile table, band,
-// pitches, views and scenes and checks that everything it reads and writes lies in "device memory".
-// converge_stub_fail_next(): the next launch of any kind fails once.
+// accumulate_family_stub.cpp -- TEST INFRASTRUCTURE, never shipped: the stand-in for the three accumulate launchers
+// (kifs_accumulate_kernels.hip) beside hip_stub.cpp's stand-ins for the HIP runtime and the other launchers, so that the
+// host side of the accumulated calls runs under AddressSanitizer and UndefinedBehaviorSanitizer on a box without a GPU
+// (`make asan-accumulate`, `asan-jitter`, `asan-progressive`, `asan-converge`: one stand-in for the four drivers).
+//
+// Every launcher goes through the launch's own tile table, band, pitches, view table (or inline views) and scene table
+// and checks that everything it reads and writes lies in "device memory" (hipPointerGetAttributes of the first and last
+// byte), that the tile table is a permutation and that the launch carries what the host promises: the views are
+// frames x samples, a view table exactly beyond the inline views, no costs, diagnostics, geometry plane, stripes or
+// rounds, a grid of 1..8, every view's cell inside the grid and no pad word set beyond the cell (an unjittered launch:
+// all zero), the sub-frames of a frame with one destination, a destination exactly when the pass has a picture, and
+// of a pass every plane-layout rule the API refuses by.  family_stub_expect_grid(g) adds the unjittered driver's rule:
+// a launch with any other grid aborts.
+//
+// The model: launch_accumulate_render writes accumulate_model.hpp's fold of the frame's sub-frames in order, each
+// sampled at ITS pixel of the virtual screen.  launch_accumulate_carry models the pass on a plane of 16-byte texels: word
+// 0 is the fold (started from the texel when prior > 0, from the first sub-frame otherwise: with prior == 0 the texel is
+// NOT read), words 1 and 2 are derived from it, word 3 holds float(total); the fold is a left fold, so passes that
+// concatenate to one call's views leave that call's pixel.  launch_accumulate_converge models the pass on the two
+// planes with converge_model.hpp: a pixel is active on restart, or when the model's rule says so of the texel and the
+// moment it READS; an active pixel's word 0 is the fold (started from the texel unless the pass restarts), its w grows
+// by the pass's sub-frames and its moment folds the same samples; an inactive pixel's two texels are not written; every
+// pixel of a pass with destinations gets the model's pixel of its state; the pixels active afterwards are ADDED to the
+// frame's count, which must have been zeroed before the launch (the stand-in refuses a word that is not).
+//
+// What the last launch of each kind that was not made to fail carried is recorded: the Params and the uploaded scene
+// table of any launch, a carried pass's CarryParams, a converging pass's ConvergeParams.  family_stub_fail_next(): the
+// next launch of any kind fails once (hipErrorLaunchFailure).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -23,21 +39,25 @@
 namespace {
 
 bool g_fail_next = false;
+int g_expect_grid = 0;  // 0: any
 long g_launches = 0, g_carries = 0, g_converges = 0;
-kifs::accum::ConvergeParams g_last{};
+kifs::accum::Params g_params{};
+std::vector<kifs::anim::SceneView> g_scenes;
+kifs::accum::CarryParams g_carry{};
+kifs::accum::ConvergeParams g_converge{};
 
 void need_device(const void* p, size_t bytes, const char* what) {
     if (!bytes) return;
     hipPointerAttribute_t a, b;
     if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice ||
         hipPointerGetAttributes(&b, static_cast<const char*>(p) + bytes - 1) != hipSuccess || b.type != hipMemoryTypeDevice) {
-        std::fprintf(stderr, "converge_stub: %s touches %zu bytes at %p outside device memory\n", what, bytes, p);
+        std::fprintf(stderr, "accumulate_family_stub: %s touches %zu bytes at %p outside device memory\n", what, bytes, p);
         std::abort();
     }
 }
 
 void refuse(const char* what) {
-    std::fprintf(stderr, "converge_stub: %s\n", what);
+    std::fprintf(stderr, "accumulate_family_stub: %s\n", what);
     std::abort();
 }
 
@@ -57,20 +77,32 @@ hipError_t run(const kifs::accum::Params& A, uint32_t group, const kifs::accum::
     if ((A.B.table != nullptr) != (views > MAX_BATCH_INLINE)) refuse("a view table for an inline launch, or none beyond the inline views");
     if (P.tile_cost || P.counters || P.geom || P.stripe_rows || P.round_steps != 0 || P.out_frame_rows) refuse("costs, diagnostics, a geometry plane, stripes or rounds");
     if (g < 1 || g > 8) refuse("a grid outside 1..8");
+    if (g_expect_grid && g != g_expect_grid) refuse("a grid other than the one the driver expects");
     if (group > 2u || !A.scenes) refuse("no pipeline or no scene table");
     need_device(A.scenes, sizeof(anim::SceneView) * size_t(views), "the scene table");
     if (A.B.table) need_device(A.B.table, sizeof(BatchView) * size_t(views), "the view table");
+    g_params = A;
+    g_scenes.assign(A.scenes, A.scenes + views);
+    for (int v = 0; v < views; ++v) {
+        const uint32_t* pad = A.scenes[v].pad;
+        if (pad[1] || pad[2] || pad[3] || (pad[0] >> 16)) refuse("pad words beyond the cell");
+        if (int(pad[0] & 0xffu) >= g || int(pad[0] >> 8) >= g) refuse("a cell outside its grid (an unjittered launch: a pad word that is not zero)");
+    }
     const bool picture = V ? V->picture != 0 : !C || C->picture != 0;
     float* const sums = V ? V->sums : C ? C->sums : nullptr;
     const uint32_t sums_pitch = V ? V->sums_pitch_texels : C ? C->sums_pitch_texels : 0u;
     const uint32_t sums_stride = V ? V->sums_stride_texels : C ? C->sums_stride_texels : 0u;
     const size_t rows = size_t(P.y1 - P.y0);
-    if (sums || C || V) {
+    if (C || V) {
         if (!sums || (reinterpret_cast<uintptr_t>(sums) & 15u) != 0) refuse("no plane, or a misaligned one");
         if (sums_pitch < uint32_t(P.width)) refuse("a plane row shorter than the frame's");
         if (A.frames > 1 && uint64_t(sums_stride) < rows * sums_pitch) refuse("planes that overlap");
     }
-    if (C && uint64_t(C->prior) + uint64_t(A.samples) > (1ull << 24)) refuse("more sub-frames than float(total) holds");
+    if (C) {
+        if (C->picture > 1u) refuse("the picture flag is 0 or 1");
+        if (uint64_t(C->prior) + uint64_t(A.samples) > (1ull << 24)) refuse("more sub-frames than float(total) holds");
+        g_carry = *C;
+    }
     if (V) {
         if (V->picture > 1u || V->restart > 1u) refuse("the picture and restart flags are 0 or 1");
         if (!V->moments || (reinterpret_cast<uintptr_t>(V->moments) & 3u) != 0) refuse("no moments plane, or a misaligned one");
@@ -82,7 +114,7 @@ hipError_t run(const kifs::accum::Params& A, uint32_t group, const kifs::accum::
             for (int f = 0; f < A.frames; ++f)
                 if (V->counts[f] != 0u) refuse("a count that was not zeroed before the launch");
         }
-        g_last = *V;
+        g_converge = *V;
     }
     need_device(P.tile_order, size_t(P.tile_count) * 4, "the tile order");
     const int tiles_x = (P.width + TILE_W - 1) / TILE_W;
@@ -160,13 +192,16 @@ hipError_t run(const kifs::accum::Params& A, uint32_t group, const kifs::accum::
 }  // namespace
 
 extern "C" {
-void converge_stub_fail_next() { g_fail_next = true; }
-long converge_stub_launches() { return g_launches; }  // of any kind
-long converge_stub_carries() { return g_carries; }
-long converge_stub_converges() { return g_converges; }
+void family_stub_fail_next() { g_fail_next = true; }
+void family_stub_expect_grid(int grid) { g_expect_grid = grid; }  // 0: any
+long family_stub_launches() { return g_launches; }  // of any kind
+long family_stub_carries() { return g_carries; }
+long family_stub_converges() { return g_converges; }
 }
-// what the last converging pass that was not made to fail carried
-const kifs::accum::ConvergeParams& converge_stub_last() { return g_last; }
+const kifs::accum::Params& family_stub_last_params() { return g_params; }
+const std::vector<kifs::anim::SceneView>& family_stub_last_scenes() { return g_scenes; }
+const kifs::accum::CarryParams& family_stub_last_carry() { return g_carry; }
+const kifs::accum::ConvergeParams& family_stub_last_converge() { return g_converge; }
 
 namespace kifs {
 

@@ -1,6 +1,6 @@
 // accumulate_jitter_driver.cpp -- TEST INFRASTRUCTURE: drives the host side of kifs_render_accumulate_jittered_async
 // (kifs_accumulate.cpp, with the seven other host units) against tests/hip_stub/hip_stub.cpp and
-// accumulate_jitter_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make asan-jitter`;
+// accumulate_family_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make asan-jitter`;
 // tests/test_jitter_host_sanitizers.py).  A stand-alone CPU program: 1 x 1, 6 x 8, 8 x 64 (the view-table path), 13 x 5
 // and 2 x 9 views at grids 1, 3 and 8, cells given and NULL (where samples == grid^2), options given and NULL, bands with
 // a padded pitch; after every launch the recorded Params and scene table are checked view by view (pad[0], ssaa,
@@ -19,18 +19,6 @@
 #include "../../include/kifs_hip.h"
 #include "accumulate_model.hpp"
 
-extern "C" {
-void stub_fail_in(long n);
-long stub_calls();
-long stub_launches();
-size_t stub_live_device_allocations();
-size_t stub_live_streams_and_events();
-void jitter_stub_fail_next();
-long jitter_stub_launches();
-}
-const kifs::accum::Params& jitter_stub_last_params();
-const std::vector<kifs::anim::SceneView>& jitter_stub_last_scenes();
-
 static long g_checks = 0;
 #define CHECK(cond)                                                                                     \
     do {                                                                                                \
@@ -41,92 +29,9 @@ static long g_checks = 0;
         }                                                                                               \
     } while (0)
 
+#include "accumulate_driver_common.hpp"
+
 namespace {
-
-struct Scene {
-    KifsScreenUniform screen;
-    KifsOptionsUniform options;
-    int w, h;
-};
-
-Scene scene(int w, int h, uint8_t bg) {
-    Scene s{};
-    s.w = w;
-    s.h = h;
-    CHECK(kifs_host_screen(uint32_t(w), uint32_t(h), &s.screen) == KIFS_OK);
-    KifsGuiData gui;
-    kifs_host_gui_default(&gui);
-    gui.fractal_group = 1;  // Julia
-    gui.background_color[0] = bg;
-    CHECK(kifs_host_options(&gui, &s.options) == KIFS_OK);
-    return s;
-}
-
-std::vector<KifsCameraUniform> cameras(int n, int first) {
-    std::vector<KifsCameraUniform> out(static_cast<size_t>(n), KifsCameraUniform{});
-    for (int i = 0; i < n; ++i) {
-        KifsCameraData c;
-        kifs_host_camera_default(&c);
-        c.origin_distance = 3.0f + 0.25f * float((first + i) % 7);
-        c.phi = 0.37f * float(first + i);
-        c.theta = 0.2f * float((first + i) % 5) - 0.4f;
-        CHECK(kifs_host_camera(&c, &out[size_t(i)]) == KIFS_OK);
-    }
-    return out;
-}
-
-std::vector<KifsOptionsUniform> morph(const KifsOptionsUniform& base, int n) {
-    std::vector<KifsOptionsUniform> out(static_cast<size_t>(n), base);
-    for (int i = 0; i < n; ++i) {
-        KifsOptionsUniform& o = out[size_t(i)];
-        o.constant[0] += 0.01f * float(i);
-        o.power = 2.0f + 0.125f * float(i % 16);
-        o.fractal_color[1] = 0.25f + 0.001f * float(i);
-        o.background_color[2] = 0.002f * float(i);
-    }
-    return out;
-}
-
-// Cells that differ from view to view and reach every corner of the grid.
-std::vector<KifsSubpixel> cells_for(int views, int g) {
-    std::vector<KifsSubpixel> out(static_cast<size_t>(views));
-    for (int v = 0; v < views; ++v) out[size_t(v)] = KifsSubpixel{uint8_t((5 * v + 2) % g), uint8_t((g - 1 - (3 * v) % g))};
-    if (views > 1) out[1] = KifsSubpixel{uint8_t(g - 1), uint8_t(g - 1)};
-    return out;
-}
-
-uint8_t* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    CHECK(hipMalloc(&p, bytes) == hipSuccess);
-    return static_cast<uint8_t*>(p);
-}
-
-kifs_ctx* context_for(const Scene& s, bool with_options) {
-    int st = 0;
-    kifs_ctx* c = kifs_create(0, &st);
-    CHECK(c && st == KIFS_OK);
-    CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
-    if (with_options) CHECK(kifs_set_options(c, &s.options) == KIFS_OK);
-    return c;
-}
-
-kifs::BatchView view_of(const KifsCameraUniform& cam) {
-    kifs::BatchView v{};
-    v.origin = {cam.origin[0], cam.origin[1], cam.origin[2]};
-    v.m0 = {cam.matrix[0][0], cam.matrix[0][1], cam.matrix[0][2]};
-    v.m1 = {cam.matrix[1][0], cam.matrix[1][1], cam.matrix[1][2]};
-    v.m2 = {cam.matrix[2][0], cam.matrix[2][1], cam.matrix[2][2]};
-    return v;
-}
-
-kifs::anim::SceneView scene_of(const KifsOptionsUniform& o) {
-    kifs::anim::SceneView s{};
-    s.c = {o.constant[0], o.constant[1], o.constant[2], o.constant[3]};
-    s.power = o.power;
-    s.fractal_color = {o.fractal_color[0], o.fractal_color[1], o.fractal_color[2]};
-    s.background_color = {o.background_color[0], o.background_color[1], o.background_color[2]};
-    return s;
-}
 
 // One call's destinations, expectation and checks.  `opts` empty: options NULL.  grid 0: the UNJITTERED entry point.
 // `cells` empty: cells NULL.
@@ -172,18 +77,18 @@ struct Call {
         const size_t band = pitch() * size_t(y1 - y0);
         for (int f = 0; f < count; ++f) outs[size_t(f)] = dev + band * size_t(f);
         std::memset(dev, 0xEE, bytes());
-        const long launches = jitter_stub_launches();
+        const long launches = family_stub_launches();
         const int st = call(c, outs.data(), y0, y1, encode);
         if (st != KIFS_OK) return st;
         if (y1 == y0) {
-            CHECK(jitter_stub_launches() == launches);
+            CHECK(family_stub_launches() == launches);
         } else {
-            CHECK(jitter_stub_launches() == launches + 1);
+            CHECK(family_stub_launches() == launches + 1);
             CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ACCUMULATE && kifs_debug_last_round_steps(c) == 0);
             CHECK(kifs_debug_last_group_tiles(c) == -1 && kifs_debug_last_bunny_form(c) == -1);
             // what the launch carried: the grid, the virtual screen's 1 / height, a cell per view
-            const kifs::accum::Params& A = jitter_stub_last_params();
-            const std::vector<kifs::anim::SceneView>& scenes = jitter_stub_last_scenes();
+            const kifs::accum::Params& A = family_stub_last_params();
+            const std::vector<kifs::anim::SceneView>& scenes = family_stub_last_scenes();
             const int views = count * samples;
             CHECK(A.frames == count && A.samples == samples && A.B.count == views && int(scenes.size()) == views);
             CHECK(A.B.frame.ssaa == g());
@@ -273,9 +178,9 @@ void refusals() {
     std::vector<KifsSubpixel> zero(513, KifsSubpixel{0, 0}), in3 = cells_for(6, 3);
     auto call = [&](kifs_ctx* ctx, int count, int samples, const KifsCameraUniform* cam, const KifsOptionsUniform* o, int grid,
                     const KifsSubpixel* cells, uint8_t* const* to, size_t p, int y0, int y1, int encode) {
-        const long calls = stub_calls(), launches = stub_launches() + jitter_stub_launches();  // a refused call makes no HIP call
+        const long calls = stub_calls(), launches = stub_launches() + family_stub_launches();  // a refused call makes no HIP call
         const int st = kifs_render_accumulate_jittered_async(ctx, nullptr, count, samples, cam, o, grid, cells, to, p, y0, y1, encode);
-        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + jitter_stub_launches() == launches);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + family_stub_launches() == launches);
         return st;
     };
     // the jittered call's own
@@ -371,7 +276,7 @@ void injected_failures() {
             if (warm)
                 for (int k = 0; k < KIFS_ANIMATION_RING; ++k) CHECK(T.run(c, 0, s.h) == KIFS_OK);
             const long before = stub_calls();
-            if (n == 0) jitter_stub_fail_next();
+            if (n == 0) family_stub_fail_next();
             else stub_fail_in(n);
             const int st = T.run(c, 0, s.h);  // (KIFS_OK: the frames have been compared)
             const bool reached = n == 0 || stub_calls() - before >= n;

@@ -1,5 +1,5 @@
-// accumulate_model.hpp -- TEST INFRASTRUCTURE, shared by accumulate_stub.cpp (the stand-in for launch_accumulate_render)
-// and accumulate_driver.cpp (which restates what the stand-in must have written): the stand-in "colour" of a sub-frame's
+// accumulate_model.hpp -- TEST INFRASTRUCTURE, shared by accumulate_family_stub.cpp (the stand-in for the accumulate launchers)
+// and the four drivers of the accumulated calls (which restate what the stand-in must have written): the stand-in "colour" of a sub-frame's
 // pixel and the order-dependent fold of a frame's sub-frames into one output pixel.
 #pragma once
 

@@ -1,6 +1,6 @@
 // converge_driver.cpp -- TEST INFRASTRUCTURE: drives the host side of kifs_render_accumulate_converge_async
 // (kifs_converge.cpp on top of kifs_accumulate.cpp, with kifs_progressive.cpp and the seven other host units) against
-// tests/hip_stub/hip_stub.cpp and converge_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer
+// tests/hip_stub/hip_stub.cpp and accumulate_family_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer
 // (`make asan-converge`; tests/test_converge_host_sanitizers.py).  A stand-alone CPU program: frames of 1 x 2, 6 x 8,
 // 8 x 64 and 13 x 5 views per pass (8 x 64 and 13 x 5: the view-table path) as sequences of three passes over one pair
 // of planes, the first restarting over planes of 0xEE bytes or continuing from seeded planes; a picture from every pass,
@@ -10,7 +10,9 @@
 // ConvergeParams, both planes, the picture and the counts are checked against converge_model.hpp restated here, and an
 // existing resume call and an existing jittered call on the same context still give their texels and pixels; every
 // refusal, with nothing launched and no HIP call made; a failure injected into every HIP call and into the launch of an
-// 8 x 64 pass; and a final census of what is still alive.  Prints "converge_driver: N checks ok".
+// 8 x 64 pass; the animated call and the four accumulated ones in one sequence on one context (shared_launch_path: the
+// only driver that links them all), with a failure injected at every HIP call of it; and a final census of what is
+// still alive.  Prints "converge_driver: N checks ok".
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -24,19 +26,6 @@
 #include "../../include/kifs_hip.h"
 #include "converge_model.hpp"
 
-extern "C" {
-void stub_fail_in(long n);
-long stub_calls();
-long stub_launches();
-size_t stub_live_device_allocations();
-size_t stub_live_streams_and_events();
-void converge_stub_fail_next();
-long converge_stub_launches();
-long converge_stub_carries();
-long converge_stub_converges();
-}
-const kifs::accum::ConvergeParams& converge_stub_last();
-
 static long g_checks = 0;
 #define CHECK(cond)                                                                                  \
     do {                                                                                             \
@@ -47,90 +36,9 @@ static long g_checks = 0;
         }                                                                                            \
     } while (0)
 
+#include "accumulate_driver_common.hpp"
+
 namespace {
-
-struct Scene {
-    KifsScreenUniform screen;
-    KifsOptionsUniform options;
-    int w, h;
-};
-
-Scene scene(int w, int h, uint8_t bg) {
-    Scene s{};
-    s.w = w;
-    s.h = h;
-    CHECK(kifs_host_screen(uint32_t(w), uint32_t(h), &s.screen) == KIFS_OK);
-    KifsGuiData gui;
-    kifs_host_gui_default(&gui);
-    gui.fractal_group = 1;  // Julia
-    gui.background_color[0] = bg;
-    CHECK(kifs_host_options(&gui, &s.options) == KIFS_OK);
-    return s;
-}
-
-std::vector<KifsCameraUniform> cameras(int n, int first) {
-    std::vector<KifsCameraUniform> out(static_cast<size_t>(n), KifsCameraUniform{});
-    for (int i = 0; i < n; ++i) {
-        KifsCameraData c;
-        kifs_host_camera_default(&c);
-        c.origin_distance = 3.0f + 0.25f * float((first + i) % 7);
-        c.phi = 0.37f * float(first + i);
-        c.theta = 0.2f * float((first + i) % 5) - 0.4f;
-        CHECK(kifs_host_camera(&c, &out[size_t(i)]) == KIFS_OK);
-    }
-    return out;
-}
-
-std::vector<KifsOptionsUniform> morph(const KifsOptionsUniform& base, int n) {
-    std::vector<KifsOptionsUniform> out(static_cast<size_t>(n), base);
-    for (int i = 0; i < n; ++i) {
-        KifsOptionsUniform& o = out[size_t(i)];
-        o.constant[0] += 0.01f * float(i);
-        o.power = 2.0f + 0.125f * float(i % 16);
-        o.fractal_color[1] = 0.25f + 0.001f * float(i);
-        o.background_color[2] = 0.002f * float(i);
-    }
-    return out;
-}
-
-std::vector<KifsSubpixel> cells_for(int views, int g) {
-    std::vector<KifsSubpixel> out(static_cast<size_t>(views));
-    for (int v = 0; v < views; ++v) out[size_t(v)] = KifsSubpixel{uint8_t((5 * v + 2) % g), uint8_t((g - 1 - (3 * v) % g))};
-    return out;
-}
-
-uint8_t* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    CHECK(hipMalloc(&p, bytes) == hipSuccess);
-    return static_cast<uint8_t*>(p);
-}
-
-kifs_ctx* context_for(const Scene& s, bool with_options) {
-    int st = 0;
-    kifs_ctx* c = kifs_create(0, &st);
-    CHECK(c && st == KIFS_OK);
-    CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
-    if (with_options) CHECK(kifs_set_options(c, &s.options) == KIFS_OK);
-    return c;
-}
-
-kifs::BatchView view_of(const KifsCameraUniform& cam) {
-    kifs::BatchView v{};
-    v.origin = {cam.origin[0], cam.origin[1], cam.origin[2]};
-    v.m0 = {cam.matrix[0][0], cam.matrix[0][1], cam.matrix[0][2]};
-    v.m1 = {cam.matrix[1][0], cam.matrix[1][1], cam.matrix[1][2]};
-    v.m2 = {cam.matrix[2][0], cam.matrix[2][1], cam.matrix[2][2]};
-    return v;
-}
-
-kifs::anim::SceneView scene_of(const KifsOptionsUniform& o) {
-    kifs::anim::SceneView s{};
-    s.c = {o.constant[0], o.constant[1], o.constant[2], o.constant[3]};
-    s.power = o.power;
-    s.fractal_color = {o.fractal_color[0], o.fractal_color[1], o.fractal_color[2]};
-    s.background_color = {o.background_color[0], o.background_color[1], o.background_color[2]};
-    return s;
-}
 
 enum Picture { EVERY, LAST, NEVER };
 
@@ -180,11 +88,11 @@ struct Frame {
         std::vector<uint8_t*> outs(static_cast<size_t>(count));
         for (int f = 0; f < count; ++f) outs[size_t(f)] = side + tp * size_t(s.h) * size_t(count) + sp * size_t(s.h) * size_t(f);
         const KifsOptionsUniform* o = po.empty() ? nullptr : po.data();
-        const long converges = converge_stub_converges(), carries = converge_stub_carries(), launches = converge_stub_launches();
+        const long converges = family_stub_converges(), carries = family_stub_carries(), launches = family_stub_launches();
         CHECK(kifs_render_accumulate_resume_async(c, nullptr, count, n, pc.data(), o, grid, pcells.data(), reinterpret_cast<float*>(texels), tp,
                                                   tp * size_t(s.h), 0, nullptr, 0, 0, s.h, 1) == KIFS_OK);
         CHECK(kifs_render_accumulate_jittered_async(c, nullptr, count, n, pc.data(), o, grid, pcells.data(), outs.data(), sp, 0, s.h, 1) == KIFS_OK);
-        CHECK(converge_stub_converges() == converges && converge_stub_carries() == carries + 1 && converge_stub_launches() == launches + 2);
+        CHECK(family_stub_converges() == converges && family_stub_carries() == carries + 1 && family_stub_launches() == launches + 2);
         for (int f = 0; f < count; ++f)
             for (int y = 0; y < s.h; y += 3)
                 for (int x = 0; x < s.w; x += 5) {
@@ -250,7 +158,7 @@ struct Frame {
             const bool with_picture = picture == EVERY || (picture == LAST && p == 2);
             const bool restart = p == 0 && !seeded;
             for (int f = 0; f < count + 2; ++f) counts[f] = 0xEEEEEEEEu;  // garbage: the library zeroes its words
-            const long converges = converge_stub_converges(), launches = converge_stub_launches(), calls = stub_calls();
+            const long converges = family_stub_converges(), launches = family_stub_launches(), calls = stub_calls();
             const int st = kifs_render_accumulate_converge_async(
                 c, stream, count, n, pc.data(), po.empty() ? nullptr : po.data(), grid, pcells.data(), reinterpret_cast<float*>(plane),
                 plane_pitch(), stride, reinterpret_cast<float*>(moments), moments_pitch(), mstride, restart ? 7 : 0, &rules[p],
@@ -258,13 +166,13 @@ struct Frame {
             if (st != KIFS_OK) return st;
             CHECK(counts[0] == 0xEEEEEEEEu && counts[count + 1] == 0xEEEEEEEEu);
             if (rows == 0) {  // an empty band: nothing enqueued, the counts untouched
-                CHECK(converge_stub_launches() == launches && stub_calls() == calls);
+                CHECK(family_stub_launches() == launches && stub_calls() == calls);
                 for (int f = 0; f < count; ++f) CHECK(counts[f + 1] == 0xEEEEEEEEu);
                 continue;
             }
-            CHECK(converge_stub_converges() == converges + 1 && converge_stub_launches() == launches + 1);
+            CHECK(family_stub_converges() == converges + 1 && family_stub_launches() == launches + 1);
             CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ACCUMULATE && kifs_debug_last_round_steps(c) == 0);
-            const kifs::accum::ConvergeParams& K = converge_stub_last();
+            const kifs::accum::ConvergeParams& K = family_stub_last_converge();
             CHECK(K.sums == reinterpret_cast<float*>(plane) && K.sums_pitch_texels == plane_pitch() / 16 && K.sums_stride_texels == stride / 16);
             CHECK(K.moments == reinterpret_cast<float*>(moments) && K.moments_pitch_words == moments_pitch() / 4 && K.moments_stride_words == mstride / 4);
             CHECK(K.restart == (restart ? 1u : 0u) && K.picture == (with_picture ? 1u : 0u) && K.min_samples == rules[p].min_samples);
@@ -358,7 +266,7 @@ void shapes(int w, int h) {
             const std::vector<kifs_ctx*> one = {a}, two = {a, b};
             const std::vector<hipStream_t> own = {nullptr}, both = {extra[0], extra[1]};
             for (const int g : {1, 3, 8}) {
-                Frame F{s, count, n, cams, given ? opts : none, g, g == 1 ? std::vector<KifsSubpixel>(size_t(views), KifsSubpixel{0, 0}) : cells_for(views, g)};
+                Frame F{s, count, n, cams, given ? opts : none, g, g == 1 ? std::vector<KifsSubpixel>(size_t(views), KifsSubpixel{0, 0}) : cells_for(views, g, false)};
                 F.alloc();
                 CHECK(F.run(one, own, 0, h, false, EVERY, true, LOOSE, 1, g == 3) == KIFS_OK);
                 CHECK(F.run(one, own, 0, h, true, LAST, true, TIGHTENED, 0) == KIFS_OK);
@@ -405,7 +313,7 @@ void refusals() {
     float* sums = reinterpret_cast<float*>(plane);
     float* q = reinterpret_cast<float*>(mom);
     const KifsConvergence good{0.25f, 4u};
-    std::vector<KifsSubpixel> zero(513, KifsSubpixel{0, 0}), in3 = cells_for(6, 3);
+    std::vector<KifsSubpixel> zero(513, KifsSubpixel{0, 0}), in3 = cells_for(6, 3, false);
     struct Args {
         kifs_ctx* ctx;
         int count, samples;
@@ -426,10 +334,10 @@ void refusals() {
     };
     const Args ok{c, 3, 2, cm, op, 3, in3.data(), sums, pp, pb, q, mp, mb, 0, &good, counts, out, pitch, 0, s.h, 1};
     auto call = [&](const Args& a) {
-        const long calls = stub_calls(), launches = stub_launches() + converge_stub_launches();  // a refused call makes no HIP call
+        const long calls = stub_calls(), launches = stub_launches() + family_stub_launches();  // a refused call makes no HIP call
         const int st = kifs_render_accumulate_converge_async(a.ctx, nullptr, a.count, a.samples, a.cam, a.o, a.grid, a.cells, a.sums, a.sp, a.ss, a.q,
                                                              a.qp, a.qs, a.restart, a.rule, a.counts, a.to, a.p, a.y0, a.y1, a.encode);
-        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + converge_stub_launches() == launches);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + family_stub_launches() == launches);
         return st;
     };
     auto with = [&](auto change) {
@@ -512,7 +420,7 @@ void refusals() {
     CHECK(hipFree(dev) == hipSuccess && hipFree(plane) == hipSuccess && hipFree(mom) == hipSuccess && hipFree(counts) == hipSuccess);
     // and the same arguments unrefused, the rule at its limits
     const KifsConvergence limits[3] = {{0.0f, 2u}, {INF, 1u << 24}, {0.0f, 2u}};
-    Frame A{s, 3, 2, cams, opts, 3, cells_for(18, 3)};
+    Frame A{s, 3, 2, cams, opts, 3, cells_for(18, 3, false)};
     A.alloc();
     CHECK(A.run({c}, {nullptr}, 0, s.h, false, LAST, true, limits) == KIFS_OK);
     A.release();
@@ -526,7 +434,7 @@ void injected_failures() {
     const Scene s = scene(40, 13, 10);
     const auto cams = cameras(8 * 3 * 64, 13);
     const auto opts = morph(s.options, 8 * 3 * 64);
-    Frame T{s, 8, 64, cams, opts, 8, cells_for(8 * 3 * 64, 8)};
+    Frame T{s, 8, 64, cams, opts, 8, cells_for(8 * 3 * 64, 8, false)};
     T.alloc();
     const size_t own_allocations = stub_live_device_allocations(), own_handles = stub_live_streams_and_events();
     for (int warm = 0; warm < 2; ++warm) {
@@ -535,7 +443,7 @@ void injected_failures() {
             kifs_ctx* c = context_for(s, true);
             if (warm) CHECK(T.run({c}, {nullptr}, 0, s.h, false, LAST, true, LOOSE) == KIFS_OK);
             const long before = stub_calls();
-            if (n == 0) converge_stub_fail_next();
+            if (n == 0) family_stub_fail_next();
             else stub_fail_in(n);
             const int st = T.run({c}, {nullptr}, 0, s.h, false, LAST, true, LOOSE);  // (KIFS_OK: everything has been compared)
             const bool reached = n == 0 || stub_calls() - before >= n;
@@ -559,6 +467,189 @@ void injected_failures() {
     T.release();
 }
 
+// Where the animated call and the four accumulated ones meet (launch_scenes, kifs_animation.cpp): one context, two streams
+// in turn, nine calls -- animation, accumulate, jittered, resume, converge, animation, accumulate, resume, animation: more
+// than two laps of the scene ring -- of 3 and 65 views in turn (65: the view ring, on every other call), a 45 x 19 frame's
+// rows 3..17, every call into a region of its own of one arena.
+struct Mixed {
+    enum Kind { ANIMATION, ACCUMULATE, JITTERED, RESUME, CONVERGE };
+    static constexpr int CALLS = 9, W = 45, H = 19, Y0 = 3, Y1 = 17, ROWS = Y1 - Y0, GRID = 3;
+    static constexpr size_t PITCH = size_t(W) * 4, SUMS_PITCH = size_t(W) * 16;
+    const Kind kinds[CALLS] = {ANIMATION, ACCUMULATE, JITTERED, RESUME, CONVERGE, ANIMATION, ACCUMULATE, RESUME, ANIMATION};
+    const Scene s = scene(W, H, 40);
+    const std::vector<KifsCameraUniform> cams = cameras(65, 5);
+    const std::vector<KifsOptionsUniform> opts = morph(s.options, 65);
+    const std::vector<KifsSubpixel> cells = cells_for(65, GRID);
+    std::vector<uint32_t> animated;  // the animated call's 65 whole frames, by the stand-in's model
+    size_t pictures[CALLS], sums[CALLS], moments = 0, counts = 0, bytes = 0;  // offsets into the arena
+    uint8_t* arena = nullptr;
+    std::vector<uint8_t> first;  // the arena after the first clean sequence
+
+    int views(int k) const { return k % 2 ? 65 : 3; }
+    int frames(int k) const { return kinds[k] == ANIMATION ? views(k) : views(k) == 3 ? 1 : 5; }
+    int samples(int k) const { return views(k) / frames(k); }
+    size_t take(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 15) & ~size_t(15);
+        return at;
+    }
+    // hip_stub.cpp's model of an animated frame (stub_key, stub_hit, stub_scene_key), restated: a plain render of the
+    // frame's camera and options, every pixel that is not background also a function of the frame's scene.
+    void model_animation() {
+        int st = 0;
+        kifs_ctx* c = kifs_create(0, &st);
+        CHECK(c && st == KIFS_OK && kifs_set_screen(c, &s.screen) == KIFS_OK);
+        animated.resize(size_t(65) * W * H);
+        for (size_t f = 0; f < 65; ++f) {
+            uint32_t* frame = animated.data() + f * W * H;
+            CHECK(kifs_set_camera(c, &cams[f]) == KIFS_OK && kifs_set_options(c, &opts[f]) == KIFS_OK);
+            CHECK(kifs_render(c, reinterpret_cast<uint8_t*>(frame), PITCH, 0, H, 1) == KIFS_OK);
+            const KifsCameraUniform& cam = cams[f];
+            const uint32_t key = accumulate_model::bits(cam.origin[0]) * 2654435761u ^ accumulate_model::bits(cam.origin[1]) * 40503u ^
+                                 accumulate_model::bits(cam.origin[2]) * 69069u ^ accumulate_model::bits(cam.matrix[1][0]);
+            const kifs::anim::SceneView sc = scene_of(opts[f]);
+            uint32_t scene_key = 2166136261u;
+            for (float v : {sc.c.x, sc.c.y, sc.c.z, sc.c.w, sc.power, sc.fractal_color.x, sc.fractal_color.y, sc.fractal_color.z,
+                            sc.background_color.x, sc.background_color.y, sc.background_color.z})
+                scene_key = (scene_key ^ accumulate_model::bits(v)) * 16777619u;
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x)
+                    if ((((unsigned(x) >> 5) + 3u * (unsigned(y) >> 3) + (key >> 7)) & 3u) == 0u) frame[y * W + x] ^= scene_key & 0x00ffffffu;
+        }
+        kifs_destroy(c);
+    }
+    uint32_t expected(int k, int f, int x, int y) const {
+        if (kinds[k] == ANIMATION) return animated[(size_t(f) * H + size_t(y)) * W + size_t(x)];
+        const int g = kinds[k] == ACCUMULATE ? 1 : GRID;
+        uint32_t acc = 0;
+        for (int n = 0; n < samples(k); ++n) {
+            const size_t v = size_t(f) * size_t(samples(k)) + size_t(n);
+            const KifsSubpixel at = g == 1 ? KifsSubpixel{0, 0} : cells[v];
+            const uint32_t one = accumulate_model::sample(view_of(cams[v]), scene_of(opts[v]), g * x + at.i, g * y + at.j);
+            acc = n == 0 ? one : accumulate_model::fold(acc, one);
+        }
+        return accumulate_model::pixel(acc, samples(k));
+    }
+    void alloc() {
+        for (int k = 0; k < CALLS; ++k) {
+            pictures[k] = take(PITCH * ROWS * size_t(frames(k)));
+            sums[k] = kinds[k] >= RESUME ? take(SUMS_PITCH * ROWS * size_t(frames(k))) : 0;
+        }
+        moments = take(PITCH * ROWS);
+        counts = take(4);
+        arena = dev_alloc(bytes);
+        model_animation();
+    }
+    // The nine calls; status[k]: call k's, fired[k]: whether an injected failure (the `fail_at`-th HIP call from the start;
+    // `fail_launch` >= 0: that call's accumulate launch) struck during it.
+    void sequence(kifs_ctx* c, hipStream_t (&streams)[2], long fail_at, int fail_launch, int (&status)[CALLS], bool (&fired)[CALLS]) {
+        std::memset(arena, 0xEE, bytes);
+        const KifsConvergence rule{0.25f, 2u};
+        const long start = stub_calls();
+        if (fail_at > 0) stub_fail_in(fail_at);
+        for (int k = 0; k < CALLS; ++k) {
+            const int count = frames(k), n = samples(k);
+            std::vector<uint8_t*> outs(static_cast<size_t>(count));
+            for (int f = 0; f < count; ++f) outs[size_t(f)] = arena + pictures[k] + PITCH * ROWS * size_t(f);
+            float* const plane = reinterpret_cast<float*>(arena + sums[k]);
+            hipStream_t stream = streams[k % 2];
+            const long before = stub_calls() - start;
+            if (k == fail_launch) family_stub_fail_next();
+            switch (kinds[k]) {
+            case ANIMATION:
+                status[k] = kifs_render_animation_async(c, stream, count, cams.data(), opts.data(), outs.data(), PITCH, Y0, Y1, 1);
+                break;
+            case ACCUMULATE:
+                status[k] = kifs_render_accumulate_async(c, stream, count, n, cams.data(), opts.data(), outs.data(), PITCH, Y0, Y1, 1);
+                break;
+            case JITTERED:
+                status[k] = kifs_render_accumulate_jittered_async(c, stream, count, n, cams.data(), opts.data(), GRID, cells.data(), outs.data(),
+                                                                  PITCH, Y0, Y1, 1);
+                break;
+            case RESUME:
+                status[k] = kifs_render_accumulate_resume_async(c, stream, count, n, cams.data(), opts.data(), GRID, cells.data(), plane, SUMS_PITCH,
+                                                                SUMS_PITCH * ROWS, 0, outs.data(), PITCH, Y0, Y1, 1);
+                break;
+            case CONVERGE:
+                status[k] = kifs_render_accumulate_converge_async(c, stream, count, n, cams.data(), opts.data(), GRID, cells.data(), plane, SUMS_PITCH,
+                                                                  SUMS_PITCH * ROWS, reinterpret_cast<float*>(arena + moments), PITCH, PITCH * ROWS, 1,
+                                                                  &rule, reinterpret_cast<uint32_t*>(arena + counts), outs.data(), PITCH, Y0, Y1, 1);
+                break;
+            }
+            fired[k] = k == fail_launch || (fail_at > 0 && before < fail_at && stub_calls() - start >= fail_at);
+            if (status[k] == KIFS_OK)
+                CHECK(kifs_debug_last_kernel(c) == (kinds[k] == ANIMATION ? KIFS_KERNEL_ANIMATION : KIFS_KERNEL_ACCUMULATE));
+        }
+        stub_fail_in(-1);
+    }
+    // A clean sequence: every call succeeds, every picture is the model's, and the arena is the first clean sequence's.
+    void clean(kifs_ctx* c, hipStream_t (&streams)[2]) {
+        int status[CALLS];
+        bool fired[CALLS];
+        const long launches = family_stub_launches(), carries = family_stub_carries(), converges = family_stub_converges();
+        sequence(c, streams, 0, -1, status, fired);
+        for (int k = 0; k < CALLS; ++k) CHECK(status[k] == KIFS_OK);
+        CHECK(family_stub_launches() == launches + 6 && family_stub_carries() == carries + 2 && family_stub_converges() == converges + 1);
+        for (int k = 0; k < CALLS; ++k) {
+            for (int f = 0; f < frames(k); ++f)
+                for (int y = Y0; y < Y1; ++y)
+                    for (int x = 0; x < W; ++x) {
+                        uint32_t px;
+                        std::memcpy(&px, arena + pictures[k] + PITCH * (size_t(ROWS) * size_t(f) + size_t(y - Y0)) + 4 * size_t(x), 4);
+                        if (px != expected(k, f, x, y)) CHECK(false);
+                    }
+            ++g_checks;
+        }
+        if (first.empty()) first.assign(arena, arena + bytes);
+        CHECK(std::memcmp(first.data(), arena, bytes) == 0);
+    }
+};
+
+// The sequence clean on a fresh context, twice; then a failure injected at every HIP call of the sequence in turn and at
+// each of its six accumulate launches, on a fresh context and on a warm one: a call returns KIFS_ERR_RUNTIME only if the
+// failure struck during it, the launch's own always, and the next clean sequence on the same context gives the same bytes.
+void shared_launch_path() {
+    Mixed M;
+    M.alloc();
+    hipStream_t streams[2] = {nullptr, nullptr};
+    CHECK(hipStreamCreateWithFlags(&streams[0], hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&streams[1], hipStreamNonBlocking) == hipSuccess);
+    const size_t own_allocations = stub_live_device_allocations(), own_handles = stub_live_streams_and_events();
+    {
+        kifs_ctx* c = context_for(M.s, true);
+        M.clean(c, streams);
+        const long syncs = stub_event_synchronizes();
+        M.clean(c, streams);
+        // a warm lap: every call waits for its scene slot's last reader, every 65-view call for its view slot's as well
+        CHECK(stub_event_synchronizes() - syncs == Mixed::CALLS + 4);
+        kifs_destroy(c);
+    }
+    for (int warm = 0; warm < 2; ++warm) {
+        int failed = 0;
+        for (long n = 1 - Mixed::CALLS; n < 2000; ++n) {  // n <= 0: the accumulate launch of call -n (an animated call's is a HIP call)
+            if (n <= 0 && M.kinds[-n] == Mixed::ANIMATION) continue;
+            kifs_ctx* c = context_for(M.s, true);
+            if (warm) M.clean(c, streams);
+            int status[Mixed::CALLS];
+            bool fired[Mixed::CALLS];
+            const long before = stub_calls();
+            M.sequence(c, streams, n > 0 ? n : 0, n > 0 ? -1 : int(-n), status, fired);
+            const bool reached = n <= 0 || stub_calls() - before >= n;
+            for (int k = 0; k < Mixed::CALLS; ++k) {
+                CHECK(status[k] == KIFS_OK || (status[k] == KIFS_ERR_RUNTIME && fired[k]));
+                if (n <= 0 && fired[k]) CHECK(status[k] == KIFS_ERR_RUNTIME);
+                if (status[k] != KIFS_OK) ++failed;
+            }
+            M.clean(c, streams);
+            kifs_destroy(c);
+            CHECK(stub_live_device_allocations() == own_allocations && stub_live_streams_and_events() == own_handles);
+            if (!reached) break;
+        }
+        CHECK(failed >= 6 + 2 * Mixed::CALLS);  // (the six launches; of every call at least the scene table's copy and record)
+    }
+    CHECK(hipStreamDestroy(streams[0]) == hipSuccess && hipStreamDestroy(streams[1]) == hipSuccess);
+    CHECK(hipFree(M.arena) == hipSuccess);
+}
+
 }  // namespace
 
 int main() {
@@ -566,6 +657,7 @@ int main() {
     shapes(64, 8);
     refusals();
     injected_failures();
+    shared_launch_path();
     CHECK(stub_live_device_allocations() == 0);
     CHECK(stub_live_streams_and_events() == 0);
     std::printf("converge_driver: %ld checks ok\n", g_checks);

@@ -1,4 +1,4 @@
-// converge_model.hpp -- TEST INFRASTRUCTURE, shared by converge_stub.cpp (the stand-in for launch_accumulate_converge) and
+// converge_model.hpp -- TEST INFRASTRUCTURE, shared by accumulate_family_stub.cpp (the stand-in for the accumulate launchers) and
 // converge_driver.cpp (which restates what the stand-in must have written): the stand-in state of a pixel of a
 // converging pass and a stand-in stopping rule.  Nothing here is the kernel's arithmetic: it only has to depend on
 // everything the host side hands over -- both planes as read, min_samples, tol2, the pass's sub-frames -- so that a

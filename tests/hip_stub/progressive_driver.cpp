@@ -1,6 +1,6 @@
 // progressive_driver.cpp -- TEST INFRASTRUCTURE: drives the host side of kifs_render_accumulate_resume_async
 // (kifs_progressive.cpp and kifs_accumulate.cpp, with the seven other host units) against tests/hip_stub/hip_stub.cpp and
-// progressive_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make asan-progressive`;
+// accumulate_family_stub.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make asan-progressive`;
 // tests/test_progressive_host_sanitizers.py).  A stand-alone CPU program: frames of 1 x 1, 6 x 8, 8 x 64 and 13 x 5 views per
 // pass (8 x 64 and 13 x 5: the view-table path) as sequences of passes over one plane, started from prior 0, 1 and
 // 2^24 - the frame's sub-frames; a picture from every pass, from the last one, from none; bands with padded pitches on
@@ -20,19 +20,6 @@
 #include "../../include/kifs_hip.h"
 #include "accumulate_model.hpp"
 
-extern "C" {
-void stub_fail_in(long n);
-long stub_calls();
-long stub_launches();
-size_t stub_live_device_allocations();
-size_t stub_live_streams_and_events();
-void progressive_stub_fail_next();
-long progressive_stub_launches();
-long progressive_stub_carries();
-}
-const kifs::accum::CarryParams& progressive_stub_last_carry();
-const std::vector<kifs::anim::SceneView>& progressive_stub_last_scenes();
-
 static long g_checks = 0;
 #define CHECK(cond)                                                                                     \
     do {                                                                                                \
@@ -43,93 +30,11 @@ static long g_checks = 0;
         }                                                                                               \
     } while (0)
 
+#include "accumulate_driver_common.hpp"
+
 namespace {
 
 constexpr uint32_t LIMIT = KIFS_MAX_PROGRESSIVE_SAMPLES;
-
-struct Scene {
-    KifsScreenUniform screen;
-    KifsOptionsUniform options;
-    int w, h;
-};
-
-Scene scene(int w, int h, uint8_t bg) {
-    Scene s{};
-    s.w = w;
-    s.h = h;
-    CHECK(kifs_host_screen(uint32_t(w), uint32_t(h), &s.screen) == KIFS_OK);
-    KifsGuiData gui;
-    kifs_host_gui_default(&gui);
-    gui.fractal_group = 1;  // Julia
-    gui.background_color[0] = bg;
-    CHECK(kifs_host_options(&gui, &s.options) == KIFS_OK);
-    return s;
-}
-
-std::vector<KifsCameraUniform> cameras(int n, int first) {
-    std::vector<KifsCameraUniform> out(static_cast<size_t>(n), KifsCameraUniform{});
-    for (int i = 0; i < n; ++i) {
-        KifsCameraData c;
-        kifs_host_camera_default(&c);
-        c.origin_distance = 3.0f + 0.25f * float((first + i) % 7);
-        c.phi = 0.37f * float(first + i);
-        c.theta = 0.2f * float((first + i) % 5) - 0.4f;
-        CHECK(kifs_host_camera(&c, &out[size_t(i)]) == KIFS_OK);
-    }
-    return out;
-}
-
-std::vector<KifsOptionsUniform> morph(const KifsOptionsUniform& base, int n) {
-    std::vector<KifsOptionsUniform> out(static_cast<size_t>(n), base);
-    for (int i = 0; i < n; ++i) {
-        KifsOptionsUniform& o = out[size_t(i)];
-        o.constant[0] += 0.01f * float(i);
-        o.power = 2.0f + 0.125f * float(i % 16);
-        o.fractal_color[1] = 0.25f + 0.001f * float(i);
-        o.background_color[2] = 0.002f * float(i);
-    }
-    return out;
-}
-
-std::vector<KifsSubpixel> cells_for(int views, int g) {
-    std::vector<KifsSubpixel> out(static_cast<size_t>(views));
-    for (int v = 0; v < views; ++v) out[size_t(v)] = KifsSubpixel{uint8_t((5 * v + 2) % g), uint8_t((g - 1 - (3 * v) % g))};
-    if (views > 1) out[1] = KifsSubpixel{uint8_t(g - 1), uint8_t(g - 1)};
-    return out;
-}
-
-uint8_t* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    CHECK(hipMalloc(&p, bytes) == hipSuccess);
-    return static_cast<uint8_t*>(p);
-}
-
-kifs_ctx* context_for(const Scene& s, bool with_options) {
-    int st = 0;
-    kifs_ctx* c = kifs_create(0, &st);
-    CHECK(c && st == KIFS_OK);
-    CHECK(kifs_set_screen(c, &s.screen) == KIFS_OK);
-    if (with_options) CHECK(kifs_set_options(c, &s.options) == KIFS_OK);
-    return c;
-}
-
-kifs::BatchView view_of(const KifsCameraUniform& cam) {
-    kifs::BatchView v{};
-    v.origin = {cam.origin[0], cam.origin[1], cam.origin[2]};
-    v.m0 = {cam.matrix[0][0], cam.matrix[0][1], cam.matrix[0][2]};
-    v.m1 = {cam.matrix[1][0], cam.matrix[1][1], cam.matrix[1][2]};
-    v.m2 = {cam.matrix[2][0], cam.matrix[2][1], cam.matrix[2][2]};
-    return v;
-}
-
-kifs::anim::SceneView scene_of(const KifsOptionsUniform& o) {
-    kifs::anim::SceneView s{};
-    s.c = {o.constant[0], o.constant[1], o.constant[2], o.constant[3]};
-    s.power = o.power;
-    s.fractal_color = {o.fractal_color[0], o.fractal_color[1], o.fractal_color[2]};
-    s.background_color = {o.background_color[0], o.background_color[1], o.background_color[2]};
-    return s;
-}
 
 uint32_t seed_of(int f, int x, int y) { return 0x9e3779b9u * uint32_t(f + 1) ^ uint32_t(x) * 2654435761u ^ uint32_t(y) * 40503u; }
 
@@ -186,11 +91,11 @@ struct Frame {
         const size_t sp = size_t(s.w) * 4;
         std::vector<uint8_t*> outs(static_cast<size_t>(count));
         for (int f = 0; f < count; ++f) outs[size_t(f)] = side + sp * size_t(s.h) * size_t(f);
-        const long carries = progressive_stub_carries(), launches = progressive_stub_launches();
+        const long carries = family_stub_carries(), launches = family_stub_launches();
         const KifsOptionsUniform* o = po.empty() ? nullptr : po.data();
         const int st = jittered ? kifs_render_accumulate_jittered_async(c, nullptr, count, n, pc.data(), o, grid, pcells.data(), outs.data(), sp, 0, s.h, 1)
                                 : kifs_render_accumulate_async(c, nullptr, count, n, pc.data(), o, outs.data(), sp, 0, s.h, 1);
-        CHECK(st == KIFS_OK && progressive_stub_carries() == carries && progressive_stub_launches() == launches + 1);
+        CHECK(st == KIFS_OK && family_stub_carries() == carries && family_stub_launches() == launches + 1);
         for (int f = 0; f < count; ++f)
             for (int y = 0; y < s.h; y += 3)
                 for (int x = 0; x < s.w; x += 5) {
@@ -246,19 +151,19 @@ struct Frame {
             if (p > 0 && streams.size() > 1)  // the caller orders passes on different streams
                 CHECK(kifs_order_after(c, stream, streams[(p - 1) % streams.size()]) == KIFS_OK);
             const bool with_picture = picture == EVERY || (picture == LAST && p + 1 == splits.size());
-            const long carries = progressive_stub_carries(), launches = progressive_stub_launches(), calls = stub_calls();
+            const long carries = family_stub_carries(), launches = family_stub_launches(), calls = stub_calls();
             const int st = kifs_render_accumulate_resume_async(c, stream, count, n, pc.data(), po.empty() ? nullptr : po.data(), grid,
                                                                pcells.data(), reinterpret_cast<float*>(plane), plane_pitch(), stride, in_plane,
                                                                with_picture ? outs.data() : nullptr, with_picture ? pitch() : 1, y0, y1, encode);
             if (st != KIFS_OK) return st;
             if (rows == 0) {
-                CHECK(progressive_stub_launches() == launches && stub_calls() == calls);  // an empty band: nothing enqueued
+                CHECK(family_stub_launches() == launches && stub_calls() == calls);  // an empty band: nothing enqueued
             } else {
-                CHECK(progressive_stub_carries() == carries + 1 && progressive_stub_launches() == launches + 1);
+                CHECK(family_stub_carries() == carries + 1 && family_stub_launches() == launches + 1);
                 CHECK(kifs_debug_last_kernel(c) == KIFS_KERNEL_ACCUMULATE && kifs_debug_last_round_steps(c) == 0);
                 CHECK(kifs_debug_last_group_tiles(c) == -1 && kifs_debug_last_bunny_form(c) == -1);
-                const kifs::accum::CarryParams& K = progressive_stub_last_carry();
-                const std::vector<kifs::anim::SceneView>& scenes = progressive_stub_last_scenes();
+                const kifs::accum::CarryParams& K = family_stub_last_carry();
+                const std::vector<kifs::anim::SceneView>& scenes = family_stub_last_scenes();
                 CHECK(K.sums == reinterpret_cast<float*>(plane) && K.sums_pitch_texels == plane_pitch() / 16 && K.sums_stride_texels == stride / 16);
                 CHECK(K.prior == in_plane && K.picture == (with_picture ? 1u : 0u));
                 CHECK(K.A.frames == count && K.A.samples == n && K.A.B.count == count * n && int(scenes.size()) == count * n);
@@ -380,10 +285,10 @@ void refusals() {
     auto call = [&](kifs_ctx* ctx, int count, int samples, const KifsCameraUniform* cam, const KifsOptionsUniform* o, int grid,
                     const KifsSubpixel* cells, float* plane_at, size_t plane_pitch, size_t plane_stride, uint32_t prior, uint8_t* const* to,
                     size_t p, int y0, int y1, int encode) {
-        const long calls = stub_calls(), launches = stub_launches() + progressive_stub_launches();  // a refused call makes no HIP call
+        const long calls = stub_calls(), launches = stub_launches() + family_stub_launches();  // a refused call makes no HIP call
         const int st = kifs_render_accumulate_resume_async(ctx, nullptr, count, samples, cam, o, grid, cells, plane_at, plane_pitch, plane_stride,
                                                            prior, to, p, y0, y1, encode);
-        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + progressive_stub_launches() == launches);
+        CHECK(st != KIFS_OK && stub_calls() == calls && stub_launches() + family_stub_launches() == launches);
         return st;
     };
     // the jittered call's, with their statuses
@@ -483,7 +388,7 @@ void injected_failures() {
             if (warm)
                 for (int k = 0; k < KIFS_ANIMATION_RING; ++k) CHECK(T.run({c}, {nullptr}, 0, s.h, 1, LAST, 1, false) == KIFS_OK);
             const long before = stub_calls();
-            if (n == 0) progressive_stub_fail_next();
+            if (n == 0) family_stub_fail_next();
             else stub_fail_in(n);
             const int st = T.run({c}, {nullptr}, 0, s.h, 1, LAST, 1, false);  // (KIFS_OK: frames and plane have been compared)
             const bool reached = n == 0 || stub_calls() - before >= n;

@@ -2,7 +2,7 @@
 rings it shares with the animated call) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU:
 `make asan-accumulate` compiles the seven host units and kifs_accumulate.cpp as plain C++ with
 -fsanitize=address,undefined and links them with tests/hip_stub/hip_stub.cpp (unchanged), a stand-in for
-launch_accumulate_render (accumulate_stub.cpp) and a stand-alone driver (accumulate_driver.cpp) that runs 1 x 1, 6 x 8,
+launch_accumulate_render (accumulate_family_stub.cpp, which stands in for all three accumulate launchers) and a stand-alone driver (accumulate_driver.cpp) that runs 1 x 1, 6 x 8,
 8 x 64 and 13 x 5 views with and without options, bands, two streams, every refusal, a failure injected into every HIP
 call of an 8 x 64 call, and a final leak census.  Nothing sanitized is loaded into Python or run on a GPU."""
 import subprocess

@@ -2,7 +2,7 @@
 check / check_jitter / enqueue of kifs_accumulate.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU:
 `make asan-converge` compiles the seven host units, kifs_accumulate.cpp, kifs_progressive.cpp and kifs_converge.cpp as
 plain C++ with -fsanitize=address,undefined and links them with tests/hip_stub/hip_stub.cpp (unchanged), a stand-in that
-defines ALL THREE accumulate launchers and records a pass's ConvergeParams (converge_stub.cpp) and a stand-alone driver with
+defines ALL THREE accumulate launchers and records a pass's ConvergeParams (accumulate_family_stub.cpp) and a stand-alone driver with
 its own main (converge_driver.cpp): sequences of passes with and without restart, picture and counts, bands with padded
 pitches on all three destinations, two streams and two contexts on one pair of planes, the counts zeroed before the launch,
 every refusal with no HIP call made, a failure injected into every HIP call and the launch, an existing resume call and an

@@ -3,7 +3,7 @@ refusals, the cell of every view in pad[0] of its scene record, the grid as the 
 screen's 1 / height) under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU: `make asan-jitter` compiles the seven
 host units and kifs_accumulate.cpp as plain C++ with -fsanitize=address,undefined and links them with
 tests/hip_stub/hip_stub.cpp (unchanged), a stand-in for launch_accumulate_render that records what a launch carries
-(accumulate_jitter_stub.cpp) and a stand-alone driver (accumulate_jitter_driver.cpp) that runs 1 x 1, 6 x 8, 8 x 64, 13 x 5
+(accumulate_family_stub.cpp) and a stand-alone driver (accumulate_jitter_driver.cpp) that runs 1 x 1, 6 x 8, 8 x 64, 13 x 5
 and 2 x 9 views at grids 1, 3 and 8 with cells given and NULL, options given and NULL, unjittered calls in between (zero
 pad words, a grid of 1), every refusal, a failure injected into every HIP call of an 8 x 64 call, and a final leak census.
 Nothing sanitized is loaded into Python or run on a GPU."""

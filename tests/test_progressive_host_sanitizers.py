@@ -2,7 +2,7 @@
 shared check / check_jitter / enqueue of kifs_accumulate.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, on the
 CPU: `make asan-progressive` compiles the seven host units, kifs_accumulate.cpp and kifs_progressive.cpp as plain C++ with
 -fsanitize=address,undefined and links them with tests/hip_stub/hip_stub.cpp (unchanged), a stand-in that defines BOTH
-accumulate launchers and records a pass's CarryParams (progressive_stub.cpp) and a stand-alone driver with its own main
+accumulate launchers and records a pass's CarryParams (accumulate_family_stub.cpp) and a stand-alone driver with its own main
 (progressive_driver.cpp): 1 x 1, 6 x 8, 8 x 64 and 13 x 5 views per pass as sequences of passes over one plane from prior 0,
 1 and 2^24 - the frame's sub-frames, a picture from every pass, the last or none, bands with padded pitches on both
 destinations, two streams, two contexts on one plane, an existing jittered and an existing unjittered call after every
