@@ -531,6 +531,50 @@ int kifs_trace_rays_async(kifs_ctx* ctx, void* hip_stream, const KifsRay* dev_ra
                           float* dev_geometry /* n texels of 16 B, or NULL */,
                           uint8_t* dev_rgba8  /* n pixels of 4 B, or NULL */, int encode);
 
+/* ---- extension: ambient occlusion (not in the reference) ------------------------------------------------------------
+ * kifs_render_batch_async whose hits are additionally attenuated by how closed the surface is around them: a few
+ * estimates taken along the normal, each compared with how far it stands off the hit.  The call is a render of its own
+ * (kifs_occlusion_kernels.hip); no other entry point computes the term.
+ *   factor    a primary ray that hit at the tested position p with the normal n the shading used (the vector get_normal
+ *             returned, kifs_render_geometry_async's texel), S = samples; all f32, no fused operation but the one written:
+ *                 occ = 0; w = 1
+ *                 for i = 1..S:  h = step * float(i);  q = fma(h, n, p) per component;  d = scene_SDF(q)
+ *                                occ = occ + w * (h - d);  w = w * decay
+ *                 a = min(max(1 - strength * occ, 0), 1)      (as C ternaries: a NaN stays a NaN)
+ *   colour    (a r, a g, a b) of the hit's colour (r, g, b) exactly as every other entry point computes it, the
+ *             soft-shadow factor included when that extension is on; a miss -- every ray the culls drop -- is the
+ *             background; a heatmap frame's colour is the counter's, unattenuated.  A NaN factor makes a NaN colour, which
+ *             the encoders map to 0 (the generalised Julia set's NaN normals).
+ *   samples   the context's supersampling factor k is honoured: each of the k^2 samples of a pixel is attenuated by its
+ *             own factor and the samples are resolved exactly as kifs_set_supersampling specifies.
+ *   plane     dev_occlusion NULL, or one f32 per pixel: row y of frame i at dev_occlusion + i * occlusion_stride_bytes +
+ *             (y - y0) * occlusion_pitch_bytes.  A hit stores a (in heatmap mode too), a miss 1.0f; bytes beyond 4 W of a
+ *             row are not touched.  The base is 4-byte aligned, the pitch at least 4 W and a multiple of 4, the stride a
+ *             multiple of 4 and, for count > 1, at least (y1 - y0) * pitch.  With k > 1 a resolved pixel has no single
+ *             factor: a plane is refused.
+ *   frames    1 <= count <= KIFS_MAX_OCCLUSION_BATCH; cameras NULL with count 1: the context's camera.  Rows [y0, y1) are
+ *             bit-identical to the same rows of the full frame, every frame of a batch to the lone call.
+ *   refusals  a refused call launches nothing and writes nothing.  KIFS_ERR_BAD_ARG: a NULL ctx, dev_outs_rgba8 or ao; a
+ *             field of ao outside its range or not finite; count outside 1..KIFS_MAX_OCCLUSION_BATCH; NULL cameras with
+ *             count != 1; a bad band, plane layout or encode; a plane with k > 1.  KIFS_ERR_BAD_SIZE (pitch, frame size)
+ *             and KIFS_ERR_UNCONFIGURED as kifs_render_batch_async.
+ *   ordering  enqueued on hip_stream (NULL: the context's own) as the other async calls: kifs_order_after applies.
+ *   launch    not a feedback launch: it neither records tile costs nor advances the tile order, leaves
+ *             kifs_debug_last_kernel and kifs_debug_last_round_steps as they were and touches no profiling record.
+ * Every byte and every factor equals the CPU restatement of the contract bit for bit (tests/occlusion_reference.c). */
+#define KIFS_MAX_AO_SAMPLES 16
+#define KIFS_MAX_OCCLUSION_BATCH 64
+typedef struct KifsAmbientOcclusion {
+    int32_t samples;   /* S: 1..KIFS_MAX_AO_SAMPLES */
+    float   step;      /* probe spacing along the normal, scene units: finite, > 0 */
+    float   decay;     /* weight of probe i+1 over probe i: finite, 0 < decay <= 1 */
+    float   strength;  /* finite, >= 0 */
+} KifsAmbientOcclusion;
+int kifs_render_occlusion_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                                uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsAmbientOcclusion* ao,
+                                float* dev_occlusion, size_t occlusion_pitch_bytes, size_t occlusion_stride_bytes,
+                                int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

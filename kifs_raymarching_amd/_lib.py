@@ -57,7 +57,13 @@ class KifsRay(C.Structure):  # a caller-supplied ray of kifs_trace_rays_async: t
     _fields_ = [("origin", C.c_float * 3), ("reserved0", C.c_float), ("direction", C.c_float * 3), ("reserved1", C.c_float)]
 
 
+class AmbientOcclusionC(C.Structure):  # KifsAmbientOcclusion: the term of kifs_render_occlusion_async
+    _fields_ = [("samples", C.c_int32), ("step", C.c_float), ("decay", C.c_float), ("strength", C.c_float)]
+
+
 MAX_RAYS = 1 << 28  # KIFS_MAX_RAYS
+MAX_AO_SAMPLES = 16  # KIFS_MAX_AO_SAMPLES
+MAX_OCCLUSION_BATCH = 64  # KIFS_MAX_OCCLUSION_BATCH
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -90,6 +96,7 @@ assert C.sizeof(ScreenUniform) == 12
 assert C.sizeof(CameraUniform) == 64
 assert C.sizeof(OptionsUniform) == 80
 assert C.sizeof(KifsSubpixel) == 2
+assert C.sizeof(AmbientOcclusionC) == 16
 
 # every symbol include/kifs_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -132,6 +139,9 @@ SIGNATURES = {
                                                         C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _P(KifsConvergence),
                                                         C.c_void_p, _P(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "kifs_trace_rays_async": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "kifs_render_occlusion_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                              _P(AmbientOcclusionC), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
+                                              C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

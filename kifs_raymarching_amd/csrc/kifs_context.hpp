@@ -11,6 +11,7 @@
 //   kifs_progressive.cpp progressive accumulation (kifs_render_accumulate_resume_async): a plane of sums across launches
 //   kifs_converge.cpp  converging accumulation (kifs_render_accumulate_converge_async): sums, moments and a rule
 //   kifs_rays.cpp      ray queries (kifs_trace_rays_async): caller-supplied rays, one launch
+//   kifs_occlusion.cpp ambient occlusion (kifs_render_occlusion_async): the batch call's frames, hits attenuated, one launch
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -163,6 +164,10 @@ const RowTable* row_table(kifs_ctx* c, const int* stripes, int n, int height);
 TileTable* tile_table(kifs_ctx* c, int width, int height, int y0, int y1, const RowTable* rows = nullptr);
 // The background pixel, encoded exactly as the kernels would (unorm8 / srgb8 of kifs_device_math.hpp).
 uint32_t background_pixel(const kifs_ctx* c, kifs::V3 colour, int encode);
+// Band, pitch and geometry plane of a launch: checked against the frame (P.y1 still its height), then written into P
+// (kifs_schedule.cpp; kifs_occlusion.cpp fills its launch with it as enqueue_batch does).
+int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, uint8_t* out, size_t pitch, int y0, int y1, int encode,
+                    bool striped, float* geom, size_t geom_pitch, size_t geom_stride);
 // One launch: `count` frames (count == 1 and cameras NULL: the context's camera; else cameras[i] -> outs[i])
 // sharing everything else.  `stripes` non-null: the launch renders that row shard (y0 = 0, y1 = height)
 // instead of a band, into packed rows (in_place == 0) or at the rows' frame positions (in_place != 0).

@@ -1,6 +1,6 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
 // kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip,
-// kifs_rays_kernels.hip).
+// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +34,9 @@ hipError_t launch_accumulate_converge(const accum::ConvergeParams& K, uint32_t g
 // Ray queries (kifs_trace_rays_async; kifs_rays_kernels.hip, the host side is kifs_rays.cpp): one caller-supplied ray per
 // lane, ceil(n / 256) workgroups (rays::trace_render_kernel).
 hipError_t launch_trace_rays(const rays::Params& R, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Ambient occlusion (kifs_render_occlusion_async; kifs_occlusion_kernels.hip, the host side is kifs_occlusion.cpp): the
+// supersampled launch's shape from k = 1 up, every hit attenuated by its own factor (occl::render_kernel).
+hipError_t launch_occlusion(const occl::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

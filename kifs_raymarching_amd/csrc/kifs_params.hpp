@@ -230,4 +230,26 @@ constexpr uint32_t workgroups(int n) { return n > 0 ? (uint32_t(n) + RAYS_PER_WO
 
 }  // namespace rays
 
+namespace occl {
+
+// The ambient-occlusion term of kifs_render_occlusion_async (KifsAmbientOcclusion, include/kifs_hip.h), as the kernels
+// read it.
+struct AO {
+    int samples;                  // 1..KIFS_MAX_AO_SAMPLES
+    float step, decay, strength;
+};
+
+// The argument of occl::render_kernel (kifs_occlusion_kernels.hip): the launch's frame constants and views as every render
+// kernel takes them (frame.ssaa = k, 1 included), the term, and the optional plane of one f32 per pixel -- row r of the
+// band of view i at plane + i * stride_words + r * pitch_words floats.
+struct Params {
+    BatchParams B;
+    AO ao;
+    float* plane;                 // null: no plane (always with k > 1)
+    uint32_t pitch_words, stride_words;
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace occl
+
 }  // namespace kifs

@@ -1219,4 +1219,96 @@ KIFS_DEV V3 raymarch_geometry(const FrameParams& P, V3 dir, bool valid, bool& hi
     });
 }
 
+// ---- extension: ambient occlusion (kifs_render_occlusion_async, include/kifs_hip.h) -------------------------------
+// The factor of a hit at the tested position p with the shading's normal n, operation for operation as the header
+// states it: ao.samples estimates along the normal, each held against how far it stands off the hit.  Every lane takes
+// every estimate (a lane that did not hit holds a valid old position and reads nothing of its result); `lanes`: the
+// lanes whose factor is used.
+template <class Sdf>
+KIFS_DEV float ambient_occlusion(const FrameParams& P, const occl::AO& ao, V3 p, V3 n, unsigned long long lanes, Sdf sdf) {
+    float occ = 0.0f, w = 1.0f;
+    for (int i = 1; i <= ao.samples; ++i) {  // uniform
+        const float h = ao.step * float(i);
+        const V3 q{fmaf_(h, n.x, p.x), fmaf_(h, n.y, p.y), fmaf_(h, n.z, p.z)};
+        const float d = sdf(q, lanes);
+        occ = occ + w * (h - d);
+        w = w * ao.decay;
+    }
+    return clamp_(1.0f - ao.strength * occ, 0.0f, 1.0f);
+}
+
+// The occlusion kernel's phases read the kernel argument anew, each where it works (kifs_occlusion_kernels.hip): held in
+// SGPRs from the kernel's start, the term and the shading's constants would stay live across the march, whose
+// hand-written loops pin s74-s97 and leave the frame constants barely enough.  The empty asm ties the loads that follow
+// to its place; they are scalar loads of a uniform address, like the kernel argument's own.
+namespace occl {
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+KIFS_DEV ConstParams anew(ConstParams K) {
+    asm volatile("" : "+s"(K));
+    return K;
+}
+}  // namespace occl
+
+// generic_shade's colour of a hit at p times the hit's factor, from the same pieces in the same order.  A lane that did
+// not hit gets `miss` and the factor 1.  The normal and the shadow ray belong to the hit lanes, as in whole_ray_colour;
+// the probes run for the whole wave, outside any divergent region, as the march's estimates do (generic_loop).
+struct Occluded {
+    V3 colour;
+    float a;  // the hit's factor; 1 on a miss
+};
+template <class Sdf, class Normal>
+KIFS_DEV Occluded occluded_shade(const FrameParams& P, const occl::AO& ao, V3 p, bool hit, V3 miss, Sdf sdf, Normal normal) {
+    V3 n{0.0f, 0.0f, 0.0f};
+    V3 shade = miss;
+    if (hit) {
+        n = normal(p);
+        float lit = direct_term(n);
+        if (__builtin_expect(P.soft_shadow != 0u, 0)) lit = lit * soft_shadow(P, p, n, lit > 0.0f, sdf);
+        shade = lit_colour(P, lit);
+    }
+    const float f = ambient_occlusion(P, ao, p, n, __builtin_amdgcn_ballot_w64(hit), sdf);
+    if (!hit) return Occluded{miss, 1.0f};
+    return Occluded{V3{f * shade.x, f * shade.y, f * shade.z}, f};
+}
+
+// raymarch<GROUP, PRIM> for the occlusion launch (kifs_occlusion_kernels.hip): the same whole ray per lane through the
+// view P, a hit's colour attenuated by its factor.  The factor is the hit's in heatmap mode too (the colour is the
+// counter's there).  The shading reads the scene's constants and the term from the kernel argument K: nothing of a view
+// is among them.  The Julia pipeline probes through the plain scene_sdf<GROUP_JULIA, 0>, as its shadow rays do.
+// (always_inline: the bunny's estimate is large enough for the inliner to leave its ninth copy a call, which costs the
+// kernel a stack.)
+template <int GROUP, int PRIM>
+KIFS_DEV Occluded raymarch_occluded(const FrameParams& P, occl::ConstParams K, V3 dir, bool valid) {
+    constexpr int NPRIM = GROUP == GROUP_JULIA ? 0 : PRIM;
+    float t = 0.0f;
+    V3 p = P.origin;
+    bool hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = whole_ray_sets_out(P, dir, valid);
+    if constexpr (GROUP == GROUP_JULIA) {
+        JuliaDiag diag;
+        julia_loop<(PRIM & 1) != 0, false>(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, diag);
+    } else {
+        generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations,
+                     [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });
+    }
+    __builtin_amdgcn_s_setprio(0);
+    const occl::ConstParams L = occl::anew(K);
+    const FrameParams S = *(const FrameParams*)&L->B.frame;  // the scene, as every view of the launch shares it
+    Occluded r{S.background_color, 1.0f};
+    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {  // wave-uniform
+        const occl::AO ao{L->ao.samples, L->ao.step, L->ao.decay, L->ao.strength};
+        const auto sdf = [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, NPRIM>(S, q, lanes); };
+        r = occluded_shade(S, ao, p, hit, S.background_color, sdf, [&](V3 q) __attribute__((always_inline)) {
+            if constexpr (GROUP == GROUP_KIFS)  // kifs_normal<PRIM>, its estimate inlined
+                return normal_fd(S.epsilon, q, [&](V3 e) __attribute__((always_inline)) { return kifs_sdf<PRIM>(S, e); });
+            else
+                return scene_normal<GROUP, NPRIM>(S, q);
+        });
+    }
+    if (S.is_heatmap) r.colour = heatmap_colour(S, i_final);
+    return r;
+}
+
 }  // namespace kifs

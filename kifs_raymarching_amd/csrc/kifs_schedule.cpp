@@ -636,7 +636,7 @@ void fill_views(const kifs_ctx* c, kifs::FrameParams& P, kifs::BatchView* views,
 }
 
 // Band, pitch and geometry plane: checked against the frame (P.y1 is still its height), then written into P.
-static int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, uint8_t* out, size_t pitch, int y0, int y1, int encode,
+int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, uint8_t* out, size_t pitch, int y0, int y1, int encode,
                            bool striped, float* geom, size_t geom_pitch, size_t geom_stride) {
     if (y0 < 0 || y1 > P.y1 || y0 > y1) return KIFS_ERR_BAD_ARG;
     if (pitch < size_t(P.width) * 4 || (pitch & 3u) != 0 || (pitch >> 2) > 0xffffffffull) return KIFS_ERR_BAD_SIZE;

@@ -25,7 +25,7 @@ STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
 MAX_JITTER_GRID = _lib.MAX_JITTER_GRID  # KIFS_MAX_JITTER_GRID
-from ._lib import (AdaptiveAAC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
+from ._lib import (AdaptiveAAC, AmbientOcclusionC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -129,6 +129,17 @@ class GuiData:  # data.rs:131-160 (defaults = GuiData::default)
         u = OptionsUniform()
         check(lib.kifs_host_options(C.byref(g), C.byref(u)), "GuiData")
         return u
+
+
+@dataclass
+class AmbientOcclusion:  # KifsAmbientOcclusion: the term of kifs_render_occlusion_async
+    samples: int = 5       # probes along the normal, 1..KIFS_MAX_AO_SAMPLES
+    step: float = 0.02     # their spacing, scene units
+    decay: float = 0.75    # weight of probe i + 1 over probe i, (0, 1]
+    strength: float = 4.0  # >= 0; 0: the plain frame
+
+    def into_buffer_data(self) -> AmbientOcclusionC:
+        return AmbientOcclusionC(int(self.samples), float(self.step), float(self.decay), float(self.strength))
 
 
 def uniform_bytes(u) -> bytes:
@@ -467,6 +478,63 @@ class GraphicState:
         else:
             torch.cuda.synchronize(colour.device)
         return colour[0], geometry[0]
+
+    # ---- ambient occlusion (kifs_render_occlusion_async): every hit attenuated, optionally the factors as a plane
+    def render_occlusion_batch(self, cameras=None, ao: AmbientOcclusion = None, occlusion: bool = False, stream=None,
+                               y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, colour=None, plane=None):
+        """The frames of len(cameras) cameras (cameras None: one frame with the context's camera) with ambient
+        occlusion `ao` (None: AmbientOcclusion()), the context's supersampling factor honoured.  Returns
+        (colour, plane): a uint8 (count, rows, W, 4) torch tensor on this context's device and, with `occlusion`, a
+        float32 (count, rows, W) one -- the factor of every hit, 1.0 on a miss (one sample per pixel only) -- else None.
+        `colour` / `plane`: contiguous destination tensors of those shapes to reuse.  The library takes
+        MAX_OCCLUSION_BATCH cameras per launch; more are fed to it that many at a time.  Enqueued on `stream` like
+        render_async; the caller synchronises before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if n < 1:
+            raise ValueError("render_occlusion_batch: at least one frame")
+        dev = torch.device("cuda", self.device)
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=dev)
+        if tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_occlusion_batch: colour uint8 ({n}, {rows}, {w}, 4), contiguous")
+        if occlusion or plane is not None:
+            if plane is None:
+                plane = torch.empty((n, rows, w), dtype=torch.float32, device=dev)
+            if tuple(plane.shape) != (n, rows, w) or plane.dtype != torch.float32 or not plane.is_contiguous():
+                raise ValueError(f"render_occlusion_batch: plane float32 ({n}, {rows}, {w}), contiguous")
+        term = (AmbientOcclusion() if ao is None else ao).into_buffer_data()
+        stream = self._stream_handle(stream, "render_occlusion_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        self._order_after_producer(colour, stream)
+        if plane is not None:
+            self._order_after_producer(plane, stream)
+        step = _lib.MAX_OCCLUSION_BATCH
+        base, frame_bytes = _device_pointer(colour), rows * w * 4  # (a plane of one f32 per pixel is as many bytes)
+        planes = None if plane is None else _device_pointer(plane)
+        for first in range(0, n, step):
+            m = min(step, n - first)
+            ptrs = (C.c_void_p * m)(*[base + (first + i) * frame_bytes for i in range(m)])
+            part = None if cams is None else C.cast(C.byref(cams, first * C.sizeof(CameraUniform)), C.POINTER(CameraUniform))
+            check(lib.kifs_render_occlusion_async(self._ctx, stream, m, part, ptrs, w * 4, C.byref(term),
+                                                  None if planes is None else planes + first * frame_bytes, w * 4,
+                                                  frame_bytes, y0, y1, encode), "render_occlusion")
+        return colour, plane
+
+    def render_occlusion(self, ao: AmbientOcclusion = None, occlusion: bool = False, y0: int = 0, y1: int = None,
+                         encode: int = ENCODE_SRGB, stream=None):
+        """The context's frame with ambient occlusion, synchronously: (colour uint8 rows x W x 4, plane float32
+        rows x W or None) torch tensors on this context's device."""
+        import torch
+        colour, plane = self.render_occlusion_batch(None, ao=ao, occlusion=occlusion, stream=stream, y0=y0, y1=y1, encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0], None if plane is None else plane[0]
 
     # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
     def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):

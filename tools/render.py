@@ -16,6 +16,8 @@
     python tools/render.py cfg2_julia_1080p orbit_%03d.png --frames 0 1 2 --motion-blur 16 --spp 150   # 64 + 64 + 22 sub-frames
     python tools/render.py cfg2_julia_1080p pano.png --panorama 0,0,2.5                        # 360 degrees from a point
     python tools/render.py cfg2_julia_1080p out.png --dof 0.05 --focus-at 960,540 --samples 32 # focus on what that pixel hits
+    python tools/render.py cfg2_julia_1080p out.png --ao --ao-png ao.png                       # ambient occlusion + its factors
+    python tools/render.py cfg5_sierpinski_8k_orbit orbit_%03d.png --frames 0 30 60 --scale 0.25 --ao 8,0.01,0.8,3 --aa 2
 """
 import argparse
 import sys
@@ -84,6 +86,11 @@ ap.add_argument("--focus-at", metavar="X,Y", default=None,
                 help="with --dof APERTURE (no FOCUS): focus on what pixel X,Y of the frame shows -- its ray is traced "
                      "(kifs_trace_rays_async) and the focus distance is t * dot(dir, -m0), which is printed; a pixel that "
                      "shows the background ends the run with status 1; one frame, not with --frames")
+ap.add_argument("--ao", metavar="S,STEP,DECAY,STRENGTH", nargs="?", const="5,0.02,0.75,4.0", default=None,
+                help="ambient occlusion: S probes along the normal STEP apart, each weighted DECAY times the one before, "
+                     "times STRENGTH (default 5,0.02,0.75,4.0); goes with --aa, --frames and the shadow workloads")
+ap.add_argument("--ao-png", metavar="OUT.png", default=None,
+                help="with --ao (one frame, no --aa): also write the factors as a grey picture, white = open")
 args = ap.parse_args()
 def _numbers(text, count):
     try:
@@ -94,9 +101,10 @@ def _numbers(text, count):
 panorama = None
 if args.panorama is not None:
     panorama = _numbers(args.panorama, 3)
-    others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at)
+    others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at, args.ao, args.ao_png)
     if panorama is None or args.aa != 1 or args.aa_adaptive or args.motion_blur or args.jitter or any(o is not None for o in others):
-        ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply)")
+        ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply; no --ao: ray queries "
+                 "do not compute the term)")
 focus_at = None
 if args.focus_at is not None:
     focus_at = _numbers(args.focus_at, 2)
@@ -141,6 +149,19 @@ if args.aa_adaptive and (args.aa != 1 or args.geometry or args.frames is not Non
     ap.error("--aa-adaptive renders one frame, without --aa or --geometry")
 if args.depth_png and not args.geometry:
     ap.error("--depth-png goes with --geometry")
+ao = None
+if args.ao is not None:
+    numbers = _numbers(args.ao, 4)
+    if numbers is None or numbers[0] != int(numbers[0]):
+        ap.error("--ao takes four numbers S,STEP,DECAY,STRENGTH (S a whole number)")
+    ao = K.AmbientOcclusion(int(numbers[0]), numbers[1], numbers[2], numbers[3])
+    # the term exists in kifs_render_occlusion_async alone
+    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None:
+        ap.error("--ao renders without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry and --morph-to: "
+                 "the accumulate, adaptive, geometry and animation entry points do not compute the term")
+    aa_grid = False  # several supersampled frames go through the occlusion batch, not through the accumulate family
+if args.ao_png and (ao is None or args.aa != 1 or args.frames is not None):
+    ap.error("--ao-png goes with --ao, one frame, without --aa: a resolved pixel has no single factor")
 morph_to = None
 if args.morph_to is not None:
     try:
@@ -300,6 +321,25 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
                       + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})")
                       + (f", jittered over a {args.jitter}x{args.jitter} grid" if args.jitter else ""))
+    elif ao is not None:
+        import numpy as np
+        indices = args.frames if args.frames is not None else [None]
+        cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
+        try:
+            colour, plane = gs.render_occlusion_batch(cams, ao=ao, occlusion=bool(args.ao_png))
+        except K.KifsError as e:
+            sys.exit(f"--ao {args.ao}: {e}")
+        gs.synchronize()
+        for k, frame in zip(indices, colour.cpu().numpy()):
+            path = args.out if k is None else args.out % k
+            write_png(path, frame)
+            print(f"{path}: {screen.width}x{screen.height}, ambient occlusion ({ao.samples} probes {ao.step} apart, decay "
+                  f"{ao.decay}, strength {ao.strength})" + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
+        if args.ao_png:
+            a = plane.cpu().numpy()[0]
+            grey = np.where(np.isnan(a), 0.0, a * 255.0).astype(np.uint8)
+            write_png(args.ao_png, np.dstack([grey, grey, grey, np.full_like(grey, 255)]))
+            print(f"{args.ao_png}: {int((a < 1).sum())} pixels occluded, {int((a == 0).sum())} of them fully")
     elif aa_grid:
         # the whole grid: K x K sub-frames per frame that differ in their cell alone -- the supersampled frame's bytes
         S = args.aa * args.aa
