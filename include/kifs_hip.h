@@ -575,6 +575,59 @@ int kifs_render_occlusion_async(kifs_ctx* ctx, void* hip_stream, int count, cons
                                 float* dev_occlusion, size_t occlusion_pitch_bytes, size_t occlusion_stride_bytes,
                                 int y0, int y1, int encode);
 
+/* ---- extension: a configurable light (not in the reference) --------------------------------------------------------
+ * kifs_render_batch_async with a different shading of the hits: the light's direction, its ambient and diffuse weights
+ * and a Blinn-Phong highlight are the caller's, and the occlusion term of kifs_render_occlusion_async may be applied on
+ * top.  The call is a render of its own (kifs_lighting_kernels.hip); one light per call.
+ *   hit       p is the tested position, n the normal the shading uses, dir the ray direction of the sample, fc the
+ *             fractal colour.  All f32 with dot3(a,b) = fma(a.z,b.z, fma(a.y,b.y, a.x*b.x)), normalize3(v) =
+ *             v / sqrt(dot3(v,v)) with IEEE divide and square root, clamp_ as C ternaries (a NaN stays a NaN); no fused
+ *             operation but those written:
+ *                 l = light.direction;  Lh = normalize3(l);  lit0 = clamp_(dot3(n, l), 0, 1)
+ *                 sh = 1;  if the soft-shadow extension is on and lit0 > 0: sh = the secondary march of
+ *                          KifsExtensions, unchanged, with Lh in the place of normalize((1,1,1))
+ *                 lit = lit0 * sh  (only when the extension is on; otherwise lit = lit0)
+ *                 k = fma(light.diffuse, lit, light.ambient);  c = (k fc.r, k fc.g, k fc.b)
+ *                 if any of light.specular[] is not zero:
+ *                     h = normalize3(Lh - dir);  s = clamp_(dot3(n, h), 0, 1);  e times: s = s * s
+ *                     spec = (lit0 > 0) ? s * sh : 0      (a select: a NaN in the unselected arm is not used)
+ *                     c.x = fma(light.specular[x], spec, c.x)  per channel
+ *                 if ao != NULL: a = the factor of kifs_render_occlusion_async at (p, n), unchanged;  c = (a c.r, a c.g, a c.b)
+ *   other     a miss -- every ray the culls drop -- is the background; a heatmap frame's colour is the counter's, unlit
+ *             and unattenuated.
+ *   samples   the context's supersampling factor k is honoured sample by sample, as kifs_render_occlusion_async does.
+ *   frames    1 <= count <= KIFS_MAX_LIGHT_BATCH; cameras NULL with count 1: the context's camera.  Rows [y0, y1) are
+ *             bit-identical to the same rows of the full frame, every frame of a batch to the lone call.
+ *   identity  the light {(1,1,1), 0.1, 0.9, (0,0,0), any e} with ao NULL writes the bytes of kifs_render_batch_async, and
+ *             with a term those of kifs_render_occlusion_async -- for every pipeline, with soft shadows, heatmap and
+ *             k > 1: with l = (1,1,1) the fma chain of dot3 is (n.x + n.y) + n.z bit for bit.
+ *   refusals  a refused call launches nothing and writes nothing.  KIFS_ERR_BAD_ARG: a NULL ctx, dev_outs_rgba8 or
+ *             light; a direction component that is not finite, or a direction whose dot3(l,l) in f32 is zero, subnormal
+ *             or infinite; a negative or non-finite ambient, diffuse or specular weight; shininess_log2 outside
+ *             0..KIFS_MAX_SHININESS_LOG2; a non-NULL ao that kifs_render_occlusion_async would refuse; count outside
+ *             1..KIFS_MAX_LIGHT_BATCH; NULL cameras with count != 1; a bad band or encode; a NULL or misaligned
+ *             destination entry.  KIFS_ERR_BAD_SIZE and KIFS_ERR_UNCONFIGURED as kifs_render_occlusion_async.  y1 == y0
+ *             returns KIFS_OK and enqueues nothing.
+ *   launch    exactly the occlusion call's: not a feedback launch, no tile costs, no sort, no profiling record, the
+ *             kifs_debug_last_* values left alone; ordered around the table's feedback launches on other streams.
+ *   scope     deliberately absent: a plane of factors (the occlusion call has one); per-frame lights; a form in the
+ *             accumulate, animation, adaptive, geometry and ray-query calls, in kifs_multi_* or in the viewer; a light
+ *             colour; a second light.
+ * Every byte equals the CPU restatement of the contract (tests/lighting_reference.c), which is normative where this text
+ * and it could be read differently. */
+#define KIFS_MAX_SHININESS_LOG2 10
+#define KIFS_MAX_LIGHT_BATCH 64
+typedef struct KifsLight {
+    float   direction[3];    /* towards the light; used AS GIVEN in the direct term, normalised for shadow and highlight */
+    float   ambient;         /* finite, >= 0   (reference: 0.1) */
+    float   diffuse;         /* finite, >= 0   (reference: 0.9) */
+    float   specular[3];     /* linear RGB weight of the highlight; finite, >= 0; all three zero: no highlight is computed */
+    int32_t shininess_log2;  /* e: the Blinn-Phong exponent is 2^e, by e squarings; 0..KIFS_MAX_SHININESS_LOG2 */
+} KifsLight;
+int kifs_render_lit_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                          uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsLight* light,
+                          const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -61,9 +61,16 @@ class AmbientOcclusionC(C.Structure):  # KifsAmbientOcclusion: the term of kifs_
     _fields_ = [("samples", C.c_int32), ("step", C.c_float), ("decay", C.c_float), ("strength", C.c_float)]
 
 
+class KifsLightC(C.Structure):  # KifsLight: the light of kifs_render_lit_async
+    _fields_ = [("direction", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float * 3),
+                ("shininess_log2", C.c_int32)]
+
+
 MAX_RAYS = 1 << 28  # KIFS_MAX_RAYS
 MAX_AO_SAMPLES = 16  # KIFS_MAX_AO_SAMPLES
 MAX_OCCLUSION_BATCH = 64  # KIFS_MAX_OCCLUSION_BATCH
+MAX_SHININESS_LOG2 = 10  # KIFS_MAX_SHININESS_LOG2
+MAX_LIGHT_BATCH = 64  # KIFS_MAX_LIGHT_BATCH
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -97,6 +104,7 @@ assert C.sizeof(CameraUniform) == 64
 assert C.sizeof(OptionsUniform) == 80
 assert C.sizeof(KifsSubpixel) == 2
 assert C.sizeof(AmbientOcclusionC) == 16
+assert C.sizeof(KifsLightC) == 36
 
 # every symbol include/kifs_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -142,6 +150,8 @@ SIGNATURES = {
     "kifs_render_occlusion_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
                                               _P(AmbientOcclusionC), C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
                                               C.c_int]),
+    "kifs_render_lit_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                        _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int, C.c_int]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

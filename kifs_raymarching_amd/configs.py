@@ -186,6 +186,15 @@ def lens_cameras(camera_data: CameraData, aperture: float, focus_distance: float
     return out
 
 
+def light_direction(azimuth: float, elevation: float) -> tuple:
+    """The unit vector towards a light at `azimuth` (radians about the z axis, from +x towards +y) and `elevation`
+    (radians above the xy plane): a direction for Light / KifsLight."""
+    ce = math.cos(elevation)
+    v = np.array([ce * math.cos(azimuth), ce * math.sin(azimuth), math.sin(elevation)], dtype=np.float64)
+    v = v / np.linalg.norm(v)
+    return (float(v[0]), float(v[1]), float(v[2]))
+
+
 def pass_splits(total: int, per_pass: int = 64) -> list:
     """The pass sizes of a progressive frame of `total` sub-frames (GraphicState.render_accumulate_resume, Accumulator):
     total // per_pass passes of `per_pass` and, if anything is left, one of the remainder -- [64, 64, 22] for 150.  A

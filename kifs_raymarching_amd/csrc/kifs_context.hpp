@@ -12,6 +12,7 @@
 //   kifs_converge.cpp  converging accumulation (kifs_render_accumulate_converge_async): sums, moments and a rule
 //   kifs_rays.cpp      ray queries (kifs_trace_rays_async): caller-supplied rays, one launch
 //   kifs_occlusion.cpp ambient occlusion (kifs_render_occlusion_async): the batch call's frames, hits attenuated, one launch
+//   kifs_lighting.cpp  a configurable light (kifs_render_lit_async): the batch call's frames under the caller's light, one launch
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -20,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -165,7 +167,7 @@ TileTable* tile_table(kifs_ctx* c, int width, int height, int y0, int y1, const 
 // The background pixel, encoded exactly as the kernels would (unorm8 / srgb8 of kifs_device_math.hpp).
 uint32_t background_pixel(const kifs_ctx* c, kifs::V3 colour, int encode);
 // Band, pitch and geometry plane of a launch: checked against the frame (P.y1 still its height), then written into P
-// (kifs_schedule.cpp; kifs_occlusion.cpp fills its launch with it as enqueue_batch does).
+// (kifs_schedule.cpp; kifs_occlusion.cpp and kifs_lighting.cpp fill their launches with it as enqueue_batch does).
 int set_destination(const kifs_ctx* c, kifs::FrameParams& P, int count, uint8_t* out, size_t pitch, int y0, int y1, int encode,
                     bool striped, float* geom, size_t geom_pitch, size_t geom_stride);
 // One launch: `count` frames (count == 1 and cameras NULL: the context's camera; else cameras[i] -> outs[i])
@@ -178,10 +180,23 @@ int enqueue_batch(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUn
                   const int* stripes = nullptr, int n_stripes = 0, int in_place = 0,
                   float* geom = nullptr, size_t geom_pitch = 0, size_t geom_stride = 0);
 int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int y0, int y1, int encode);
+// A launch that reads the table's current order without becoming one of its feedback launches (kifs_occlusion.cpp,
+// kifs_lighting.cpp).  When the table's feedback launches run on another stream, the buffer rotation's "nobody still
+// reads it" guarantee (feedback_before, kifs_schedule.cpp) needs this launch ordered after theirs (`before`), and theirs
+// to come after it (!before).
+bool order_around(TileTable* tt, hipStream_t stream, bool before);
 // hipMalloc-backed buffer that only ever grows
 bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what);
 
 }  // namespace host
+
+// The ranges of KifsAmbientOcclusion (include/kifs_hip.h): kifs_occlusion.cpp's term, which kifs_lighting.cpp takes too.
+namespace occl {
+inline bool term_ok(const KifsAmbientOcclusion& ao) {
+    return ao.samples >= 1 && ao.samples <= KIFS_MAX_AO_SAMPLES && std::isfinite(ao.step) && ao.step > 0.0f &&
+           std::isfinite(ao.decay) && ao.decay > 0.0f && ao.decay <= 1.0f && std::isfinite(ao.strength) && ao.strength >= 0.0f;
+}
+}  // namespace occl
 
 // What every launch that carries a scene table shares (kifs_animation.cpp): the animated call and the four accumulated
 // ones differ in their checks and in the last step, the launch itself.

@@ -13,11 +13,6 @@ namespace occl {
 
 static_assert(KIFS_MAX_OCCLUSION_BATCH == MAX_BATCH_INLINE, "the views of a call travel in the kernel argument");
 
-static bool term_ok(const KifsAmbientOcclusion& ao) {
-    return ao.samples >= 1 && ao.samples <= KIFS_MAX_AO_SAMPLES && std::isfinite(ao.step) && ao.step > 0.0f &&
-           std::isfinite(ao.decay) && ao.decay > 0.0f && ao.decay <= 1.0f && std::isfinite(ao.strength) && ao.strength >= 0.0f;
-}
-
 // What a caller can get wrong that needs no look at the frame.
 static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, const KifsAmbientOcclusion* ao,
                  const float* plane, int encode) {
@@ -40,16 +35,6 @@ static int check_plane(const float* plane, size_t pitch, size_t stride, int widt
         (count > 1 && stride < rows * pitch) || (pitch >> 2) > 0xffffffffull || (stride >> 2) > 0xffffffffull)
         return KIFS_ERR_BAD_ARG;
     return KIFS_OK;
-}
-
-// The launch reads the table's current order without becoming one of its feedback launches.  When the table's feedback
-// launches run on another stream, the buffer rotation's "nobody still reads it" guarantee (feedback_before,
-// kifs_schedule.cpp) needs this launch ordered after theirs, and theirs to come after it.
-static bool order_around(TileTable* tt, hipStream_t stream, bool before) {
-    if (!tt->last_stream || tt->last_stream == stream) return true;
-    hipStream_t from = before ? tt->last_stream : stream, to = before ? stream : tt->last_stream;
-    return host::hip_ok(hipEventRecord(tt->stream_left, from), "record(occlusion order)") &&
-           host::hip_ok(hipStreamWaitEvent(to, tt->stream_left, 0), "wait(occlusion order)");
 }
 
 static int enqueue(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, size_t pitch,
@@ -80,10 +65,10 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraU
     O.plane = plane;
     O.pitch_words = uint32_t(plane_pitch >> 2);
     O.stride_words = uint32_t(plane_stride >> 2);
-    if (!order_around(tt, stream, true)) return KIFS_ERR_RUNTIME;
+    if (!host::order_around(tt, stream, true)) return KIFS_ERR_RUNTIME;
     if (!host::hip_ok(launch_occlusion(O, c->options.fractal_group_id, c->options.primitive_id, stream), "occlusion render_kernel launch"))
         return KIFS_ERR_RUNTIME;
-    return order_around(tt, stream, false) ? KIFS_OK : KIFS_ERR_RUNTIME;
+    return host::order_around(tt, stream, false) ? KIFS_OK : KIFS_ERR_RUNTIME;
 }
 
 }  // namespace occl

@@ -24,27 +24,7 @@ namespace occl {
 // Held in SGPRs from the kernel's start, the frame constants, the term and the plane would stay live across the sample
 // loop's back edge and across the march, whose hand-written loops pin s74-s97: that cost the Julia builds spill slots
 // for whole SGPR tuples and the bunny's two dozen parked registers.  occl::anew (kifs_scene.hpp) ties a phase's loads to its place.
-struct Pixel {
-    FrameParams P;  // the view's parameters
-    uint32_t view;
-    int tile_x, tile_y, frame_y;  // the OUTPUT tile, as TileOrigin's
-    int lx, ly, x, y;             // this lane's output pixel: within the tile, of the frame
-    bool valid;                   // inside the frame and the launch's rows
-};
-// `tile`: the workgroup's entry of the tile order (x | y << 16), the one scalar the phases hand on.
-__device__ __forceinline__ Pixel pixel_of(ConstParams at, uint32_t tile) {
-    const ConstParams K = anew(at);
-    const BatchParams& B = *(const BatchParams*)&K->B;
-    const LaunchSlot S = launch_slot(B);
-    const FrameParams P = batch_frame(B, S.view);
-    const int tile_x = int(tile & 0xffffu) * TILE_W, tile_y = int(tile >> 16) * TILE_H;
-    const int frame_y = tile_frame_row(P, tile >> 16);
-    // wave w owns columns [8 w, 8 w + 8) of the tile, its lanes the pixels of that block row by row (tile_frame)
-    const int tid = threadIdx.x, wave = tid >> 6, pixel = tid & 63;
-    const int lx = (wave << 3) | (pixel & 7), ly = pixel >> 3;
-    const int x = tile_x + lx, y = frame_y + ly;
-    return Pixel{P, S.view, tile_x, tile_y, frame_y, lx, ly, x, y, (x < P.width) && (y < P.y1)};
-}
+// A phase's view of the lane's pixel is tile_pixel (kifs_render_common.hpp).
 
 // (amdgpu_waves_per_eu: as ssaa::render_kernel)
 template <int GROUP, int PRIM>
@@ -59,14 +39,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
     // (from the argument as the compiler sees it: the entry's load stays a scalar one)
     const uint32_t tile = O.B.frame.tile_order[launch_slot(O.B).index];
     {
-        const Pixel F = pixel_of(K, tile);
+        const TilePixel F = tile_pixel(K, tile);
         if (F.P.encode == 1) s_srgb[tid] = F.P.srgb_table[tid];  // visible after the next barrier
     }
     // The resolve of kifs_set_supersampling, per channel in f32: acc = c(0,0), then acc + c(i,j) with j outer and i
     // inner, mean = acc / k^2 correctly rounded (k = 1: c / 1 = c).  A culled sample is the background colour.
     float a = 1.0f;  // the plane's value: the factor of the (one) sample's hit, 1 on a miss
     for (int s = 0;; ++s) {
-        const Pixel F = pixel_of(K, tile);
+        const TilePixel F = tile_pixel(K, tile);
         const int k = F.P.ssaa;  // uniform, 1..KIFS_MAX_SUPERSAMPLING
         if (s >= k * k || __ballot(F.valid) == 0ull) break;  // wave-uniform; a wave without a pixel in the frame marches nothing
         // The virtual screen, as ssaa::render_kernel's: height k H, same aspect float, its own 1 / height for the
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void
         s_acc[1][tid] = s == 0 ? c.y : s_acc[1][tid] + c.y;
         s_acc[2][tid] = s == 0 ? c.z : s_acc[2][tid] + c.z;
     }
-    const Pixel F = pixel_of(K, tile);
+    const TilePixel F = tile_pixel(K, tile);
     // the factor of pixel (x, y): row y - y0 of view `view`'s plane (rows of a band are packed, as the colour's)
     const ConstParams L = anew(K);
     float* const plane = L->plane;

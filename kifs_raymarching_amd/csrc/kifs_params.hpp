@@ -252,4 +252,31 @@ static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
 
 }  // namespace occl
 
+namespace light {
+
+// The light of kifs_render_lit_async (KifsLight, include/kifs_hip.h), as the kernels read it: the caller's direction as
+// given (the direct term's) and normalised on the host (`unit`: the shadow ray's and the highlight's), the weights, the
+// highlight's squarings.
+struct Light {
+    V3 direction;
+    V3 unit;             // normalize(direction), f32 with IEEE divide and square root (kifs_lighting.cpp)
+    float ambient, diffuse;
+    V3 specular;
+    int shininess_log2;  // 0..KIFS_MAX_SHININESS_LOG2
+    uint32_t highlight;  // != 0: some weight of `specular` is not zero (decided on the host: a scalar branch here)
+};
+
+// The argument of light::render_kernel (kifs_lighting_kernels.hip): the launch's frame constants and views as every
+// render kernel takes them (frame.ssaa = k, 1 included), the light, and the occlusion term with the flag that says
+// whether there is one.
+struct Params {
+    BatchParams B;
+    Light light;
+    occl::AO ao;         // read only when has_ao != 0
+    uint32_t has_ao;
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace light
+
 }  // namespace kifs

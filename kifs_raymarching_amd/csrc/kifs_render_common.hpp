@@ -204,6 +204,32 @@ __device__ __forceinline__ V3 ray_at(const FrameParams& P, float t, V3 dir) {
     return V3{fmaf_(t, dir.x, P.origin.x), fmaf_(t, dir.y, P.origin.y), fmaf_(t, dir.z, P.origin.z)};
 }
 
+// A lane's output pixel in the kernels whose phases read the kernel argument anew (occl::render_kernel,
+// light::render_kernel): the view's parameters and the pixel, made from the argument and the workgroup's tile alone.
+struct TilePixel {
+    FrameParams P;  // the view's parameters
+    uint32_t view;
+    int tile_x, tile_y, frame_y;  // the OUTPUT tile, as TileOrigin's
+    int lx, ly, x, y;             // this lane's output pixel: within the tile, of the frame
+    bool valid;                   // inside the frame and the launch's rows
+};
+// `at`: the kernel argument (occl::ConstParams, light::ConstParams: a BatchParams B first; anew is the namespace's own);
+// `tile`: the workgroup's entry of the tile order (x | y << 16), the one scalar the phases hand on.
+template <class Args>
+__device__ __forceinline__ TilePixel tile_pixel(Args at, uint32_t tile) {
+    const Args K = anew(at);
+    const BatchParams& B = *(const BatchParams*)&K->B;
+    const LaunchSlot S = launch_slot(B);
+    const FrameParams P = batch_frame(B, S.view);
+    const int tile_x = int(tile & 0xffffu) * TILE_W, tile_y = int(tile >> 16) * TILE_H;
+    const int frame_y = tile_frame_row(P, tile >> 16);
+    // wave w owns columns [8 w, 8 w + 8) of the tile, its lanes the pixels of that block row by row (tile_frame)
+    const int tid = threadIdx.x, wave = tid >> 6, pixel = tid & 63;
+    const int lx = (wave << 3) | (pixel & 7), ly = pixel >> 3;
+    const int x = tile_x + lx, y = frame_y + ly;
+    return TilePixel{P, S.view, tile_x, tile_y, frame_y, lx, ly, x, y, (x < P.width) && (y < P.y1)};
+}
+
 // The staged tile to the destination, 256 threads: thread -> (tid & 31, tid >> 5), linear rows of 128 bytes, the first
 // ROWS rows of `s_tile`, under the guards of a ragged frame edge and a band's last row.
 template <int ROWS = TILE_H>

@@ -1311,4 +1311,128 @@ KIFS_DEV Occluded raymarch_occluded(const FrameParams& P, occl::ConstParams K, V
     return r;
 }
 
+// ---- extension: a configurable light (kifs_render_lit_async, include/kifs_hip.h) ----------------------------------
+// The lighting model above with the light's constants as arguments, operation for operation as the header states it.
+// With the reference's light -- (1,1,1), 0.1, 0.9, no highlight -- every piece computes the bits of the one it stands
+// beside: dot's fma chain with ones is (n.x + n.y) + n.z.
+// The direct term towards the light vector l, used as given (direct_term).
+KIFS_DEV float direct_term_towards(V3 n, V3 l) { return clamp_(dot(n, l), 0.0f, 1.0f); }
+// The colour of a hit whose (attenuated) direct term is `lit` (lit_colour).
+KIFS_DEV V3 lit_colour_with(const FrameParams& P, float ambient, float diffuse, float lit) {
+    const float k = fmaf_(diffuse, lit, ambient);
+    return V3{k * P.fractal_color.x, k * P.fractal_color.y, k * P.fractal_color.z};
+}
+// shadow_point for a ray towards the unit vector L, and soft_shadow with it: start, step and count are theirs.
+KIFS_DEV V3 shadow_point_towards(const ShadowRay& s, V3 L) {
+    return V3{fmaf_(s.t, L.x, s.start.x), fmaf_(s.t, L.y, s.start.y), fmaf_(s.t, L.z, s.start.z)};
+}
+// (`towards()`: the unit vector, asked for step by step, so that a caller short of scalar registers can read it anew.)
+template <class Sdf, class Unit>
+KIFS_DEV float soft_shadow_towards(const FrameParams& P, V3 p, V3 n, Unit towards, bool lanes_hit, Sdf sdf) {
+    ShadowRay s = shadow_ray_from(P, shadow_start(P, p, n));
+    bool marching = lanes_hit && (0 < P.shadow_steps);
+    for (; __builtin_amdgcn_ballot_w64(marching) != 0ull; ++s.j) {
+        if (marching) marching = !shadow_step(P, sdf(shadow_point_towards(s, towards()), ~0ull), s);
+    }
+    return s.res;
+}
+// The Blinn-Phong highlight before its attenuation: the normal against the half vector of the unit light vector L and
+// the way back along the ray, raised to 2^e by e squarings (e: uniform).
+KIFS_DEV float highlight(V3 n, V3 L, V3 dir, int e) {
+    const V3 h = normalize(V3{L.x - dir.x, L.y - dir.y, L.z - dir.z});
+    float s = clamp_(dot(n, h), 0.0f, 1.0f);
+    for (int i = 0; i < e; ++i) s = s * s;
+    return s;
+}
+
+// The lit kernel's phases read the kernel argument anew as the occlusion kernel's do (occl::anew).
+namespace light {
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+KIFS_DEV ConstParams anew(ConstParams K) {
+    asm volatile("" : "+s"(K));
+    return K;
+}
+}  // namespace light
+
+// occluded_shade with the launch's light, and the factor only when the launch has a term.  A lane that did not hit gets
+// `miss`.  The light and the term are read from the kernel argument K where each is used -- the direction for the direct
+// term and the highlight, the unit vector again for the shadow ray, the weights after it, the term last -- so that only
+// the shadow ray's unit vector crosses a march (the bunny's estimate leaves few scalar registers to park anything in).
+// `dir()`: the ray direction of the lane's sample, asked for where the highlight needs it -- after the march and the
+// normal, so that the caller can recompute it instead of carrying it.  The highlight is taken before the shadow ray sets
+// out: one register crosses the secondary march, not the half vector's three.
+KIFS_DEV V3 load3(const V3 __attribute__((address_space(4))) * v) { return V3{v->x, v->y, v->z}; }
+template <class Sdf, class Normal, class Dir>
+KIFS_DEV V3 lit_shade(const FrameParams& P, light::ConstParams K, V3 p, bool hit, V3 miss, Sdf sdf, Normal normal, Dir dir) {
+    V3 n{0.0f, 0.0f, 0.0f};
+    V3 shade = miss;
+    if (hit) {
+        n = normal(p);
+        const light::ConstParams A = light::anew(K);
+        const bool highlit = A->light.highlight != 0u;  // uniform
+        const float lit0 = direct_term_towards(n, load3(&A->light.direction));
+        float s = 0.0f;
+        if (highlit) s = highlight(n, load3(&A->light.unit), dir(), A->light.shininess_log2);
+        float sh = 1.0f, lit = lit0;
+        if (__builtin_expect(P.soft_shadow != 0u, 0)) {
+            sh = soft_shadow_towards(
+                P, p, n, [&]() __attribute__((always_inline)) { return load3(&light::anew(K)->light.unit); }, lit0 > 0.0f, sdf);
+            lit = lit0 * sh;
+        }
+        const light::ConstParams B = light::anew(K);
+        shade = lit_colour_with(P, B->light.ambient, B->light.diffuse, lit);
+        if (highlit) {
+            const float spec = (lit0 > 0.0f) ? s * sh : 0.0f;
+            const V3 w = load3(&B->light.specular);
+            shade = V3{fmaf_(w.x, spec, shade.x), fmaf_(w.y, spec, shade.y), fmaf_(w.z, spec, shade.z)};
+        }
+    }
+    const light::ConstParams C = light::anew(K);
+    if (C->has_ao != 0u) {  // uniform; the probes run for the whole wave, as occluded_shade's
+        const occl::AO ao{C->ao.samples, C->ao.step, C->ao.decay, C->ao.strength};
+        const float f = ambient_occlusion(P, ao, p, n, __builtin_amdgcn_ballot_w64(hit), sdf);
+        shade = V3{f * shade.x, f * shade.y, f * shade.z};
+    }
+    return hit ? shade : miss;
+}
+
+// raymarch_occluded for the lit launch (kifs_lighting_kernels.hip): the same whole ray per lane through the view P, a
+// hit's colour from the launch's light and, when the launch has a term, attenuated by the hit's factor.  The shading
+// reads the scene's constants, the light and the term from the kernel argument K.
+template <int GROUP, int PRIM, class Dir>
+KIFS_DEV V3 raymarch_lit(const FrameParams& P, light::ConstParams K, V3 dir, bool valid, Dir redo_dir) {
+    constexpr int NPRIM = GROUP == GROUP_JULIA ? 0 : PRIM;
+    float t = 0.0f;
+    V3 p = P.origin;
+    bool hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = whole_ray_sets_out(P, dir, valid);
+    if constexpr (GROUP == GROUP_JULIA) {
+        JuliaDiag diag;
+        julia_loop<(PRIM & 1) != 0, false>(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, diag);
+    } else {
+        generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations,
+                     [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });
+    }
+    __builtin_amdgcn_s_setprio(0);
+    const light::ConstParams L = light::anew(K);
+    const FrameParams S = *(const FrameParams*)&L->B.frame;  // the scene, as every view of the launch shares it
+    V3 colour = S.background_color;
+    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {  // wave-uniform
+        const auto sdf = [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, NPRIM>(S, q, lanes); };
+        colour = lit_shade(
+            S, K, p, hit, S.background_color, sdf,
+            [&](V3 q) __attribute__((always_inline)) {
+                if constexpr (GROUP == GROUP_KIFS)  // kifs_normal<PRIM>, its estimate inlined
+                    return normal_fd(S.epsilon, q, [&](V3 e) __attribute__((always_inline)) { return kifs_sdf<PRIM>(S, e); });
+                else
+                    return scene_normal<GROUP, NPRIM>(S, q);
+            },
+            redo_dir);
+    }
+    if (S.is_heatmap) colour = heatmap_colour(S, i_final);
+    return colour;
+}
+
 }  // namespace kifs

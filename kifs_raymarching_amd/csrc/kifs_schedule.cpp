@@ -985,6 +985,13 @@ int enqueue(kifs_ctx* c, hipStream_t stream, uint8_t* dev_out, size_t pitch, int
     return enqueue_batch(c, stream, 1, nullptr, &dev_out, pitch, y0, y1, encode);
 }
 
+bool order_around(TileTable* tt, hipStream_t stream, bool before) {
+    if (!tt->last_stream || tt->last_stream == stream) return true;
+    hipStream_t from = before ? tt->last_stream : stream, to = before ? stream : tt->last_stream;
+    return hip_ok(hipEventRecord(tt->stream_left, from), "record(order around feedback launches)") &&
+           hip_ok(hipStreamWaitEvent(to, tt->stream_left, 0), "wait(order around feedback launches)");
+}
+
 bool grow(uint8_t*& buf, size_t& have, size_t need, const char* what) {
     if (need <= have) return true;
     if (buf) (void)hipFree(buf);

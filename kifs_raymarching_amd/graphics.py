@@ -25,7 +25,7 @@ STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
 MAX_JITTER_GRID = _lib.MAX_JITTER_GRID  # KIFS_MAX_JITTER_GRID
-from ._lib import (AdaptiveAAC, AmbientOcclusionC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
+from ._lib import (AdaptiveAAC, AmbientOcclusionC, KifsLightC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -140,6 +140,19 @@ class AmbientOcclusion:  # KifsAmbientOcclusion: the term of kifs_render_occlusi
 
     def into_buffer_data(self) -> AmbientOcclusionC:
         return AmbientOcclusionC(int(self.samples), float(self.step), float(self.decay), float(self.strength))
+
+
+@dataclass
+class Light:  # KifsLight: the light of kifs_render_lit_async; the defaults are the reference's light, no highlight
+    direction: tuple = (1.0, 1.0, 1.0)     # towards the light; as given in the direct term, normalised for shadow and highlight
+    ambient: float = 0.1                   # >= 0
+    diffuse: float = 0.9                   # >= 0
+    specular: tuple = (0.0, 0.0, 0.0)      # linear RGB weight of the highlight, >= 0; all zero: none
+    shininess_log2: int = 5                # the Blinn-Phong exponent is 2 ** shininess_log2, 0..KIFS_MAX_SHININESS_LOG2
+
+    def into_buffer_data(self) -> KifsLightC:
+        return KifsLightC((C.c_float * 3)(*[float(v) for v in self.direction]), float(self.ambient), float(self.diffuse),
+                          (C.c_float * 3)(*[float(v) for v in self.specular]), int(self.shininess_log2))
 
 
 def uniform_bytes(u) -> bytes:
@@ -535,6 +548,53 @@ class GraphicState:
         else:
             torch.cuda.synchronize(colour.device)
         return colour[0], None if plane is None else plane[0]
+
+    # ---- a configurable light (kifs_render_lit_async): every hit shaded by `light`, optionally occluded
+    def render_lit_batch(self, cameras, light: Light, ao: AmbientOcclusion = None, stream=None, y0: int = 0, y1: int = None,
+                         encode: int = ENCODE_SRGB, colour=None):
+        """The frames of len(cameras) cameras (cameras None: one frame with the context's camera) under `light`, with
+        the ambient-occlusion term `ao` on top when one is given (None: none), the context's supersampling factor and
+        soft-shadow extension honoured.  Returns a uint8 (count, rows, W, 4) torch tensor on this context's device;
+        `colour`: a contiguous destination tensor of that shape to reuse.  The library takes MAX_LIGHT_BATCH cameras per
+        launch; more are fed to it that many at a time.  Enqueued on `stream` like render_async; the caller synchronises
+        before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if n < 1:
+            raise ValueError("render_lit_batch: at least one frame")
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_lit_batch: colour uint8 ({n}, {rows}, {w}, 4), contiguous")
+        lit = light.into_buffer_data()
+        term = None if ao is None else ao.into_buffer_data()
+        stream = self._stream_handle(stream, "render_lit_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        self._order_after_producer(colour, stream)
+        step = _lib.MAX_LIGHT_BATCH
+        base, frame_bytes = _device_pointer(colour), rows * w * 4
+        for first in range(0, n, step):
+            m = min(step, n - first)
+            ptrs = (C.c_void_p * m)(*[base + (first + i) * frame_bytes for i in range(m)])
+            part = None if cams is None else C.cast(C.byref(cams, first * C.sizeof(CameraUniform)), C.POINTER(CameraUniform))
+            check(lib.kifs_render_lit_async(self._ctx, stream, m, part, ptrs, w * 4, C.byref(lit),
+                                            None if term is None else C.byref(term), y0, y1, encode), "render_lit")
+        return colour
+
+    def render_lit(self, light: Light, ao: AmbientOcclusion = None, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB,
+                   stream=None):
+        """The context's frame under `light` (and `ao`), synchronously: a uint8 rows x W x 4 torch tensor on this
+        context's device."""
+        import torch
+        colour = self.render_lit_batch(None, light, ao=ao, stream=stream, y0=y0, y1=y1, encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0]
 
     # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
     def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):

@@ -18,6 +18,7 @@
     python tools/render.py cfg2_julia_1080p out.png --dof 0.05 --focus-at 960,540 --samples 32 # focus on what that pixel hits
     python tools/render.py cfg2_julia_1080p out.png --ao --ao-png ao.png                       # ambient occlusion + its factors
     python tools/render.py cfg5_sierpinski_8k_orbit orbit_%03d.png --frames 0 30 60 --scale 0.25 --ao 8,0.01,0.8,3 --aa 2
+    python tools/render.py cfg2_julia_1080p out.png --light -0.55,0.75,0.36,0.15,0.85 --specular 0.6,0.6,0.5,3 --ao  # a moved light
 """
 import argparse
 import sys
@@ -91,6 +92,12 @@ ap.add_argument("--ao", metavar="S,STEP,DECAY,STRENGTH", nargs="?", const="5,0.0
                      "times STRENGTH (default 5,0.02,0.75,4.0); goes with --aa, --frames and the shadow workloads")
 ap.add_argument("--ao-png", metavar="OUT.png", default=None,
                 help="with --ao (one frame, no --aa): also write the factors as a grey picture, white = open")
+ap.add_argument("--light", metavar="X,Y,Z[,AMBIENT,DIFFUSE]", default=None,
+                help="light the hits from direction X,Y,Z (towards the light, used as given in the direct term) with the "
+                     "weights AMBIENT,DIFFUSE (default 0.1,0.9); goes with --ao, --aa, --frames and the shadow workloads")
+ap.add_argument("--specular", metavar="R,G,B[,E]", default=None,
+                help="a Blinn-Phong highlight of linear weight R,G,B and exponent 2^E (E 0..10, default 5) under --light "
+                     "(without --light: under the reference's light 1,1,1)")
 args = ap.parse_args()
 def _numbers(text, count):
     try:
@@ -101,10 +108,11 @@ def _numbers(text, count):
 panorama = None
 if args.panorama is not None:
     panorama = _numbers(args.panorama, 3)
-    others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at, args.ao, args.ao_png)
+    others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at, args.ao, args.ao_png,
+              args.light, args.specular)
     if panorama is None or args.aa != 1 or args.aa_adaptive or args.motion_blur or args.jitter or any(o is not None for o in others):
-        ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply; no --ao: ray queries "
-                 "do not compute the term)")
+        ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply; no --ao, --light or "
+                 "--specular: ray queries compute neither the term nor a light of the caller's)")
 focus_at = None
 if args.focus_at is not None:
     focus_at = _numbers(args.focus_at, 2)
@@ -162,6 +170,26 @@ if args.ao is not None:
     aa_grid = False  # several supersampled frames go through the occlusion batch, not through the accumulate family
 if args.ao_png and (ao is None or args.aa != 1 or args.frames is not None):
     ap.error("--ao-png goes with --ao, one frame, without --aa: a resolved pixel has no single factor")
+light = None
+if args.light is not None or args.specular is not None:
+    # the light exists in kifs_render_lit_async alone
+    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None:
+        ap.error("--light and --specular render without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry and "
+                 "--morph-to: the accumulate, adaptive, geometry and animation entry points shade with the reference's light")
+    if args.ao_png:
+        ap.error("--ao-png goes without --light and --specular: the lit call writes no plane of factors")
+    lit = (1.0, 1.0, 1.0, 0.1, 0.9)
+    if args.light is not None:
+        lit = _numbers(args.light, 5) or ((_numbers(args.light, 3) or ()) + (0.1, 0.9))
+        if len(lit) != 5:
+            ap.error("--light takes three numbers X,Y,Z or five X,Y,Z,AMBIENT,DIFFUSE")
+    shine = (0.0, 0.0, 0.0, 5.0)
+    if args.specular is not None:
+        shine = _numbers(args.specular, 4) or ((_numbers(args.specular, 3) or ()) + (5.0,))
+        if len(shine) != 4 or shine[3] != int(shine[3]):
+            ap.error("--specular takes three numbers R,G,B or four R,G,B,E (E a whole number)")
+    light = K.Light(direction=lit[:3], ambient=lit[3], diffuse=lit[4], specular=shine[:3], shininess_log2=int(shine[3]))
+    aa_grid = False  # several supersampled frames go through the lit batch, not through the accumulate family
 morph_to = None
 if args.morph_to is not None:
     try:
@@ -321,6 +349,21 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
                       + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})")
                       + (f", jittered over a {args.jitter}x{args.jitter} grid" if args.jitter else ""))
+    elif light is not None:
+        indices = args.frames if args.frames is not None else [None]
+        cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
+        try:
+            colour = gs.render_lit_batch(cams, light, ao=ao)
+        except K.KifsError as e:
+            sys.exit(f"--light {args.light} --specular {args.specular}: {e}")
+        gs.synchronize()
+        for k, frame in zip(indices, colour.cpu().numpy()):
+            path = args.out if k is None else args.out % k
+            write_png(path, frame)
+            print(f"{path}: {screen.width}x{screen.height}, lit from {tuple(light.direction)} (ambient {light.ambient}, diffuse "
+                  f"{light.diffuse}" + (f", highlight {tuple(light.specular)} at 2^{light.shininess_log2}" if any(light.specular) else "")
+                  + ")" + (f", ambient occlusion ({ao.samples} probes)" if ao is not None else "")
+                  + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
     elif ao is not None:
         import numpy as np
         indices = args.frames if args.frames is not None else [None]
