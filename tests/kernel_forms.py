@@ -345,11 +345,12 @@ SSAA_FORMS = {
 }
 
 
-# geom::, adaptive::, anim:: and accum::render_kernel<G, P>, accum::jitter_render_kernel<G, P> and
+# geom::, adaptive::, anim::, accum::, occl:: and light::render_kernel<G, P>, accum::jitter_render_kernel<G, P> and
 # accum::carry_render_kernel<G, P> (progressive accumulation), chosen by
 # dispatch_pipeline<2>(group, primitive, sdf_iters <= 24): each is claimed by the geometry_cases.PIPELINES name that reaches
 # it in test_every_pipeline_bit_exact of tests/test_gpu_geometry.py, test_gpu_adaptive.py, test_gpu_animation.py,
-# test_gpu_accumulate.py, test_gpu_accumulate_jitter.py and test_gpu_progressive.py (and in the seeded scenes of tests/extension_fuzz_cases.py, which
+# test_gpu_accumulate.py, test_gpu_accumulate_jitter.py, test_gpu_progressive.py, test_gpu_occlusion.py and
+# test_gpu_lighting.py (and in the seeded scenes of tests/extension_fuzz_cases.py, which
 # take the same names).  adaptive::classify_kernel is no render form -- it reads a
 # geometry plane and marches nothing -- and stays out of the table.
 _EXTENSION_PIPELINES = {(0, 0): "sphere", (0, 1): "cylinder", (0, 2): "box", (0, 3): "torus", (0, 4): "sierpinski",
@@ -366,9 +367,12 @@ ANIMATION_FORMS = _extension_forms("anim", "kifs::anim::Params")
 ACCUMULATE_FORMS = _extension_forms("accum", "kifs::accum::Params")
 JITTER_FORMS = _extension_forms("accum", "kifs::accum::Params", "jitter_render_kernel")
 CARRY_FORMS = _extension_forms("accum", "kifs::accum::CarryParams", "carry_render_kernel")
+OCCLUSION_FORMS = _extension_forms("occl", "kifs::occl::Params")
+LIGHTING_FORMS = _extension_forms("light", "kifs::light::Params")
 EXTENSION_FORMS = {"test_gpu_geometry.py": GEOMETRY_FORMS, "test_gpu_adaptive.py": ADAPTIVE_FORMS,
                    "test_gpu_animation.py": ANIMATION_FORMS, "test_gpu_accumulate.py": ACCUMULATE_FORMS,
-                   "test_gpu_accumulate_jitter.py": JITTER_FORMS, "test_gpu_progressive.py": CARRY_FORMS}
+                   "test_gpu_accumulate_jitter.py": JITTER_FORMS, "test_gpu_progressive.py": CARRY_FORMS,
+                   "test_gpu_occlusion.py": OCCLUSION_FORMS, "test_gpu_lighting.py": LIGHTING_FORMS}
 
 
 def short(name):

@@ -4,7 +4,8 @@ to the occlusion model by tests/test_lighting_reference.py, which also shows tha
 light), and with the reference's light they are the bytes of the plain render and of the occlusion call.  Bytes exactly,
 no tolerance: both sides run the contract's operation sequence.  Frames are 102 x 45 unless said -- width no multiple of
 32, height no multiple of 8, four tile columns and six tile rows -- and every destination is pre-filled with a sentinel and
-padded, so that a missing store and a store outside the frame both show."""
+padded, so that a missing store and a store outside the frame both show.  The lights at the edges of what the entry point
+accepts are compared like any other (test_accepted_edges_bit_exact); tests/test_gpu_shading_fuzz.py has the seeded scenes."""
 import ctypes as C
 
 import numpy as np
@@ -292,6 +293,29 @@ def test_band_equals_the_rows_of_the_full_frame(name, lgs, kifs, oracle):
     assert empty.st == OK and empty.untouched()
 
 
+# The edges of the ranges a light is accepted at, and a fourth light whose weights carry an infinite channel into the encode.
+EDGES = [dict(LR.A, direction=(1.1e-19, 0.0, 0.0), shininess_log2=0),            # dot3 = 1.21e-38: the smallest normals
+         dict(LR.A, direction=(1.0e19, -1.0e19, 1.0e19), shininess_log2=10),
+         dict(LR.A, ambient=0.0, diffuse=0.0, specular=(3.0e38, 0.0, 0.0)),
+         dict(LR.A, ambient=3.0e38, diffuse=3.0e38)]
+
+
+@pytest.mark.parametrize("edge", range(len(EDGES)))
+@pytest.mark.parametrize("name", ["julia_24", "torus"])
+def test_accepted_edges_bit_exact(name, edge, lgs, kifs, oracle):
+    """What the accepted edges write, not only that they are accepted: the model's bytes in both encodes."""
+    screen, cam, gui, iters = scene = cases(kifs, W, H)[name]
+    _setup(lgs, *scene)
+    m = LR.lit_frame(oracle, kifs, screen, cam, gui, iters, EDGES[edge])
+    assert m.hit.any() and not m.hit.all()
+    print(name, edge, "hits", int(m.hit.sum()), "lit0 > 0:", int((m.hit & (m.lit0 > 0)).sum()), "lit0 = 1:", int((m.hit & (m.lit0 == 1)).sum()),
+          "s > 0:", int((m.hit & (m.s > 0)).sum()), "non-finite channels:", int((~np.isfinite(m.rgb)).sum()))
+    for encode in (1, 0):
+        r = _call(lgs, kifs, spec=EDGES[edge], encode=encode)
+        assert r.st == OK
+        _assert_bytes(r.colour[0], LR.encode(oracle, m.rgb, encode), (name, edge, encode))
+
+
 def _bad_lights():
     nan, inf = float("nan"), float("inf")
     good = dict(LR.A)
@@ -344,10 +368,7 @@ def test_refusals_write_nothing(lgs, kifs):
         r = _call(lgs, kifs, **kw)
         assert r.st == BAD_SIZE and r.untouched(), kw
     # the edges of the ranges are accepted
-    edges = [dict(LR.A, direction=(1.1e-19, 0.0, 0.0), shininess_log2=0),            # dot3 = 1.21e-38: the smallest normals
-             dict(LR.A, direction=(1.0e19, -1.0e19, 1.0e19), shininess_log2=10),
-             dict(LR.A, ambient=0.0, diffuse=0.0, specular=(3.0e38, 0.0, 0.0))]
-    for s in edges:
+    for s in EDGES[:3]:
         assert _call(lgs, kifs, spec=s).st == OK, s
     assert _call(lgs, kifs, cpad=0).st == OK
 

@@ -10,6 +10,10 @@ product's own uniform bytes; there is no tolerance.  Destinations are pre-filled
   geometry   E, R, D, X and I at 64 x 48: render_geometry's texels against tests/geometry_reference.py -- the f32 t and normal
              show a wrong square root or orbit trip that a colour byte may round away
   rays       1024 generated rays in every E, D, X, M (0, -5) and P scene against tests/ray_reference.py, texels and bytes
+  shading    E, R, D, X, I and M at 64 x 48 through kifs_render_lit_async (light A, the default term) and
+             kifs_render_occlusion_async (the default term, with its plane) against tests/lighting_reference.py and
+             tests/occlusion_reference.py: both kernels take the culls, the doubled trip and the rounds' permissions from the
+             same launch parameters as the plain forms and shade from a second reading of them
 
 Children run one after another, each under `timeout`.  A child that ends with any other status than 0 stops the module,
 as in tests/test_gpu_kernel_forms.py: every later parameter of the forms fails without starting anything."""
@@ -23,6 +27,8 @@ import pytest
 
 import geometry_reference as GR
 import kernel_forms as F
+import lighting_reference as LR
+import occlusion_reference as OR
 import option_gates as G
 import ray_cases
 import ray_reference as RR
@@ -235,3 +241,42 @@ def test_ray_queries(name, ogs, kifs, oracle):
         assert st == 0
         _assert_same_bits(geom, want_geom, (name, encode))
         _assert_bytes(rgba, want_rgba, f"{name} encode={encode}")
+
+
+# ---- the lit and the occlusion kernels ---------------------------------------------------------------------------------
+SHADING_GATES = "ERDXIM"
+
+
+def _shading_views(ogs, kifs, oracle, name):
+    """The context set up for the case at the geometry planes' size, its two cameras, and per camera the oracle-side
+    uniforms the models march with.  Cases the plan marks `background_only` are compared like the others."""
+    _scene(ogs, kifs, name, GEOMETRY)
+    cams = [G.camera(kifs, name, c) for c in GEOMETRY_CAMERAS]
+    ogs.set_camera(cams[0])
+    return cams, [_uniforms(oracle, kifs, name, GEOMETRY, c) for c in GEOMETRY_CAMERAS]
+
+
+@pytest.mark.parametrize("name", G.names(SHADING_GATES))
+def test_lit_frame(name, ogs, kifs, oracle):
+    """Both cameras in one call of kifs_render_lit_async under light A with the default term: every colour byte."""
+    from test_gpu_lighting import _assert_bytes, _call
+    cams, uniforms = _shading_views(ogs, kifs, oracle, name)
+    r = _call(ogs, kifs, LR.A, ao=OR.DEFAULT, cams=cams, count=len(cams))
+    assert r.st == 0
+    for v, (c, (s, cam, o)) in enumerate(zip(GEOMETRY_CAMERAS, uniforms)):
+        m = LR.march(oracle, s, cam, o, oracle.iters(*G.SCENES[name].iters), LR.A, OR.DEFAULT)
+        _assert_bytes(r.colour[v], LR.encode(oracle, m.rgb, 1), (name, c))
+
+
+@pytest.mark.parametrize("name", G.names(SHADING_GATES))
+def test_occlusion_frame(name, ogs, kifs, oracle):
+    """Both cameras in one call of kifs_render_occlusion_async with the default term: every colour byte, and every
+    factor of the plane by bit pattern."""
+    from test_gpu_occlusion import _assert_bytes, _assert_plane, _call
+    cams, uniforms = _shading_views(ogs, kifs, oracle, name)
+    r = _call(ogs, kifs, OR.DEFAULT, cams=cams, count=len(cams))
+    assert r.st == 0
+    for v, (c, (s, cam, o)) in enumerate(zip(GEOMETRY_CAMERAS, uniforms)):
+        m = OR.march(oracle, s, cam, o, oracle.iters(*G.SCENES[name].iters), OR.DEFAULT)
+        _assert_bytes(r.colour[v], OR.encode(oracle, m.rgb, 1), (name, c))
+        _assert_plane(r.plane[v], m.plane, (name, c))

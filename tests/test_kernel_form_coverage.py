@@ -11,19 +11,19 @@ import pytest
 import kernel_forms as F
 from kernel_report import kernel_report
 
-RENDER = re.compile(r"\bkifs::((ssaa|geom|adaptive|anim|accum)::)?(jitter_|carry_)?render\w*_kernel\b")  # (not adaptive::classify_kernel: no render form)
+RENDER = re.compile(r"\bkifs::((ssaa|geom|adaptive|anim|accum|occl|light)::)?(jitter_|carry_)?render\w*_kernel\b")  # (not adaptive::classify_kernel: no render form)
 
 
 def test_table_equals_the_compiled_render_instantiations():
     compiled = {n for n in kernel_report() if RENDER.search(n)}
     tables = [F.RENDER_FORMS, F.SSAA_FORMS, F.GEOMETRY_FORMS, F.ADAPTIVE_FORMS, F.ANIMATION_FORMS, F.ACCUMULATE_FORMS, F.JITTER_FORMS,
-              F.CARRY_FORMS]
+              F.CARRY_FORMS, F.OCCLUSION_FORMS, F.LIGHTING_FORMS]
     table = set().union(*tables)
     assert len(table) == sum(len(t) for t in tables)  # no instantiation in two tables
     assert not any("classify" in n for n in table) and any("adaptive::classify_kernel" in n for n in kernel_report())
     assert sorted(compiled - table) == [], "compiled, but no recipe in tests/kernel_forms.py"
     assert sorted(table - compiled) == [], "a recipe for an instantiation that is no longer compiled"
-    assert len(F.ACCUMULATE_FORMS) == len(F.JITTER_FORMS) == len(F.CARRY_FORMS) == 10
+    assert len(F.ACCUMULATE_FORMS) == len(F.JITTER_FORMS) == len(F.CARRY_FORMS) == len(F.OCCLUSION_FORMS) == len(F.LIGHTING_FORMS) == 10
     # every extension table is claimed by a test file (test_extension_claims_name_cases_of_the_extension_tests runs per file)
     assert sorted(map(sorted, F.EXTENSION_FORMS.values())) == sorted(map(sorted, tables[2:]))
 

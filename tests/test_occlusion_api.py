@@ -78,12 +78,13 @@ def test_refusals_without_a_device(kifs):
 
 def test_every_pipeline_is_compiled_inside_the_render_budgets(kifs):
     from geometry_cases import PIPELINES
-    from test_kernel_form_coverage import RENDER  # the form table's pattern must not claim the new family
+    from kernel_forms import OCCLUSION_FORMS
+    from test_kernel_form_coverage import RENDER  # the form table's own pattern: it claims the family (kernel_forms.OCCLUSION_FORMS)
     from test_kernel_resources import _budget     # ... and the resource test grants it the render kernels' budgets
     report = kernel_report()
     names = [n for n in report if "occl::render_kernel<" in n]
     assert len(names) == len(PIPELINES) == 10, names
-    assert not any(RENDER.search(n) for n in names)
+    assert all(RENDER.search(n) for n in names) and sorted(names) == sorted(OCCLUSION_FORMS)
     pairs = sorted(tuple(int(v) for v in re.search(r"render_kernel<(\d+), (\d+)>", n).groups()) for n in names)
     assert pairs == sorted([(1, 0), (1, 1), (2, 0)] + [(0, p) for p in range(7)])  # as dispatch_pipeline<2> picks them
     for n in names:

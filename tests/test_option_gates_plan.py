@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 import kernel_forms as F
+import lighting_reference as LR
+import occlusion_reference as OR
 import option_gates as G
 
 W, H = 96, 64
@@ -162,3 +164,30 @@ def test_expected_tuple_agrees_with_the_cpu_driver():
             elif config == "wave" and want == 8 and s.group == F.KIFS:
                 want = 4
             assert G.expected_tuple(config, L)[3] == want, (config, L.label)
+
+
+def test_the_light_shows_in_a_fractal_case_of_every_gate_pipeline(oracle, kifs):
+    """The rows of test_lit_frame and test_occlusion_frame (tests/test_gpu_option_gates.py) cannot pass with the light
+    or the term ignored: for each of the five gate pipelines some case shown as `fractal` has, at the size and from the
+    cameras of those tests, lit bytes under light A and the default term that are not the oracle's plain bytes, and a
+    factor below 1."""
+    O, K = oracle, kifs
+    size, cams = (64, 48), (1, 2)  # GEOMETRY and GEOMETRY_CAMERAS of tests/test_gpu_option_gates.py
+    ub = K.uniform_bytes
+    screen = O.from_bytes(O.Screen, ub(K.ScreenData(*size).into_buffer_data()))
+    assert set(G.PIPELINES) == {G.SCENES[n].pipeline for n in G.names("ERDXIM")} and len(G.PIPELINES) == 5
+    for p in G.PIPELINES:
+        lit, occluded = [], []
+        for n in G.names("ERDXIM", (p,)):
+            if G.SCENES[n].shows != "fractal" or G.SCENES[n].heatmap:
+                continue
+            options, it = O.from_bytes(O.Options, ub(G.options(K, n))), O.iters(*G.SCENES[n].iters)
+            for c in cams:
+                camera = O.from_bytes(O.Camera, ub(G.camera(K, n, c).into_buffer_data()))
+                m = LR.march(O, screen, camera, options, it, LR.A, OR.DEFAULT)
+                if (LR.encode(O, m.rgb, 1) != O.render(screen, camera, options, it, encode=1)).any():
+                    lit.append((n, c))
+                if (m.hit & (m.a < 1)).any():
+                    occluded.append((n, c))
+        print(p, ": views whose lit bytes are not the plain frame's:", len(lit), "; views with a factor below 1:", len(occluded))
+        assert lit and occluded, p
