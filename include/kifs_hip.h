@@ -628,6 +628,66 @@ int kifs_render_lit_async(kifs_ctx* ctx, void* hip_stream, int count, const Kifs
                           uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsLight* light,
                           const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
 
+/* ---- extension: orbit-trap surface colouring (not in the reference) ------------------------------------------------
+ * kifs_render_lit_async with a colour per hit in the place of the one fractal colour: a gradient over how close the
+ * orbit that the pipeline iterates from the hit point comes to a trap -- a point, a line or a plane of orbit space.  The
+ * call is a render of its own (kifs_trap_kernels.hip); one trap per call.  All f32 in the order written, fma only where
+ * written, square root correctly rounded, comparisons as C ternaries.
+ *   orbit     of a hit at the tested position p (the geometry texel's, the occlusion probes'): z_0 = (p.x, p.y, p.z, w0),
+ *             w0 = 0.1 for the two Julia groups and 0 for KIFS_GROUP_KIFS.
+ *               Julia (power 2)      z_{k+1} = quat_sq_add(z_k, c): real = fma(x,x,-d) + c.x with d = fma(w,w, y*y + z*z),
+ *                                    ijk = fma(2x, ijk, c.ijk).  Point k+1 takes part in the minimum; after that the orbit
+ *                                    stops if fma(x,x,d) of z_{k+1} > max_distance.
+ *               generalised Julia    z_{k+1} = quat_pow(z_k, power) + c per component, quat_pow as the normal's
+ *                                    estimate takes it; the stop rule is the Julia one.
+ *               Sierpinski           z_{k+1}.xyz = fma(2, tetrahedral_fold(z_k.xyz), -1) per component, w stays 0; no stop
+ *                                    rule.
+ *               every other primitive, the bunny and unknown primitive ids: z_0 only -- the trap is a function of position.
+ *   distance  e = z - centre per component; d(z) = 0, then d = fma(e_i, e_i, d) for the components i of `axes` in the
+ *             order x, y, z, w (all four bits: a point trap; one bit: a plane; two or three: a line or an axis).
+ *             m = d(z_0), then m = (d(z_k) < m) ? d(z_k) : m for k = 1..K as far as the orbit ran (a NaN distance is
+ *             never taken);  u = sqrt(m).
+ *   gradient  v = fma(scale, u, bias);  t = (v > 0) ? v : 0, then t = (t < 1) ? t : 1 (a NaN gives 0);  x = t * 2;
+ *             j = (x >= 1) ? 1 : 0;  f = x - float(j);  the stops are s_0 = the options' fractal_color, s_1 = mid,
+ *             s_2 = far;  per channel col = fma(f, s_{j+1} - s_j, s_j).
+ *   shading   exactly kifs_render_lit_async's with col in the place of fc -- the direct term, the soft-shadow march
+ *             towards the light, the weights, the highlight and the optional occlusion factor, in that call's order.
+ *             light NULL: the light {(1,1,1), 0.1, 0.9, no highlight}.  A miss -- every ray the culls drop -- is the
+ *             background; a heatmap frame's colour is the counter's and no trap is evaluated.
+ *   samples, frames, ordering, launch: kifs_render_lit_async's -- supersampling honoured sample by sample; 1..
+ *             KIFS_MAX_TRAP_BATCH frames, cameras NULL with count 1; bands bit-identical to the frame's rows and every
+ *             frame of a batch to the lone call; not a feedback launch, the kifs_debug_last_* values left alone.
+ *   identity  (a) scale = bias = 0 writes the bytes of kifs_render_lit_async for the same light and term -- with light
+ *             NULL those of kifs_render_batch_async, and with a term those of kifs_render_occlusion_async: t = 0, f = 0 and
+ *             fma(0, ., s_0) = s_0; a NaN or infinite u cannot leak through the ternaries.  (b) mid = far = fractal_color
+ *             with any scale and bias writes the same bytes as (a).  Both hold for every pipeline, with soft shadows,
+ *             heatmap and k > 1.
+ *   refusals  a refused call launches nothing and writes nothing.  Everything kifs_render_lit_async refuses is refused
+ *             with its status (a NULL light is not refused here).  KIFS_ERR_BAD_ARG also: a NULL trap; a centre
+ *             component, scale or bias that is not finite; axes 0 or above 15; iterations outside
+ *             0..KIFS_MAX_TRAP_ITERATIONS; a negative or non-finite colour.  y1 == y0 returns KIFS_OK and enqueues nothing.
+ *   scope     deliberately absent: a plane of u; more than three stops; per-frame traps; a form in the accumulate,
+ *             animation, adaptive, geometry, ray-query and multi-GPU calls or in the viewer.
+ * kifs_eval_trap writes u for n positions (host pointers, like kifs_eval_points) with the context's options; it reads and
+ * validates only centre, axes and iterations.  It exists for parity tests and for choosing a range for scale and bias.
+ * Every byte and every u equals the CPU restatement of the contract (tests/trap_reference.c), which is normative where
+ * this text and it could be read differently. */
+#define KIFS_MAX_TRAP_ITERATIONS 32
+#define KIFS_MAX_TRAP_BATCH 64
+typedef struct KifsOrbitTrap {      /* 56 bytes */
+    float    centre[4];   /* the trap point a, in orbit space (x, y, z, w); finite */
+    uint32_t axes;        /* bit i set: component i takes part in the distance; 1..15 */
+    int32_t  iterations;  /* K: orbit points after z_0; 0..KIFS_MAX_TRAP_ITERATIONS */
+    float    scale, bias; /* t = clamp(scale * u + bias); finite */
+    float    mid[3];      /* linear RGB at t = 1/2; finite, >= 0 */
+    float    far[3];      /* linear RGB at t = 1;   finite, >= 0 */
+} KifsOrbitTrap;
+int kifs_render_trapped_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                              uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsOrbitTrap* trap,
+                              const KifsLight* light /* NULL: the reference's light */,
+                              const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
+int kifs_eval_trap(kifs_ctx* ctx, const KifsOrbitTrap* trap, const float* points_xyz, int n, float* u_out);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -66,11 +66,18 @@ class KifsLightC(C.Structure):  # KifsLight: the light of kifs_render_lit_async
                 ("shininess_log2", C.c_int32)]
 
 
+class KifsOrbitTrapC(C.Structure):  # KifsOrbitTrap: the trap of kifs_render_trapped_async
+    _fields_ = [("centre", C.c_float * 4), ("axes", C.c_uint32), ("iterations", C.c_int32), ("scale", C.c_float),
+                ("bias", C.c_float), ("mid", C.c_float * 3), ("far", C.c_float * 3)]
+
+
 MAX_RAYS = 1 << 28  # KIFS_MAX_RAYS
 MAX_AO_SAMPLES = 16  # KIFS_MAX_AO_SAMPLES
 MAX_OCCLUSION_BATCH = 64  # KIFS_MAX_OCCLUSION_BATCH
 MAX_SHININESS_LOG2 = 10  # KIFS_MAX_SHININESS_LOG2
 MAX_LIGHT_BATCH = 64  # KIFS_MAX_LIGHT_BATCH
+MAX_TRAP_ITERATIONS = 32  # KIFS_MAX_TRAP_ITERATIONS
+MAX_TRAP_BATCH = 64  # KIFS_MAX_TRAP_BATCH
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -105,6 +112,7 @@ assert C.sizeof(OptionsUniform) == 80
 assert C.sizeof(KifsSubpixel) == 2
 assert C.sizeof(AmbientOcclusionC) == 16
 assert C.sizeof(KifsLightC) == 36
+assert C.sizeof(KifsOrbitTrapC) == 56
 
 # every symbol include/kifs_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -152,6 +160,10 @@ SIGNATURES = {
                                               C.c_int]),
     "kifs_render_lit_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
                                         _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int, C.c_int]),
+    "kifs_render_trapped_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                            _P(KifsOrbitTrapC), _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int,
+                                            C.c_int]),
+    "kifs_eval_trap": (C.c_int, [_ctx, _P(KifsOrbitTrapC), _f32p, C.c_int, _f32p]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

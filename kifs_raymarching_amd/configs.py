@@ -195,6 +195,16 @@ def light_direction(azimuth: float, elevation: float) -> tuple:
     return (float(v[0]), float(v[1]), float(v[2]))
 
 
+def trap_range(lo: float, hi: float) -> tuple:
+    """(scale, bias) for OrbitTrap / KifsOrbitTrap that put u = lo at t = 0 and u = hi at t = 1, as np.float32:
+    scale = 1 / (hi - lo) and bias = -lo * scale, each operation in f32.  hi < lo inverts the gradient."""
+    lo, hi = np.float32(lo), np.float32(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo == hi:
+        raise ValueError("trap_range: two different finite distances")
+    scale = np.float32(np.float32(1.0) / np.float32(hi - lo))
+    return scale, np.float32(np.float32(-lo) * scale)
+
+
 def pass_splits(total: int, per_pass: int = 64) -> list:
     """The pass sizes of a progressive frame of `total` sub-frames (GraphicState.render_accumulate_resume, Accumulator):
     total // per_pass passes of `per_pass` and, if anything is left, one of the remainder -- [64, 64, 22] for 150.  A

@@ -13,6 +13,7 @@
 //   kifs_rays.cpp      ray queries (kifs_trace_rays_async): caller-supplied rays, one launch
 //   kifs_occlusion.cpp ambient occlusion (kifs_render_occlusion_async): the batch call's frames, hits attenuated, one launch
 //   kifs_lighting.cpp  a configurable light (kifs_render_lit_async): the batch call's frames under the caller's light, one launch
+//   kifs_trap.cpp      orbit-trap colouring (kifs_render_trapped_async, kifs_eval_trap): the lit call's frames, hits coloured by a trap
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -197,6 +198,36 @@ inline bool term_ok(const KifsAmbientOcclusion& ao) {
            std::isfinite(ao.decay) && ao.decay > 0.0f && ao.decay <= 1.0f && std::isfinite(ao.strength) && ao.strength >= 0.0f;
 }
 }  // namespace occl
+
+// The ranges of KifsLight and the light as the kernels read it: kifs_lighting.cpp's, which kifs_trap.cpp takes too.
+namespace light {
+// The contract's dot3 and normalize3 in f32 (the units are built with -ffp-contract=off; fmaf is the one fused operation).
+inline float dot3(const float a[3], const float b[3]) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
+
+inline bool weight_ok(float w) { return std::isfinite(w) && w >= 0.0f; }
+
+inline bool light_ok(const KifsLight& l) {
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(l.direction[i]) || !weight_ok(l.specular[i])) return false;
+    const float d2 = dot3(l.direction, l.direction);
+    if (!std::isnormal(d2)) return false;  // zero, subnormal, infinite: no unit vector to march towards
+    return weight_ok(l.ambient) && weight_ok(l.diffuse) && l.shininess_log2 >= 0 && l.shininess_log2 <= KIFS_MAX_SHININESS_LOG2;
+}
+
+// The light as the kernel reads it: the direction as given, Lh = normalize3(direction) with IEEE divide and square root.
+inline Light device_light(const KifsLight& l) {
+    const float len = std::sqrt(dot3(l.direction, l.direction));
+    Light d;
+    d.direction = V3{l.direction[0], l.direction[1], l.direction[2]};
+    d.unit = V3{l.direction[0] / len, l.direction[1] / len, l.direction[2] / len};
+    d.ambient = l.ambient;
+    d.diffuse = l.diffuse;
+    d.specular = V3{l.specular[0], l.specular[1], l.specular[2]};
+    d.shininess_log2 = l.shininess_log2;
+    d.highlight = (l.specular[0] != 0.0f || l.specular[1] != 0.0f || l.specular[2] != 0.0f) ? 1u : 0u;
+    return d;
+}
+}  // namespace light
 
 // What every launch that carries a scene table shares (kifs_animation.cpp): the animated call and the four accumulated
 // ones differ in their checks and in the last step, the launch itself.

@@ -1,6 +1,6 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
 // kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip,
-// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip).
+// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip, kifs_trap_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,6 +40,11 @@ hipError_t launch_occlusion(const occl::Params& O, uint32_t group, uint32_t prim
 // A configurable light (kifs_render_lit_async; kifs_lighting_kernels.hip, the host side is kifs_lighting.cpp): the same
 // shape, every hit shaded by the launch's light and, with a term, attenuated by its factor (light::render_kernel).
 hipError_t launch_lit(const light::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Orbit-trap surface colouring (kifs_render_trapped_async; kifs_trap_kernels.hip, the host side is kifs_trap.cpp): the
+// lit launch with every hit's colour from the launch's trap (trap::render_kernel); and kifs_eval_trap's u of E.n
+// positions, one per lane (trap::eval_kernel).
+hipError_t launch_trapped(const trap::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
+hipError_t launch_eval_trap(const trap::EvalParams& E, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

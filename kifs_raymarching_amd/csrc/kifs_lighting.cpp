@@ -13,18 +13,8 @@ namespace light {
 
 static_assert(KIFS_MAX_LIGHT_BATCH == MAX_BATCH_INLINE, "the views of a call travel in the kernel argument");
 
-// The contract's dot3 and normalize3 in f32 (this unit is built with -ffp-contract=off; fmaf is the one fused operation).
-static float dot3(const float a[3], const float b[3]) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
-
-static bool weight_ok(float w) { return std::isfinite(w) && w >= 0.0f; }
-
-static bool light_ok(const KifsLight& l) {
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(l.direction[i]) || !weight_ok(l.specular[i])) return false;
-    const float d2 = dot3(l.direction, l.direction);
-    if (!std::isnormal(d2)) return false;  // zero, subnormal, infinite: no unit vector to march towards
-    return weight_ok(l.ambient) && weight_ok(l.diffuse) && l.shininess_log2 >= 0 && l.shininess_log2 <= KIFS_MAX_SHININESS_LOG2;
-}
+// (light_ok and device_light -- the ranges of KifsLight, the light as the kernel reads it -- are kifs_context.hpp's, shared
+// with kifs_trap.cpp.)
 
 // What a caller can get wrong that needs no look at the frame.
 static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, const KifsLight* light,
@@ -39,20 +29,6 @@ static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras,
         if (!outs[i] || (reinterpret_cast<uintptr_t>(outs[i]) & 3u) != 0) return KIFS_ERR_BAD_ARG;
     if (!c->have_screen || !c->have_options || (!c->have_camera && !cameras)) return KIFS_ERR_UNCONFIGURED;
     return KIFS_OK;
-}
-
-// The light as the kernel reads it: the direction as given, Lh = normalize3(direction) with IEEE divide and square root.
-static Light device_light(const KifsLight& l) {
-    const float len = std::sqrt(dot3(l.direction, l.direction));
-    Light d;
-    d.direction = V3{l.direction[0], l.direction[1], l.direction[2]};
-    d.unit = V3{l.direction[0] / len, l.direction[1] / len, l.direction[2] / len};
-    d.ambient = l.ambient;
-    d.diffuse = l.diffuse;
-    d.specular = V3{l.specular[0], l.specular[1], l.specular[2]};
-    d.shininess_log2 = l.shininess_log2;
-    d.highlight = (l.specular[0] != 0.0f || l.specular[1] != 0.0f || l.specular[2] != 0.0f) ? 1u : 0u;
-    return d;
 }
 
 static int enqueue(kifs_ctx* c, hipStream_t stream, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, size_t pitch,

@@ -279,4 +279,41 @@ static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
 
 }  // namespace light
 
+namespace trap {
+
+// The orbit trap of kifs_render_trapped_async (KifsOrbitTrap, include/kifs_hip.h), as the kernels read it: the record as
+// the caller gave it, field for field.
+struct Trap {
+    V4 centre;
+    uint32_t axes;       // 1..15: bit i set, component i takes part in the distance
+    int iterations;      // 0..KIFS_MAX_TRAP_ITERATIONS
+    float scale, bias;
+    V3 mid, far;
+};
+static_assert(sizeof(Trap) == 56, "the record is KifsOrbitTrap's 56 bytes");
+
+// The argument of trap::render_kernel (kifs_trap_kernels.hip): light::Params -- the same fields at the same offsets --
+// and the trap behind them.
+struct Params {
+    BatchParams B;
+    light::Light light;
+    occl::AO ao;         // read only when has_ao != 0
+    uint32_t has_ao;
+    Trap trap;
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+// The argument of trap::eval_kernel (kifs_eval_trap): the scene's frame constants -- nothing of a screen or a camera is
+// read -- the trap, of which only centre, axes and iterations are, and the arrays.
+struct EvalParams {
+    FrameParams frame;
+    Trap trap;
+    const float* points;  // n positions of three floats (device memory)
+    int n;
+    float* u;             // n floats
+};
+static_assert(sizeof(EvalParams) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace trap
+
 }  // namespace kifs

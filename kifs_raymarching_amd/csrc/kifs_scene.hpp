@@ -1435,4 +1435,181 @@ KIFS_DEV V3 raymarch_lit(const FrameParams& P, light::ConstParams K, V3 dir, boo
     return colour;
 }
 
+// ---- extension: orbit-trap surface colouring (kifs_render_trapped_async, include/kifs_hip.h) -----------------------
+// The colour of a hit from where its orbit goes, operation for operation as the header states it: the squared distance
+// of an orbit point to the trap over the components the trap names, its minimum over z_0 .. z_K, and a gradient of three
+// stops over the clamped, scaled square root of that minimum.
+namespace trap {
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+KIFS_DEV ConstParams anew(ConstParams K) {
+    asm volatile("" : "+s"(K));
+    return K;
+}
+typedef const Trap __attribute__((address_space(4))) * ConstTrap;
+KIFS_DEV Trap load(ConstTrap t) {
+    return Trap{V4{t->centre.x, t->centre.y, t->centre.z, t->centre.w}, t->axes, t->iterations, t->scale, t->bias,
+                V3{t->mid.x, t->mid.y, t->mid.z}, V3{t->far.x, t->far.y, t->far.z}};
+}
+}  // namespace trap
+
+// d(z): e = z - centre, d = 0, then d = fma(e_i, e_i, d) for the components of `axes` (uniform) in the order x, y, z, w.
+KIFS_DEV float trap_distance(const trap::Trap& T, V4 z) {
+    float d = 0.0f;
+    if (T.axes & 1u) {
+        const float e = z.x - T.centre.x;
+        d = fmaf_(e, e, d);
+    }
+    if (T.axes & 2u) {
+        const float e = z.y - T.centre.y;
+        d = fmaf_(e, e, d);
+    }
+    if (T.axes & 4u) {
+        const float e = z.z - T.centre.z;
+        d = fmaf_(e, e, d);
+    }
+    if (T.axes & 8u) {
+        const float e = z.w - T.centre.w;
+        d = fmaf_(e, e, d);
+    }
+    return d;
+}
+
+// u of the position p: the square root of the least d over the orbit z_0 .. z_K of pipeline <GROUP, PRIM> (Julia: the
+// PRIM slot is not a primitive and is not read).  `lanes`: the lanes whose u is used; the trip count is wave-uniform --
+// the loop leaves when none of them still runs -- and a lane that has stopped takes no further minimum.  The generalised
+// Julia step is genjulia_normal's quat_pow, with its wave-level repeat on the general functions asked for by running
+// lanes only.
+template <int GROUP, int PRIM>
+KIFS_DEV float orbit_trap(const FrameParams& S, const trap::Trap& T, V3 p, bool lanes = true) {
+    constexpr bool JULIA = GROUP == GROUP_JULIA || GROUP == GROUP_GENJULIA;
+    V4 z{p.x, p.y, p.z, JULIA ? 0.1f : 0.0f};
+    float m = trap_distance(T, z);
+    if constexpr (JULIA) {
+        bool run = lanes;
+        for (int k = 0; k < T.iterations && __builtin_amdgcn_ballot_w64(run) != 0ull; ++k) {
+            if constexpr (GROUP == GROUP_JULIA) {
+                z = quat_sq_add(z, S.c);
+            } else {
+                const float d = quat_ijk2(z);
+                const float qs = fmaf_(z.x, z.x, d);
+                float unused;
+                const V4 t = quat_pow_shared(z, d, qs, S.power, unused, run);
+                z = V4{t.x + S.c.x, t.y + S.c.y, t.z + S.c.z, t.w + S.c.w};
+            }
+            const float d = trap_distance(T, z);
+            m = (run && (d < m)) ? d : m;
+            run = run && !(quat_norm2(z) > S.max_distance);
+        }
+    } else if constexpr (PRIM == PRIM_SIERPINSKI) {
+        V3 q = p;
+        for (int k = 0; k < T.iterations; ++k) {  // uniform
+            q = tetrahedral_fold(q);
+            q = V3{fmaf_(2.0f, q.x, -1.0f), fmaf_(2.0f, q.y, -1.0f), fmaf_(2.0f, q.z, -1.0f)};
+            const float d = trap_distance(T, V4{q.x, q.y, q.z, 0.0f});
+            m = (d < m) ? d : m;
+        }
+    }
+    return sqrt_(m);
+}
+
+// The gradient at u: t = clamp(fma(scale, u, bias)) as two ternaries (a NaN gives 0), the stops fractal_color, mid and
+// far at t = 0, 1/2 and 1.
+KIFS_DEV V3 trap_colour(const FrameParams& S, const trap::Trap& T, float u) {
+    const float v = fmaf_(T.scale, u, T.bias);
+    float t = (v > 0.0f) ? v : 0.0f;
+    t = (t < 1.0f) ? t : 1.0f;
+    const float x = t * 2.0f;
+    const bool upper = x >= 1.0f;
+    const float f = x - (upper ? 1.0f : 0.0f);
+    const V3 a{upper ? T.mid.x : S.fractal_color.x, upper ? T.mid.y : S.fractal_color.y, upper ? T.mid.z : S.fractal_color.z};
+    const V3 b{upper ? T.far.x : T.mid.x, upper ? T.far.y : T.mid.y, upper ? T.far.z : T.mid.z};
+    return V3{fmaf_(f, b.x - a.x, a.x), fmaf_(f, b.y - a.y, a.y), fmaf_(f, b.z - a.z, a.z)};
+}
+
+// lit_shade with the hit's own colour in the place of fractal_color: `colour(p)` is asked for after the shadow ray, where
+// the weights are, so that no colour crosses the secondary march.  Everything else -- the direct term, the highlight, the
+// shadow ray, the weights, the optional factor, and where each reads the kernel argument K anew -- is lit_shade's, in its
+// order (trap::Params carries light::Params' fields at their offsets).
+template <class Sdf, class Normal, class Dir, class Colour>
+KIFS_DEV V3 trapped_shade(const FrameParams& P, trap::ConstParams K, V3 p, bool hit, V3 miss, Sdf sdf, Normal normal, Dir dir,
+                          Colour colour) {
+    V3 n{0.0f, 0.0f, 0.0f};
+    V3 shade = miss;
+    if (hit) {
+        n = normal(p);
+        const trap::ConstParams A = trap::anew(K);
+        const bool highlit = A->light.highlight != 0u;  // uniform
+        const float lit0 = direct_term_towards(n, load3(&A->light.direction));
+        float s = 0.0f;
+        if (highlit) s = highlight(n, load3(&A->light.unit), dir(), A->light.shininess_log2);
+        float sh = 1.0f, lit = lit0;
+        if (__builtin_expect(P.soft_shadow != 0u, 0)) {
+            sh = soft_shadow_towards(
+                P, p, n, [&]() __attribute__((always_inline)) { return load3(&trap::anew(K)->light.unit); }, lit0 > 0.0f, sdf);
+            lit = lit0 * sh;
+        }
+        const V3 col = colour(p);
+        const trap::ConstParams B = trap::anew(K);
+        const float k = fmaf_(B->light.diffuse, lit, B->light.ambient);
+        shade = V3{k * col.x, k * col.y, k * col.z};
+        if (highlit) {
+            const float spec = (lit0 > 0.0f) ? s * sh : 0.0f;
+            const V3 w = load3(&B->light.specular);
+            shade = V3{fmaf_(w.x, spec, shade.x), fmaf_(w.y, spec, shade.y), fmaf_(w.z, spec, shade.z)};
+        }
+    }
+    const trap::ConstParams C = trap::anew(K);
+    if (C->has_ao != 0u) {  // uniform; the probes run for the whole wave, as occluded_shade's
+        const occl::AO ao{C->ao.samples, C->ao.step, C->ao.decay, C->ao.strength};
+        const float f = ambient_occlusion(P, ao, p, n, __builtin_amdgcn_ballot_w64(hit), sdf);
+        shade = V3{f * shade.x, f * shade.y, f * shade.z};
+    }
+    return hit ? shade : miss;
+}
+
+// raymarch_lit for the trapped launch (kifs_trap_kernels.hip): the same whole ray per lane through the view P, a hit's
+// colour the gradient at its orbit's trap distance, shaded by the launch's light and, when the launch has a term,
+// attenuated by the hit's factor.  The trap is read from the kernel argument K after the march and the shadow ray, where
+// it is used.  A heatmap frame evaluates no trap: its colour is the counter's.
+template <int GROUP, int PRIM, class Dir>
+KIFS_DEV V3 raymarch_trapped(const FrameParams& P, trap::ConstParams K, V3 dir, bool valid, Dir redo_dir) {
+    constexpr int NPRIM = GROUP == GROUP_JULIA ? 0 : PRIM;
+    float t = 0.0f;
+    V3 p = P.origin;
+    bool hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = whole_ray_sets_out(P, dir, valid);
+    if constexpr (GROUP == GROUP_JULIA) {
+        JuliaDiag diag;
+        julia_loop<(PRIM & 1) != 0, false>(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, diag);
+    } else {
+        generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations,
+                     [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, PRIM>(P, q, lanes); });
+    }
+    __builtin_amdgcn_s_setprio(0);
+    const trap::ConstParams L = trap::anew(K);
+    const FrameParams S = *(const FrameParams*)&L->B.frame;  // the scene, as every view of the launch shares it
+    V3 colour = S.background_color;
+    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {  // wave-uniform
+        const auto sdf = [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return scene_sdf<GROUP, NPRIM>(S, q, lanes); };
+        colour = trapped_shade(
+            S, K, p, hit, S.background_color, sdf,
+            [&](V3 q) __attribute__((always_inline)) {
+                if constexpr (GROUP == GROUP_KIFS)  // kifs_normal<PRIM>, its estimate inlined
+                    return normal_fd(S.epsilon, q, [&](V3 e) __attribute__((always_inline)) { return kifs_sdf<PRIM>(S, e); });
+                else
+                    return scene_normal<GROUP, NPRIM>(S, q);
+            },
+            redo_dir,
+            [&](V3 q) __attribute__((always_inline)) {
+                if (S.is_heatmap) return S.fractal_color;  // uniform
+                const trap::Trap T = trap::load(&trap::anew(K)->trap);
+                return trap_colour(S, T, orbit_trap<GROUP, NPRIM>(S, T, q));
+            });
+    }
+    if (S.is_heatmap) colour = heatmap_colour(S, i_final);
+    return colour;
+}
+
 }  // namespace kifs

@@ -25,7 +25,7 @@ STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
 MAX_JITTER_GRID = _lib.MAX_JITTER_GRID  # KIFS_MAX_JITTER_GRID
-from ._lib import (AdaptiveAAC, AmbientOcclusionC, KifsLightC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
+from ._lib import (AdaptiveAAC, AmbientOcclusionC, KifsLightC, KifsOrbitTrapC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -153,6 +153,42 @@ class Light:  # KifsLight: the light of kifs_render_lit_async; the defaults are 
     def into_buffer_data(self) -> KifsLightC:
         return KifsLightC((C.c_float * 3)(*[float(v) for v in self.direction]), float(self.ambient), float(self.diffuse),
                           (C.c_float * 3)(*[float(v) for v in self.specular]), int(self.shininess_log2))
+
+
+@dataclass
+class OrbitTrap:  # KifsOrbitTrap: the trap of kifs_render_trapped_async; the gradient's first stop is the options' fractal_color
+    centre: tuple = (0.0, 0.0, 0.0, 0.0)   # the trap point in orbit space (x, y, z, w)
+    axes: int = 15                         # bit i set: component i takes part in the distance; 15: a point, one bit: a plane
+    iterations: int = 8                    # orbit points after the hit point's own, 0..KIFS_MAX_TRAP_ITERATIONS
+    scale: float = 1.0                     # t = clamp(scale * u + bias): configs.trap_range(lo, hi) makes the pair
+    bias: float = 0.0
+    mid: tuple = (255, 140, 0)             # sRGB bytes like GuiData's colours: the stop at t = 1/2
+    far: tuple = (20, 60, 200)             # ... and at t = 1
+
+    def into_buffer_data(self) -> KifsOrbitTrapC:
+        """The record the library takes; refuses here what it would refuse.  The colours go through the conversion the
+        options' colours go through (kifs_host_options)."""
+        centre = [float(v) for v in self.centre]
+        if len(centre) != 4 or not all(np.isfinite(centre)):
+            raise ValueError("OrbitTrap: centre is four finite numbers (x, y, z, w)")
+        if int(self.axes) != self.axes or not 1 <= int(self.axes) <= 15:
+            raise ValueError("OrbitTrap: axes is a mask of the components x = 1, y = 2, z = 4, w = 8: 1..15")
+        if int(self.iterations) != self.iterations or not 0 <= int(self.iterations) <= _lib.MAX_TRAP_ITERATIONS:
+            raise ValueError(f"OrbitTrap: 0..{_lib.MAX_TRAP_ITERATIONS} iterations")
+        if not all(abs(float(v)) <= 3.4028234663852886e38 for v in (self.scale, self.bias)):  # (false for a NaN)
+            raise ValueError("OrbitTrap: scale and bias are finite in float32")
+        for name in ("mid", "far"):
+            v = getattr(self, name)
+            if len(v) != 3 or any(int(b) != b or not 0 <= int(b) <= 255 for b in v):
+                raise ValueError(f"OrbitTrap: {name} is three sRGB bytes")
+        g = GuiDataC()
+        lib.kifs_host_gui_default(C.byref(g))
+        g.fractal_color = (C.c_uint8 * 3)(*[int(b) for b in self.mid])
+        g.background_color = (C.c_uint8 * 3)(*[int(b) for b in self.far])
+        u = OptionsUniform()
+        check(lib.kifs_host_options(C.byref(g), C.byref(u)), "OrbitTrap")
+        return KifsOrbitTrapC((C.c_float * 4)(*centre), int(self.axes), int(self.iterations), float(self.scale), float(self.bias),
+                              (C.c_float * 3)(*u.fractal_color), (C.c_float * 3)(*u.background_color))
 
 
 def uniform_bytes(u) -> bytes:
@@ -595,6 +631,67 @@ class GraphicState:
         else:
             torch.cuda.synchronize(colour.device)
         return colour[0]
+
+    # ---- orbit-trap surface colouring (kifs_render_trapped_async): every hit coloured by `trap`, lit and optionally occluded
+    def render_trapped_batch(self, cameras, trap: OrbitTrap, light: Light = None, ao: AmbientOcclusion = None, stream=None,
+                             y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, colour=None):
+        """The frames of len(cameras) cameras (cameras None: one frame with the context's camera) with every hit coloured
+        by the orbit trap `trap`, under `light` (None: the reference's light) and with the ambient-occlusion term `ao` on
+        top when one is given, the context's supersampling factor and soft-shadow extension honoured.  Returns a uint8
+        (count, rows, W, 4) torch tensor on this context's device; `colour`: a contiguous destination tensor of that shape
+        to reuse.  The library takes MAX_TRAP_BATCH cameras per launch; more are fed to it that many at a time.  Enqueued
+        on `stream` like render_async; the caller synchronises before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if n < 1:
+            raise ValueError("render_trapped_batch: at least one frame")
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_trapped_batch: colour uint8 ({n}, {rows}, {w}, 4), contiguous")
+        record = trap.into_buffer_data() if hasattr(trap, "into_buffer_data") else trap  # (or a KifsOrbitTrapC, linear colours)
+        lit = None if light is None else light.into_buffer_data()
+        term = None if ao is None else ao.into_buffer_data()
+        stream = self._stream_handle(stream, "render_trapped_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        self._order_after_producer(colour, stream)
+        step = _lib.MAX_TRAP_BATCH
+        base, frame_bytes = _device_pointer(colour), rows * w * 4
+        for first in range(0, n, step):
+            m = min(step, n - first)
+            ptrs = (C.c_void_p * m)(*[base + (first + i) * frame_bytes for i in range(m)])
+            part = None if cams is None else C.cast(C.byref(cams, first * C.sizeof(CameraUniform)), C.POINTER(CameraUniform))
+            check(lib.kifs_render_trapped_async(self._ctx, stream, m, part, ptrs, w * 4, C.byref(record),
+                                                None if lit is None else C.byref(lit),
+                                                None if term is None else C.byref(term), y0, y1, encode), "render_trapped")
+        return colour
+
+    def render_trapped(self, trap: OrbitTrap, light: Light = None, ao: AmbientOcclusion = None, y0: int = 0, y1: int = None,
+                       encode: int = ENCODE_SRGB, stream=None):
+        """The context's frame coloured by `trap` (under `light`, with `ao`), synchronously: a uint8 rows x W x 4 torch
+        tensor on this context's device."""
+        import torch
+        colour = self.render_trapped_batch(None, trap, light=light, ao=ao, stream=stream, y0=y0, y1=y1, encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0]
+
+    def eval_trap(self, trap: OrbitTrap, points):
+        """u -- the least distance of the orbit to the trap -- of (n, 3) positions with the context's options: (n,) float32.
+        Only the trap's centre, axes and iterations are read: for parity tests and for choosing a range
+        (configs.trap_range) from the positions a frame hits."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        u = np.empty(n, dtype=np.float32)
+        record = trap.into_buffer_data() if hasattr(trap, "into_buffer_data") else trap
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib.kifs_eval_trap(self._ctx, C.byref(record), fp(pts), n, fp(u)), "eval_trap")
+        return u
 
     # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
     def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):

@@ -19,6 +19,7 @@
     python tools/render.py cfg2_julia_1080p out.png --ao --ao-png ao.png                       # ambient occlusion + its factors
     python tools/render.py cfg5_sierpinski_8k_orbit orbit_%03d.png --frames 0 30 60 --scale 0.25 --ao 8,0.01,0.8,3 --aa 2
     python tools/render.py cfg2_julia_1080p out.png --light -0.55,0.75,0.36,0.15,0.85 --specular 0.6,0.6,0.5,3 --ao  # a moved light
+    python tools/render.py cfg2_julia_1080p out.png --trap 0,0,0,0 --trap-colours 255,140,0:20,60,200 --trap-range auto --ao  # orbit-trap colours
 """
 import argparse
 import sys
@@ -27,7 +28,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
 from kifs_raymarching_amd.configs import (WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, panorama_rays,  # noqa: E402
-                                          pass_splits, pixel_rays, shutter_cameras)
+                                          pass_splits, pixel_rays, shutter_cameras, trap_range)
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -98,6 +99,16 @@ ap.add_argument("--light", metavar="X,Y,Z[,AMBIENT,DIFFUSE]", default=None,
 ap.add_argument("--specular", metavar="R,G,B[,E]", default=None,
                 help="a Blinn-Phong highlight of linear weight R,G,B and exponent 2^E (E 0..10, default 5) under --light "
                      "(without --light: under the reference's light 1,1,1)")
+ap.add_argument("--trap", metavar="CX,CY,CZ,CW[,AXES[,K]]", default=None,
+                help="colour the hits by an orbit trap (kifs_render_trapped_async): the least distance of the hit point's orbit to "
+                     "the point CX,CY,CZ,CW of orbit space over the components of the mask AXES (x = 1, y = 2, z = 4, w = 8; "
+                     "default 15, a point trap) within K orbit points (0..32, default 8), through a gradient from the workload's "
+                     "colour; goes with --light, --specular, --ao, --aa, --frames and the shadow workloads")
+ap.add_argument("--trap-colours", metavar="R,G,B:R,G,B", default="255,140,0:20,60,200",
+                help="with --trap: the gradient's middle and far stops as sRGB bytes")
+ap.add_argument("--trap-range", metavar="LO,HI|auto", default="auto",
+                help="with --trap: the distances that take the gradient's first and last stop; auto: the 5th and 95th "
+                     "percentile of the distances at the first frame's hits (kifs_render_geometry_async, kifs_eval_trap)")
 args = ap.parse_args()
 def _numbers(text, count):
     try:
@@ -109,7 +120,7 @@ panorama = None
 if args.panorama is not None:
     panorama = _numbers(args.panorama, 3)
     others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at, args.ao, args.ao_png,
-              args.light, args.specular)
+              args.light, args.specular, args.trap)
     if panorama is None or args.aa != 1 or args.aa_adaptive or args.motion_blur or args.jitter or any(o is not None for o in others):
         ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply; no --ao, --light or "
                  "--specular: ray queries compute neither the term nor a light of the caller's)")
@@ -190,6 +201,33 @@ if args.light is not None or args.specular is not None:
             ap.error("--specular takes three numbers R,G,B or four R,G,B,E (E a whole number)")
     light = K.Light(direction=lit[:3], ambient=lit[3], diffuse=lit[4], specular=shine[:3], shininess_log2=int(shine[3]))
     aa_grid = False  # several supersampled frames go through the lit batch, not through the accumulate family
+trap = None
+if args.trap is not None:
+    # the trap exists in kifs_render_trapped_async alone
+    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None:
+        ap.error("--trap renders without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry and --morph-to: the "
+                 "accumulate, adaptive, geometry and animation entry points colour with the one fractal colour")
+    if args.ao_png:
+        ap.error("--ao-png goes without --trap: the trapped call writes no plane of factors")
+    given = args.trap.count(",") + 1
+    numbers = (_numbers(args.trap, given) or ()) + (15.0, 8.0)[max(given - 4, 0):]  # (the defaults of what was left out)
+    if not 4 <= given <= 6 or len(numbers) != 6 or numbers[4] != int(numbers[4]) or numbers[5] != int(numbers[5]):
+        ap.error("--trap takes four numbers CX,CY,CZ,CW, then optionally the mask AXES and the count K (whole numbers)")
+    stops = [_numbers(part, 3) for part in args.trap_colours.split(":")]
+    if len(stops) != 2 or None in stops or any(v != int(v) or not 0 <= v <= 255 for stop in stops for v in stop):
+        ap.error("--trap-colours takes two sRGB colours R,G,B:R,G,B of bytes")
+    span = None if args.trap_range == "auto" else _numbers(args.trap_range, 2)
+    if args.trap_range != "auto" and (span is None or span[0] == span[1]):
+        ap.error("--trap-range takes two different distances LO,HI, or auto")
+    trap = K.OrbitTrap(centre=numbers[:4], axes=int(numbers[4]), iterations=int(numbers[5]), mid=tuple(int(v) for v in stops[0]),
+                       far=tuple(int(v) for v in stops[1]))
+    try:
+        trap.into_buffer_data()
+    except ValueError as e:
+        ap.error(f"--trap: {e}")
+    if span is not None:
+        trap.scale, trap.bias = (float(v) for v in trap_range(*span))
+    aa_grid = False  # several supersampled frames go through the trapped batch, not through the accumulate family
 morph_to = None
 if args.morph_to is not None:
     try:
@@ -349,6 +387,40 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
                       + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})")
                       + (f", jittered over a {args.jitter}x{args.jitter} grid" if args.jitter else ""))
+    elif trap is not None:
+        import numpy as np
+        indices = args.frames if args.frames is not None else [None]
+        cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
+        if args.trap_range == "auto":
+            # where the first frame's rays hit (one ray per pixel), what the trap measures there, and its middle nine tenths
+            gs.set_supersampling(1)
+            gs.set_camera(cams[0])
+            _, geometry = gs.render_geometry()
+            gs.set_supersampling(args.aa)
+            t = geometry.cpu().numpy()[..., 3].reshape(-1)
+            hit = np.isfinite(t)
+            if not hit.any():
+                sys.exit("--trap-range auto: no ray of the first frame hits the scene, nothing to take a range from")
+            rays = pixel_rays(screen, cams[0])[hit]
+            u = gs.eval_trap(trap, rays[:, 0:3] + t[hit, None] * rays[:, 4:7])
+            lo, hi = (float(v) for v in np.percentile(u[np.isfinite(u)], [5.0, 95.0]))
+            if not hi > lo:
+                hi = lo + 1.0  # (a trap that measures one distance everywhere: the first stop's colour)
+            trap.scale, trap.bias = (float(v) for v in trap_range(lo, hi))
+            print(f"--trap-range auto: {int(hit.sum())} hits, distances {float(u.min()):.4g} .. {float(u.max()):.4g}, range {lo:.4g},{hi:.4g}")
+        try:
+            colour = gs.render_trapped_batch(cams, trap, light=light, ao=ao)
+        except K.KifsError as e:
+            sys.exit(f"--trap {args.trap}: {e}")
+        gs.synchronize()
+        for k, frame in zip(indices, colour.cpu().numpy()):
+            path = args.out if k is None else args.out % k
+            write_png(path, frame)
+            print(f"{path}: {screen.width}x{screen.height}, orbit trap at {tuple(trap.centre)} (axes {trap.axes}, {trap.iterations} orbit "
+                  f"points, scale {trap.scale:.6g}, bias {trap.bias:.6g}), stops {tuple(trap.mid)} and {tuple(trap.far)}"
+                  + (f", lit from {tuple(light.direction)}" if light is not None else "")
+                  + (f", ambient occlusion ({ao.samples} probes)" if ao is not None else "")
+                  + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
     elif light is not None:
         indices = args.frames if args.frames is not None else [None]
         cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
