@@ -688,6 +688,75 @@ int kifs_render_trapped_async(kifs_ctx* ctx, void* hip_stream, int count, const 
                               const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
 int kifs_eval_trap(kifs_ctx* ctx, const KifsOrbitTrap* trap, const float* points_xyz, int n, float* u_out);
 
+/* ---- extension: kaleidoscopic IFS scenes (not in the reference) -----------------------------------------------------
+ * kifs_render_lit_async with the scene's distance estimate replaced by that of a base primitive seen through N rounds of
+ * fold, rotate and scale: Menger sponges, octahedral and rotated tetrahedral flakes, kaleidoscoped tori and bunnies.  The
+ * call is a render of its own (kifs_fold_kernels.hip); one fold system per call.  All f32 in the order written, fma only
+ * where written, divide and square root correctly rounded, comparisons as C ternaries (a NaN compares false).
+ *   host      k = scale - 1;  t_i = -(k * offset[i]);  h = 0.5 * t_z   (f32)
+ *   estimate  at the position p: acc = 1; for j = 0 .. N-1, while sqrt(dot3(p,p)) < max_distance (the reference's
+ *             r < options.max_distance, dot3(a,b) = fma(a.z,b.z, fma(a.y,b.y, a.x*b.x)); a position whose test fails
+ *             stops for good and keeps its p and acc), the stages of `stages` in THIS order, whatever the mask:
+ *               1 ABS       p = (|x|, |y|, |z|)
+ *               2 SORT      if (x < y) swap(x, y);  if (x < z) swap(x, z);  if (y < z) swap(y, z)   (descending; a NaN
+ *                           is not moved)
+ *               3 TETRA     the reference's tetrahedral_fold (kifs.wgsl:56-66): for the pairs (x,y), (y,z), (x,z):
+ *                           sd = (a + b) * fl(1/sqrt(2));  m = 2 * min(sd, 0);  a = fma(-m, fl(1/sqrt(2)), a), b likewise
+ *               4 ROTATE    q.x = fma(R[2], p.z, fma(R[1], p.y, R[0]*p.x)), q.y with R[3..5], q.z with R[6..8];  p = q.
+ *                           Without the bit the matrix is not read; there is no hidden test for the identity
+ *                           (fma(0, y, x) loses the sign of a zero)
+ *               5 scale     always: p_i = fma(scale, p_i, t_i)
+ *               6 MIRROR_Z  p.z = |p.z - h| + h   (the Menger rule "subtract the z offset only beyond its half", written
+ *                           as a mirror so that it stays continuous under any base shape; scale 3, offset (1,1,1),
+ *                           ABS|SORT|MIRROR_Z and the box: the sponge)
+ *               7 acc = acc * scale
+ *             the estimate is base(p) / acc, base the KIFS group's estimate of options.primitive_id at the folded point
+ *             -- sphere, cylinder, box, torus, the Sierpinski estimate with the context's fold iterations, the bunny,
+ *             the constant 1 of an unknown id.  The normal is the reference's central differences with h = epsilon
+ *             over this estimate.
+ *   frame     exactly kifs_render_lit_async's with the folded estimate wherever that call evaluates the scene's: the
+ *             primary march, the normal, the soft-shadow march towards the light and the occlusion probes.  light NULL:
+ *             the light {(1,1,1), 0.1, 0.9, no highlight}.  A heatmap frame shows the counter.
+ *   culls     none: a ray is a miss only if the march says so.  The bounding-sphere culls of the other calls stand on
+ *             the base primitive's radius, which a folded scene leaves (offset (3,0,0): the shape sits around
+ *             |x| = 1.5); the launch runs with all three off.
+ *   samples, frames, ordering, launch: kifs_render_lit_async's -- supersampling honoured sample by sample; 1..
+ *             KIFS_MAX_FOLD_BATCH frames, cameras NULL with count 1; bands bit-identical to the frame's rows and every
+ *             frame of a batch to the lone call; not a feedback launch, the kifs_debug_last_* values left alone.
+ *   identity  iterations == 0 with any stages, matrix, scale and offset in range writes the bytes of
+ *             kifs_render_lit_async for the same light and term -- with light NULL those of kifs_render_batch_async, and
+ *             with a term those of kifs_render_occlusion_async -- for every KIFS primitive, with soft shadows, heatmap
+ *             and k > 1: x / 1.0f is x.  kifs_eval_fold then gives kifs_eval_points' values.
+ *   refusals  a refused call launches nothing and writes nothing.  Everything kifs_render_lit_async refuses is refused
+ *             with its status (a NULL light is not refused here).  KIFS_ERR_BAD_ARG also: a NULL fold; stages > 31;
+ *             iterations outside 0..KIFS_MAX_FOLD_ITERATIONS; a scale that is not finite or outside [1, 16]; an offset
+ *             component that is not finite; with KIFS_FOLD_ROTATE a matrix entry that is not finite (without the bit the
+ *             matrix is not looked at); options.fractal_group_id != KIFS_GROUP_KIFS -- the two Julia pipelines have no
+ *             folded form.  y1 == y0 returns KIFS_OK and enqueues nothing.
+ *   scope     deliberately absent: per-frame systems (an animated fold is a sequence of calls); a trap on a folded
+ *             scene; a form in the accumulate, animation, adaptive, geometry, ray-query and multi-GPU calls or in the
+ *             viewer; negative scales (Mandelbox-style folds); a certified cull radius for folded scenes.
+ * kifs_eval_fold writes the folded estimate and/or its normal for n positions (host pointers, either output may be NULL,
+ * like kifs_eval_points) with the context's options.
+ * Every byte, every estimate and every normal equals the CPU restatement of the contract (tests/fold_reference.c), which
+ * is normative where this text and it could be read differently. */
+#define KIFS_MAX_FOLD_ITERATIONS 24
+#define KIFS_MAX_FOLD_BATCH 64
+enum KifsFoldStage { KIFS_FOLD_ABS = 1, KIFS_FOLD_SORT = 2, KIFS_FOLD_TETRA = 4, KIFS_FOLD_ROTATE = 8, KIFS_FOLD_MIRROR_Z = 16 };
+typedef struct KifsFoldSystem {   /* 60 bytes */
+    uint32_t stages;       /* OR of KifsFoldStage, 0..31; the stages run in the order above whatever the mask */
+    int32_t  iterations;   /* N: 0..KIFS_MAX_FOLD_ITERATIONS */
+    float    scale;        /* s: finite, 1 <= s <= 16 (s^24 stays a normal f32) */
+    float    offset[3];    /* c: the fixed point of the scaling; finite */
+    float    rotation[9];  /* row-major 3x3, USED AS GIVEN (not checked for orthonormality); finite; read only with KIFS_FOLD_ROTATE */
+} KifsFoldSystem;
+int kifs_render_folded_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                             uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsFoldSystem* fold,
+                             const KifsLight* light /* NULL: the reference's light */,
+                             const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
+int kifs_eval_fold(kifs_ctx* ctx, const KifsFoldSystem* fold, const float* points_xyz, int n,
+                   float* sdf_out, float* normal_out_xyz);
+
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */
 int kifs_band_range(int height, int rank, int world, int* y0, int* y1);

@@ -71,6 +71,11 @@ class KifsOrbitTrapC(C.Structure):  # KifsOrbitTrap: the trap of kifs_render_tra
                 ("bias", C.c_float), ("mid", C.c_float * 3), ("far", C.c_float * 3)]
 
 
+class KifsFoldSystemC(C.Structure):  # KifsFoldSystem: the fold system of kifs_render_folded_async
+    _fields_ = [("stages", C.c_uint32), ("iterations", C.c_int32), ("scale", C.c_float), ("offset", C.c_float * 3),
+                ("rotation", C.c_float * 9)]
+
+
 MAX_RAYS = 1 << 28  # KIFS_MAX_RAYS
 MAX_AO_SAMPLES = 16  # KIFS_MAX_AO_SAMPLES
 MAX_OCCLUSION_BATCH = 64  # KIFS_MAX_OCCLUSION_BATCH
@@ -78,6 +83,9 @@ MAX_SHININESS_LOG2 = 10  # KIFS_MAX_SHININESS_LOG2
 MAX_LIGHT_BATCH = 64  # KIFS_MAX_LIGHT_BATCH
 MAX_TRAP_ITERATIONS = 32  # KIFS_MAX_TRAP_ITERATIONS
 MAX_TRAP_BATCH = 64  # KIFS_MAX_TRAP_BATCH
+MAX_FOLD_ITERATIONS = 24  # KIFS_MAX_FOLD_ITERATIONS
+MAX_FOLD_BATCH = 64  # KIFS_MAX_FOLD_BATCH
+FOLD_STAGES = {"abs": 1, "sort": 2, "tetra": 4, "rotate": 8, "mirror_z": 16}  # KifsFoldStage
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
 
@@ -113,6 +121,7 @@ assert C.sizeof(KifsSubpixel) == 2
 assert C.sizeof(AmbientOcclusionC) == 16
 assert C.sizeof(KifsLightC) == 36
 assert C.sizeof(KifsOrbitTrapC) == 56
+assert C.sizeof(KifsFoldSystemC) == 60
 
 # every symbol include/kifs_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -164,6 +173,10 @@ SIGNATURES = {
                                             _P(KifsOrbitTrapC), _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int,
                                             C.c_int]),
     "kifs_eval_trap": (C.c_int, [_ctx, _P(KifsOrbitTrapC), _f32p, C.c_int, _f32p]),
+    "kifs_render_folded_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                           _P(KifsFoldSystemC), _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int,
+                                           C.c_int]),
+    "kifs_eval_fold": (C.c_int, [_ctx, _P(KifsFoldSystemC), _f32p, C.c_int, _f32p, _f32p]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

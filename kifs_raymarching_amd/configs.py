@@ -205,6 +205,48 @@ def trap_range(lo: float, hi: float) -> tuple:
     return scale, np.float32(np.float32(-lo) * scale)
 
 
+def fold_rotation(*axis_angle_pairs) -> tuple:
+    """The row-major 3 x 3 matrix for FoldSystem.rotation / KifsFoldSystem.rotation of a chain of axis rotations:
+    fold_rotation(("y", 0.4), ("z", -0.2)) is R_y(0.4) R_z(-0.2) -- the last pair turns the point first.  An axis is
+    "x", "y", "z" or 0, 1, 2, an angle is in radians.  Every factor is the library's kifs_host_rotation_matrix and every
+    product its kifs_host_mat3_mul (f32, column-major); the result is transposed to the row-major order the record
+    takes.  No pair: the identity."""
+    import ctypes as C
+
+    from ._lib import lib
+    m = (C.c_float * 9)(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+    for pair in axis_angle_pairs:
+        axis, angle = pair
+        index = {"x": 0, "y": 1, "z": 2}.get(axis, axis) if isinstance(axis, str) else axis
+        if index not in (0, 1, 2):
+            raise ValueError(f"fold_rotation: axis {axis!r} is not x, y, z or 0, 1, 2")
+        if not math.isfinite(float(angle)):
+            raise ValueError("fold_rotation: a finite angle in radians")
+        r, out = (C.c_float * 9)(), (C.c_float * 9)()
+        lib.kifs_host_rotation_matrix(int(index), float(angle), r)
+        lib.kifs_host_mat3_mul(m, r, out)
+        m = out
+    return tuple(float(m[3 * c + r]) for r in range(3) for c in range(3))
+
+
+def _fold_presets():
+    from .graphics import FoldSystem
+    return {
+        # the Menger sponge: sort the folded point, scale by 3 about the corner, mirror z about its half offset
+        "menger": (PrimitiveShape.Box, FoldSystem(stages=("abs", "sort", "mirror_z"), iterations=4, scale=3.0, offset=(1.0, 1.0, 1.0))),
+        # an octahedral flake of boxes, turned a little every round
+        "flake": (PrimitiveShape.Box, FoldSystem(stages=("abs", "sort", "rotate"), iterations=6, scale=2.0, offset=(1.0, 0.0, 0.0),
+                                                 rotation=fold_rotation(("z", 0.25), ("y", 0.15)))),
+        # a rotated tetrahedral flake of tori
+        "tetra": (PrimitiveShape.Torus, FoldSystem(stages=("tetra", "rotate"), iterations=5, scale=2.0, offset=(1.0, 1.0, 1.0),
+                                                   rotation=fold_rotation(("z", 0.3), ("x", 0.2)))),
+    }
+
+
+# name -> (base PrimitiveShape, FoldSystem)
+FOLD_PRESETS = _fold_presets()
+
+
 def pass_splits(total: int, per_pass: int = 64) -> list:
     """The pass sizes of a progressive frame of `total` sub-frames (GraphicState.render_accumulate_resume, Accumulator):
     total // per_pass passes of `per_pass` and, if anything is left, one of the remainder -- [64, 64, 22] for 150.  A

@@ -1,6 +1,6 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
 // kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip,
-// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip, kifs_trap_kernels.hip).
+// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip, kifs_trap_kernels.hip, kifs_fold_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,6 +45,11 @@ hipError_t launch_lit(const light::Params& O, uint32_t group, uint32_t primitive
 // positions, one per lane (trap::eval_kernel).
 hipError_t launch_trapped(const trap::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
 hipError_t launch_eval_trap(const trap::EvalParams& E, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Kaleidoscopic IFS scenes (kifs_render_folded_async; kifs_fold_kernels.hip, the host side is kifs_fold.cpp): the lit
+// launch with the folded estimate in the place of the scene's (fold::render_kernel); and kifs_eval_fold's estimate and
+// normal at E.n positions, one per lane (fold::eval_kernel).  KIFS group only.
+hipError_t launch_folded(const fold::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
+hipError_t launch_eval_fold(const fold::EvalParams& E, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

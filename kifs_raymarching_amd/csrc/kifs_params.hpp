@@ -316,4 +316,45 @@ static_assert(sizeof(EvalParams) <= 4096, "the kernel argument is limited to 4 K
 
 }  // namespace trap
 
+namespace fold {
+
+// The fold system of kifs_render_folded_async (KifsFoldSystem, include/kifs_hip.h), as the kernels read it: the stage
+// mask, the trip count and the scale as given, the constants of the scaling step computed on the host in f32 --
+// t_i = -((scale - 1) * offset[i]), h = 0.5 * t_z -- and the matrix as given, row-major.
+enum : uint32_t { ABS = 1u, SORT = 2u, TETRA = 4u, ROTATE = 8u, MIRROR_Z = 16u };
+struct Fold {
+    uint32_t stages;     // 0..31
+    int iterations;      // 0..KIFS_MAX_FOLD_ITERATIONS
+    float scale;         // 1..16
+    float t[3];
+    float h;
+    float R[9];          // read only with ROTATE
+};
+static_assert(sizeof(Fold) == 64, "the record is 64 bytes");
+
+// The argument of fold::render_kernel (kifs_fold_kernels.hip): light::Params -- the same fields at the same offsets --
+// and the fold system behind them.
+struct Params {
+    BatchParams B;
+    light::Light light;
+    occl::AO ao;         // read only when has_ao != 0
+    uint32_t has_ao;
+    Fold fold;
+};
+static_assert(sizeof(Params) <= 4096, "the kernel argument is limited to 4 KB");
+
+// The argument of fold::eval_kernel (kifs_eval_fold): the scene's frame constants -- nothing of a screen or a camera is
+// read -- the fold system and the arrays.
+struct EvalParams {
+    FrameParams frame;
+    Fold fold;
+    const float* points;  // n positions of three floats (device memory)
+    int n;
+    float* sdf;           // null, or n floats
+    float* normal;        // null, or n normals of three floats
+};
+static_assert(sizeof(EvalParams) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace fold
+
 }  // namespace kifs

@@ -1612,4 +1612,106 @@ KIFS_DEV V3 raymarch_trapped(const FrameParams& P, trap::ConstParams K, V3 dir, 
     return colour;
 }
 
+// ---- extension: kaleidoscopic IFS scenes (kifs_render_folded_async, include/kifs_hip.h) ----------------------------
+// The estimate of a base primitive seen through N rounds of fold, rotate and scale, operation for operation as the header
+// states it.  The fold system is read from the kernel argument where the estimate runs (fold::anew), at the head of every
+// estimate: its eighteen words held from the kernel's start would cross the bunny's estimate, which leaves few scalar
+// registers.
+namespace fold {
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+typedef const Fold __attribute__((address_space(4))) * ConstFold;
+KIFS_DEV ConstFold anew(ConstFold F) {
+    asm volatile("" : "+s"(F));
+    return F;
+}
+KIFS_DEV ConstParams anew(ConstParams K) {
+    asm volatile("" : "+s"(K));
+    return K;
+}
+}  // namespace fold
+
+// base(p') / acc of the position p.  `lanes`: the lanes whose estimate is used (the others get an unspecified value).
+// The stage mask, N and the exit -- once no lane of `lanes` still folds -- are wave-uniform: the stages are scalar
+// branches.  A lane whose |p| has reached max_distance (on the squared norm: FrameParams::fold_n2_stop; a NaN compares
+// false) stops for good and keeps its p and acc.  SORT is the contract's ternaries: the hardware maximum and minimum
+// would move a NaN and may order a pair of zeros of either sign differently.  With N = 0 the loop is never entered and
+// base(p) / 1.0f is base(p).
+template <int PRIM>
+KIFS_DEV float folded_sdf(const FrameParams& S, fold::ConstFold F0, V3 p, unsigned long long lanes) {
+    const fold::ConstFold F = fold::anew(F0);
+    const int n = F->iterations;  // uniform
+    float acc = 1.0f;
+    if (n > 0) {
+        const uint32_t stages = F->stages;
+        // The loop's constants, read once here and held in scalar registers for the length of the loop alone (the empty
+        // asm keeps the compiler from sinking the loads back into it: a scalar load and its wait per round otherwise);
+        // they are dead again when the base estimate starts.
+        float s = F->scale, t0 = F->t[0], t1 = F->t[1], t2 = F->t[2], h = F->h;
+        asm volatile("" : "+s"(s), "+s"(t0), "+s"(t1), "+s"(t2), "+s"(h));
+        float R[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (stages & fold::ROTATE) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) R[i] = F->R[i];
+        }
+        asm volatile("" : "+s"(R[0]), "+s"(R[1]), "+s"(R[2]), "+s"(R[3]), "+s"(R[4]), "+s"(R[5]), "+s"(R[6]), "+s"(R[7]), "+s"(R[8]));
+        bool run = true;
+        for (int j = 0; j < n; ++j) {
+            run = run && (dot(p, p) < S.fold_n2_stop);
+            if ((__builtin_amdgcn_ballot_w64(run) & lanes) == 0ull) break;
+            V3 q = p;
+            if (stages & fold::ABS) q = V3{abs_(q.x), abs_(q.y), abs_(q.z)};
+            if (stages & fold::SORT) {
+                const bool a = q.x < q.y;
+                const float x1 = a ? q.y : q.x, y1 = a ? q.x : q.y;
+                const bool b = x1 < q.z;
+                const float x2 = b ? q.z : x1, z2 = b ? x1 : q.z;
+                const bool c = y1 < z2;
+                q = V3{x2, c ? z2 : y1, c ? y1 : z2};
+            }
+            if (stages & fold::TETRA) q = tetrahedral_fold(q);
+            if (stages & fold::ROTATE) {
+                q = V3{fmaf_(R[2], q.z, fmaf_(R[1], q.y, R[0] * q.x)), fmaf_(R[5], q.z, fmaf_(R[4], q.y, R[3] * q.x)),
+                       fmaf_(R[8], q.z, fmaf_(R[7], q.y, R[6] * q.x))};
+            }
+            q = V3{fmaf_(s, q.x, t0), fmaf_(s, q.y, t1), fmaf_(s, q.z, t2)};
+            if (stages & fold::MIRROR_Z) q.z = abs_(q.z - h) + h;
+            p = V3{run ? q.x : p.x, run ? q.y : p.y, run ? q.z : p.z};
+            acc = run ? acc * s : acc;
+        }
+    }
+    return kifs_sdf<PRIM>(S, p, lanes) / acc;
+}
+
+// raymarch_lit for the folded launch (kifs_fold_kernels.hip): the same whole ray per lane through the view P, with the
+// folded estimate wherever the lit call takes the scene's -- the march, the normal, the shadow ray and the probes.  The
+// shading is lit_shade itself: fold::Params carries light::Params' fields at their offsets.  The launch runs with every
+// cull off (kifs_fold.cpp): a folded scene reaches beyond the base primitive's bounding sphere.
+template <int PRIM, class Dir>
+KIFS_DEV V3 raymarch_folded(const FrameParams& P, fold::ConstParams K, V3 dir, bool valid, Dir redo_dir) {
+    float t = 0.0f;
+    V3 p = P.origin;
+    bool hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = whole_ray_sets_out(P, dir, valid);
+    generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations,
+                 [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return folded_sdf<PRIM>(P, &K->fold, q, lanes); });
+    __builtin_amdgcn_s_setprio(0);
+    const light::ConstParams KL = (light::ConstParams)K;
+    const light::ConstParams L = light::anew(KL);
+    const FrameParams S = *(const FrameParams*)&L->B.frame;  // the scene, as every view of the launch shares it
+    V3 colour = S.background_color;
+    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {  // wave-uniform
+        const auto sdf = [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) { return folded_sdf<PRIM>(S, &K->fold, q, lanes); };
+        colour = lit_shade(
+            S, KL, p, hit, S.background_color, sdf,
+            [&](V3 q) __attribute__((always_inline)) {
+                return normal_fd(S.epsilon, q, [&](V3 e) __attribute__((always_inline)) { return folded_sdf<PRIM>(S, &K->fold, e, ~0ull); });
+            },
+            redo_dir);
+    }
+    if (S.is_heatmap) colour = heatmap_colour(S, i_final);
+    return colour;
+}
+
 }  // namespace kifs

@@ -25,7 +25,7 @@ STRIPE_ROWS = 8  # KIFS_STRIPE_ROWS
 ANIMATION_RING = 4  # KIFS_ANIMATION_RING
 MAX_ACCUMULATE = 64  # KIFS_MAX_ACCUMULATE
 MAX_JITTER_GRID = _lib.MAX_JITTER_GRID  # KIFS_MAX_JITTER_GRID
-from ._lib import (AdaptiveAAC, AmbientOcclusionC, KifsLightC, KifsOrbitTrapC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
+from ._lib import (AdaptiveAAC, AmbientOcclusionC, KifsLightC, KifsOrbitTrapC, KifsFoldSystemC, CameraDataC, CameraUniform, ExtensionsC, GuiDataC, KifsError, KifsSubpixel, OptionsUniform,
                    ScreenUniform, check, lib)
 
 ENCODE_UNORM = _lib.ENCODE_UNORM
@@ -189,6 +189,52 @@ class OrbitTrap:  # KifsOrbitTrap: the trap of kifs_render_trapped_async; the gr
         check(lib.kifs_host_options(C.byref(g), C.byref(u)), "OrbitTrap")
         return KifsOrbitTrapC((C.c_float * 4)(*centre), int(self.axes), int(self.iterations), float(self.scale), float(self.bias),
                               (C.c_float * 3)(*u.fractal_color), (C.c_float * 3)(*u.background_color))
+
+
+_F32_MAX = 3.4028234663852886e38
+
+
+@dataclass
+class FoldSystem:  # KifsFoldSystem: the fold system of kifs_render_folded_async; the defaults fold nothing (iterations 0)
+    stages: object = 0                      # a mask of KifsFoldStage bits, or names: "abs", "sort", "tetra", "rotate", "mirror_z"
+    iterations: int = 0                     # rounds of fold, rotate and scale, 0..KIFS_MAX_FOLD_ITERATIONS
+    scale: float = 2.0                      # 1..16
+    offset: tuple = (1.0, 1.0, 1.0)         # the fixed point of the scaling
+    rotation: tuple = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)  # row-major 3 x 3, used as given; read only with "rotate"
+
+    def stage_bits(self) -> int:
+        if isinstance(self.stages, str):
+            names = [n for n in self.stages.replace("|", ",").replace("+", ",").split(",") if n.strip()]
+        elif isinstance(self.stages, (list, tuple, set, frozenset)):
+            names = list(self.stages)
+        else:
+            if int(self.stages) != self.stages or not 0 <= int(self.stages) <= 31:
+                raise ValueError("FoldSystem: stages is a mask 0..31 or stage names")
+            return int(self.stages)
+        bits = 0
+        for n in names:
+            key = str(n).strip().lower()
+            if key not in _lib.FOLD_STAGES:
+                raise ValueError(f"FoldSystem: unknown stage {n!r}; one of {sorted(_lib.FOLD_STAGES)}")
+            bits |= _lib.FOLD_STAGES[key]
+        return bits
+
+    def into_buffer_data(self) -> KifsFoldSystemC:
+        """The record the library takes; refuses here what it would refuse."""
+        bits = self.stage_bits()
+        if int(self.iterations) != self.iterations or not 0 <= int(self.iterations) <= _lib.MAX_FOLD_ITERATIONS:
+            raise ValueError(f"FoldSystem: 0..{_lib.MAX_FOLD_ITERATIONS} iterations")
+        if not 1.0 <= float(np.float32(self.scale)) <= 16.0:  # (false for a NaN)
+            raise ValueError("FoldSystem: scale is in [1, 16]")
+        offset = [float(v) for v in self.offset]
+        if len(offset) != 3 or not all(abs(v) <= _F32_MAX for v in offset):  # (false for a NaN)
+            raise ValueError("FoldSystem: offset is three numbers finite in float32")
+        rotation = [float(v) for v in np.asarray(self.rotation, dtype=np.float64).reshape(-1)]
+        if len(rotation) != 9:
+            raise ValueError("FoldSystem: rotation is a row-major 3 x 3 matrix")
+        if (bits & _lib.FOLD_STAGES["rotate"]) and not all(abs(v) <= _F32_MAX for v in rotation):
+            raise ValueError("FoldSystem: rotation is finite in float32")
+        return KifsFoldSystemC(bits, int(self.iterations), float(self.scale), (C.c_float * 3)(*offset), (C.c_float * 9)(*rotation))
 
 
 def uniform_bytes(u) -> bytes:
@@ -692,6 +738,67 @@ class GraphicState:
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         check(lib.kifs_eval_trap(self._ctx, C.byref(record), fp(pts), n, fp(u)), "eval_trap")
         return u
+
+    # ---- kaleidoscopic IFS scenes (kifs_render_folded_async): the base primitive seen through `fold`, lit and optionally occluded
+    def render_folded_batch(self, cameras, fold: FoldSystem, light: Light = None, ao: AmbientOcclusion = None, stream=None,
+                            y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, colour=None):
+        """The frames of len(cameras) cameras (cameras None: one frame with the context's camera) of the context's KIFS
+        primitive seen through the fold system `fold`, under `light` (None: the reference's light) and with the
+        ambient-occlusion term `ao` on top when one is given, the context's supersampling factor and soft-shadow extension
+        honoured.  Returns a uint8 (count, rows, W, 4) torch tensor on this context's device; `colour`: a contiguous
+        destination tensor of that shape to reuse.  The library takes MAX_FOLD_BATCH cameras per launch; more are fed to
+        it that many at a time.  Enqueued on `stream` like render_async; the caller synchronises before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if n < 1:
+            raise ValueError("render_folded_batch: at least one frame")
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        if tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_folded_batch: colour uint8 ({n}, {rows}, {w}, 4), contiguous")
+        record = fold.into_buffer_data() if hasattr(fold, "into_buffer_data") else fold  # (or a KifsFoldSystemC)
+        lit = None if light is None else light.into_buffer_data()
+        term = None if ao is None else ao.into_buffer_data()
+        stream = self._stream_handle(stream, "render_folded_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        self._order_after_producer(colour, stream)
+        step = _lib.MAX_FOLD_BATCH
+        base, frame_bytes = _device_pointer(colour), rows * w * 4
+        for first in range(0, n, step):
+            m = min(step, n - first)
+            ptrs = (C.c_void_p * m)(*[base + (first + i) * frame_bytes for i in range(m)])
+            part = None if cams is None else C.cast(C.byref(cams, first * C.sizeof(CameraUniform)), C.POINTER(CameraUniform))
+            check(lib.kifs_render_folded_async(self._ctx, stream, m, part, ptrs, w * 4, C.byref(record),
+                                               None if lit is None else C.byref(lit),
+                                               None if term is None else C.byref(term), y0, y1, encode), "render_folded")
+        return colour
+
+    def render_folded(self, fold: FoldSystem, light: Light = None, ao: AmbientOcclusion = None, y0: int = 0, y1: int = None,
+                      encode: int = ENCODE_SRGB, stream=None):
+        """The context's frame seen through `fold` (under `light`, with `ao`), synchronously: a uint8 rows x W x 4 torch
+        tensor on this context's device."""
+        import torch
+        colour = self.render_folded_batch(None, fold, light=light, ao=ao, stream=stream, y0=y0, y1=y1, encode=encode)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0]
+
+    def eval_fold(self, fold: FoldSystem, points, sdf: bool = True, normal: bool = True):
+        """(sdf, normal) -- the folded estimate, (n,) float32, and its normal, (n, 3) float32 -- of (n, 3) positions with
+        the context's options; None for the one not asked for."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        d = np.empty(n, dtype=np.float32) if sdf else None
+        nr = np.empty((n, 3), dtype=np.float32) if normal else None
+        record = fold.into_buffer_data() if hasattr(fold, "into_buffer_data") else fold
+        fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib.kifs_eval_fold(self._ctx, C.byref(record), fp(pts), n, fp(d), fp(nr)), "eval_fold")
+        return d, nr
 
     # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
     def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):

@@ -20,6 +20,8 @@
     python tools/render.py cfg5_sierpinski_8k_orbit orbit_%03d.png --frames 0 30 60 --scale 0.25 --ao 8,0.01,0.8,3 --aa 2
     python tools/render.py cfg2_julia_1080p out.png --light -0.55,0.75,0.36,0.15,0.85 --specular 0.6,0.6,0.5,3 --ao  # a moved light
     python tools/render.py cfg2_julia_1080p out.png --trap 0,0,0,0 --trap-colours 255,140,0:20,60,200 --trap-range auto --ao  # orbit-trap colours
+    python tools/render.py cfg5_sierpinski_8k_orbit out.png --scale 0.25 --fold menger --ao    # a Menger sponge (kaleidoscopic IFS)
+    python tools/render.py cfg5_sierpinski_8k_orbit out.png --scale 0.25 --fold abs+sort,6,2,1,0,0 --fold-rotate z,14,y,9 --light -0.55,0.75,0.36
 """
 import argparse
 import sys
@@ -28,7 +30,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import kifs_raymarching_amd as K  # noqa: E402
 from kifs_raymarching_amd.configs import (WORKLOADS, jitter_cells, lens_cameras, morph_options, orbit_camera, panorama_rays,  # noqa: E402
-                                          pass_splits, pixel_rays, shutter_cameras, trap_range)
+                                          pass_splits, pixel_rays, shutter_cameras, trap_range, FOLD_PRESETS, fold_rotation)
 from kifs_raymarching_amd.image import write_png  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -109,6 +111,14 @@ ap.add_argument("--trap-colours", metavar="R,G,B:R,G,B", default="255,140,0:20,6
 ap.add_argument("--trap-range", metavar="LO,HI|auto", default="auto",
                 help="with --trap: the distances that take the gradient's first and last stop; auto: the 5th and 95th "
                      "percentile of the distances at the first frame's hits (kifs_render_geometry_async, kifs_eval_trap)")
+ap.add_argument("--fold", metavar="PRESET|STAGES,N,SCALE,CX,CY,CZ", default=None,
+                help="a kaleidoscopic IFS scene (kifs_render_folded_async): the base primitive seen through N rounds of the "
+                     "stages STAGES (a mask 0..31, or names joined by +: abs+sort+tetra+rotate+mirror_z), scaled by SCALE about "
+                     f"CX,CY,CZ -- or a preset ({', '.join(sorted(FOLD_PRESETS))}), which also picks the base primitive; a KIFS "
+                     "workload; goes with --light, --specular, --ao, --aa, --frames and the shadow workloads")
+ap.add_argument("--fold-rotate", metavar="AXIS,DEG[,AXIS,DEG..]", default=None,
+                help="with --fold STAGES,..: the rotation of the rotate stage as a chain of axis rotations in degrees "
+                     "(configs.fold_rotation), which also switches that stage on")
 args = ap.parse_args()
 def _numbers(text, count):
     try:
@@ -120,7 +130,7 @@ panorama = None
 if args.panorama is not None:
     panorama = _numbers(args.panorama, 3)
     others = (args.frames, args.morph_to, args.geometry, args.depth_png, args.dof, args.spp, args.tolerance, args.focus_at, args.ao, args.ao_png,
-              args.light, args.specular, args.trap)
+              args.light, args.specular, args.trap, args.fold)
     if panorama is None or args.aa != 1 or args.aa_adaptive or args.motion_blur or args.jitter or any(o is not None for o in others):
         ap.error("--panorama takes three numbers X,Y,Z and renders on its own (--scale and --heatmap apply; no --ao, --light or "
                  "--specular: ray queries compute neither the term nor a light of the caller's)")
@@ -228,6 +238,43 @@ if args.trap is not None:
     if span is not None:
         trap.scale, trap.bias = (float(v) for v in trap_range(*span))
     aa_grid = False  # several supersampled frames go through the trapped batch, not through the accumulate family
+fold, fold_base = None, None
+if args.fold is not None:
+    # the folded estimate exists in kifs_render_folded_async alone
+    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None or trap is not None:
+        ap.error("--fold renders without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry, --morph-to and --trap: "
+                 "the accumulate, adaptive, geometry, animation and trapped entry points march the unfolded scene")
+    if args.ao_png:
+        ap.error("--ao-png goes without --fold: the folded call writes no plane of factors")
+    if args.fold in FOLD_PRESETS:
+        if args.fold_rotate is not None:
+            ap.error("--fold-rotate goes with --fold STAGES,..: a preset brings its own rotation")
+        fold_base, fold = FOLD_PRESETS[args.fold]
+    else:
+        parts = args.fold.split(",")
+        numbers = _numbers(",".join(parts[1:]), 5) if len(parts) == 6 else None
+        if numbers is None or numbers[0] != int(numbers[0]):
+            ap.error(f"--fold takes a preset ({', '.join(sorted(FOLD_PRESETS))}) or STAGES,N,SCALE,CX,CY,CZ (N a whole number)")
+        stages = int(parts[0]) if parts[0].strip().isdigit() else parts[0].replace("+", ",")
+        fold = K.FoldSystem(stages=stages, iterations=int(numbers[0]), scale=numbers[1], offset=numbers[2:5])
+        if args.fold_rotate is not None:
+            turns = args.fold_rotate.split(",")
+            try:
+                import math
+                pairs = [(turns[i].strip(), math.radians(float(turns[i + 1]))) for i in range(0, len(turns) - 1, 2)]
+                if len(turns) % 2 or not pairs:
+                    raise ValueError("pairs of AXIS,DEG")
+                fold.rotation = fold_rotation(*pairs)
+                fold.stages = fold.stage_bits() | 8
+            except (ValueError, TypeError) as e:
+                ap.error(f"--fold-rotate takes AXIS,DEG[,AXIS,DEG..] with the axes x, y, z: {e}")
+    try:
+        fold.into_buffer_data()
+    except ValueError as e:
+        ap.error(f"--fold: {e}")
+    aa_grid = False  # several supersampled frames go through the folded batch, not through the accumulate family
+elif args.fold_rotate is not None:
+    ap.error("--fold-rotate goes with --fold")
 morph_to = None
 if args.morph_to is not None:
     try:
@@ -243,6 +290,11 @@ if args.morph_to is not None:
 w = WORKLOADS[args.workload]
 screen = K.ScreenData(max(1, int(w.screen.width * args.scale)), max(1, int(w.screen.height * args.scale)))
 gui = w.gui
+if fold is not None:
+    if gui.fractal_group != K.FractalGroup.KaleidoscopicIFS:
+        ap.error("--fold takes a KIFS workload: the two Julia pipelines have no folded form")
+    if fold_base is not None:
+        gui = K.GuiData(**{**gui.__dict__, "primitive_shape": fold_base})
 if args.heatmap:
     gui = K.GuiData(**{**gui.__dict__, "is_heatmap": True, "fractal_color": (255, 255, 255)})
 with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) as gs:
@@ -418,6 +470,22 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
             write_png(path, frame)
             print(f"{path}: {screen.width}x{screen.height}, orbit trap at {tuple(trap.centre)} (axes {trap.axes}, {trap.iterations} orbit "
                   f"points, scale {trap.scale:.6g}, bias {trap.bias:.6g}), stops {tuple(trap.mid)} and {tuple(trap.far)}"
+                  + (f", lit from {tuple(light.direction)}" if light is not None else "")
+                  + (f", ambient occlusion ({ao.samples} probes)" if ao is not None else "")
+                  + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
+    elif fold is not None:
+        indices = args.frames if args.frames is not None else [None]
+        cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
+        try:
+            colour = gs.render_folded_batch(cams, fold, light=light, ao=ao)
+        except K.KifsError as e:
+            sys.exit(f"--fold {args.fold}: {e}")
+        gs.synchronize()
+        for k, frame in zip(indices, colour.cpu().numpy()):
+            path = args.out if k is None else args.out % k
+            write_png(path, frame)
+            print(f"{path}: {screen.width}x{screen.height}, {K.PrimitiveShape(gui.primitive_shape).name} folded {fold.iterations} times "
+                  f"(stages {fold.stage_bits()}, scale {fold.scale}, offset {tuple(fold.offset)})"
                   + (f", lit from {tuple(light.direction)}" if light is not None else "")
                   + (f", ambient occlusion ({ao.samples} probes)" if ao is not None else "")
                   + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
