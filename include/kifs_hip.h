@@ -733,9 +733,10 @@ int kifs_eval_trap(kifs_ctx* ctx, const KifsOrbitTrap* trap, const float* points
  *             component that is not finite; with KIFS_FOLD_ROTATE a matrix entry that is not finite (without the bit the
  *             matrix is not looked at); options.fractal_group_id != KIFS_GROUP_KIFS -- the two Julia pipelines have no
  *             folded form.  y1 == y0 returns KIFS_OK and enqueues nothing.
- *   scope     deliberately absent: per-frame systems (an animated fold is a sequence of calls); a trap on a folded
- *             scene; a form in the accumulate, animation, adaptive, geometry, ray-query and multi-GPU calls or in the
- *             viewer; negative scales (Mandelbox-style folds); a certified cull radius for folded scenes.
+ *   scope     deliberately absent: per-frame systems (an animated fold is a sequence of calls); a form in the
+ *             accumulate, animation, adaptive, geometry, ray-query and multi-GPU calls or in the viewer; negative scales
+ *             (Mandelbox-style folds); a certified cull radius for folded scenes.  (No longer absent: a trap on a folded
+ *             scene is kifs_render_folded_trapped_async, below.)
  * kifs_eval_fold writes the folded estimate and/or its normal for n positions (host pointers, either output may be NULL,
  * like kifs_eval_points) with the context's options.
  * Every byte, every estimate and every normal equals the CPU restatement of the contract (tests/fold_reference.c), which
@@ -756,6 +757,63 @@ int kifs_render_folded_async(kifs_ctx* ctx, void* hip_stream, int count, const K
                              const KifsAmbientOcclusion* ao /* may be NULL */, int y0, int y1, int encode);
 int kifs_eval_fold(kifs_ctx* ctx, const KifsFoldSystem* fold, const float* points_xyz, int n,
                    float* sdf_out, float* normal_out_xyz);
+
+/* ---- extension: orbit-trap colouring of folded scenes (not in the reference) ----------------------------------------
+ * The two extensions above composed: kifs_render_folded_async with a colour per hit in the place of the one fractal
+ * colour, from the orbit that the folded estimate already iterates -- the point after each round -- continued by the base
+ * primitive's own.  The call is a render of its own (kifs_fold_trap_kernels.hip); one fold system and one trap per call.
+ * All f32 in the order written, fma only where written, square root correctly rounded, comparisons as C ternaries (a NaN
+ * compares false).  K is trap->iterations, N is fold->iterations.
+ *   orbit     of a hit at the tested position p (the one the shading uses): z_0 = (p.x, p.y, p.z, 0).
+ *               fold part   the folded estimate's loop exactly as kifs_render_folded_async states it: the same stop test
+ *                           sqrt(dot3(p,p)) < max_distance, the same stages in the same order, the same scale step.
+ *                           After each round j = 0..N-1 that ran for this position z_{j+1} = (p after MIRROR_Z, 0).  A
+ *                           position whose stop test fails contributes no further fold points and keeps its p.  Fold
+ *                           point k takes part only while k <= K.
+ *               base part   K_b = max(K - N, 0), from N and not from the rounds that ran.  Base primitive Sierpinski:
+ *                           the orbit goes on from the final folded p with the trapped call's rule, q = fma(2,
+ *                           tetrahedral_fold(q), -1) per component, w stays 0, for K_b points; no stop rule.  Every other
+ *                           primitive, the bunny and unknown primitive ids contribute nothing.
+ *   distance  kifs_render_trapped_async's d(z) over `axes` in the order x, y, z, w;  m = d(z_0), then m = (d < m) ? d : m
+ *             in orbit order (a NaN distance is never taken);  u = sqrt(m).
+ *   colour    kifs_render_trapped_async's gradient at u with the stops fractal_color, mid and far, and its shading -- the
+ *             colour in the place of fc in kifs_render_lit_async's, in that call's order.  light NULL: the light
+ *             {(1,1,1), 0.1, 0.9, no highlight}.
+ *   frame     the folded estimate stands wherever kifs_render_folded_async puts it: the primary march, the normal, the
+ *             soft-shadow march and the occlusion probes.  No culls, as there.  A heatmap frame shows the counter.
+ *   plane     dev_trap_u NULL, or one f32 per pixel laid out as kifs_render_occlusion_async's plane: row y of frame i at
+ *             dev_trap_u + i * u_stride_bytes + (y - y0) * u_pitch_bytes; its alignment, pitch and stride rules.  A hit
+ *             stores its u -- in heatmap mode too: with a plane u is evaluated for every hit whatever the mode, without
+ *             one a heatmap frame evaluates none.  A miss stores +inf.  With supersampling k > 1 a plane is refused.
+ *   samples, frames, ordering, launch: kifs_render_folded_async's -- supersampling honoured sample by sample; 1..
+ *             KIFS_MAX_FOLD_TRAP_BATCH frames, cameras NULL with count 1; bands bit-identical to the frame's rows and
+ *             every frame of a batch to the lone call; a caller's stream; not a feedback launch, the kifs_debug_last_*
+ *             values left alone.  The two records travel in device memory, through a slot of the ring that
+ *             kifs_render_animation_async's scene tables use (KIFS_ANIMATION_RING deep): the call may wait for the launch
+ *             that read the slot KIFS_ANIMATION_RING calls ago.
+ *   identity  each for every KIFS primitive, with soft shadows, heatmap and k > 1:  (a) scale = bias = 0, or mid = far =
+ *             fractal_color, writes the bytes of kifs_render_folded_async for the same fold, light and term.  (b)
+ *             fold->iterations == 0 writes the bytes of kifs_render_trapped_async for the same trap, light and term (K_b
+ *             = K: the Sierpinski orbit is that call's), and kifs_eval_fold_trap gives kifs_eval_trap's values.  (c) the
+ *             plane at a hit pixel equals kifs_eval_fold_trap at the hit position.
+ *   refusals  a refused call launches nothing and writes nothing.  Everything kifs_render_folded_async refuses is refused
+ *             with its status, the two Julia groups included; everything kifs_render_trapped_async refuses of a trap; a
+ *             NULL fold or trap; kifs_render_occlusion_async's refusals of a plane.  A record that cannot be copied to
+ *             the device returns KIFS_ERR_RUNTIME and launches nothing.  y1 == y0 returns KIFS_OK and enqueues nothing.
+ *   scope     deliberately absent: per-frame systems or traps; a certified cull radius; folded forms of the other entry
+ *             points.
+ * kifs_eval_fold_trap writes u for n positions (host pointers, like kifs_eval_trap) with the context's options; it
+ * validates the fold, and only centre, axes and iterations of the trap.
+ * Every byte and every u equals the CPU restatement of the contract (tests/fold_trap_reference.c), which is normative
+ * where this text and it could be read differently. */
+#define KIFS_MAX_FOLD_TRAP_BATCH 64
+int kifs_render_folded_trapped_async(kifs_ctx* ctx, void* hip_stream, int count, const KifsCameraUniform* cameras,
+                                     uint8_t* const* dev_outs_rgba8, size_t pitch_bytes, const KifsFoldSystem* fold,
+                                     const KifsOrbitTrap* trap, const KifsLight* light /* NULL: the reference's light */,
+                                     const KifsAmbientOcclusion* ao /* may be NULL */, float* dev_trap_u /* may be NULL */,
+                                     size_t u_pitch_bytes, size_t u_stride_bytes, int y0, int y1, int encode);
+int kifs_eval_fold_trap(kifs_ctx* ctx, const KifsFoldSystem* fold, const KifsOrbitTrap* trap, const float* points_xyz,
+                        int n, float* u_out);
 
 /* Contiguous row-band partition used for multi-GPU frames: rank r
  * of `world` owns rows [y0, y1); bands differ by at most one row. */

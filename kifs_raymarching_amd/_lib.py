@@ -85,6 +85,7 @@ MAX_TRAP_ITERATIONS = 32  # KIFS_MAX_TRAP_ITERATIONS
 MAX_TRAP_BATCH = 64  # KIFS_MAX_TRAP_BATCH
 MAX_FOLD_ITERATIONS = 24  # KIFS_MAX_FOLD_ITERATIONS
 MAX_FOLD_BATCH = 64  # KIFS_MAX_FOLD_BATCH
+MAX_FOLD_TRAP_BATCH = 64  # KIFS_MAX_FOLD_TRAP_BATCH
 FOLD_STAGES = {"abs": 1, "sort": 2, "tetra": 4, "rotate": 8, "mirror_z": 16}  # KifsFoldStage
 MAX_JITTER_GRID = 8  # KIFS_MAX_JITTER_GRID
 MAX_PROGRESSIVE_SAMPLES = 1 << 24  # KIFS_MAX_PROGRESSIVE_SAMPLES
@@ -177,6 +178,10 @@ SIGNATURES = {
                                            _P(KifsFoldSystemC), _P(KifsLightC), _P(AmbientOcclusionC), C.c_int, C.c_int,
                                            C.c_int]),
     "kifs_eval_fold": (C.c_int, [_ctx, _P(KifsFoldSystemC), _f32p, C.c_int, _f32p, _f32p]),
+    "kifs_render_folded_trapped_async": (C.c_int, [_ctx, C.c_void_p, C.c_int, _P(CameraUniform), _P(C.c_void_p), C.c_size_t,
+                                                   _P(KifsFoldSystemC), _P(KifsOrbitTrapC), _P(KifsLightC), _P(AmbientOcclusionC),
+                                                   C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "kifs_eval_fold_trap": (C.c_int, [_ctx, _P(KifsFoldSystemC), _P(KifsOrbitTrapC), _f32p, C.c_int, _f32p]),
     "kifs_band_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     "kifs_shard_stripes": (C.c_int, [C.c_int, C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_int,
                                      _P(C.c_int), _P(C.c_int)]),

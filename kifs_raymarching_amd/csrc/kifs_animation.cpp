@@ -40,7 +40,7 @@ static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras,
 
 // The next slot of the scene-table ring, as take_view_slot takes one of the view tables: allocated on first use, and
 // rewritten only after the launch that last read it is over.
-static int take_scene_slot(kifs_ctx* c, int* slot) {
+int take_scene_slot(kifs_ctx* c, int* slot) {
     const int ss = *slot = c->scene_slot;
     c->scene_slot = (ss + 1) % kifs_ctx::SCENE_RING;
     // (each part on its own: a slot that a failed allocation left half made is completed when the ring comes round to it)
@@ -52,6 +52,13 @@ static int take_scene_slot(kifs_ctx* c, int* slot) {
     if (c->scenes_busy[ss] && !host::hip_ok(hipEventSynchronize(c->scenes_used[ss]), "wait(scene table)")) return KIFS_ERR_RUNTIME;
     c->scenes_busy[ss] = false;
     return KIFS_OK;
+}
+
+// The event behind the launch that reads the slot (kifs_context.hpp).
+bool mark_scene_slot(kifs_ctx* c, int slot, hipStream_t stream) {
+    const bool marked = host::hip_ok(hipEventRecord(c->scenes_used[slot], stream), "record(scene table)");
+    c->scenes_busy[slot] = true;
+    return marked;
 }
 
 // A launch on another stream than the tile table's feedback launches follows them, as a geometry launch does
@@ -150,8 +157,7 @@ static int enqueue(kifs_ctx* c, hipStream_t stream, const SceneLaunch& L) {
     const bool launched = host::hip_ok(L.launch(A, first.fractal_group_id, first.primitive_id, stream, L.user),
                                        L.last_kernel == KIFS_KERNEL_ANIMATION ? "animation render_kernel launch" : "accumulate render_kernel launch");
     // (also after a failed launch: the copies above are enqueued and read the pinned images)
-    bool marked = host::hip_ok(hipEventRecord(c->scenes_used[ss], stream), "record(scene table)");
-    c->scenes_busy[ss] = true;
+    bool marked = mark_scene_slot(c, ss, stream);
     if (big) {
         marked = host::hip_ok(hipEventRecord(c->views_used[vs], stream), "record(view table)") && marked;
         c->views_busy[vs] = true;

@@ -14,6 +14,9 @@
 //   kifs_occlusion.cpp ambient occlusion (kifs_render_occlusion_async): the batch call's frames, hits attenuated, one launch
 //   kifs_lighting.cpp  a configurable light (kifs_render_lit_async): the batch call's frames under the caller's light, one launch
 //   kifs_trap.cpp      orbit-trap colouring (kifs_render_trapped_async, kifs_eval_trap): the lit call's frames, hits coloured by a trap
+//   kifs_fold.cpp      kaleidoscopic IFS scenes (kifs_render_folded_async, kifs_eval_fold): the lit call's frames through a fold system
+//   kifs_fold_trap.cpp orbit-trap colouring of folded scenes (kifs_render_folded_trapped_async, kifs_eval_fold_trap): the
+//                      two above composed, their records in a slot of the scene-table ring
 // A kifs_ctx plays the part of the reference's GraphicState (render/graphics.rs:25-37): it owns the
 // "device objects" (stream, events, the sRGB table in HBM, a scratch frame for host-destination renders)
 // and a copy of the three uniform images.  There is no CPU path: every entry point that produces pixels
@@ -229,6 +232,67 @@ inline Light device_light(const KifsLight& l) {
 }
 }  // namespace light
 
+// The ranges of KifsOrbitTrap and the trap as the kernels read it: kifs_trap.cpp's, which kifs_fold_trap.cpp takes too.
+namespace trap {
+// What kifs_eval_trap reads of a trap: where it is and how far the orbit runs.
+inline bool orbit_ok(const KifsOrbitTrap& t) {
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(t.centre[i])) return false;
+    return t.axes >= 1u && t.axes <= 15u && t.iterations >= 0 && t.iterations <= KIFS_MAX_TRAP_ITERATIONS;
+}
+
+inline bool trap_ok(const KifsOrbitTrap& t) {
+    if (!orbit_ok(t) || !std::isfinite(t.scale) || !std::isfinite(t.bias)) return false;
+    for (int i = 0; i < 3; ++i)
+        if (!light::weight_ok(t.mid[i]) || !light::weight_ok(t.far[i])) return false;
+    return true;
+}
+
+inline Trap device_trap(const KifsOrbitTrap& t) {
+    return Trap{V4{t.centre[0], t.centre[1], t.centre[2], t.centre[3]}, t.axes, t.iterations, t.scale, t.bias,
+                V3{t.mid[0], t.mid[1], t.mid[2]}, V3{t.far[0], t.far[1], t.far[2]}};
+}
+}  // namespace trap
+
+// The ranges of KifsFoldSystem, the system as the kernels read it and the launch without a cull: kifs_fold.cpp's, which
+// kifs_fold_trap.cpp takes too.
+namespace fold {
+inline bool fold_ok(const KifsFoldSystem& f) {
+    if (f.stages > 31u || f.iterations < 0 || f.iterations > KIFS_MAX_FOLD_ITERATIONS) return false;
+    if (!std::isfinite(f.scale) || !(f.scale >= 1.0f && f.scale <= 16.0f)) return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(f.offset[i])) return false;
+    if (f.stages & KIFS_FOLD_ROTATE)  // without the bit the matrix is not looked at
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(f.rotation[i])) return false;
+    return true;
+}
+
+// The record as the kernels read it: the constants of the scaling step in f32, t_i = -((s - 1) c_i) and h = t_z / 2.  A
+// matrix that the stages do not name is not carried (it may hold anything): the kernel argument gets zeros.
+inline Fold device_fold(const KifsFoldSystem& f) {
+    Fold F{};
+    F.stages = f.stages;
+    F.iterations = f.iterations;
+    F.scale = f.scale;
+    const float k = f.scale - 1.0f;
+    for (int i = 0; i < 3; ++i) F.t[i] = -(k * f.offset[i]);
+    F.h = 0.5f * F.t[2];
+    if (f.stages & KIFS_FOLD_ROTATE)
+        for (int i = 0; i < 9; ++i) F.R[i] = f.rotation[i];
+    return F;
+}
+
+// A folded scene reaches beyond the bounding sphere of its base primitive, on whose radius fill_params stands the per-ray
+// cull, the wave-level quick exit and the tile-level one; the contract has no cull.  0 is each test's "disabled".
+inline void culls_off(FrameParams& P) {
+    P.cull_n2 = 0.0f;
+    P.quick_cull_n2 = 0.0f;
+    P.tile_cull_beta = 0.0f;
+    P.tile_cull_sqrtk = 0.0f;
+}
+}  // namespace fold
+
 // What every launch that carries a scene table shares (kifs_animation.cpp): the animated call and the four accumulated
 // ones differ in their checks and in the last step, the launch itself.
 namespace accum {
@@ -288,6 +352,14 @@ struct SceneLaunch {
 // The call itself: the context's device and stream (`hip_stream` null), view 0's options for the context's, and the one
 // launch -- views, scene table, rings, tile table, copies, launch step, events.
 int launch_scenes(kifs_ctx* c, void* hip_stream, const SceneLaunch& L);
+
+// The scene-table ring's two steps, for a call that brings a record of its own through a slot (kifs_fold_trap.cpp).
+// take_scene_slot: the next slot -- allocated on first use, and free to be rewritten when the call returns: it has waited
+// for the launch that last read the slot.  mark_scene_slot: the event behind the launch that reads the slot, recorded on
+// that launch's stream (also after a failed launch, once the copy is enqueued: it reads the pinned image); false when
+// the record failed.
+int take_scene_slot(kifs_ctx* c, int* slot);
+bool mark_scene_slot(kifs_ctx* c, int slot, hipStream_t stream);
 
 }  // namespace anim
 

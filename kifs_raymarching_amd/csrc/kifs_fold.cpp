@@ -19,41 +19,6 @@ static_assert(KIFS_FOLD_ABS == ABS && KIFS_FOLD_SORT == SORT && KIFS_FOLD_TETRA 
 
 static const KifsLight REFERENCE_LIGHT = {{1.0f, 1.0f, 1.0f}, 0.1f, 0.9f, {0.0f, 0.0f, 0.0f}, 0};
 
-static bool fold_ok(const KifsFoldSystem& f) {
-    if (f.stages > 31u || f.iterations < 0 || f.iterations > KIFS_MAX_FOLD_ITERATIONS) return false;
-    if (!std::isfinite(f.scale) || !(f.scale >= 1.0f && f.scale <= 16.0f)) return false;
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(f.offset[i])) return false;
-    if (f.stages & KIFS_FOLD_ROTATE)  // without the bit the matrix is not looked at
-        for (int i = 0; i < 9; ++i)
-            if (!std::isfinite(f.rotation[i])) return false;
-    return true;
-}
-
-// The record as the kernels read it: the constants of the scaling step in f32, t_i = -((s - 1) c_i) and h = t_z / 2.  A
-// matrix that the stages do not name is not carried (it may hold anything): the kernel argument gets zeros.
-static Fold device_fold(const KifsFoldSystem& f) {
-    Fold F{};
-    F.stages = f.stages;
-    F.iterations = f.iterations;
-    F.scale = f.scale;
-    const float k = f.scale - 1.0f;
-    for (int i = 0; i < 3; ++i) F.t[i] = -(k * f.offset[i]);
-    F.h = 0.5f * F.t[2];
-    if (f.stages & KIFS_FOLD_ROTATE)
-        for (int i = 0; i < 9; ++i) F.R[i] = f.rotation[i];
-    return F;
-}
-
-// A folded scene reaches beyond the bounding sphere of its base primitive, on whose radius fill_params stands the per-ray
-// cull, the wave-level quick exit and the tile-level one; the contract has no cull.  0 is each test's "disabled".
-static void culls_off(FrameParams& P) {
-    P.cull_n2 = 0.0f;
-    P.quick_cull_n2 = 0.0f;
-    P.tile_cull_beta = 0.0f;
-    P.tile_cull_sqrtk = 0.0f;
-}
-
 // What a caller can get wrong that needs no look at the frame.
 static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, const KifsFoldSystem* fold,
                  const KifsLight* light, const KifsAmbientOcclusion* ao, int encode) {

@@ -1,6 +1,7 @@
 // kifs_internal.hpp -- launcher prototypes shared by the host code and the kernel files (kifs_kernels.hip,
 // kifs_support_kernels.hip, kifs_adaptive_kernels.hip, kifs_animation_kernels.hip, kifs_accumulate_kernels.hip,
-// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip, kifs_trap_kernels.hip, kifs_fold_kernels.hip).
+// kifs_rays_kernels.hip, kifs_occlusion_kernels.hip, kifs_lighting_kernels.hip, kifs_trap_kernels.hip, kifs_fold_kernels.hip,
+// kifs_fold_trap_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +51,12 @@ hipError_t launch_eval_trap(const trap::EvalParams& E, uint32_t group, uint32_t 
 // normal at E.n positions, one per lane (fold::eval_kernel).  KIFS group only.
 hipError_t launch_folded(const fold::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
 hipError_t launch_eval_fold(const fold::EvalParams& E, uint32_t group, uint32_t primitive, hipStream_t stream);
+// Orbit-trap colouring of folded scenes (kifs_render_folded_trapped_async; kifs_fold_trap_kernels.hip, the host side is
+// kifs_fold_trap.cpp): the folded launch with every hit's colour from the orbit of the fold and the launch's trap, both
+// read from O.record in device memory, and the optional plane of u (foldorbit::render_kernel); and kifs_eval_fold_trap's u
+// of E.n positions, one per lane (foldorbit::eval_kernel).  KIFS group only.
+hipError_t launch_folded_trapped(const foldorbit::Params& O, uint32_t group, uint32_t primitive, hipStream_t stream);
+hipError_t launch_eval_fold_trap(const foldorbit::EvalParams& E, uint32_t group, uint32_t primitive, hipStream_t stream);
 // Device-side counting sort: order[] = tile ids (x | y << 16) by descending cost[] >> shift (1024 bins);
 // clears cost[].
 hipError_t launch_tile_order(uint32_t* cost, uint32_t* order, uint32_t tile_count,

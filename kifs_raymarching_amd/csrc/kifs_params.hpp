@@ -357,4 +357,45 @@ static_assert(sizeof(EvalParams) <= 4096, "the kernel argument is limited to 4 K
 
 }  // namespace fold
 
+namespace foldorbit {
+
+// What kifs_render_folded_trapped_async carries beside light::Params' fields: the fold system and the trap as the two
+// calls' kernels read them.  light::Params is 4024 of the kernel argument's 4096 bytes and the two records are 120, so
+// they travel in device memory -- one record per launch, in a slot of the context's scene-table ring -- and the argument
+// holds a pointer.  Nothing writes the record while a launch that reads it runs.
+struct Record {
+    fold::Fold fold;
+    trap::Trap trap;
+    uint32_t pad[2];
+};
+static_assert(sizeof(Record) == 128, "the record is 128 bytes: the fold system, the trap, padding");
+
+// The argument of foldorbit::render_kernel (kifs_fold_trap_kernels.hip): light::Params -- the same fields at the same
+// offsets -- and behind them the record, and the optional plane of one f32 per pixel, laid out as occl::Params' -- row r
+// of the band of view i at plane + i * stride_words + r * pitch_words floats.
+struct Params {
+    BatchParams B;
+    light::Light light;
+    occl::AO ao;         // read only when has_ao != 0
+    uint32_t has_ao;
+    const Record* record;  // device memory
+    float* plane;          // null: no plane (always with k > 1)
+    uint32_t pitch_words, stride_words;
+};
+static_assert(sizeof(Params) == 4048, "the kernel argument is limited to 4 KB");
+
+// The argument of foldorbit::eval_kernel (kifs_eval_fold_trap): the scene's frame constants -- nothing of a screen or a
+// camera is read -- the two records, which fit here, and the arrays.  Of the trap only centre, axes and iterations are read.
+struct EvalParams {
+    FrameParams frame;
+    fold::Fold fold;
+    trap::Trap trap;
+    const float* points;  // n positions of three floats (device memory)
+    int n;
+    float* u;             // n floats
+};
+static_assert(sizeof(EvalParams) <= 4096, "the kernel argument is limited to 4 KB");
+
+}  // namespace foldorbit
+
 }  // namespace kifs

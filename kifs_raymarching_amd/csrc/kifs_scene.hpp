@@ -1714,4 +1714,150 @@ KIFS_DEV V3 raymarch_folded(const FrameParams& P, fold::ConstParams K, V3 dir, b
     return colour;
 }
 
+// ---- extension: orbit-trap colouring of folded scenes (kifs_render_folded_trapped_async, include/kifs_hip.h) --------
+// The two extensions above composed: the folded estimate wherever the folded call puts it, and a hit's colour from the
+// orbit that the estimate iterates -- the point after each round -- continued by the base primitive's own.  The fold
+// system and the trap are read from a record in device memory, through a pointer cast to the constant address space
+// (foldorbit::Record, kifs_params.hpp): scalar loads of a uniform address, like the kernel argument's own.
+namespace foldorbit {
+typedef const Params __attribute__((address_space(4))) * ConstParams;
+typedef const Record __attribute__((address_space(4))) * ConstRecord;
+KIFS_DEV ConstParams anew(ConstParams K) {
+    asm volatile("" : "+s"(K));
+    return K;
+}
+KIFS_DEV ConstRecord anew(ConstRecord R) {
+    asm volatile("" : "+s"(R));
+    return R;
+}
+// The launch's record: the pointer is read from the kernel argument where it is asked for.
+KIFS_DEV ConstRecord record_of(ConstParams K) { return (ConstRecord)anew(K)->record; }
+}  // namespace foldorbit
+
+// u of the position p on a folded scene: folded_sdf's loop restated with the running minimum.  Orbit point j + 1 is the
+// point after round j (w = 0) and takes part while j + 1 <= K, K the trap's iterations; with the Sierpinski estimate as
+// the base the orbit goes on from the folded p with orbit_trap's Sierpinski rule for max(K - N, 0) points.  So
+// min(N, K) rounds are all the orbit needs: beyond them no fold point takes part, and the base part runs only with
+// K > N, when every round has run.  The fold constants and the trap's centre and axes sit in scalar registers for the
+// length of the loop only; the trip count and the exit -- once no lane still folds -- are wave-uniform (called from a
+// divergent region, the ballot is of the region's lanes); a lane that has stopped takes no further fold point and keeps
+// its p.  The trap's gradient fields are not read.
+template <int PRIM>
+KIFS_DEV float folded_orbit_trap(const FrameParams& S, fold::ConstFold F0, trap::ConstTrap T0, V3 p) {
+    const fold::ConstFold F = fold::anew(F0);
+    const trap::ConstTrap Tc = T0;
+    const int n = F->iterations;       // uniform
+    const int K = Tc->iterations;      // uniform
+    trap::Trap T{};
+    T.axes = Tc->axes;
+    float cx = Tc->centre.x, cy = Tc->centre.y, cz = Tc->centre.z, cw = Tc->centre.w;
+    asm volatile("" : "+s"(cx), "+s"(cy), "+s"(cz), "+s"(cw));
+    T.centre = V4{cx, cy, cz, cw};
+    float m = trap_distance(T, V4{p.x, p.y, p.z, 0.0f});
+    const int rounds = n < K ? n : K;
+    if (rounds > 0) {
+        const uint32_t stages = F->stages;
+        float s = F->scale, t0 = F->t[0], t1 = F->t[1], t2 = F->t[2], h = F->h;
+        asm volatile("" : "+s"(s), "+s"(t0), "+s"(t1), "+s"(t2), "+s"(h));
+        float R[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (stages & fold::ROTATE) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) R[i] = F->R[i];
+        }
+        asm volatile("" : "+s"(R[0]), "+s"(R[1]), "+s"(R[2]), "+s"(R[3]), "+s"(R[4]), "+s"(R[5]), "+s"(R[6]), "+s"(R[7]), "+s"(R[8]));
+        bool run = true;
+        for (int j = 0; j < rounds; ++j) {
+            run = run && (dot(p, p) < S.fold_n2_stop);
+            if (__builtin_amdgcn_ballot_w64(run) == 0ull) break;
+            V3 q = p;
+            if (stages & fold::ABS) q = V3{abs_(q.x), abs_(q.y), abs_(q.z)};
+            if (stages & fold::SORT) {
+                const bool a = q.x < q.y;
+                const float x1 = a ? q.y : q.x, y1 = a ? q.x : q.y;
+                const bool b = x1 < q.z;
+                const float x2 = b ? q.z : x1, z2 = b ? x1 : q.z;
+                const bool c = y1 < z2;
+                q = V3{x2, c ? z2 : y1, c ? y1 : z2};
+            }
+            if (stages & fold::TETRA) q = tetrahedral_fold(q);
+            if (stages & fold::ROTATE) {
+                q = V3{fmaf_(R[2], q.z, fmaf_(R[1], q.y, R[0] * q.x)), fmaf_(R[5], q.z, fmaf_(R[4], q.y, R[3] * q.x)),
+                       fmaf_(R[8], q.z, fmaf_(R[7], q.y, R[6] * q.x))};
+            }
+            q = V3{fmaf_(s, q.x, t0), fmaf_(s, q.y, t1), fmaf_(s, q.z, t2)};
+            if (stages & fold::MIRROR_Z) q.z = abs_(q.z - h) + h;
+            p = V3{run ? q.x : p.x, run ? q.y : p.y, run ? q.z : p.z};
+            const float d = trap_distance(T, V4{q.x, q.y, q.z, 0.0f});
+            m = (run && (d < m)) ? d : m;
+        }
+    }
+    if constexpr (PRIM == PRIM_SIERPINSKI) {
+        V3 q = p;
+        for (int k = n; k < K; ++k) {  // uniform: max(K - N, 0) points, from N and not from the rounds that ran
+            q = tetrahedral_fold(q);
+            q = V3{fmaf_(2.0f, q.x, -1.0f), fmaf_(2.0f, q.y, -1.0f), fmaf_(2.0f, q.z, -1.0f)};
+            const float d = trap_distance(T, V4{q.x, q.y, q.z, 0.0f});
+            m = (d < m) ? d : m;
+        }
+    }
+    return sqrt_(m);
+}
+
+// raymarch_folded for the folded trapped launch (kifs_fold_trap_kernels.hip): the same whole ray per lane through the
+// view P with the folded estimate in the march, the normal, the shadow ray and the probes, and trapped_shade's colour of
+// a hit from folded_orbit_trap (foldorbit::Params carries light::Params' fields at their offsets, which is all that
+// trapped_shade reads of its argument).  `u`: the hit's trap distance, written when the launch has a plane -- then for
+// every hit, heatmap frames included -- or when the colour needs it; a lane that did not hit leaves it alone.
+template <int PRIM, class Dir>
+KIFS_DEV V3 raymarch_folded_trapped(const FrameParams& P, foldorbit::ConstParams K, V3 dir, bool valid, float& u, Dir redo_dir) {
+    float t = 0.0f;
+    V3 p = P.origin;
+    bool hit = false;
+    int trips = 0;
+    int i_final = 0;
+    bool marching = whole_ray_sets_out(P, dir, valid);
+    generic_loop(P, dir, t, p, hit, marching, trips, i_final, P.max_iterations, [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) {
+        return folded_sdf<PRIM>(P, &foldorbit::record_of(K)->fold, q, lanes);
+    });
+    __builtin_amdgcn_s_setprio(0);
+    const trap::ConstParams KT = (trap::ConstParams)K;
+    const foldorbit::ConstParams L = foldorbit::anew(K);
+    const FrameParams S = *(const FrameParams*)&L->B.frame;  // the scene, as every view of the launch shares it
+    V3 colour = S.background_color;
+    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {  // wave-uniform
+        const auto sdf = [&](V3 q, unsigned long long lanes) __attribute__((always_inline)) {
+            return folded_sdf<PRIM>(S, &foldorbit::record_of(K)->fold, q, lanes);
+        };
+        colour = trapped_shade(
+            S, KT, p, hit, S.background_color, sdf,
+            [&](V3 q) __attribute__((always_inline)) {
+                return normal_fd(S.epsilon, q, [&](V3 e) __attribute__((always_inline)) {
+                    return folded_sdf<PRIM>(S, &foldorbit::record_of(K)->fold, e, ~0ull);
+                });
+            },
+            redo_dir,
+            [&](V3 q) __attribute__((always_inline)) {
+                // (the scene's constants anew: what the gradient and the counter's colour read of them need not cross
+                // the normal's and the shadow ray's estimates, which leave the bunny few scalar registers)
+                const foldorbit::ConstParams A = foldorbit::anew(K);
+                const bool heatmap = A->B.frame.is_heatmap != 0u, planed = A->plane != nullptr;  // uniform
+                V3 col{A->B.frame.fractal_color.x, A->B.frame.fractal_color.y, A->B.frame.fractal_color.z};
+                if (heatmap && !planed) return col;  // the colour is the counter's
+                const foldorbit::ConstRecord R = foldorbit::record_of(K);
+                u = folded_orbit_trap<PRIM>(S, &R->fold, &R->trap, q);
+                if (!heatmap) {
+                    const foldorbit::ConstParams B = foldorbit::anew(K);
+                    const FrameParams G = *(const FrameParams*)&B->B.frame;
+                    const trap::Trap T = trap::load(&foldorbit::anew(R)->trap);
+                    col = trap_colour(G, T, u);
+                }
+                return col;
+            });
+    }
+    const foldorbit::ConstParams E = foldorbit::anew(K);
+    const FrameParams H = *(const FrameParams*)&E->B.frame;
+    if (H.is_heatmap) colour = heatmap_colour(H, i_final);
+    return colour;
+}
+
 }  // namespace kifs

@@ -16,25 +16,6 @@ static_assert(sizeof(KifsOrbitTrap) == sizeof(Trap), "the record travels as it i
 
 static const KifsLight REFERENCE_LIGHT = {{1.0f, 1.0f, 1.0f}, 0.1f, 0.9f, {0.0f, 0.0f, 0.0f}, 0};
 
-// What kifs_eval_trap reads of a trap: where it is and how far the orbit runs.
-static bool orbit_ok(const KifsOrbitTrap& t) {
-    for (int i = 0; i < 4; ++i)
-        if (!std::isfinite(t.centre[i])) return false;
-    return t.axes >= 1u && t.axes <= 15u && t.iterations >= 0 && t.iterations <= KIFS_MAX_TRAP_ITERATIONS;
-}
-
-static bool trap_ok(const KifsOrbitTrap& t) {
-    if (!orbit_ok(t) || !std::isfinite(t.scale) || !std::isfinite(t.bias)) return false;
-    for (int i = 0; i < 3; ++i)
-        if (!light::weight_ok(t.mid[i]) || !light::weight_ok(t.far[i])) return false;
-    return true;
-}
-
-static Trap device_trap(const KifsOrbitTrap& t) {
-    return Trap{V4{t.centre[0], t.centre[1], t.centre[2], t.centre[3]}, t.axes, t.iterations, t.scale, t.bias,
-                V3{t.mid[0], t.mid[1], t.mid[2]}, V3{t.far[0], t.far[1], t.far[2]}};
-}
-
 // What a caller can get wrong that needs no look at the frame.
 static int check(const kifs_ctx* c, int count, const KifsCameraUniform* cameras, uint8_t* const* outs, const KifsOrbitTrap* trap,
                  const KifsLight* light, const KifsAmbientOcclusion* ao, int encode) {

@@ -800,6 +800,85 @@ class GraphicState:
         check(lib.kifs_eval_fold(self._ctx, C.byref(record), fp(pts), n, fp(d), fp(nr)), "eval_fold")
         return d, nr
 
+    # ---- orbit-trap colouring of folded scenes (kifs_render_folded_trapped_async): the two above composed
+    def render_folded_trapped_batch(self, cameras, fold: FoldSystem, trap: OrbitTrap, light: Light = None,
+                                    ao: AmbientOcclusion = None, u_plane=False, stream=None, y0: int = 0, y1: int = None,
+                                    encode: int = ENCODE_SRGB, colour=None):
+        """The frames of len(cameras) cameras (cameras None: one frame with the context's camera) of the context's KIFS
+        primitive seen through the fold system `fold`, every hit coloured by the orbit trap `trap` over the fold's own
+        orbit, under `light` (None: the reference's light) and with the ambient-occlusion term `ao` on top when one is
+        given, the context's supersampling factor and soft-shadow extension honoured.  `u_plane`: True, or a contiguous
+        float32 (count, rows, W) torch tensor to reuse -- the trap distance u of every hit, +inf on a miss (one sample
+        per pixel only).  Returns a uint8 (count, rows, W, 4) torch tensor on this context's device, or with a plane the
+        pair (colour, plane); `colour`: a contiguous destination tensor of that shape to reuse.  The library takes
+        MAX_FOLD_TRAP_BATCH cameras per launch; more are fed to it that many at a time.  Enqueued on `stream` like
+        render_async; the caller synchronises before reading."""
+        import torch
+        w, h = self.screen_data.width, self.screen_data.height
+        y1 = h if y1 is None else y1
+        rows = max(y1 - y0, 0)
+        n = 1 if cameras is None else len(cameras)
+        if n < 1:
+            raise ValueError("render_folded_trapped_batch: at least one frame")
+        dev = torch.device("cuda", self.device)
+        if colour is None:
+            colour = torch.empty((n, rows, w, 4), dtype=torch.uint8, device=dev)
+        if tuple(colour.shape) != (n, rows, w, 4) or colour.dtype != torch.uint8 or not colour.is_contiguous():
+            raise ValueError(f"render_folded_trapped_batch: colour uint8 ({n}, {rows}, {w}, 4), contiguous")
+        plane = None
+        if u_plane is not None and u_plane is not False:
+            plane = torch.empty((n, rows, w), dtype=torch.float32, device=dev) if u_plane is True else u_plane
+            if tuple(plane.shape) != (n, rows, w) or plane.dtype != torch.float32 or not plane.is_contiguous():
+                raise ValueError(f"render_folded_trapped_batch: u_plane float32 ({n}, {rows}, {w}), contiguous")
+        system = fold.into_buffer_data() if hasattr(fold, "into_buffer_data") else fold  # (or a KifsFoldSystemC)
+        record = trap.into_buffer_data() if hasattr(trap, "into_buffer_data") else trap  # (or a KifsOrbitTrapC, linear colours)
+        lit = None if light is None else light.into_buffer_data()
+        term = None if ao is None else ao.into_buffer_data()
+        stream = self._stream_handle(stream, "render_folded_trapped_batch")
+        cams = None if cameras is None else camera_array(cameras)
+        self._order_after_producer(colour, stream)
+        if plane is not None:
+            self._order_after_producer(plane, stream)
+        step = _lib.MAX_FOLD_TRAP_BATCH
+        base, frame_bytes = _device_pointer(colour), rows * w * 4  # (a plane of one f32 per pixel is as many bytes)
+        planes = None if plane is None else _device_pointer(plane)
+        for first in range(0, n, step):
+            m = min(step, n - first)
+            ptrs = (C.c_void_p * m)(*[base + (first + i) * frame_bytes for i in range(m)])
+            part = None if cams is None else C.cast(C.byref(cams, first * C.sizeof(CameraUniform)), C.POINTER(CameraUniform))
+            check(lib.kifs_render_folded_trapped_async(self._ctx, stream, m, part, ptrs, w * 4, C.byref(system), C.byref(record),
+                                                       None if lit is None else C.byref(lit),
+                                                       None if term is None else C.byref(term),
+                                                       None if planes is None else planes + first * frame_bytes, w * 4,
+                                                       frame_bytes, y0, y1, encode), "render_folded_trapped")
+        return colour if plane is None else (colour, plane)
+
+    def render_folded_trapped(self, fold: FoldSystem, trap: OrbitTrap, light: Light = None, ao: AmbientOcclusion = None,
+                              u_plane=False, y0: int = 0, y1: int = None, encode: int = ENCODE_SRGB, stream=None):
+        """The context's frame seen through `fold` and coloured by `trap` (under `light`, with `ao`), synchronously: a
+        uint8 rows x W x 4 torch tensor on this context's device, or with `u_plane` the pair (colour, float32 rows x W)."""
+        import torch
+        r = self.render_folded_trapped_batch(None, fold, trap, light=light, ao=ao, u_plane=u_plane, stream=stream, y0=y0, y1=y1,
+                                             encode=encode)
+        colour, plane = r if isinstance(r, tuple) else (r, None)
+        if stream is None:
+            self.synchronize()
+        else:
+            torch.cuda.synchronize(colour.device)
+        return colour[0] if plane is None else (colour[0], plane[0])
+
+    def eval_fold_trap(self, fold: FoldSystem, trap: OrbitTrap, points):
+        """u -- the least distance to the trap of the fold's orbit, continued by the base primitive's -- of (n, 3)
+        positions with the context's options: (n,) float32.  Of the trap only centre, axes and iterations are read."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        u = np.empty(n, dtype=np.float32)
+        system = fold.into_buffer_data() if hasattr(fold, "into_buffer_data") else fold
+        record = trap.into_buffer_data() if hasattr(trap, "into_buffer_data") else trap
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib.kifs_eval_fold_trap(self._ctx, C.byref(system), C.byref(record), fp(pts), n, fp(u)), "eval_fold_trap")
+        return u
+
     # ---- ray queries (kifs_trace_rays_async): caller-supplied rays to hit, normal and colour
     def trace_rays(self, rays, colours: bool = True, geometry: bool = True, encode: int = ENCODE_SRGB, stream=None):
         """Trace n rays of the caller's own through the context's scene (options, iteration counts, extensions; the

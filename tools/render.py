@@ -21,6 +21,7 @@
     python tools/render.py cfg2_julia_1080p out.png --light -0.55,0.75,0.36,0.15,0.85 --specular 0.6,0.6,0.5,3 --ao  # a moved light
     python tools/render.py cfg2_julia_1080p out.png --trap 0,0,0,0 --trap-colours 255,140,0:20,60,200 --trap-range auto --ao  # orbit-trap colours
     python tools/render.py cfg5_sierpinski_8k_orbit out.png --scale 0.25 --fold menger --ao    # a Menger sponge (kaleidoscopic IFS)
+    python tools/render.py cfg5_sierpinski_8k_orbit out.png --scale 0.25 --fold menger --trap 0,0,0,0,4 --trap-colours 255,140,0:20,60,200 --trap-range auto --ao  # ... coloured by its fold orbit
     python tools/render.py cfg5_sierpinski_8k_orbit out.png --scale 0.25 --fold abs+sort,6,2,1,0,0 --fold-rotate z,14,y,9 --light -0.55,0.75,0.36
 """
 import argparse
@@ -105,12 +106,14 @@ ap.add_argument("--trap", metavar="CX,CY,CZ,CW[,AXES[,K]]", default=None,
                 help="colour the hits by an orbit trap (kifs_render_trapped_async): the least distance of the hit point's orbit to "
                      "the point CX,CY,CZ,CW of orbit space over the components of the mask AXES (x = 1, y = 2, z = 4, w = 8; "
                      "default 15, a point trap) within K orbit points (0..32, default 8), through a gradient from the workload's "
-                     "colour; goes with --light, --specular, --ao, --aa, --frames and the shadow workloads")
+                     "colour; goes with --light, --specular, --ao, --aa, --frames and the shadow workloads, and with --fold "
+                     "(kifs_render_folded_trapped_async: the orbit is then the fold's own, continued by the base primitive's)")
 ap.add_argument("--trap-colours", metavar="R,G,B:R,G,B", default="255,140,0:20,60,200",
                 help="with --trap: the gradient's middle and far stops as sRGB bytes")
 ap.add_argument("--trap-range", metavar="LO,HI|auto", default="auto",
                 help="with --trap: the distances that take the gradient's first and last stop; auto: the 5th and 95th "
-                     "percentile of the distances at the first frame's hits (kifs_render_geometry_async, kifs_eval_trap)")
+                     "percentile of the distances at the first frame's hits (kifs_render_geometry_async and kifs_eval_trap; with "
+                     "--fold the plane of u of kifs_render_folded_trapped_async)")
 ap.add_argument("--fold", metavar="PRESET|STAGES,N,SCALE,CX,CY,CZ", default=None,
                 help="a kaleidoscopic IFS scene (kifs_render_folded_async): the base primitive seen through N rounds of the "
                      "stages STAGES (a mask 0..31, or names joined by +: abs+sort+tetra+rotate+mirror_z), scaled by SCALE about "
@@ -240,12 +243,12 @@ if args.trap is not None:
     aa_grid = False  # several supersampled frames go through the trapped batch, not through the accumulate family
 fold, fold_base = None, None
 if args.fold is not None:
-    # the folded estimate exists in kifs_render_folded_async alone
-    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None or trap is not None:
-        ap.error("--fold renders without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry, --morph-to and --trap: "
-                 "the accumulate, adaptive, geometry, animation and trapped entry points march the unfolded scene")
+    # the folded estimate exists in kifs_render_folded_async and, with --trap, in kifs_render_folded_trapped_async
+    if accumulate or args.jitter or args.aa_adaptive or args.geometry or args.morph_to is not None:
+        ap.error("--fold renders without --motion-blur, --dof, --spp, --jitter, --aa-adaptive, --geometry and --morph-to: "
+                 "the accumulate, adaptive, geometry and animation entry points march the unfolded scene")
     if args.ao_png:
-        ap.error("--ao-png goes without --fold: the folded call writes no plane of factors")
+        ap.error("--ao-png goes without --fold: the folded calls write no plane of factors")
     if args.fold in FOLD_PRESETS:
         if args.fold_rotate is not None:
             ap.error("--fold-rotate goes with --fold STAGES,..: a preset brings its own rotation")
@@ -439,6 +442,41 @@ with K.GraphicState(0, screen_data=screen, camera_data=w.camera, gui_data=gui) a
                 print(f"{path}: {screen.width}x{screen.height}, the mean of {S} sub-frames "
                       + (f"(lens radius {dof[0]}, focus at {dof[1]})" if dof else f"(shutter {args.shutter})")
                       + (f", jittered over a {args.jitter}x{args.jitter} grid" if args.jitter else ""))
+    elif trap is not None and fold is not None:
+        import numpy as np
+        indices = args.frames if args.frames is not None else [None]
+        cams = [w.camera if k is None else orbit_camera(w, k) for k in indices]
+        try:
+            if args.trap_range == "auto":
+                # the first frame once with the plane of u (one ray per pixel), and the middle nine tenths of what the trap
+                # measures at its hits -- what render_geometry and eval_trap do for an unfolded scene
+                gs.set_supersampling(1)
+                gs.set_camera(cams[0])
+                _, plane = gs.render_folded_trapped(fold, trap, u_plane=True)
+                gs.set_supersampling(args.aa)
+                u = plane.cpu().numpy().reshape(-1)
+                u = u[np.isfinite(u)]
+                if not u.size:
+                    sys.exit("--trap-range auto: no ray of the first frame hits the scene, nothing to take a range from")
+                lo, hi = (float(v) for v in np.percentile(u, [5.0, 95.0]))
+                if not hi > lo:
+                    hi = lo + 1.0  # (a trap that measures one distance everywhere: the first stop's colour)
+                trap.scale, trap.bias = (float(v) for v in trap_range(lo, hi))
+                print(f"--trap-range auto: {u.size} hits, distances {float(u.min()):.4g} .. {float(u.max()):.4g}, range {lo:.4g},{hi:.4g}")
+            colour = gs.render_folded_trapped_batch(cams, fold, trap, light=light, ao=ao)
+        except K.KifsError as e:
+            sys.exit(f"--fold {args.fold} --trap {args.trap}: {e}")
+        gs.synchronize()
+        for k, frame in zip(indices, colour.cpu().numpy()):
+            path = args.out if k is None else args.out % k
+            write_png(path, frame)
+            print(f"{path}: {screen.width}x{screen.height}, {K.PrimitiveShape(gui.primitive_shape).name} folded {fold.iterations} times "
+                  f"(stages {fold.stage_bits()}, scale {fold.scale}, offset {tuple(fold.offset)}), orbit trap at {tuple(trap.centre)} "
+                  f"(axes {trap.axes}, {trap.iterations} orbit points, scale {trap.scale:.6g}, bias {trap.bias:.6g}), stops "
+                  f"{tuple(trap.mid)} and {tuple(trap.far)}"
+                  + (f", lit from {tuple(light.direction)}" if light is not None else "")
+                  + (f", ambient occlusion ({ao.samples} probes)" if ao is not None else "")
+                  + (f", {args.aa}x{args.aa} supersampled" if args.aa > 1 else ""))
     elif trap is not None:
         import numpy as np
         indices = args.frames if args.frames is not None else [None]
